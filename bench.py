@@ -27,6 +27,13 @@ The step is a jitted, donated, HIP-graph-captured function; the timed region is 
 bracketed by barrier + device synchronize, and the reported time is the max over ranks.
 Rank 0 prints one JSON line; ``value`` is the whole-job TFLOPS (summed over the N GPUs, the
 driver's aggregate convention) and ``tflops_per_gpu`` the per-GPU rate the metric names.
+
+A plain run does only what that line needs: set up, warm up, time ``--steps`` steps, print.
+``--full`` adds the measurements that take runs of their own: the reference's 2-D layout as the
+line's ``secondary`` object (even N >= 2) and the timed eager all-reduce probe of
+``comm_detail.all_reduce_probe`` (N >= 2).  ``--dump-outputs DIR`` writes what the last timed step
+returned (the train state, or the forward output) as ``DIR/<name>.npy`` for output-for-output
+comparison of two builds; inputs and initial weights are seeded.
 """
 from __future__ import annotations
 
@@ -81,8 +88,20 @@ def parse():
                         "case5 (embed->data: FSDP-sharded weights, case5_attention_dense.py:109-112), gspmd2d, megatron, dp")
     p.add_argument("--secondary", default=os.environ.get("LJS_BENCH_SECONDARY", "auto"),
                    choices=["auto", "on", "off", "0", "1"],
-                   help="also time the reference's 2-D DP x TP layout ((N/2, 2) mesh) in the same job and report it "
-                        "as the JSON line's 'secondary' object (auto: the headline block, --mesh dp, even N >= 2)")
+                   help="with --full: also time the reference's 2-D DP x TP layout ((N/2, 2) mesh) in the same job and "
+                        "report it as the JSON line's 'secondary' object (auto: the headline block, --mesh dp, even "
+                        "N >= 2)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the secondary 2-D layout (--secondary) and "
+                        "the timed eager all-reduce of the gradient size through each path "
+                        "(comm_detail.all_reduce_probe).  Off by default: a plain run sets up, warms up, times "
+                        "--steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (train: every array of the "
+                        "train state - parameters, Adam moments, step count; fwd: the block's output) as "
+                        "DIR/<name>.npy in float32 / float64, global values, at most 64 MB in all (a fixed, seeded "
+                        "sample of each array beyond that).  Inputs and initial weights are seeded, so the same "
+                        "arguments give the same inputs in every run")
     p.add_argument("--comm-timeout", type=float, default=None,
                    help="seconds a phase may run before the watchdog aborts the communicators and exits "
                         "(default LJS_COMM_TIMEOUT_S or 300)")
@@ -197,7 +216,8 @@ def main():
 
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
-    cuda = torch.cuda.is_available()
+    # host devices (LJS_PLATFORM=cpu) stay host devices where a GPU is present: no capture, no device syncs
+    cuda = on_gpu
     rank = int(os.environ.get("RANK", "0"))
     # physical GPUs doing the work: one per rank, or the one GPU under N virtual devices
     n_gpus = world if world > 1 else (1 if cuda else 0)
@@ -221,8 +241,10 @@ def main():
             wd.phase(name, timeout)
 
     env = dict(n=n, world=world, torch=torch, ljs=ljs, dist=dist, dist_on=dist_on, cuda=cuda,
-               barrier_sync=barrier_sync, phase=phase, probe=dist_on and world > 1)
+               barrier_sync=barrier_sync, phase=phase, probe=args.full and dist_on and world > 1,
+               dump=args.dump_outputs)
     res = _measure_with_fallback(args, args.mesh, env)
+    env["dump"] = None   # the headline layout's outputs only
     comm = "none"
     if dist_on:
         c = get_comm()
@@ -343,9 +365,10 @@ def _comm_detail(env, res):
 
 
 def _want_secondary(args, n) -> bool:
-    """Time the reference's 2-D layout too: on by default for the headline block with an even
-    device count >= 2 under the DP mesh (``--secondary off`` / LJS_BENCH_SECONDARY=0 disables)."""
-    if args.secondary == "off":
+    """Time the reference's 2-D layout too (``--full`` runs only): then on by default for the headline
+    block with an even device count >= 2 under the DP mesh (``--secondary off`` / LJS_BENCH_SECONDARY=0
+    disables)."""
+    if not args.full or args.secondary == "off":
         return False
     if args.secondary == "on":
         return n >= 2 and n % 2 == 0
@@ -365,6 +388,50 @@ def _parallelism(args, mshape) -> str:
     if args.model == "fsdp" or (args.rules in ("case5", "fsdp", "gspmd2d") and mshape[0] > 1):
         par = f"fsdp{mshape[0]}" + (f"xtp{mshape[1]}" if mshape[1] > 1 else "")
     return par
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000   # --dump-outputs writes at most this much array data (documented limit: 64 MB)
+
+
+def _dump_outputs(directory, tree) -> None:
+    """Write every array of ``tree`` as ``directory/<path>.npy`` (the global value; float64 stays,
+    everything else becomes float32; an integer such as the step count becomes float64).  Beyond
+    DUMP_LIMIT_BYTES in all, each array is cut to the same fraction of its elements, taken at fixed
+    seeded positions of the flattened array (sorted; the same positions in every run).  Gathering a
+    sharded array is a collective: every rank calls this, rank 0 writes."""
+    import numpy as np
+    import torch
+    from learning_jax_sharding_amd.array import ShardedArray
+    from learning_jax_sharding_amd.utils import tree as T
+
+    def is_arr(v):
+        return isinstance(v, (ShardedArray, torch.Tensor))
+    items = [(p, v) for p, v in T.tree_leaves_with_path(tree, is_leaf=is_arr) if is_arr(v)]
+
+    def out_dtype(v):
+        return np.float32 if v.dtype.is_floating_point and v.dtype != torch.float64 else np.float64
+    sizes = [(int(np.prod(v.shape, dtype=np.int64)), np.dtype(out_dtype(v)).itemsize) for _, v in items]
+    whole = sum(sz * it for sz, it in sizes if sz <= 1)   # scalars are written as they are
+    total = sum(sz * it for sz, it in sizes if sz > 1)
+    frac = min(1.0, max(0, DUMP_LIMIT_BYTES - whole) / max(1, total))
+    write = int(os.environ.get("RANK", "0")) == 0
+    if write:
+        os.makedirs(directory, exist_ok=True)
+    seen = set()
+    for li, (path, v) in enumerate(items):
+        t = v.to_torch() if isinstance(v, ShardedArray) else v.detach().to("cpu")
+        if not write:
+            continue
+        a = t.to(torch.float64 if out_dtype(v) is np.float64 else torch.float32).numpy()
+        if frac < 1.0 and a.size > 1:
+            k = max(1, int(a.size * frac))
+            idx = np.sort(np.random.default_rng(li).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        name = ".".join(str(p) for p in path).replace(os.sep, "_") or "output"
+        while name in seen:
+            name += "_"
+        seen.add(name)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _measure(args, mesh_arg, env, phase_timeout=None):
@@ -437,8 +504,8 @@ def _measure(args, mesh_arg, env, phase_timeout=None):
     def fwd_step(state, x):
         return model.apply({"params": state.params}, x)
 
-    capture = not args.no_graph and torch.cuda.is_available()
-    clock_probe = os.environ.get("LJS_CLOCK_PROBE") and torch.cuda.is_available()
+    capture = not args.no_graph and cuda
+    clock_probe = os.environ.get("LJS_CLOCK_PROBE") and cuda
     aten_trace = os.environ.get("LJS_ATEN_TRACE")   # diagnostics: eager steps, one traced (utils/aten_trace.py)
     if aten_trace:
         capture = False
@@ -530,12 +597,16 @@ def _measure(args, mesh_arg, env, phase_timeout=None):
         barrier_sync()
         phase(f"timed steps ({mesh_arg})", phase_timeout)
         t0 = time.perf_counter()
-        run(args.steps)
+        out = run(args.steps)
         th = time.perf_counter()  # host side done enqueuing (diagnostic: host- vs device-bound)
         barrier_sync()
         t1 = time.perf_counter()
         phase(f"report ({mesh_arg})", phase_timeout)
         _p2p_check(env, f"timed steps ({mesh_arg})")
+        if env.get("dump"):
+            # what the last timed step returned to its caller: the new train state, or the output
+            _dump_outputs(env["dump"], {"state": state} if args.mode == "train" else {"output": out})
+        del out
     elapsed = t1 - t0
     if clock_probe and int(os.environ.get("RANK", "0")) == 0:
         from learning_jax_sharding_amd.ops import hip as _hip

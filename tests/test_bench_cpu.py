@@ -13,8 +13,7 @@ TINY = ["--batch-per-gpu", "2", "--seq", "32", "--dim", "64", "--heads", "2", "-
 
 @pytest.mark.parametrize("model", ["attention", "layer", "ff", "fsdp"])
 def test_bench_json_contract(model):
-    env = dict(os.environ, LJS_NUM_DEVICES="1")
-    env.pop("LJS_PLATFORM", None)
+    env = dict(os.environ, LJS_NUM_DEVICES="1", LJS_PLATFORM="cpu")   # host devices, also where a GPU is present
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", model, *TINY],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -40,8 +39,8 @@ def test_bench_spawns_ranks(gpus, mesh, par):
     env = dict(os.environ, LJS_PLATFORM="cpu")
     env.pop("LJS_NUM_DEVICES", None)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--mesh", mesh, *TINY],
-                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--mesh", mesh, "--full",
+                        *TINY], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -87,7 +86,7 @@ def test_bench_secondary_2d_two_ranks(gpus):
     env = dict(os.environ, LJS_PLATFORM="cpu")
     env.pop("LJS_NUM_DEVICES", None)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), *TINY],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--full", *TINY],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -96,6 +95,93 @@ def test_bench_secondary_2d_two_ranks(gpus):
     assert rec["config"]["parallelism"] == "dp2" and rec["config"]["mesh"] == [2, 1]
     assert rec["secondary"]["mesh"] == [1, 2] and rec["secondary"]["parallelism"] == "dp1xtp2"
     assert "error" not in rec["secondary"]
+
+
+def test_bench_plain_run_has_no_secondary_or_probe():
+    """Without --full a 2-rank run measures the headline layout only: no secondary 2-D layout and
+    no timed all-reduce probe; which paths carried the step's own collectives is still reported."""
+    env = dict(os.environ, LJS_PLATFORM="cpu")
+    env.pop("LJS_NUM_DEVICES", None)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *TINY],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["config"]["parallelism"] == "dp2" and rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert "secondary" not in rec and "all_reduce_probe" not in rec["comm_detail"]
+    assert rec["comm_detail"]["routes"] and rec["comm_detail"]["grad_buckets"]
+
+
+def _dump_run(tmp_path, tag, *extra):
+    import numpy as np
+    env = dict(os.environ, LJS_NUM_DEVICES="1", LJS_PLATFORM="cpu")   # host devices, also where a GPU is present
+    d = tmp_path / tag
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(d), *extra, *TINY],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    return rec, {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_bench_dump_outputs_train_state(tmp_path):
+    """--dump-outputs writes the train state the last timed step returned (parameters, both Adam
+    moments, the step count) as float32 / float64 .npy files, and two runs with the same arguments
+    start from the same inputs: on host devices they write the same values."""
+    import numpy as np
+    rec, a = _dump_run(tmp_path, "a")
+    _, b = _dump_run(tmp_path, "b")
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert sorted(a) == sorted(b) and a
+    kernels = [k for k in a if ".kernel" in k]
+    # Wq, Wk, Wv, Wo as parameters and as each of the two Adam moments
+    assert len(kernels) == 12, sorted(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), (k, a[k].dtype)
+        assert np.isfinite(a[k]).all(), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    shapes = sorted(a[k].shape for k in kernels)
+    assert shapes == sorted([(64, 64)] * 12), shapes
+    # the state after warmup + timed steps: the step count is written too, and the moments moved
+    counts = [v.item() for v in a.values() if v.size == 1]
+    assert counts and all(c == rec["warmup"] + rec["steps"] for c in counts), (counts, rec["warmup"])
+    assert any(np.abs(a[k]).max() > 0 for k in kernels if "mu" in k or "nu" in k)
+
+
+def test_bench_dump_outputs_forward(tmp_path):
+    rec, a = _dump_run(tmp_path, "f", "--mode", "fwd")
+    assert list(a) == ["output"] and a["output"].shape == (2, 32, 64) and a["output"].dtype.name == "float32"
+    assert rec["config"]["mode"] == "fwd"
+
+
+def test_dump_outputs_samples_large_outputs(tmp_path, monkeypatch):
+    """Beyond the size limit every array is cut to the same fraction of its elements, at positions
+    that are the same in every run."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("ljs_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4000)
+    g = torch.Generator().manual_seed(0)
+    tree = {"w": torch.randn(40, 50, generator=g), "v": torch.randn(2000, generator=g, dtype=torch.float64),
+            "n": torch.tensor(7)}
+    b._dump_outputs(str(tmp_path / "x"), tree)
+    b._dump_outputs(str(tmp_path / "y"), tree)
+    x = {f: np.load(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")}
+    y = {f: np.load(tmp_path / "y" / f) for f in os.listdir(tmp_path / "y")}
+    assert sorted(x) == ["n.npy", "v.npy", "w.npy"]
+    assert sum(v.nbytes for v in x.values()) <= 4000
+    assert x["w.npy"].dtype == np.float32 and x["v.npy"].dtype == np.float64 and x["n.npy"].dtype == np.float64
+    assert x["n.npy"].item() == 7.0
+    # 2000 f32 + 2000 f64 = 24000 bytes share what the scalar's 8 bytes leave: a sixth of each array
+    assert x["w.npy"].size == x["v.npy"].size == 2000 * (4000 - 8) // 24000
+    assert np.isin(x["w.npy"], tree["w"].numpy()).all()
+    for f in x:
+        np.testing.assert_array_equal(x[f], y[f])
 
 
 def test_watchdog_on_fail_hook_reports_and_sets_exit():
@@ -137,8 +223,7 @@ def test_watchdog_on_fail_none_keeps_nonzero_exit():
 
 
 def test_bench_min_warmup_counts_every_untimed_step():
-    env = dict(os.environ, LJS_NUM_DEVICES="1")
-    env.pop("LJS_PLATFORM", None)
+    env = dict(os.environ, LJS_NUM_DEVICES="1", LJS_PLATFORM="cpu")   # host devices, also where a GPU is present
     args = [a if a != "0" else "6" for a in TINY]  # --min-warmup 6
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)

@@ -86,6 +86,22 @@ def test_mse_loss_bench_line():
     assert rec["config"]["loss"].startswith("mean") and rec["ms_per_step"] > 0
 
 
+def test_dump_outputs_is_the_captured_steps_train_state(tmp_path):
+    """--dump-outputs on the GPU path (G-step HIP graphs, donated state): the files hold the train
+    state after every untimed and timed step, in float32 / float64, within the size limit."""
+    import numpy as np
+    rec = _bench({}, "--steps", "16", "--warmup", "2", "--batch-per-gpu", "8", "--dump-outputs", str(tmp_path / "o"))
+    a = {f[:-4]: np.load(tmp_path / "o" / f) for f in os.listdir(tmp_path / "o")}
+    assert rec["steps"] == 16 and rec["config"]["hip_graph"] and rec["config"]["steps_per_graph"] == 8
+    kernels = {k: v for k, v in a.items() if ".kernel" in k}
+    assert len(kernels) == 12 and sorted({v.shape for v in kernels.values()}) == [(512, 640), (640, 512)], sorted(a)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    counts = [v.item() for v in a.values() if v.size == 1]
+    assert counts and all(c == rec["warmup"] + 16 for c in counts), (counts, rec["warmup"])
+    assert all(np.abs(v).max() > 0 for v in kernels.values())
+
+
 def test_launcher_and_rank_agree_on_gpu_count():
     """The launcher's sysfs GPU count (no HIP init) matches what a rank's torch sees."""
     import importlib.util
