@@ -2003,7 +2003,8 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
 
 // Kernel-variant switches.  The defaults are the measured winners (profiles/PERF_NOTES.md); the
 // setters (ops/hip.py set_attention_*) exist so the GPU tests can run every variant and check it
-// bit-exact against the default -- they are not environment knobs.
+// bit-exact against the default -- they are not environment knobs.  (ljs_attn_set_cus, the grid of
+// the fused projection + forward, is one of them: it sits with g_attn_cus below.)
 //  * split backward as ONE launch of dQ and dK/dV blocks (attn_bwd_pair_kernel), else two launches
 static int g_bwd_pair = 1;
 LJS_API void ljs_attn_set_bwd_pair(int v) { g_bwd_pair = v < 0 ? 1 : v; }
@@ -2022,6 +2023,10 @@ static bool vst_ok(const void* p, const long* st) {
   return (((uintptr_t)p) & 15) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0;
 }
 static int g_attn_cus = 0;   // CUs of the current device (the fused projection's grid)
+//  * the fused projection + forward's grid: n > 0 blocks instead of one per CU (the tests run many
+//    items per block on small shapes this way); <= 0 = the device's CU count again
+static int g_attn_cus_forced = 0;
+LJS_API void ljs_attn_set_cus(int v) { g_attn_cus_forced = v > 0 ? v : 0; }
 //  * K/V-resident forward for Sk <= 256: 8 (or 4) waves per block; 0 = the tiled kernel
 static int g_fwd_res = 8;
 LJS_API void ljs_attn_set_fwd_res(int v) { g_fwd_res = v < 0 ? 8 : v; }
@@ -2067,11 +2072,13 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, v
     const int nqb = (Sq + 16 * nw - 1) / (16 * nw);
     a.fd_nx = make_fastdiv(nqb);
     a.fd_h = make_fastdiv(H);
+    ljs_launch_rec(nw == 8 ? "attn_fwd_res<8>" : "attn_fwd_res<4>", dim3(nqb * H * B), 64 * nw, acc_mode);
     if (nw == 8) hipLaunchKernelGGL(attn_fwd_res_kernel<8>, dim3(nqb * H * B), dim3(512), 0, stream, a);
     else hipLaunchKernelGGL(attn_fwd_res_kernel<4>, dim3(nqb * H * B), dim3(256), 0, stream, a);
     return (int)hipGetLastError();
   }
   const int nqb = (Sq + BLK - 1) / BLK;
+  ljs_launch_rec("attn_fwd_tiled<1>", dim3(nqb * H * B), 256, acc_mode);
   hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3(nqb * H * B), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
@@ -2118,7 +2125,9 @@ LJS_API int ljs_qkv_attn_fwd(const void* x, long ldx, const void* w, void* qkv, 
   a.scale_log2 = scale * LOG2E;
   a.trace = (unsigned long long*)trace;
   const int items = T / QA_S * H;
-  const int grid = items < g_attn_cus ? items : g_attn_cus;   // one 8-wave block per CU, items dealt round-robin
+  const int cus = g_attn_cus_forced > 0 ? g_attn_cus_forced : g_attn_cus;
+  const int grid = items < cus ? items : cus;   // one 8-wave block per CU, items dealt round-robin
+  ljs_launch_rec("qkv_attn_fwd", dim3(grid), 512);
   hipLaunchKernelGGL(qkv_attn_fwd_kernel, dim3(grid), dim3(512), 0, stream, a);
   return (int)hipGetLastError();
 }
@@ -2160,6 +2169,9 @@ LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void
     // neutral (0.2194 vs 0.2196 ms), so the register copy stays there
     const bool kv_dma = g_bwd_kv_dma == 1 || (g_bwd_kv_dma == 2 && Sq <= 2 * BLK);
     const bool sw1 = f.vst == 1 && Sq % BLK == 0 && Sk == FK && !causal;
+    ljs_launch_rec(kv_dma ? (sw1 ? "attn_bwd_fused<dma=1,sw=1>" : "attn_bwd_fused<dma=1,sw=0>")
+                          : (sw1 ? "attn_bwd_fused<dma=0,sw=1>" : "attn_bwd_fused<dma=0,sw=0>"),
+                   dim3(H, B), FT);
     if (kv_dma && sw1) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, 1>), dim3(H, B), dim3(FT), 0, stream, f);
     else if (kv_dma) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, 0>), dim3(H, B), dim3(FT), 0, stream, f);
     else if (sw1) hipLaunchKernelGGL((attn_bwd_fused_kernel<false, 1>), dim3(H, B), dim3(FT), 0, stream, f);
@@ -2178,16 +2190,21 @@ LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void
     const long nk128 = (Sk + 127) / 128;
     c.flags32 = g_dq32;
     const long nqb = c.flags32 ? (Sq + 127) / 128 : nq;
+    ljs_launch_rec(c.flags32 ? "attn_bwd_pair32<dq32=1>" : "attn_bwd_pair32<dq32=0>",
+                   dim3((unsigned)((nqb + nk128) * H * B)), 256);
     hipLaunchKernelGGL(attn_bwd_pair32_kernel, dim3((unsigned)((nqb + nk128) * H * B)), dim3(256), 0, stream, c, b);
     return (int)hipGetLastError();
   }
   if (g_bwd_pair && (nq + nk) * H * B < (1L << 30)) {
     // one launch: dQ blocks and dK/dV blocks (which form delta themselves) side by side
+    ljs_launch_rec("attn_bwd_pair", dim3((unsigned)((nq + nk) * H * B)), 256);
     hipLaunchKernelGGL(attn_bwd_pair_kernel, dim3((unsigned)((nq + nk) * H * B)), dim3(256), 0, stream, c, b);
     return (int)hipGetLastError();
   }
   // dQ first: it also computes delta, which the dK/dV kernel consumes (stream order)
+  ljs_launch_rec("attn_bwd_dq", dim3(nq * H * B), 256);
   hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(nq * H * B), dim3(256), 0, stream, c);
+  ljs_launch_rec("attn_bwd_dkv", dim3(nk * H * B), 256);
   hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(nk * H * B), dim3(256), 0, stream, b);
   return (int)hipGetLastError();
 }

@@ -3,8 +3,45 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include <mutex>
 
 #define LJS_API extern "C" __attribute__((visibility("default")))
+
+// ---- host-side launch record (gemm.hip, attention.hip; read back through ljs_launch_count /
+// ljs_launch_get, ops/hip.py last_launch / launch_log).  Every launch site stores which kernel
+// instance it launched, on what grid, and what the launcher resolved the request to, so a test can
+// tell the kernel it asked for from the kernel that ran.  Plain host stores into a ring of the last
+// 32 launches; nothing is formatted until a record is read.  The ring is one per process, under a
+// lock, not one per thread: autograd runs a backward on its own engine thread, and the thread that
+// asked for the step has to see those launches too.
+struct LjsLaunchRec {
+  const char* name;          // kernel instance (static storage)
+  unsigned gx, gy, gz, block;
+  int req_tile, res_tile;    // GEMMs: the tile code asked for / the one the launcher resolved; else -1
+  int splitk, splitk1;       // GEMMs: the launched split count (grouped pair: of each GEMM); else -1
+  int variant;               // LDS-DMA / lean GEMMs: the epilogue instance (RES); else -1
+  int acc_mode;              // attention forward: AttnArgs::acc_mode; else -1
+};
+constexpr int kLjsLaunchRing = 32;
+inline LjsLaunchRec g_ljs_launch_ring[kLjsLaunchRing];
+inline long g_ljs_launch_count = 0;
+inline std::mutex g_ljs_launch_mu;
+inline LjsLaunchRec ljs_launch_make(const char* name, dim3 grid, unsigned block) {
+  LjsLaunchRec r;
+  r.name = name;
+  r.gx = grid.x; r.gy = grid.y; r.gz = grid.z; r.block = block;
+  r.req_tile = r.res_tile = r.splitk = r.splitk1 = r.variant = r.acc_mode = -1;
+  return r;
+}
+inline void ljs_launch_push(const LjsLaunchRec& r) {
+  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
+  g_ljs_launch_ring[g_ljs_launch_count++ % kLjsLaunchRing] = r;
+}
+inline void ljs_launch_rec(const char* name, dim3 grid, unsigned block, int acc_mode = -1) {
+  LjsLaunchRec r = ljs_launch_make(name, grid, block);
+  r.acc_mode = acc_mode;
+  ljs_launch_push(r);
+}
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;

@@ -15,6 +15,7 @@
 // the other LDS buffer after; one barrier per K-tile), XOR-swizzled LDS images so both
 // the row reads and the transposed reads are bank-conflict free, XCD-aware tile order.
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1287,6 +1288,48 @@ LJS_LEAN_INST(64, 64, 2, 2, 4)
 int g_cus = 0;
 unsigned long long* g_gemm_trace = nullptr;  // LJS_GEMM_TRACE builds: the next LDS-DMA launches' stamps
 
+// Launch record (common.h): the tile code ljs_gemm_bf16 was asked for and the one it resolved it
+// to, for the launch sites below (a grouped GEMM carries its own in its GroupRec).
+thread_local int g_req_tile = -1, g_res_tile = -1;
+
+// instance names, formatted once per instantiation: "gemm_dma<128,128,2,2,4,kc,kc,bf16>"
+struct LaunchName { char s[64]; };
+template <int BM, int BN, int WM, int WN, int NST, bool AK, bool BKc, bool OF, bool GROUP2>
+const char* dma_name() {
+  static const LaunchName n = [] {
+    LaunchName x;
+    snprintf(x.s, sizeof x.s, "%s<%d,%d,%d,%d,%d,%s,%s,%s>", GROUP2 ? "gemm_dma_group2" : "gemm_dma", BM, BN, WM, WN,
+             NST, AK ? "kc" : "mn", BKc ? "kc" : "mn", OF ? "f32" : "bf16");
+    return x;
+  }();
+  return n.s;
+}
+template <int BM, int BN, int WM, int WN, int NST>
+const char* lean_name() {
+  static const LaunchName n = [] {
+    LaunchName x;
+    snprintf(x.s, sizeof x.s, "gemm_lean<%d,%d,%d,%d,%d>", BM, BN, WM, WN, NST);
+    return x;
+  }();
+  return n.s;
+}
+template <int BM, int BN, bool AK, bool BKc, bool OF>
+const char* reg_name() {
+  static const LaunchName n = [] {
+    LaunchName x;
+    snprintf(x.s, sizeof x.s, "gemm_bf16<%d,%d,%s,%s,%s>", BM, BN, AK ? "kc" : "mn", BKc ? "kc" : "mn",
+             OF ? "f32" : "bf16");
+    return x;
+  }();
+  return n.s;
+}
+inline void gemm_rec(const char* name, dim3 grid, unsigned block, int splitk, int variant, int splitk1 = -1) {
+  LjsLaunchRec r = ljs_launch_make(name, grid, block);
+  r.req_tile = g_req_tile; r.res_tile = g_res_tile;
+  r.splitk = splitk; r.splitk1 = splitk1; r.variant = variant;
+  ljs_launch_push(r);
+}
+
 template <int BM, int BN, int WM, int WN, int NST, bool AK, bool BKc, bool OF, int RES = 0>
 hipError_t launch_dma(const GemmArgs& a, hipStream_t s, int blocks_per_cu) {
   if (!g_cus) {
@@ -1312,6 +1355,7 @@ hipError_t launch_dma(const GemmArgs& a, hipStream_t s, int blocks_per_cu) {
   if (bpc == 0 && items > g_cus * kNatural && items % (g_cus * kNatural) == 0) bpc = kNatural;
   int grid = bpc > 0 ? g_cus * bpc : items;
   if (grid > items) grid = items;
+  gemm_rec(dma_name<BM, BN, WM, WN, NST, AK, BKc, OF, false>(), dim3(grid), WM * WN * 64, a.splitk, RES);
   hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, NST, AK, BKc, OF, RES>), dim3(grid), dim3(WM * WN * 64), 0,
                      s, a2);
   return hipGetLastError();
@@ -1339,6 +1383,7 @@ hipError_t launch_dma_kk(const GemmArgs& a, hipStream_t s) {
 // one by one.  Same kernel body per item: bit-identical to separate launches.
 struct GroupRec {
   GemmArgs a;
+  int req_tile, res_tile;   // for the launch record, as ljs_gemm_bf16 saw them
   int kind;   // 1: 128x128 2x2 waves 2 stages, 2: 128x128 2x4 4 stages, 3: 128x128 2x4 3 stages
 };
 // (per host thread: another thread's GEMMs are never recorded into this thread's open group)
@@ -1368,6 +1413,8 @@ hipError_t launch_slab(const GemmArgs& a, hipStream_t s) {
     if (kind && g_group_on && g_group_n < 2) {
       g_group[g_group_n].a = a;
       g_group[g_group_n].kind = kind;
+      g_group[g_group_n].req_tile = g_req_tile;
+      g_group[g_group_n].res_tile = g_res_tile;
       ++g_group_n;
       return hipSuccess;
     }
@@ -1378,9 +1425,13 @@ hipError_t launch_slab(const GemmArgs& a, hipStream_t s) {
 
 template <int WN, int NST>
 hipError_t launch_group_kind(const GroupRec* r, int n, hipStream_t s) {
+  g_req_tile = r[0].req_tile;
+  g_res_tile = r[0].res_tile;
   if (n == 2) {
     int i0 = 0, i1 = 0;
     const GemmArgs a0 = group_prep<128, 128>(r[0].a, &i0), a1 = group_prep<128, 128>(r[1].a, &i1);
+    gemm_rec(dma_name<128, 128, 2, WN, NST, false, false, true, true>(), dim3(i0 + i1), 2 * WN * 64, a0.splitk, 3,
+             a1.splitk);
     hipLaunchKernelGGL((gemm_dma_group2_kernel<128, 128, 2, WN, NST, false, false, true, 3>), dim3(i0 + i1),
                        dim3(2 * WN * 64), 0, s, a0, a1, i0);
     return hipGetLastError();
@@ -1411,6 +1462,7 @@ hipError_t launch_lean(const GemmArgs& a, hipStream_t s) {
   constexpr int kNatural = (WM * WN == 4 && kLdsBytes <= 80 * 1024) ? 2 : 1;
   int grid = items;
   if (items > g_cus * kNatural && items % (g_cus * kNatural) == 0) grid = g_cus * kNatural;
+  gemm_rec(lean_name<BM, BN, WM, WN, NST>(), dim3(grid), WM * WN * 64, a.splitk, RES);
   hipLaunchKernelGGL((gemm_lean_kernel<BM, BN, WM, WN, NST, RES>), dim3(grid), dim3(WM * WN * 64), 0, s, a2);
   return hipGetLastError();
 }
@@ -1430,6 +1482,7 @@ template <int BM, int BN, bool AK, bool BKc, bool OF>
 hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
   int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
   dim3 grid(ntm * ntn, a.batch * a.splitk);
+  gemm_rec(reg_name<BM, BN, AK, BKc, OF>(), grid, 256, a.splitk, -1);
   hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, AK, BKc, OF>), grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
@@ -1519,6 +1572,7 @@ LJS_API int ljs_gemm_bf16(const void* A, const void* B, void* C, const void* bia
   }
   if (psum_count) *psum_count = 0;
   // A/B: tile code + 100000 forces the lean K-loop kernel where it applies, + 200000 the general one
+  g_req_tile = tile;
   const bool gen_req = tile >= 200000;
   if (gen_req) tile -= 200000;
   const bool lean_req = tile >= 100000;
@@ -1575,6 +1629,7 @@ LJS_API int ljs_gemm_bf16(const void* A, const void* B, void* C, const void* bia
   }
   if (tile == 1602 && !(a_kc && b_kc && !out_f32 && a.splitk == 1)) tile = 1282;
   if ((tile == 12883 || tile == 12884) && !((!a_kc && !b_kc && out_f32) || (a_kc && b_kc))) tile = 1282;
+  g_res_tile = tile;
   // fused output sum (psum): LDS-DMA kernels with bf16 output only; one float per (item, wave)
   if (psum && !out_f32 && tile > 1000) {
     const int bm = (tile == 2561 || tile == 2562) ? 256 : 128;
@@ -1662,6 +1717,27 @@ LJS_API int ljs_gemm_bf16(const void* A, const void* B, void* C, const void* bia
   return (int)e;
 }
 
+// ============================================================================ launch record
+// The process's launches through gemm.hip / attention.hip so far, and record i of them (0 = the
+// first; only the last 32 are kept) as one line of "key=value" text in buf.  Returns the line's
+// length, or -1 when record i is no longer (or not yet) there or buf is too small.
+LJS_API long ljs_launch_count() {
+  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
+  return g_ljs_launch_count;
+}
+
+LJS_API int ljs_launch_get(long i, char* buf, int cap) {
+  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
+  if (i < 0 || i >= g_ljs_launch_count || i < g_ljs_launch_count - kLjsLaunchRing || !buf || cap <= 0) return -1;
+  const LjsLaunchRec r = g_ljs_launch_ring[i % kLjsLaunchRing];
+  const int n = snprintf(buf, (size_t)cap,
+                         "name=%s grid=%u,%u,%u block=%u requested_tile=%d resolved_tile=%d splitk=%d splitk1=%d "
+                         "variant=%d acc_mode=%d",
+                         r.name, r.gx, r.gy, r.gz, r.block, r.req_tile, r.res_tile, r.splitk, r.splitk1, r.variant,
+                         r.acc_mode);
+  return n < cap ? n : -1;
+}
+
 // ============================================================================ f32 GEMM
 // Exact-f32 GEMM on the f32-input MFMA (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain, no
 // reduced-precision path).  Arbitrary element strides, so any transpose is free; operands are
@@ -1707,6 +1783,7 @@ LJS_API int ljs_gemm_f32(const void* A, const void* B, void* C, int M, int N, in
   p.sA = sA; p.sB = sB; p.sC = sC;
   p.M = M; p.N = N; p.K = K;
   dim3 grid((M + 31) / 32, (N + 31) / 32, batch);
+  ljs_launch_rec("gemm_f32", grid, 256);
   hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, stream, p);
   return (int)hipGetLastError();
 }

@@ -8,6 +8,7 @@ escape hatch that routes to the torch reference implementations instead).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -79,6 +80,9 @@ _SIGS = {
     "ljs_rng_fill": [c_void_p, c_int, c_int, _LP, _LP, _LP, c_uint, c_uint, c_int, c_float, c_float, c_float,
                      c_float, c_void_p],
     "ljs_dropout": [c_void_p, c_void_p, c_int, c_int, _LP, _LP, _LP, c_uint, c_uint, c_float, c_void_p],
+    "ljs_launch_count": [],
+    "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
+    "ljs_attn_set_cus": [c_int],
 }
 
 
@@ -97,8 +101,76 @@ def lib():
                     fn.argtypes = argt
                     fn.restype = c_int
                 L.ljs_mse_colsum_ws_bytes.restype = c_long
+                L.ljs_launch_count.restype = c_long
                 _LIB = L
     return _LIB
+
+
+def _launch_at(i: int) -> Optional[dict]:
+    buf = ctypes.create_string_buffer(256)
+    if lib().ljs_launch_get(i, buf, len(buf)) < 0:
+        return None
+    rec = {}
+    for item in buf.value.decode().split(" "):
+        k, v = item.split("=", 1)
+        if k == "name":
+            rec[k] = v
+        elif k == "grid":
+            rec[k] = tuple(int(t) for t in v.split(","))
+        else:
+            rec[k] = None if int(v) < 0 else int(v)   # -1: the field does not apply to this kernel
+    rec["blocks"] = rec["grid"][0] * rec["grid"][1] * rec["grid"][2]
+    return rec
+
+
+def last_launch() -> dict:
+    """The host-side record of the last GEMM / attention kernel the library launched:
+
+    ``name`` (the kernel instance, e.g. ``gemm_lean<256,192,4,2,2>``, ``gemm_dma<128,128,2,2,4,kc,kc,bf16>``,
+    ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``),
+    ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 GEMMs
+    ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
+    it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
+    and ``variant`` (the LDS-DMA / lean kernels' epilogue instance); for the attention forward
+    ``acc_mode``.  Fields that do not apply are None.
+
+    The record is made where the launch is issued, so under graph capture it is made when the
+    launch is *recorded* into the graph, not when the graph is replayed.  Launches of every host
+    thread (autograd's backward thread included) go into one ring of the last 32."""
+    n = lib().ljs_launch_count()
+    rec = _launch_at(n - 1) if n > 0 else None
+    if rec is None:
+        raise RuntimeError("no kernel launch recorded yet")
+    return rec
+
+
+class LaunchLog(list):
+    """The records :func:`launch_log` collected; ``total`` counts the launches made inside it (only
+    the last 32 of them are kept)."""
+    total = 0
+
+
+@contextlib.contextmanager
+def launch_log():
+    """Context manager yielding a list that, on exit, holds the records (see :func:`last_launch`) of
+    the launches made inside it, oldest first.  Like the record itself it sees launches as they are
+    issued: a graph replay adds nothing, the capture that recorded the graph does."""
+    log = LaunchLog()
+    start = lib().ljs_launch_count()
+    try:
+        yield log
+    finally:
+        end = lib().ljs_launch_count()
+        log.total = end - start
+        log.extend(r for r in (_launch_at(i) for i in range(max(start, end - 32), end)) if r is not None)
+
+
+def set_attention_cus(n: Optional[int]):
+    """Grid of the fused Q/K/V projection + attention forward: ``n`` blocks instead of one per CU
+    (tests: many items per block on small shapes); None or <= 0 = the device's CU count."""
+    fn = lib().ljs_attn_set_cus
+    fn.restype = None
+    fn(0 if n is None else int(n))
 
 
 def set_attention_fwd_resident(waves: int):

@@ -94,3 +94,27 @@ def test_held_weight_gradient_jobs_pair_and_flush(chip, monkeypatch):
     linear.flush_held_dw()
     assert ran == [("o2",) + tuple(hip.pick_dw_slabs(512, 640, 16384)[:2])]
     assert linear._HELD == {}
+
+
+def test_gemm_layouts_matrix_runs_every_tile_code_as_itself():
+    """test_gemm_layouts (tests/test_kernels_gpu.py) names 13 tile codes; the launcher demotes a
+    code its layout / output type / shape does not allow.  By the launcher's rules (resolved_tile,
+    tests/test_kernel_variants_gpu.py) every code must stay itself for at least one case of that
+    matrix, or the matrix never runs that kernel."""
+    import itertools
+    import test_kernels_gpu as tk
+    from test_kernel_variants_gpu import resolved_tile
+    params = {m.args[0]: m.args[1] for m in tk.test_gemm_layouts.pytestmark if m.name == "parametrize"}
+    tiles, layouts, outs, shapes = params["tile"], params["a_kc,b_kc"], params["out_f32"], params["M,N,K"]
+    assert len(tiles) == 13 and len(set(tiles)) == 13
+    as_itself = {t: [] for t in tiles}
+    for t, (a_kc, b_kc), of, (M, N, K) in itertools.product(tiles, layouts, outs, shapes):
+        if resolved_tile(t, a_kc, b_kc, of, M, N, K) == t:
+            as_itself[t].append((a_kc, b_kc, of, M, N, K))
+    assert all(as_itself.values()), [t for t, v in as_itself.items() if not v]
+    # and the forcing codes resolve to the plain one
+    assert resolved_tile(101602, 1, 1, 0, 128, 160, 64) == 1602 == resolved_tile(201602, 1, 1, 0, 128, 160, 64)
+    # spot checks of single rules: K no multiple of 64, a layout a tile does not have, f32 output
+    assert resolved_tile(1282, 1, 1, 0, 136, 72, 40) == 128 and resolved_tile(644, 1, 1, 0, 136, 72, 40) == 64
+    assert resolved_tile(2561, 1, 0, 0, 256, 192, 320) == 1284 and resolved_tile(2562, 1, 1, 1, 256, 192, 320) == 1282
+    assert resolved_tile(2563, 1, 1, 1, 256, 192, 320) == 1282 and resolved_tile(12884, 1, 0, 0, 256, 192, 320) == 1282

@@ -44,9 +44,14 @@ def test_gemm_layouts(hip, a_kc, b_kc, out_f32, tile, M, N, K):
     Bs, ldb = _stored(B.t(), b_kc)           # KC: [N][K]; MN: [K][N]
     C = torch.full((M, N), float("nan"), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dev)
     hip.gemm(As, Bs, C, M, N, K, lda, ldb, N, bool(a_kc), bool(b_kc), tile=tile)
+    rec = hip.last_launch()
     torch.cuda.synchronize()
     tol = 2e-2 if not out_f32 else 1e-3
     torch.testing.assert_close(C.float(), ref, rtol=tol, atol=tol * math.sqrt(K))
+    # the kernel this case covered: the launcher's demotion of the requested tile, stated in Python
+    from test_kernel_variants_gpu import resolved_tile
+    assert rec["requested_tile"] == tile
+    assert rec["resolved_tile"] == resolved_tile(tile, a_kc, b_kc, out_f32, M, N, K), rec
 
 
 @pytest.mark.parametrize("tile", [1284, 1282, 2561, 12883, 12884])
@@ -163,9 +168,10 @@ def attn_fwd_nsub(request, hip):
     hip.set_attention_fwd_resident(-1)
 
 
-@pytest.mark.parametrize("B,S,H", [(2, 256, 8), (1, 200, 4), (3, 64, 2), (1, 40, 3), (1, 320, 2)])
+@pytest.mark.parametrize("B,S,H", [(2, 256, 8), (1, 200, 4), (3, 64, 2), (1, 40, 3), (1, 320, 2), (4, 200, 64)])
 @pytest.mark.parametrize("causal", [False, True])
 def test_attention_fwd_bwd(hip, attn_bwd_impl, attn_fwd_nsub, B, S, H, causal):
+    """(The last shape is the one that keeps the 8-wave resident forward: 512 blocks of 128 queries.)"""
     D = 64
     # q/k/v as column slices of one fused QKV buffer, exactly as the model produces them
     qkv = _rand(B, S, 3 * H * D, seed=7).reshape(B, S, 3, H, D)
@@ -174,7 +180,16 @@ def test_attention_fwd_bwd(hip, attn_bwd_impl, attn_fwd_nsub, B, S, H, causal):
     qr, kr, vr = (t.detach().float().requires_grad_() for t in (q, k, v))
     ref = _attn_ref(qr, kr, vr, scale, causal).float()
     out = hip.attention(q, k, v, scale, causal)
+    fwd = hip.last_launch()["name"]
     torch.testing.assert_close(out.float(), ref, rtol=2e-2, atol=2e-2)
+    # the forward kernel that ran (attention.hip attn_fwd_impl): tiled when asked for or above 256
+    # keys, else resident with 8 waves only when asked for AND >= 256 blocks of 128 queries, else 4
+    _, res = attn_fwd_nsub
+    if res == 0 or S > 256:
+        assert fwd == "attn_fwd_tiled<1>", fwd
+    else:
+        waves = 8 if res == 8 and -(-S // 128) * H * B >= 256 else 4
+        assert fwd == f"attn_fwd_res<{waves}>", fwd
     # backward vs autograd of the f32 reference
     q1, k1, v1 = (t.detach().clone().requires_grad_() for t in (q, k, v))
     out1 = hip.attention(q1, k1, v1, scale, causal)
@@ -1390,8 +1405,9 @@ def test_qkv_attn_fwd_bit_exact(hip, B, H, K):
     the same Q/K/V bits as the batched projection GEMM (same per-element MFMA sequence) and O / lse
     equal to the resident forward's over those views up to f32 rounding of the softmax state (a
     handful of rows differ by one bf16 ulp: the two kernels' instruction selection for the running
-    sum differs), and as close to an fp32 reference; item counts below and above the CU count
-    exercise the block's item loop."""
+    sum differs), and as close to an fp32 reference.  These item counts (16, 6, 20) are all below the
+    CU count, so every block takes ONE item here; the block's item loop and its cross-item prefetch
+    run in test_kernel_variants_gpu.py (test_qkv_attn_fwd_above_cu_count / _forced_grid)."""
     T, N = B * 256, 64 * H
     x = _rand(T, K, seed=31)
     wt = (_rand(3, N, K, seed=32) * 0.05).contiguous()
