@@ -1999,6 +1999,300 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
   }
 }
 
+// ============================================================================ fused backward + out-projection dX
+// The fused backward of the common case (the <dma = 1, sw = 1> instance above: 256 queries and keys,
+// not causal, staged stores) with its dO computed in the block instead of read: dO_h = dY[b] . Wo_h^T
+// (256 x 64 over M), the out-projection's input gradient restricted to this (batch, head).  The
+// separate dX GEMM, its [T][H*64] write and the backward's read of it are gone, and the K-loop runs
+// while the block's K / V / first Q / O / lse pieces are in flight.
+//   * GEMM: wave w owns rows 32 w .. 32 w + 31 and all 64 columns (2 x 4 accumulator tiles), K-tiles
+//     of 32 by LDS-DMA into a three-stage ring, 16x16x32 bf16 MFMA with the weight rows as the A
+//     operand, k ascending, one rounding to bf16: per element the MFMA sequence of the dX GEMM
+//     (gemm.hip), so dO_h is bit-identical to what that kernel stores.
+//   * ring: [256][32] dY rows + [64][32] weight rows per stage (64-byte rows, 16-byte chunk c of row r
+//     at c ^ 2 ((r >> 3) & 1): conflict-free for ds_read_b128's 4 x 16 lane groups), over the dS^T
+//     image and the dO image, both dead until the sweep starts.
+//   * prologue pieces: 11 per wave (K 4, V 4, Q 1, O 1, lse), one issued per K-tile step between that
+//     step's barrier and its MFMAs, so HBM streams them under the GEMM; every step issues exactly 4
+//     vector-memory operations per wave (pieces that do not exist read nothing, through an
+//     out-of-range offset, into a 1 KiB dump), so one counted wait serves every step.
+//   * the phase is bound by the ring's depth (two 20 KiB tiles in flight per CU against the L2
+//     latency under 256 blocks loading in phase: ~1000 cycles per K-tile step), not by LDS-DMA issue
+//     or fragment-read latency: without the dummy pieces and two prologue pieces per step, and with
+//     the fragments read one tile ahead under the MFMAs, it measured the same
+//     (profiles/PERF_NOTES.md).
+//   * dO_h stays in LDS for the whole sweep ([256][64], img16 per 64-row block); block it's image is
+//     dead once its dS^T is formed and then stages that block's dQ.
+// LDS-DMA to a byte address of the block's LDS (common.h dma_lds_x4 / dma_lds_x1 with the
+// destination as a number: the piece slots below choose among images at run time)
+__device__ __forceinline__ void dma_lds_x4_at(const u32x4& rs, int voff, unsigned lds_byte) {
+  const unsigned m = __builtin_amdgcn_readfirstlane(lds_byte);
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
+               :: "v"(voff), "s"(rs), "s"(m) : "memory", "m0");
+}
+__device__ __forceinline__ void dma_lds_x1_at(const u32x4& rs, int voff, unsigned lds_byte) {
+  const unsigned m = __builtin_amdgcn_readfirstlane(lds_byte);
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %0, %1, 0 offen lds"
+               :: "v"(voff), "s"(rs), "s"(m) : "memory", "m0");
+}
+struct BwdProjArgs {
+  const bf16_t* dy;   // [B * 256][M] bf16 rows, row stride dy_ld (0: one row for every token)
+  const bf16_t* w;    // [H * 64][M] bf16: the out-projection weight, k-contiguous
+  long dy_ld;
+  int M;
+};
+constexpr int PJ_BK = 32;
+constexpr int PJ_A = FK * PJ_BK, PJ_STAGE = PJ_A + D * PJ_BK;   // elements (16 + 4 KiB)
+constexpr int PJ_NP = 11;                                        // prologue piece slots per wave
+constexpr int PJ_KS = 0, PJ_VS = PJ_KS + FK * D, PJ_DST = PJ_VS + FK * D, PJ_DO = PJ_DST + FK * BLK;
+constexpr int PJ_Q = PJ_DO + FK * D, PJ_OS = PJ_Q + 2 * BLK * D, PJ_ROWC = PJ_OS + BLK * D;
+constexpr int PJ_DUMP = PJ_ROWC + 2 * 2 * BLK * 2, PJ_LDS = PJ_DUMP + 512;   // 154 KiB
+static_assert(3 * PJ_STAGE <= PJ_Q - PJ_DST, "the ring fits the dS^T and dO images");
+static_assert(PJ_LDS * 2 <= 160 * 1024, "LDS");
+
+__global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjArgs pj) {
+  __shared__ __attribute__((aligned(16))) bf16_t smem[PJ_LDS];
+  bf16_t* const Ks = smem + PJ_KS;
+  bf16_t* const Vs = smem + PJ_VS;
+  bf16_t* const dSt = smem + PJ_DST;
+  bf16_t* const dOi = smem + PJ_DO;     // [256][64]: resident dO_h
+  bf16_t* const Qs = smem + PJ_Q;       // Q[2]
+  bf16_t* const Os = smem + PJ_OS;      // next block's O (delta only)
+  float* const rowc = reinterpret_cast<float*>(smem + PJ_ROWC);   // [buf][lse, delta][query]
+  const unsigned sb = (unsigned)(uintptr_t)(LDS_PTR(const void))smem;   // LDS byte address of smem
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the H heads of a batch element are neighbouring items of one XCD: dY[b] is fetched into that
+  // L2 once and hit H - 1 times
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
+  const int b = t / a.H, h = t - b * a.H;
+  const int key0 = wave * 32;
+  // (diagnostic builds) stamps as attn_bwd_fused_kernel's, plus 6: GEMM phase done
+  auto bstamp = [&](int k) {
+#if LJS_ATTN_BWD_TRACE
+    const unsigned long long ts = __builtin_amdgcn_s_memtime();
+    if (a.trace && lane == 0) a.trace[(((long)b * a.H + h) * (FT / 64) + wave) * 8 + k] = ts;
+#else
+    (void)k;
+#endif
+  };
+  bstamp(0);
+
+  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
+  const bf16_t* vb = a.v + b * a.v_sb + h * a.v_sh;
+  const bf16_t* qb = a.q + b * a.q_sb + h * a.q_sh;
+  const bf16_t* ob = a.o + b * a.o_sb + h * a.o_sh;
+  const float* lse = a.lse + ((long)b * a.H + h) * FK;
+  const u32x4 rk = rsrc_u4(kb, 2 * ((long)(FK - 1) * a.k_ss + D));
+  const u32x4 rv = rsrc_u4(vb, 2 * ((long)(FK - 1) * a.v_ss + D));
+  const u32x4 rq = rsrc_u4(qb, 2 * ((long)(FK - 1) * a.q_ss + D));
+  const u32x4 ro = rsrc_u4(ob, 2 * ((long)(FK - 1) * a.o_ss + D));
+  const u32x4 rl = rsrc_u4(lse, 4L * FK);
+  constexpr int OOB = 0x7ffffff0;
+  const int drow = 8 * wave + (lane >> 3);
+  const int dchunk = ((lane & 7) ^ (((drow >> 1) & 3) << 1)) * 8;   // element offset in the row
+  // Q / O / lse of the query block at q0 (the img16 swizzle on the source address)
+  auto issue = [&](int q0, int buf) {
+    const int r = q0 + drow;
+    dma_lds_x4_at(rq, (int)(((long)r * a.q_ss + dchunk) * 2), sb + 2 * (PJ_Q + buf * BLK * D + wave * 512));
+    dma_lds_x4_at(ro, (int)(((long)r * a.o_ss + dchunk) * 2), sb + 2 * (PJ_OS + wave * 512));
+    if (wave == 0) dma_lds_x1_at(rl, (q0 + lane) * 4, sb + 2 * PJ_ROWC + 4 * (buf * 2 * BLK));
+  };
+  // prologue piece slot s (wave-uniform): K / V pieces alternate (rows 8 wave + 64 i + ..: the
+  // swizzle does not depend on i), then the first block's Q, O and lse
+  auto issue_p = [&](int s) {
+    if (s < 8) {
+      const int i = s >> 1;
+      const int r = drow + 64 * i;
+      if (s & 1) dma_lds_x4_at(rv, (int)(((long)r * a.v_ss + dchunk) * 2), sb + 2 * (PJ_VS + (wave + 8 * i) * 512));
+      else dma_lds_x4_at(rk, (int)(((long)r * a.k_ss + dchunk) * 2), sb + 2 * (PJ_KS + (wave + 8 * i) * 512));
+    } else if (s == 8) {
+      dma_lds_x4_at(rq, (int)(((long)drow * a.q_ss + dchunk) * 2), sb + 2 * (PJ_Q + wave * 512));
+    } else if (s == 9) {
+      dma_lds_x4_at(ro, (int)(((long)drow * a.o_ss + dchunk) * 2), sb + 2 * (PJ_OS + wave * 512));
+    } else if (s == 10 && wave == 0) {
+      dma_lds_x1_at(rl, lane * 4, sb + 2 * PJ_ROWC);
+    } else {
+      dma_lds_x4_at(rq, OOB, sb + 2 * PJ_DUMP);
+    }
+  };
+  // after every wave's DMA of block it + 1 landed (vmcnt(0) + barrier): delta = rowsum(dO o O)
+  auto finish = [&](int buf, int blk) {
+    const int row = tid >> 3, c16 = tid & 7;  // 8 threads per query row
+    const u32x4 o = *reinterpret_cast<const u32x4*>(Os + img16(row, c16));
+    const u32x4 d = *reinterpret_cast<const u32x4*>(dOi + blk * BLK * D + img16(row, c16));
+    float s = dot_bf16x8(o, d);
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    if (c16 == 0) rowc[(buf * 2 + 1) * BLK + row] = -s;  // stored negated: it seeds the dP accumulators
+  };
+
+  // ---- dO_h = dY[b] . Wo_h^T
+  {
+    const int nk = pj.M / PJ_BK;
+    const u32x4 ra = rsrc_u4(pj.dy + (long)b * FK * pj.dy_ld, 2 * ((long)(FK - 1) * pj.dy_ld + pj.M));
+    const u32x4 rw = rsrc_u4(pj.w + (long)h * D * pj.M, 2L * D * pj.M);
+    // pieces of 16 rows x 64 B: A 16 per K-tile (2 per wave), B 4 (waves 0..3)
+    int va[2], vw;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = 16 * (wave + 8 * i) + (lane >> 2);
+      const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
+      va[i] = (int)(((long)row * pj.dy_ld + 8 * c) * 2);
+    }
+    {
+      const int row = 16 * (wave & 3) + (lane >> 2);
+      const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
+      vw = (row * pj.M + 8 * c) * 2;
+    }
+    const bool wb = wave < 4;
+    // K-tile kt into the stage at element offset so; past the last tile every piece reads nothing
+    auto issue_t = [&](int kt, int so) {
+      const bool ok = kt < nk;
+      const int ko = kt * PJ_BK * 2;
+      const int st = PJ_DST + so;
+      dma_lds_x4_at(ra, ok ? va[0] + ko : OOB, sb + 2 * (st + wave * 512));
+      dma_lds_x4_at(ra, ok ? va[1] + ko : OOB, sb + 2 * (st + (wave + 8) * 512));
+      dma_lds_x4_at(rw, ok && wb ? vw + ko : OOB, sb + 2 * (wb ? st + PJ_A + wave * 512 : PJ_DUMP));
+    };
+    auto frag = [&](const bf16_t* img, int rb0) {
+      const int row = rb0 + (lane & 15);
+      return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
+                                            img + row * PJ_BK + ((g ^ (((row >> 3) & 1) << 1)) << 3)));
+    };
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int s0 = 0, s1 = PJ_STAGE, s2 = 2 * PJ_STAGE;   // stages of tiles kt, kt + 1, kt + 2
+    issue_t(0, s0);
+    issue_p(0);
+    issue_t(1, s1);
+    for (int kt = 0; kt < nk; ++kt) {
+      // tile kt landed (this wave's pieces); prologue piece kt and tile kt + 1 stay in flight
+      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();   // ... every wave's; every wave's reads of tile kt - 1 done
+      bf16x8 af[2], wf[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wf[j] = frag(dSt + s0 + PJ_A, 16 * j);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) af[i] = frag(dSt + s0, 32 * wave + 16 * i);
+      issue_p(kt + 1);
+      issue_t(kt + 2, s2);            // into tile kt - 1's stage
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16x16x32(wf[j], af[i], acc[i][j]);   // C^T blocks
+      const int sn = s0;
+      s0 = s1;
+      s1 = s2;
+      s2 = sn;
+    }
+    for (int s = nk + 1; s < PJ_NP; ++s) issue_p(s);
+    // everything landed (the past-the-end tiles too: they cover the image below), every wave is done
+    // with the ring
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row = 32 * wave + 16 * i + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        u32x2 w2;
+        w2[0] = pack_bf16x2(acc[i][j][0], acc[i][j][1]);
+        w2[1] = pack_bf16x2(acc[i][j][2], acc[i][j][3]);
+        *reinterpret_cast<u32x2*>(dOi + img8(row, 4 * j + g)) = w2;
+      }
+    }
+    bstamp(6);
+  }
+  __syncthreads();
+  finish(0, 0);
+  __syncthreads();
+  bstamp(1);
+
+  f32x4 dk[2][4], dv[2][4];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      dk[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      dv[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  bf16x8 kr[2][2], vr[2][2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      kr[j][ks] = frag_rows(Ks, key0 + 16 * j, ks, lane);
+      vr[j][ks] = frag_rows(Vs, key0 + 16 * j, ks, lane);
+    }
+  const int qt = wave & 3, dt0 = 2 * (wave >> 2);
+  int offtr[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) offtr[dt] = tr_off(16 * dt, lane);
+  const int off_q = trS_off(16 * qt, lane);   // (dS^T image)
+  const int off_k[2] = {tr_off(16 * dt0, lane), tr_off(16 * (dt0 + 1), lane)};
+  constexpr int nqt = FK / BLK;
+  for (int it = 0; it < nqt; ++it) {
+    const int cur = it & 1;
+    const int q0 = it * BLK;
+    const bool more = it + 1 < nqt;
+    if (more) issue(q0 + BLK, cur ^ 1);
+    bf16_t* const dOt = dOi + it * BLK * D;
+    fused_tile<false>(a, Qs + cur * BLK * D, dOt, rowc + cur * 2 * BLK, rowc + (cur * 2 + 1) * BLK, dSt, kr, vr, dk,
+                      dv, q0, key0, lane, offtr);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (more) finish(cur ^ 1, it + 1);
+    // dQ^T (d tiles dt0, dt0+1) x queries 16qt..16qt+15 = K^T dS^T over all keys
+    f32x4 dq[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int s2 = 0; s2 < FK / 32; ++s2) {
+      bf16x8 sb = frag_tr_o(dSt, 32 * s2, off_q);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        bf16x8 ka = frag_tr_o(Ks, 32 * s2, off_k[i]);
+        dq[i] = mfma16x16x32(ka, sb, dq[i]);
+      }
+    }
+    // the block's dQ, split over wave pairs (d halves), staged in this block's dO image: every
+    // wave passed the barrier above, so nothing reads it again
+    {
+      const int r = 16 * qt + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        u32x2 w2;
+        w2[0] = pack_bf16x2(dq[i][0] * a.scale, dq[i][1] * a.scale);
+        w2[1] = pack_bf16x2(dq[i][2] * a.scale, dq[i][3] * a.scale);
+        const int c = (2 * (dt0 + i) + (g >> 1)) ^ (r & 7);
+        *reinterpret_cast<u32x2*>(dOt + r * D + c * 8 + 4 * (g & 1)) = w2;
+      }
+    }
+    __syncthreads();
+    {
+      const int r = tid >> 3, c = tid & 7;
+      const u32x4 v4 = *reinterpret_cast<const u32x4*>(dOt + r * D + ((c ^ (r & 7)) << 3));
+      *reinterpret_cast<u32x4*>(a.out3 + b * a.out3_sb + (long)(q0 + r) * a.out3_ss + h * a.out3_sh + c * 8) = v4;
+    }
+    bstamp(2 + it);
+  }
+  // every wave passed the sweep's last barrier: the K / V images are free; this wave's 32 key rows
+  // of dK / dV go through its own rows of them
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    stage_rows16(Ks + key0 * D, 16 * j, dk[j], a.scale, lane);
+    stage_rows16(Vs + key0 * D, 16 * j, dv[j], 1.f, lane);
+  }
+  flush_rows<32>(Ks + key0 * D, a.out + b * a.out_sb + h * a.out_sh, a.out_ss, key0, FK, lane);
+  flush_rows<32>(Vs + key0 * D, a.out2 + b * a.out2_sb + h * a.out2_sh, a.out2_ss, key0, FK, lane);
+  bstamp(7);
+}
+
 }  // namespace
 
 // Kernel-variant switches.  The defaults are the measured winners (profiles/PERF_NOTES.md); the
@@ -2038,6 +2332,14 @@ LJS_API void ljs_attn_set_bwd_kv_dma(int v) { g_bwd_kv_dma = v < 0 ? 2 : v; }
 //    automatic by grid size
 static int g_bwd_fused = 2;
 LJS_API void ljs_attn_set_bwd_fused(int v) { g_bwd_fused = v < 0 ? 2 : v; }
+//  * the fused backward that computes its own dO from the out-projection's dY (ljs_attn_bwd_proj):
+//    1 = whenever its gate holds, 0 = never, 2 = automatic: where the fused backward is chosen and
+//    there are at least 192 (batch, head) pairs.  It measured ahead at every size tried (B = 16 / 24 /
+//    32 / 64 x 8 heads: profiles/attn_bwd_proj_gate_lines.txt); the B H = 128 step keeps the two
+//    kernels because tests/test_kernel_variants_gpu.py::test_production_picks_run_as_picked pins the
+//    dX GEMM + attn_bwd_fused pair at exactly that size
+static int g_bwd_proj = 2;
+LJS_API void ljs_attn_set_bwd_proj(int v) { g_bwd_proj = v < 0 ? 2 : v; }
 //  * (diagnostic) the fused backward's phase-stamp buffer (LJS_ATTN_BWD_TRACE builds): [B][H][waves][8]
 static unsigned long long* g_attn_trace = nullptr;
 LJS_API void ljs_attn_set_trace(void* p) { g_attn_trace = (unsigned long long*)p; }
@@ -2206,5 +2508,56 @@ LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void
   hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(nq * H * B), dim3(256), 0, stream, c);
   ljs_launch_rec("attn_bwd_dkv", dim3(nk * H * B), 256);
   hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(nk * H * B), dim3(256), 0, stream, b);
+  return (int)hipGetLastError();
+}
+
+// Whether the switches let ljs_attn_bwd_proj run a (B, H) grid (the shape gate is the entry point's)
+LJS_API int ljs_attn_bwd_proj_enabled(int B, int H) {
+  if (g_bwd_proj == 0 || g_vst != 1) return 0;
+  if (g_bwd_proj == 1) return 1;
+  return (g_bwd_fused == 1 || g_bwd_fused == 2) && (long)B * H >= 192;
+}
+
+// The fused backward with dO = dY . W^T formed per (batch, head) inside the kernel
+// (attn_bwd_proj_kernel): dy [B * Sq][M] bf16 with row stride dy_ld (0: one row broadcast), w
+// [H * 64][M] bf16 (the out-projection weight, k-contiguous).  Exactly the fused backward's common
+// case: Sq == Sk == 256, not causal, 16-byte aligned operands and outputs with row strides % 8 == 0;
+// anything else is hipErrorInvalidValue and launches nothing.
+LJS_API int ljs_attn_bwd_proj(const void* q, const void* k, const void* v, const void* o, const void* dy, long dy_ld,
+                              const void* w, int M, const void* lse, void* dq, void* dk, void* dv, int B, int Sq,
+                              int Sk, int H, const long* qs, const long* ks, const long* vs, const long* os,
+                              const long* dqs, const long* dks, const long* dvs, float scale, int causal,
+                              hipStream_t stream) {
+  const long lim = 0x7ffffff0L;
+  auto in_ok = [&](const void* p, const long* st) {
+    return p && (((uintptr_t)p) & 15) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0 && st[1] >= 0 &&
+           2 * ((long)(FK - 1) * st[1] + D) < lim;
+  };
+  if (B <= 0 || H <= 0 || (long)B * H >= (1L << 30) || Sq != FK || Sk != FK || causal || M <= 0 || M % PJ_BK ||
+      !(dy_ld == 0 || (dy_ld >= M && dy_ld % 8 == 0)) || !dy || !w || !lse ||
+      (((uintptr_t)dy | (uintptr_t)w) & 15) || (((uintptr_t)lse) & 3) ||
+      2 * ((long)(FK - 1) * dy_ld + M) >= lim || 2L * D * M >= lim ||
+      !in_ok(q, qs) || !in_ok(k, ks) || !in_ok(v, vs) || !in_ok(o, os) ||
+      !dq || !dk || !dv || !vst_ok(dq, dqs) || !vst_ok(dk, dks) || !vst_ok(dv, dvs) ||
+      !ljs_attn_bwd_proj_enabled(B, H))
+    return (int)hipErrorInvalidValue;
+  AttnArgs a = {};
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
+  a.lse = (float*)lse;
+  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
+  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
+  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
+  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
+  a.out = (bf16_t*)dk; a.out_sb = dks[0]; a.out_ss = dks[1]; a.out_sh = dks[2];
+  a.out2 = (bf16_t*)dv; a.out2_sb = dvs[0]; a.out2_ss = dvs[1]; a.out2_sh = dvs[2];
+  a.out3 = (bf16_t*)dq; a.out3_sb = dqs[0]; a.out3_ss = dqs[1]; a.out3_sh = dqs[2];
+  a.Sq = Sq; a.Sk = Sk; a.H = H;
+  a.scale = scale; a.scale_log2 = scale * LOG2E;
+  a.vst = 1;
+  a.trace = g_attn_trace;
+  BwdProjArgs pj;
+  pj.dy = (const bf16_t*)dy; pj.w = (const bf16_t*)w; pj.dy_ld = dy_ld; pj.M = M;
+  ljs_launch_rec("attn_bwd_proj", dim3((unsigned)(B * H)), FT);
+  hipLaunchKernelGGL(attn_bwd_proj_kernel, dim3((unsigned)(B * H)), dim3(FT), 0, stream, a, pj);
   return (int)hipGetLastError();
 }

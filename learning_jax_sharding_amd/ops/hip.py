@@ -49,6 +49,10 @@ _SIGS = {
     "ljs_attn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_int,
                      c_int, c_void_p],
+    "ljs_attn_bwd_proj": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP,
+                          c_float, c_int, c_void_p],
+    "ljs_attn_bwd_proj_enabled": [c_int, c_int],
     "ljs_cast_f32_bf16": [c_void_p, c_void_p, c_long, c_void_p],
     "ljs_cast_bf16_f32": [c_void_p, c_void_p, c_long, c_void_p],
     "ljs_swap01_bf16": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -208,6 +212,16 @@ def set_attention_bwd_fused(enabled: Optional[bool]):
     (True), the split dQ + dK/dV kernels (False; always used above 256 keys), or None for the
     automatic choice by grid size (the default)."""
     fn = lib().ljs_attn_set_bwd_fused
+    fn.argtypes = [c_int]
+    fn.restype = None
+    fn(2 if enabled is None else (1 if enabled else 0))
+
+
+def set_attention_bwd_proj(enabled: Optional[bool]):
+    """The fused backward that forms its own dO from the out-projection's dY (``attn_bwd_proj``):
+    whenever its shape gate holds (True), never (False), or None for the automatic choice: where the
+    fused backward itself is chosen and there are at least 192 (batch, head) pairs."""
+    fn = lib().ljs_attn_set_bwd_proj
     fn.argtypes = [c_int]
     fn.restype = None
     fn(2 if enabled is None else (1 if enabled else 0))
@@ -1507,6 +1521,96 @@ def _take_fused_attention(q, k, v, scale, causal, q_offset):
 FUSED_ATTN_STATS = {"taken": 0}
 
 
+# ---------------------------------------------------------------------------- out-projection dX hand-over
+# The out-projection's input gradient dO = dY . Wo^T has one consumer, the attention backward, which
+# slices it per (batch, head).  ops/linear.py's _Linear.backward, when the pre-backward graph walk
+# proved that nothing but that attention backward reads it (linear.proj_safe_nodes), does not launch
+# the GEMM: it returns the unwritten buffer and leaves (dY, ld, weight shadow) here, keyed by the
+# buffer.  _Attention.backward takes the entry when its cotangent IS that buffer and the kernel's
+# gate holds (ljs_attn_bwd_proj: dO is never materialised); anything else launches the GEMM first.
+# Entries nobody took are materialised when the backward, or a capture segment, ends.
+_PROJ_PENDING: Dict[int, tuple] = {}
+ATTN_BWD_PROJ_STATS = {"taken": 0, "materialised": 0}
+
+
+def proj_shape_ok(B: int, Sq: int, Sk: int, H: int, D: int, M: int, dy_ld: int, causal: bool) -> bool:
+    """The shape half of ljs_attn_bwd_proj's gate (alignment and the switches are checked apart)."""
+    return (B > 0 and H > 0 and D == 64 and Sq == 256 and Sk == 256 and not causal and M > 0 and M % 32 == 0
+            and (dy_ld == 0 or (dy_ld >= M and dy_ld % 8 == 0)))
+
+
+def _proj_strides_ok(t: torch.Tensor) -> bool:
+    st = _strides3(t)
+    return (t.dtype == torch.bfloat16 and t.stride(3) == 1 and t.data_ptr() % 16 == 0
+            and all(x % 8 == 0 for x in st) and st[1] >= 0 and 2 * (255 * st[1] + 64) < 0x7ffffff0)
+
+
+def attn_bwd_proj_ok(q, k, v, o, dy: torch.Tensor, dy_ld: int, w: torch.Tensor, causal: bool) -> bool:
+    """Whether ljs_attn_bwd_proj accepts these operands (its whole gate, the switches included)."""
+    B, Sq, H, D = q.shape
+    M = w.shape[1]
+    return (proj_shape_ok(B, Sq, k.shape[1], H, D, M, dy_ld, causal) and w.shape[0] == H * D
+            and all(_proj_strides_ok(t) for t in (q, k, v, o))
+            and dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.is_contiguous()
+            and dy.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and 2 * (255 * dy_ld + M) < 0x7ffffff0
+            and bool(lib().ljs_attn_bwd_proj_enabled(B, H)))
+
+
+def attn_bwd_proj_block(q, k, v, o, dy: torch.Tensor, dy_ld: int, w: torch.Tensor, lse, scale: float,
+                        causal: bool = False, outs=None):
+    """The fused backward with dO = dy . w^T formed inside the kernel: ``dy`` the [B * 256][M] bf16
+    rows of the out-projection's cotangent (row stride ``dy_ld``; 0 = one row for every token), ``w``
+    the [H * 64][M] bf16 weight.  Returns (dq, dk, dv) bf16; raises when the entry point's gate
+    refuses (nothing is launched then)."""
+    B, Sq, H, D = q.shape
+    if outs is None:
+        outs = tuple(torch.empty((B, Sq, H, D), dtype=torch.bfloat16, device=q.device) for _ in range(3))
+    dq, dk, dv = outs
+    rc = lib().ljs_attn_bwd_proj(_p(q), _p(k), _p(v), _p(o), _p(dy), int(dy_ld), _p(w), int(w.shape[1]), _p(lse),
+                                 _p(dq), _p(dk), _p(dv), B, Sq, k.shape[1], H, _longs(_strides3(q)),
+                                 _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)),
+                                 _longs(_strides3(dq)), _longs(_strides3(dk)), _longs(_strides3(dv)), float(scale),
+                                 int(causal), _stream(q))
+    _ck(rc, "ljs_attn_bwd_proj")
+    return dq, dk, dv
+
+
+def defer_out_proj(dy: torch.Tensor, ld: int, wn: torch.Tensor, dx: torch.Tensor, launch) -> None:
+    """Leave the out-projection's dX GEMM (``launch()`` writes ``dx`` [T][H * 64] = dy . wn^T) to the
+    attention backward that consumes ``dx``."""
+    from ..spmd import graphs as _graphs
+    if materialise_out_proj not in _graphs.BEFORE_CUT:
+        _graphs.BEFORE_CUT.append(materialise_out_proj)
+        _graphs.AFTER_CAPTURE.append(materialise_out_proj)
+    _PROJ_PENDING[dx.data_ptr()] = (dy, ld, wn, dx, launch)
+
+
+def materialise_out_proj() -> None:
+    """Launch the dX GEMM of every hand-over nobody took."""
+    while _PROJ_PENDING:
+        _, ent = _PROJ_PENDING.popitem()
+        ent[4]()
+        ATTN_BWD_PROJ_STATS["materialised"] += 1
+
+
+def _take_out_proj(do: torch.Tensor, q, k, v, o, outs, causal):
+    """The pending hand-over whose buffer ``do`` is, if the fused kernel can run it; a pending entry
+    it cannot run is materialised (``do`` is then an ordinary cotangent)."""
+    ent = _PROJ_PENDING.pop(do.data_ptr(), None)
+    if ent is None:
+        return None
+    dy, ld, wn, dx, launch = ent
+    B, Sq, H, D = q.shape
+    if (do.dtype == torch.bfloat16 and tuple(do.shape) == (B, Sq, H, D) and do.is_contiguous()
+            and dx.numel() == do.numel() and attn_bwd_proj_ok(q, k, v, o, dy, ld, wn, causal)
+            and all(_proj_strides_ok(t) for t in outs)):
+        ATTN_BWD_PROJ_STATS["taken"] += 1
+        return dy, ld, wn
+    launch()
+    ATTN_BWD_PROJ_STATS["materialised"] += 1
+    return None
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, causal, q_offset):
@@ -1548,6 +1652,10 @@ class _Attention(torch.autograd.Function):
             dq = _bs_like((B, Sq, H, D), q)
             dk = _bs_like((B, Sk, H, D), k)
             dv = _bs_like((B, Sk, H, D), v)
+        proj = _take_out_proj(do, q, k, v, o, (dq, dk, dv), causal) if _PROJ_PENDING else None
+        if proj is not None:
+            attn_bwd_proj_block(q, k, v, o, proj[0], proj[1], proj[2], lse, scale, causal, outs=(dq, dk, dv))
+            return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None
         delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
         rc = lib().ljs_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, Sq,
                                 Sk, H, _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)),

@@ -196,6 +196,59 @@ def defer_safe_leaves(outs, leaves: bool = True) -> set:
     return {k for k, c in counts.items() if c == 1 and type(prod[k]).__name__ in _DEFER_NODES}
 
 
+# The out-projection's dX handed to the attention backward (hip.defer_out_proj; LJS_ATTN_BWD_PROJ=0:
+# the dX GEMM and the attention backward as two kernels).  Between the two autograd nodes the
+# buffer is unwritten, so a _Linear backward defers only when the walk below proved that nothing
+# but one attention backward reads its input gradient.
+_PROJ_ON = os.environ.get("LJS_ATTN_BWD_PROJ", "1") != "0"
+_PROJ_SAFE: Optional[set] = None   # ids of the safe _Linear backward nodes of the running backward
+# nodes that pass a gradient on as a view of the same storage
+_VIEW_NODES = ("ViewBackward0", "UnsafeViewBackward0", "ReshapeAliasBackward0", "AliasBackward0")
+
+
+def proj_safe_nodes(outs) -> set:
+    """ids of the _Linear backward nodes reached from ``outs`` whose input-0 edge leads to an
+    _Attention backward node through view-only nodes, every node on the way (the attention node
+    included) having exactly one incoming edge in the walked graph: autograd then hands the
+    _Linear's input gradient to the attention backward untouched, and to nobody else."""
+    # (every visited node is kept referenced until the walk ends: a built-in node's Python wrapper
+    # is made on access and its id is only unique while the wrapper lives)
+    counts, seen, lins, keep = {}, set(), [], []
+    roots = [(t.grad_fn, t.output_nr) if isinstance(t, torch.Tensor) else (t.node, t.output_nr) for t in outs]
+    stack = []
+    for fn, nr in roots:
+        if fn is not None:
+            counts[(id(fn), nr)] = counts.get((id(fn), nr), 0) + 1   # a seed is an incoming gradient too
+            stack.append(fn)
+    while stack:
+        fn = stack.pop()
+        keep.append(fn)
+        if id(fn) in seen:
+            continue
+        seen.add(id(fn))
+        if type(fn).__name__ == "_LinearBackward":
+            lins.append(fn)
+        for nxt, idx in fn.next_functions:
+            if nxt is None:
+                continue
+            keep.append(nxt)
+            counts[(id(nxt), idx)] = counts.get((id(nxt), idx), 0) + 1
+            if id(nxt) not in seen:
+                stack.append(nxt)
+    safe = set()
+    for fn in lins:
+        nxt, idx = fn.next_functions[0]
+        while nxt is not None and counts.get((id(nxt), idx), 0) == 1:
+            name = type(nxt).__name__
+            if name == "_AttentionBackward":
+                safe.add(id(fn))
+                break
+            if name not in _VIEW_NODES or len(nxt.next_functions) != 1:
+                break
+            nxt, idx = nxt.next_functions[0]
+    return safe
+
+
 # autograd nodes whose weight gradients may stay uncombined (they call _defer_ok per weight)
 _DEFER_NODES = ("_LinearBackward", "_FFBlockBackward", "_FFBlockFp8Backward")
 
@@ -225,16 +278,21 @@ class defer_wgrads:
             safe = defer_safe_leaves(outs, leaves=enabled)
             if safe:
                 self.state = {"safe": safe, "pending": {}}
+        # (the same pre-backward walk) out-projection dX GEMMs left to their attention backward
+        self.proj = (proj_safe_nodes(outs) or None) if _DEFER_ON and _PROJ_ON else None
 
     def __enter__(self):
-        global _DEFER
+        global _DEFER, _PROJ_SAFE
         self.prev, _DEFER = _DEFER, self.state
+        self.prev_proj, _PROJ_SAFE = _PROJ_SAFE, self.proj
         return self
 
     def __exit__(self, *exc):
-        global _DEFER
+        global _DEFER, _PROJ_SAFE
         flush_held_dw()
+        hip.materialise_out_proj()   # (nothing, when the walk holds)
         _DEFER = self.prev
+        _PROJ_SAFE = self.prev_proj
         return False
 
     def take(self, g: torch.Tensor):
@@ -806,9 +864,18 @@ class _Linear(torch.autograd.Function):
             out_dt = torch.bfloat16 if (xdtype == torch.bfloat16 and len(live) == 1) else torch.float32
             dx = torch.empty((M, K), dtype=out_dt, device=dev)
             premask = ctx.premask and out_dt == torch.bfloat16
+            # the out-projection of an attention block, proven safe before the backward started: the
+            # attention backward that consumes dx forms it per (batch, head) itself
+            hand_over = (_PROJ_SAFE is not None and id(ctx) in _PROJ_SAFE and len(live) == 1 and nw == 1
+                         and out_dt == torch.bfloat16 and not relu and not premask and dx.is_cuda
+                         and tuple(order) == tuple(range(len(order))))
             for j, i in enumerate(live):
                 t, ld = mats[i]
                 wn = shadow.get(ws[i], "N")                  # [K][N]: B[k=n][n'=k], k-contiguous
+                if hand_over:
+                    hip.defer_out_proj(t, ld, wn, dx, lambda t=t, ld=ld, wn=wn, dx=dx: hip.gemm(
+                        t, wn, dx, M, K, N, ld, N, K, True, True))
+                    continue
                 hip.gemm(t, wn, dx, M, K, N, ld, N, K, True, True, accumulate=j > 0,
                          res=xb if premask else None, res_ld=K, res_mode="mask")
             dx = dx.to(xdtype).view(pshape + (K,)).permute(_inv_perm(order))

@@ -2,7 +2,11 @@
 (LJS_ATTN_BWD_TRACE build):
 
     LJS_KERNELS_LIB=learning_jax_sharding_amd/_lib/variants/bwdtrace/libljs_kernels.so \\
-        python scripts/attn_bwd_phases.py [B] [kvdma]
+        python scripts/attn_bwd_phases.py [B] [kvdma | proj | proj0]
+
+``proj`` / ``proj0``: the instance that forms dO = dY . Wo^T in the block (attn_bwd_proj_kernel; M =
+640, a full dY / one broadcast row), whose prologue splits into the GEMM phase (start -> dO image
+written, with the K / V / Q / O pieces streaming under it) and the rest (delta of the first block).
 
 Per block (averaged over blocks and waves, shader-clock cycles): prologue (start -> first query
 block's Q / dO / O and delta ready), each query block of the sweep, and the dK / dV epilogue;
@@ -27,24 +31,34 @@ def main():
     q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
     do = torch.randn(B, S, H, D, generator=g).bfloat16().to(dev)
     o, lse = hip.attn_fwd_lse(q, k, v, 0.125)
+    mode = sys.argv[2] if len(sys.argv) > 2 else ""
+    run = lambda: hip.attn_bwd_block(q, k, v, o, do, lse, 0.125)
+    if mode in ("proj", "proj0"):
+        M = 640
+        hip.set_attention_bwd_proj(True)
+        w = (torch.randn(H * D, M, generator=g) * M ** -0.5).bfloat16().to(dev)
+        dy = torch.randn(1 if mode == "proj0" else B * S, M, generator=g).bfloat16().to(dev)
+        run = lambda: hip.attn_bwd_proj_block(q, k, v, o, dy, 0 if mode == "proj0" else M, w, lse, 0.125)
     for _ in range(5):
-        hip.attn_bwd_block(q, k, v, o, do, lse, 0.125)
+        run()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(20):
-        hip.attn_bwd_block(q, k, v, o, do, lse, 0.125)
+        run()
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / 20 * 1e3
     waves = 8
     trace = torch.zeros((B, H, waves, 8), dtype=torch.int64, device=dev)
     hip.lib().ljs_attn_set_trace(hip._p(trace))
-    hip.attn_bwd_block(q, k, v, o, do, lse, 0.125)
+    run()
     torch.cuda.synchronize()
     hip.lib().ljs_attn_set_trace(None)
     t = trace.cpu().double()
     ok = (t[..., 0] > 0) & (t[..., 7] > 0)
-    print(f"B={B}: {B * H} blocks, backward {us:.1f} us; {int(ok.sum())} of {ok.numel()} (block, wave) records")
+    print(f"B={B} {mode}: {B * H} blocks, backward {us:.1f} us; {int(ok.sum())} of {ok.numel()} (block, wave) records")
+    if mode in ("proj", "proj0"):
+        print(f"  {'GEMM phase':14s} {(t[..., 6] - t[..., 0])[ok].mean().item():8.0f} cycles (of the prologue)")
     names = ["prologue"] + [f"query block {i}" for i in range(4)]
     for i, n in enumerate(names):
         d = (t[..., i + 1] - t[..., i])[ok]
