@@ -2012,19 +2012,25 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
 //   * ring: [256][32] dY rows + [64][32] weight rows per stage (64-byte rows, 16-byte chunk c of row r
 //     at c ^ 2 ((r >> 3) & 1): conflict-free for ds_read_b128's 4 x 16 lane groups), over the dS^T
 //     image and the dO image, both dead until the sweep starts.
-//   * prologue pieces: 11 per wave (K 4, V 4, Q 1, O 1, lse), one issued per K-tile step between that
-//     step's barrier and its MFMAs, so HBM streams them under the GEMM; every step issues exactly 4
-//     vector-memory operations per wave (pieces that do not exist read nothing, through an
-//     out-of-range offset, into a 1 KiB dump), so one counted wait serves every step.
-//   * the phase is bound by the ring's depth (two 20 KiB tiles in flight per CU against the L2
-//     latency under 256 blocks loading in phase: ~1000 cycles per K-tile step), not by LDS-DMA issue
-//     or fragment-read latency: without the dummy pieces and two prologue pieces per step, and with
-//     the fragments read one tile ahead under the MFMAs, it measured the same
-//     (profiles/PERF_NOTES.md).
+//   * two load streams, split by wave so that no counted wait spans both (vmcnt retires a wave's
+//     loads in issue order): tile waves 0..3 issue every tile piece (4 dY + 1 weight piece of 1 KiB per
+//     K-tile each) and wait with vmcnt(5) before the step's barrier; piece waves 4..7 issue the
+//     prologue pieces (K 32, V 32, first Q 8, first O 8 of 1 KiB, the lse row: 20 per wave plus one)
+//     and never wait inside the loop -- the vmcnt(0) + barrier that ends the phase covers them.  All
+//     eight waves read the same fragments and run the same MFMAs.
+//   * piece pacing: two per piece wave before step 0, then one per step, whatever nk is (a short loop
+//     issues the rest after it).  With every wave issuing both streams, one piece per wave per step
+//     behind one counted wait, steps 1-11 ran 1330 / 961 cycles (full dY / broadcast row) against
+//     896 / 859 for the tile-only steps 12-18; now every step runs about 930-1030 / 775.  All pieces
+//     up front, and 4 or 2 per step, delay the tile stream more than they save
+//     (profiles/attn_bwd_proj_phases.txt, profiles/PERF_NOTES.md).
+//   * what is left (~775 cycles per 32-deep step against a 256-cycle MFMA floor) is neither the ring's
+//     depth nor load latency: with the dY fragments loaded straight to registers four tiles ahead and
+//     only the weight tile in LDS, the steps cost the same on a broadcast row and more on a full dY.
 //   * dO_h stays in LDS for the whole sweep ([256][64], img16 per 64-row block); block it's image is
 //     dead once its dS^T is formed and then stages that block's dQ.
 // LDS-DMA to a byte address of the block's LDS (common.h dma_lds_x4 / dma_lds_x1 with the
-// destination as a number: the piece slots below choose among images at run time)
+// destination as a number: the pieces below choose among images at run time)
 __device__ __forceinline__ void dma_lds_x4_at(const u32x4& rs, int voff, unsigned lds_byte) {
   const unsigned m = __builtin_amdgcn_readfirstlane(lds_byte);
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
@@ -2040,13 +2046,15 @@ struct BwdProjArgs {
   const bf16_t* w;    // [H * 64][M] bf16: the out-projection weight, k-contiguous
   long dy_ld;
   int M;
+  unsigned long long* steps;   // LJS_ATTN_BWD_TRACE builds: K-tile step stamps [B][H][waves][PJ_TS]
 };
+constexpr int PJ_TS = 32;   // step-stamp slots per (block, wave)
 constexpr int PJ_BK = 32;
 constexpr int PJ_A = FK * PJ_BK, PJ_STAGE = PJ_A + D * PJ_BK;   // elements (16 + 4 KiB)
-constexpr int PJ_NP = 11;                                        // prologue piece slots per wave
+constexpr int PJ_NPW = 21;                                       // prologue pieces per piece wave (the last: lse)
 constexpr int PJ_KS = 0, PJ_VS = PJ_KS + FK * D, PJ_DST = PJ_VS + FK * D, PJ_DO = PJ_DST + FK * BLK;
 constexpr int PJ_Q = PJ_DO + FK * D, PJ_OS = PJ_Q + 2 * BLK * D, PJ_ROWC = PJ_OS + BLK * D;
-constexpr int PJ_DUMP = PJ_ROWC + 2 * 2 * BLK * 2, PJ_LDS = PJ_DUMP + 512;   // 154 KiB
+constexpr int PJ_LDS = PJ_ROWC + 2 * 2 * BLK * 2;   // 153 KiB
 static_assert(3 * PJ_STAGE <= PJ_Q - PJ_DST, "the ring fits the dS^T and dO images");
 static_assert(PJ_LDS * 2 <= 160 * 1024, "LDS");
 
@@ -2098,24 +2106,6 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
     dma_lds_x4_at(ro, (int)(((long)r * a.o_ss + dchunk) * 2), sb + 2 * (PJ_OS + wave * 512));
     if (wave == 0) dma_lds_x1_at(rl, (q0 + lane) * 4, sb + 2 * PJ_ROWC + 4 * (buf * 2 * BLK));
   };
-  // prologue piece slot s (wave-uniform): K / V pieces alternate (rows 8 wave + 64 i + ..: the
-  // swizzle does not depend on i), then the first block's Q, O and lse
-  auto issue_p = [&](int s) {
-    if (s < 8) {
-      const int i = s >> 1;
-      const int r = drow + 64 * i;
-      if (s & 1) dma_lds_x4_at(rv, (int)(((long)r * a.v_ss + dchunk) * 2), sb + 2 * (PJ_VS + (wave + 8 * i) * 512));
-      else dma_lds_x4_at(rk, (int)(((long)r * a.k_ss + dchunk) * 2), sb + 2 * (PJ_KS + (wave + 8 * i) * 512));
-    } else if (s == 8) {
-      dma_lds_x4_at(rq, (int)(((long)drow * a.q_ss + dchunk) * 2), sb + 2 * (PJ_Q + wave * 512));
-    } else if (s == 9) {
-      dma_lds_x4_at(ro, (int)(((long)drow * a.o_ss + dchunk) * 2), sb + 2 * (PJ_OS + wave * 512));
-    } else if (s == 10 && wave == 0) {
-      dma_lds_x1_at(rl, lane * 4, sb + 2 * PJ_ROWC);
-    } else {
-      dma_lds_x4_at(rq, OOB, sb + 2 * PJ_DUMP);
-    }
-  };
   // after every wave's DMA of block it + 1 landed (vmcnt(0) + barrier): delta = rowsum(dO o O)
   auto finish = [&](int buf, int blk) {
     const int row = tid >> 3, c16 = tid & 7;  // 8 threads per query row
@@ -2133,28 +2123,14 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
     const int nk = pj.M / PJ_BK;
     const u32x4 ra = rsrc_u4(pj.dy + (long)b * FK * pj.dy_ld, 2 * ((long)(FK - 1) * pj.dy_ld + pj.M));
     const u32x4 rw = rsrc_u4(pj.w + (long)h * D * pj.M, 2L * D * pj.M);
-    // pieces of 16 rows x 64 B: A 16 per K-tile (2 per wave), B 4 (waves 0..3)
-    int va[2], vw;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = 16 * (wave + 8 * i) + (lane >> 2);
-      const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
-      va[i] = (int)(((long)row * pj.dy_ld + 8 * c) * 2);
-    }
-    {
-      const int row = 16 * (wave & 3) + (lane >> 2);
-      const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
-      vw = (row * pj.M + 8 * c) * 2;
-    }
-    const bool wb = wave < 4;
-    // K-tile kt into the stage at element offset so; past the last tile every piece reads nothing
-    auto issue_t = [&](int kt, int so) {
-      const bool ok = kt < nk;
-      const int ko = kt * PJ_BK * 2;
-      const int st = PJ_DST + so;
-      dma_lds_x4_at(ra, ok ? va[0] + ko : OOB, sb + 2 * (st + wave * 512));
-      dma_lds_x4_at(ra, ok ? va[1] + ko : OOB, sb + 2 * (st + (wave + 8) * 512));
-      dma_lds_x4_at(rw, ok && wb ? vw + ko : OOB, sb + 2 * (wb ? st + PJ_A + wave * 512 : PJ_DUMP));
+    // (diagnostic builds) the top of K-tile step k, after its barrier; slot nk: the phase's last barrier
+    auto sstamp = [&](int k) {
+#if LJS_ATTN_BWD_TRACE
+      const unsigned long long ts = __builtin_amdgcn_s_memtime();
+      if (pj.steps && lane == 0 && k < PJ_TS) pj.steps[(((long)b * a.H + h) * (FT / 64) + wave) * PJ_TS + k] = ts;
+#else
+      (void)k;
+#endif
     };
     auto frag = [&](const bf16_t* img, int rb0) {
       const int row = rb0 + (lane & 15);
@@ -2166,22 +2142,76 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // tile waves 0..3 issue every tile piece (16 rows x 64 B: dY pieces wave + 4 i, weight piece wave)
+    // and do the counted wait; piece waves 4..7 issue every prologue piece and never wait in the loop
+    const bool tw = wave < 4;
+    const int pw = wave & 3;
+    int va[4], vw;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 16 * (pw + 4 * i) + (lane >> 2);
+      const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
+      va[i] = (int)(((long)row * pj.dy_ld + 8 * c) * 2);
+    }
+    {
+      const int row = 16 * pw + (lane >> 2);
+      const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
+      vw = (row * pj.M + 8 * c) * 2;
+    }
+    // K-tile kt into the stage at element offset so; past the last tile every piece reads nothing
+    auto issue_t = [&](int kt, int so) {
+      const bool ok = kt < nk;
+      const int ko = kt * PJ_BK * 2;
+      const int st = PJ_DST + so;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) dma_lds_x4_at(ra, ok ? va[i] + ko : OOB, sb + 2 * (st + (pw + 4 * i) * 512));
+      dma_lds_x4_at(rw, ok ? vw + ko : OOB, sb + 2 * (st + PJ_A + pw * 512));
+    };
+    // prologue piece j of this piece wave (wave-uniform): K / V pieces pw + 4 i alternate (rows 8 p +
+    // ..: the img16 swizzle on the source address depends on the lane alone), then the first block's Q
+    // and O pieces pw, pw + 4, then (pw 0) the lse row
+    const int prow = lane >> 3;
+    const int pchunk = ((lane & 7) ^ (((prow >> 1) & 3) << 1)) * 8;   // element offset in the row
+    auto issue_piece = [&](int j) {
+      if (j < 16) {
+        const int p = pw + 4 * (j >> 1);
+        const int r = 8 * p + prow;
+        if (j & 1) dma_lds_x4_at(rv, (int)(((long)r * a.v_ss + pchunk) * 2), sb + 2 * (PJ_VS + p * 512));
+        else dma_lds_x4_at(rk, (int)(((long)r * a.k_ss + pchunk) * 2), sb + 2 * (PJ_KS + p * 512));
+      } else if (j < 18) {
+        const int p = pw + 4 * (j - 16);
+        dma_lds_x4_at(rq, (int)(((long)(8 * p + prow) * a.q_ss + pchunk) * 2), sb + 2 * (PJ_Q + p * 512));
+      } else if (j < 20) {
+        const int p = pw + 4 * (j - 18);
+        dma_lds_x4_at(ro, (int)(((long)(8 * p + prow) * a.o_ss + pchunk) * 2), sb + 2 * (PJ_OS + p * 512));
+      } else if (pw == 0) {
+        dma_lds_x1_at(rl, lane * 4, sb + 2 * PJ_ROWC);
+      }
+    };
     int s0 = 0, s1 = PJ_STAGE, s2 = 2 * PJ_STAGE;   // stages of tiles kt, kt + 1, kt + 2
-    issue_t(0, s0);
-    issue_p(0);
-    issue_t(1, s1);
+    int pi = 0;                                     // a piece wave's next piece
+    if (tw) {
+      issue_t(0, s0);
+      issue_t(1, s1);
+    } else {
+      // two pieces while the first tile is on its way, then one per step: the pacing is the same for
+      // every nk, and what a short loop leaves is issued after it
+      issue_piece(pi++);
+      issue_piece(pi++);
+    }
     for (int kt = 0; kt < nk; ++kt) {
-      // tile kt landed (this wave's pieces); prologue piece kt and tile kt + 1 stay in flight
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      // tile kt landed (a tile wave's pieces); tile kt + 1 stays in flight
+      if (tw) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();   // ... every wave's; every wave's reads of tile kt - 1 done
+      __builtin_amdgcn_s_barrier();   // ... every tile wave's; every wave's reads of tile kt - 1 done
+      sstamp(kt);
       bf16x8 af[2], wf[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) wf[j] = frag(dSt + s0 + PJ_A, 16 * j);
 #pragma unroll
       for (int i = 0; i < 2; ++i) af[i] = frag(dSt + s0, 32 * wave + 16 * i);
-      issue_p(kt + 1);
-      issue_t(kt + 2, s2);            // into tile kt - 1's stage
+      if (tw) issue_t(kt + 2, s2);            // into tile kt - 1's stage
+      else if (pi < PJ_NPW) issue_piece(pi++);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -2191,12 +2221,14 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
       s1 = s2;
       s2 = sn;
     }
-    for (int s = nk + 1; s < PJ_NP; ++s) issue_p(s);
+    if (!tw)
+      for (; pi < PJ_NPW; ++pi) issue_piece(pi);
     // everything landed (the past-the-end tiles too: they cover the image below), every wave is done
     // with the ring
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    sstamp(nk);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = 32 * wave + 16 * i + (lane & 15);
@@ -2343,6 +2375,9 @@ LJS_API void ljs_attn_set_bwd_proj(int v) { g_bwd_proj = v < 0 ? 2 : v; }
 //  * (diagnostic) the fused backward's phase-stamp buffer (LJS_ATTN_BWD_TRACE builds): [B][H][waves][8]
 static unsigned long long* g_attn_trace = nullptr;
 LJS_API void ljs_attn_set_trace(void* p) { g_attn_trace = (unsigned long long*)p; }
+//  * (diagnostic) attn_bwd_proj_kernel's K-tile step stamps (same builds): [B][H][waves][32]
+static unsigned long long* g_attn_trace_steps = nullptr;
+LJS_API void ljs_attn_set_trace_steps(void* p) { g_attn_trace_steps = (unsigned long long*)p; }
 
 // strides are in elements, ordered (batch, seq, head); head_dim must be 64 and contiguous.
 static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
@@ -2557,6 +2592,7 @@ LJS_API int ljs_attn_bwd_proj(const void* q, const void* k, const void* v, const
   a.trace = g_attn_trace;
   BwdProjArgs pj;
   pj.dy = (const bf16_t*)dy; pj.w = (const bf16_t*)w; pj.dy_ld = dy_ld; pj.M = M;
+  pj.steps = g_attn_trace_steps;
   ljs_launch_rec("attn_bwd_proj", dim3((unsigned)(B * H)), FT);
   hipLaunchKernelGGL(attn_bwd_proj_kernel, dim3((unsigned)(B * H)), dim3(FT), 0, stream, a, pj);
   return (int)hipGetLastError();

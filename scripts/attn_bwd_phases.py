@@ -7,6 +7,9 @@
 ``proj`` / ``proj0``: the instance that forms dO = dY . Wo^T in the block (attn_bwd_proj_kernel; M =
 640, a full dY / one broadcast row), whose prologue splits into the GEMM phase (start -> dO image
 written, with the K / V / Q / O pieces streaming under it) and the rest (delta of the first block).
+Its K-tile steps are stamped too (top of each step, after the barrier): the mean step time over steps
+1-11 and over steps 12-19 (of the 20 at M = 640), and the phase's tail (last step's top -> everything
+landed).
 
 Per block (averaged over blocks and waves, shader-clock cycles): prologue (start -> first query
 block's Q / dO / O and delta ready), each query block of the sweep, and the dK / dV epilogue;
@@ -50,15 +53,26 @@ def main():
     us = e0.elapsed_time(e1) / 20 * 1e3
     waves = 8
     trace = torch.zeros((B, H, waves, 8), dtype=torch.int64, device=dev)
+    steps = torch.zeros((B, H, waves, 32), dtype=torch.int64, device=dev)
     hip.lib().ljs_attn_set_trace(hip._p(trace))
+    hip.lib().ljs_attn_set_trace_steps(hip._p(steps))
     run()
     torch.cuda.synchronize()
     hip.lib().ljs_attn_set_trace(None)
+    hip.lib().ljs_attn_set_trace_steps(None)
     t = trace.cpu().double()
     ok = (t[..., 0] > 0) & (t[..., 7] > 0)
     print(f"B={B} {mode}: {B * H} blocks, backward {us:.1f} us; {int(ok.sum())} of {ok.numel()} (block, wave) records")
     if mode in ("proj", "proj0"):
         print(f"  {'GEMM phase':14s} {(t[..., 6] - t[..., 0])[ok].mean().item():8.0f} cycles (of the prologue)")
+        # step k = stamp k -> stamp k + 1; stamp nk is the phase's last barrier (everything landed)
+        nk = M // 32
+        st = steps.cpu().double()
+        d = (st[..., 1:nk + 1] - st[..., :nk])[ok]           # [records][step]
+        print(f"  {'K-tile steps':14s} first stamp {(st[..., 0] - t[..., 0])[ok].mean().item():6.0f} cycles after the start; "
+              f"step 0 {d[:, 0].mean().item():6.0f}; steps 1-11 {d[:, 1:12].mean().item():6.0f} / step; "
+              f"steps 12-{nk - 2} {d[:, 12:nk - 1].mean().item():6.0f} / step; "
+              f"step {nk - 1} and the tail {d[:, nk - 1].mean().item():6.0f}")
     names = ["prologue"] + [f"query block {i}" for i in range(4)]
     for i, n in enumerate(names):
         d = (t[..., i + 1] - t[..., i])[ok]
