@@ -1739,6 +1739,94 @@ __device__ __forceinline__ void fused_tile(const AttnArgs& a, const bf16_t* Qt, 
   }
 }
 
+// ---- the rest of the query sweep, shared by attn_bwd_fused_kernel and attn_bwd_proj_kernel (one
+// body: the two kernels' dq / dk / dv are bit-identical by construction)
+
+// (diagnostic builds) shader-clock stamp k of (batch b, head h, wave): 0 start, 1 first query block
+// ready, 2 + it after query block it, 6 (attn_bwd_proj_kernel) GEMM phase done, 7 end; a vector
+// store from lane 0
+__device__ __forceinline__ void fused_stamp(const AttnArgs& a, int b, int h, int wave, int lane, int k) {
+#if LJS_ATTN_BWD_TRACE
+  const unsigned long long t = __builtin_amdgcn_s_memtime();
+  if (a.trace && lane == 0) a.trace[(((long)b * a.H + h) * (FT / 64) + wave) * 8 + k] = t;
+#else
+  (void)a; (void)b; (void)h; (void)wave; (void)lane; (void)k;
+#endif
+}
+
+// delta = rowsum(dO o O) of a staged 64-query block, once every wave's pieces of the O image Ot and
+// the dO image dOt are in LDS (vmcnt(0) + barrier); 8 threads per query row
+__device__ __forceinline__ void fused_delta(const bf16_t* Ot, const bf16_t* dOt, float* ndl, int tid) {
+  const int row = tid >> 3, c16 = tid & 7;
+  const u32x4 o = *reinterpret_cast<const u32x4*>(Ot + img16(row, c16));
+  const u32x4 d = *reinterpret_cast<const u32x4*>(dOt + img16(row, c16));
+  float s = dot_bf16x8(o, d);
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 4, 64);
+  if (c16 == 0) ndl[row] = -s;  // stored negated: it seeds the dP accumulators
+}
+
+// dQ^T (this wave's two d tiles) x its 16 queries = K^T dS^T over the key slices.  Unrolled over
+// the at most FK / 32 slices: every LDS address is a lane offset plus an immediate (the rolled
+// loop recomputed the swizzled addresses, 12 VALU per slice).  GUARD 0: all slices valid (Sk ==
+// 256), no per-slice guard, so the fragment reads of later slices can issue ahead of earlier
+// slices' MFMAs.  Accumulates into dq, which the caller zeroes where it declares it: zeroed in here,
+// through the reference, the SW 1 sweeps copied their accumulators at the loop's joins (+ 240 v_mov).
+template <bool GUARD>
+__device__ __forceinline__ void fused_dq(const bf16_t* Ks, const bf16_t* dSt, f32x4 (&dq)[2], int off_q,
+                                         const int (&off_k)[2], int nk32) {
+#pragma unroll
+  for (int s2 = 0; s2 < FK / 32; ++s2) {
+    if (!GUARD || s2 < nk32) {
+      bf16x8 sb = frag_tr_o(dSt, 32 * s2, off_q);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        bf16x8 ka = frag_tr_o(Ks, 32 * s2, off_k[i]);
+        dq[i] = mfma16x16x32(ka, sb, dq[i]);
+      }
+    }
+  }
+}
+
+// A query block's dQ is split over wave pairs (d halves), so it leaves through a [64][64] LDS image
+// (16-byte chunk XOR row) as whole 128-byte rows: every wave stages its part, the block's barrier,
+// then one 16-byte chunk per thread.  A thread's read completes before its store issues, i.e.
+// before the next block's mid-sweep barrier, after which the image may be written again.
+__device__ __forceinline__ void fused_dq_stage(bf16_t* img, const f32x4 (&dq)[2], float scale, int qt, int dt0,
+                                               int lane) {
+  const int r = 16 * qt + (lane & 15), g = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    u32x2 w;
+    w[0] = pack_bf16x2(dq[i][0] * scale, dq[i][1] * scale);
+    w[1] = pack_bf16x2(dq[i][2] * scale, dq[i][3] * scale);
+    const int c = (2 * (dt0 + i) + (g >> 1)) ^ (r & 7);
+    *reinterpret_cast<u32x2*>(img + r * D + c * 8 + 4 * (g & 1)) = w;
+  }
+}
+// GUARD (compile-time, as the sweep's VS flag): rows past Sq are not stored
+template <bool GUARD>
+__device__ __forceinline__ void fused_dq_flush(const AttnArgs& a, const bf16_t* img, int b, int h, int q0, int tid) {
+  const int r = tid >> 3, c = tid & 7;
+  const u32x4 v = *reinterpret_cast<const u32x4*>(img + r * D + ((c ^ (r & 7)) << 3));
+  if (!GUARD || q0 + r < a.Sq)
+    *reinterpret_cast<u32x4*>(a.out3 + b * a.out3_sb + (long)(q0 + r) * a.out3_ss + h * a.out3_sh + c * 8) = v;
+}
+
+// After the sweep's last barrier the K / V images are free: this wave's 32 key rows of dK / dV
+// (rows below klim) leave through its own rows of them
+__device__ __forceinline__ void fused_dkv_out(const AttnArgs& a, bf16_t* Ks, bf16_t* Vs, const f32x4 (&dk)[2][4],
+                                              const f32x4 (&dv)[2][4], int b, int h, int key0, int klim, int lane) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    stage_rows16(Ks + key0 * D, 16 * j, dk[j], a.scale, lane);
+    stage_rows16(Vs + key0 * D, 16 * j, dv[j], 1.f, lane);
+  }
+  flush_rows<32>(Ks + key0 * D, a.out + b * a.out_sb + h * a.out_sh, a.out_ss, key0, klim, lane);
+  flush_rows<32>(Vs + key0 * D, a.out2 + b * a.out2_sb + h * a.out2_sh, a.out2_ss, key0, klim, lane);
+}
+
 // SW 1: the sweep instance of the common case alone (Sq % 64 == 0, Sk == 256, not causal, dQ
 // staged: a.vst == 1), so the kernel's register allocation is that one loop's, not the maximum
 // over the four sweep instances; SW 0: all four, chosen at run time
@@ -1754,16 +1842,7 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
   const int h = blockIdx.x, b = blockIdx.y;
   const int key0 = wave * 32;
-  // (diagnostic builds) shader-clock stamps: 0 start, 1 first query block ready, 2 + it after
-  // query block it, 7 end; a vector store from lane 0
-  auto bstamp = [&](int k) {
-#if LJS_ATTN_BWD_TRACE
-    const unsigned long long t = __builtin_amdgcn_s_memtime();
-    if (a.trace && lane == 0) a.trace[(((long)b * gridDim.x + h) * (FT / 64) + wave) * 8 + k] = t;
-#else
-    (void)k;
-#endif
-  };
+  auto bstamp = [&](int k) { fused_stamp(a, b, h, wave, lane, k); };
   bstamp(0);
   const bool active = key0 < a.Sk;
   const int nk32 = (a.Sk + 31) / 32;
@@ -1828,17 +1907,8 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
     dma_lds_x4(ro, oo, Os + wave * 512);
     if (wave == 0) dma_lds_x1(rl, q0 + lane < a.Sq ? (q0 + lane) * 4 : 0x7ffffff0, &rowc[buf][0][0]);
   };
-  // after every wave's DMA of `buf` landed (vmcnt(0) + barrier): delta = rowsum(dO o O)
-  auto finish = [&](int buf) {
-    const int row = tid >> 3, c16 = tid & 7;  // 8 threads per query row
-    const u32x4 o = *reinterpret_cast<const u32x4*>(Os + img16(row, c16));
-    const u32x4 d = *reinterpret_cast<const u32x4*>(QO + (2 + buf) * BLK * D + img16(row, c16));
-    float s = dot_bf16x8(o, d);
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    if (c16 == 0) rowc[buf][1][row] = -s;  // stored negated: it seeds the dP accumulators
-  };
+  // the delta of the block whose DMA into `buf` landed
+  auto finish = [&](int buf) { fused_delta(Os, QO + (2 + buf) * BLK * D, rowc[buf][1], tid); };
   if (nqt > 0) issue(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -1846,16 +1916,12 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
   __syncthreads();
   bstamp(1);
 
-  f32x4 dk[2][4], dv[2][4];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      dk[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dv[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+  f32x4 dk[2][4] = {}, dv[2][4] = {};
   // this wave's 32 keys as MFMA B operands stay in registers for the whole query sweep (they
-  // were re-read from LDS per 16-query tile: a third of the kernel's LDS traffic)
+  // were re-read from LDS per 16-query tile: a third of the kernel's LDS traffic).  (This set-up
+  // stays written out here and in attn_bwd_proj_kernel: as a helper shared with it, however split
+  // or worded, it raised the scratch of the <dma = 1, sw = 0> instance from 24 to 28-36 bytes per
+  // lane; with dK / dV zeroed inside one, the SW 1 sweeps copied them at the loop's joins.)
   bf16x8 kr[2][2], vr[2][2];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -1900,48 +1966,12 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (more) finish(cur ^ 1);
-      // dQ^T (d tiles dt0, dt0+1) x queries 16qt..16qt+15 = K^T dS^T over all keys
-      f32x4 dq[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      // unrolled over the at most FK / 32 key slices: every LDS address is a lane offset plus an
-      // immediate (the rolled loop recomputed the swizzled addresses, 12 VALU per slice)
-      if (LJS_ATTN_DQ_UNGUARD && nk32 == FK / 32) {
-        // all key slices valid (Sk == 256): no per-slice guard, so the fragment reads of later
-        // slices can issue ahead of earlier slices' MFMAs
-  #pragma unroll
-        for (int s2 = 0; s2 < FK / 32; ++s2) {
-          bf16x8 sb = frag_tr_o(dSt, 32 * s2, off_q);
-  #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            bf16x8 ka = frag_tr_o(Ks, 32 * s2, off_k[i]);
-            dq[i] = mfma16x16x32(ka, sb, dq[i]);
-          }
-        }
-      } else {
-  #pragma unroll
-        for (int s2 = 0; s2 < FK / 32; ++s2) {
-          if (s2 < nk32) {
-            bf16x8 sb = frag_tr_o(dSt, 32 * s2, off_q);
-  #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-              bf16x8 ka = frag_tr_o(Ks, 32 * s2, off_k[i]);
-              dq[i] = mfma16x16x32(ka, sb, dq[i]);
-            }
-          }
-        }
-      }
+      f32x4 dq[2] = {};
+      if (LJS_ATTN_DQ_UNGUARD && nk32 == FK / 32) fused_dq<false>(Ks, dSt, dq, off_q, off_k, nk32);
+      else fused_dq<true>(Ks, dSt, dq, off_q, off_k, nk32);
       const int qrow = q0 + 16 * qt + (lane & 15);
       if constexpr (VS) {
-        // the block's dQ is split over wave pairs (d halves): staged in dQs (16-byte chunk XOR
-        // row), written as whole 128-byte rows after the barrier below
-        const int r = 16 * qt + (lane & 15);
-  #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          u32x2 w;
-          w[0] = pack_bf16x2(dq[i][0] * a.scale, dq[i][1] * a.scale);
-          w[1] = pack_bf16x2(dq[i][2] * a.scale, dq[i][3] * a.scale);
-          const int c = (2 * (dt0 + i) + (g >> 1)) ^ (r & 7);
-          *reinterpret_cast<u32x2*>(dQs + r * D + c * 8 + 4 * (g & 1)) = w;
-        }
+        fused_dq_stage(dQs, dq, a.scale, qt, dt0, lane);
       } else if (qrow < a.Sq) {
         bf16_t* rowp = a.out3 + b * a.out3_sb + (long)qrow * a.out3_ss + h * a.out3_sh;
   #pragma unroll
@@ -1953,14 +1983,7 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
         }
       }
       __syncthreads();
-      if constexpr (VS) {
-        // one 16-byte chunk per thread (64 rows x 8 chunks); the read completes before this
-        // thread's store issues, i.e. before the next block's mid-sweep barrier (dQs reuse)
-        const int r = tid >> 3, c = tid & 7;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(dQs + r * D + ((c ^ (r & 7)) << 3));
-        if (q0 + r < a.Sq)
-          *reinterpret_cast<u32x4*>(a.out3 + b * a.out3_sb + (long)(q0 + r) * a.out3_ss + h * a.out3_sh + c * 8) = v;
-      }
+      if constexpr (VS) fused_dq_flush<true>(a, dQs, b, h, q0, tid);
       if (it < 5) bstamp(2 + it);
     }
   };
@@ -1975,17 +1998,7 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
     else sweep(std::false_type{}, std::false_type{});
   }
   if (a.vst) {
-    // every wave passed the sweep's last barrier: the K / V images are free; this wave's 32 key
-    // rows of dK / dV go through its own rows of them
-    if (active) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        stage_rows16(Ks + key0 * D, 16 * j, dk[j], a.scale, lane);
-        stage_rows16(Vs + key0 * D, 16 * j, dv[j], 1.f, lane);
-      }
-      flush_rows<32>(Ks + key0 * D, a.out + b * a.out_sb + h * a.out_sh, a.out_ss, key0, a.Sk, lane);
-      flush_rows<32>(Vs + key0 * D, a.out2 + b * a.out2_sb + h * a.out2_sh, a.out2_ss, key0, a.Sk, lane);
-    }
+    if (active) fused_dkv_out(a, Ks, Vs, dk, dv, b, h, key0, a.Sk, lane);
     bstamp(7);
     return;
   }
@@ -2029,18 +2042,8 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
 //     only the weight tile in LDS, the steps cost the same on a broadcast row and more on a full dY.
 //   * dO_h stays in LDS for the whole sweep ([256][64], img16 per 64-row block); block it's image is
 //     dead once its dS^T is formed and then stages that block's dQ.
-// LDS-DMA to a byte address of the block's LDS (common.h dma_lds_x4 / dma_lds_x1 with the
-// destination as a number: the pieces below choose among images at run time)
-__device__ __forceinline__ void dma_lds_x4_at(const u32x4& rs, int voff, unsigned lds_byte) {
-  const unsigned m = __builtin_amdgcn_readfirstlane(lds_byte);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
-               :: "v"(voff), "s"(rs), "s"(m) : "memory", "m0");
-}
-__device__ __forceinline__ void dma_lds_x1_at(const u32x4& rs, int voff, unsigned lds_byte) {
-  const unsigned m = __builtin_amdgcn_readfirstlane(lds_byte);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %0, %1, 0 offen lds"
-               :: "v"(voff), "s"(rs), "s"(m) : "memory", "m0");
-}
+// (The pieces below choose among LDS images at run time: dma_lds_x4_at / dma_lds_x1_at, the
+// destination as a byte address of the block's LDS.)
 struct BwdProjArgs {
   const bf16_t* dy;   // [B * 256][M] bf16 rows, row stride dy_ld (0: one row for every token)
   const bf16_t* w;    // [H * 64][M] bf16: the out-projection weight, k-contiguous
@@ -2075,15 +2078,7 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
   const int t = xcd_remap(blockIdx.x, gridDim.x);
   const int b = t / a.H, h = t - b * a.H;
   const int key0 = wave * 32;
-  // (diagnostic builds) stamps as attn_bwd_fused_kernel's, plus 6: GEMM phase done
-  auto bstamp = [&](int k) {
-#if LJS_ATTN_BWD_TRACE
-    const unsigned long long ts = __builtin_amdgcn_s_memtime();
-    if (a.trace && lane == 0) a.trace[(((long)b * a.H + h) * (FT / 64) + wave) * 8 + k] = ts;
-#else
-    (void)k;
-#endif
-  };
+  auto bstamp = [&](int k) { fused_stamp(a, b, h, wave, lane, k); };
   bstamp(0);
 
   const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
@@ -2106,17 +2101,8 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
     dma_lds_x4_at(ro, (int)(((long)r * a.o_ss + dchunk) * 2), sb + 2 * (PJ_OS + wave * 512));
     if (wave == 0) dma_lds_x1_at(rl, (q0 + lane) * 4, sb + 2 * PJ_ROWC + 4 * (buf * 2 * BLK));
   };
-  // after every wave's DMA of block it + 1 landed (vmcnt(0) + barrier): delta = rowsum(dO o O)
-  auto finish = [&](int buf, int blk) {
-    const int row = tid >> 3, c16 = tid & 7;  // 8 threads per query row
-    const u32x4 o = *reinterpret_cast<const u32x4*>(Os + img16(row, c16));
-    const u32x4 d = *reinterpret_cast<const u32x4*>(dOi + blk * BLK * D + img16(row, c16));
-    float s = dot_bf16x8(o, d);
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    if (c16 == 0) rowc[(buf * 2 + 1) * BLK + row] = -s;  // stored negated: it seeds the dP accumulators
-  };
+  // the delta of query block blk, whose O landed by DMA, into rowc[buf]
+  auto finish = [&](int buf, int blk) { fused_delta(Os, dOi + blk * BLK * D, rowc + (buf * 2 + 1) * BLK, tid); };
 
   // ---- dO_h = dY[b] . Wo_h^T
   {
@@ -2247,14 +2233,8 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
   __syncthreads();
   bstamp(1);
 
-  f32x4 dk[2][4], dv[2][4];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      dk[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dv[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+  f32x4 dk[2][4] = {}, dv[2][4] = {};
+  // (as attn_bwd_fused_kernel)
   bf16x8 kr[2][2], vr[2][2];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -2281,47 +2261,15 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (more) finish(cur ^ 1, it + 1);
-    // dQ^T (d tiles dt0, dt0+1) x queries 16qt..16qt+15 = K^T dS^T over all keys
-    f32x4 dq[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int s2 = 0; s2 < FK / 32; ++s2) {
-      bf16x8 sb = frag_tr_o(dSt, 32 * s2, off_q);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        bf16x8 ka = frag_tr_o(Ks, 32 * s2, off_k[i]);
-        dq[i] = mfma16x16x32(ka, sb, dq[i]);
-      }
-    }
-    // the block's dQ, split over wave pairs (d halves), staged in this block's dO image: every
-    // wave passed the barrier above, so nothing reads it again
-    {
-      const int r = 16 * qt + (lane & 15);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        u32x2 w2;
-        w2[0] = pack_bf16x2(dq[i][0] * a.scale, dq[i][1] * a.scale);
-        w2[1] = pack_bf16x2(dq[i][2] * a.scale, dq[i][3] * a.scale);
-        const int c = (2 * (dt0 + i) + (g >> 1)) ^ (r & 7);
-        *reinterpret_cast<u32x2*>(dOt + r * D + c * 8 + 4 * (g & 1)) = w2;
-      }
-    }
+    f32x4 dq[2] = {};
+    fused_dq<false>(Ks, dSt, dq, off_q, off_k, FK / 32);
+    // staged in this block's dO image: every wave passed the barrier above, so nothing reads it again
+    fused_dq_stage(dOt, dq, a.scale, qt, dt0, lane);
     __syncthreads();
-    {
-      const int r = tid >> 3, c = tid & 7;
-      const u32x4 v4 = *reinterpret_cast<const u32x4*>(dOt + r * D + ((c ^ (r & 7)) << 3));
-      *reinterpret_cast<u32x4*>(a.out3 + b * a.out3_sb + (long)(q0 + r) * a.out3_ss + h * a.out3_sh + c * 8) = v4;
-    }
+    fused_dq_flush<false>(a, dOt, b, h, q0, tid);
     bstamp(2 + it);
   }
-  // every wave passed the sweep's last barrier: the K / V images are free; this wave's 32 key rows
-  // of dK / dV go through its own rows of them
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    stage_rows16(Ks + key0 * D, 16 * j, dk[j], a.scale, lane);
-    stage_rows16(Vs + key0 * D, 16 * j, dv[j], 1.f, lane);
-  }
-  flush_rows<32>(Ks + key0 * D, a.out + b * a.out_sb + h * a.out_sh, a.out_ss, key0, FK, lane);
-  flush_rows<32>(Vs + key0 * D, a.out2 + b * a.out2_sb + h * a.out2_sh, a.out2_ss, key0, FK, lane);
+  fused_dkv_out(a, Ks, Vs, dk, dv, b, h, key0, FK, lane);
   bstamp(7);
 }
 
@@ -2379,17 +2327,13 @@ LJS_API void ljs_attn_set_trace(void* p) { g_attn_trace = (unsigned long long*)p
 static unsigned long long* g_attn_trace_steps = nullptr;
 LJS_API void ljs_attn_set_trace_steps(void* p) { g_attn_trace_steps = (unsigned long long*)p; }
 
-// strides are in elements, ordered (batch, seq, head); head_dim must be 64 and contiguous.
-static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
-                         int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
-                         int causal, int q_offset, void* oacc, const long* oas, int acc_mode, hipStream_t stream) {
+// The fields every attention launch fills: Q / K / V / O operands (o: the forward's output, the
+// backward's saved one; the forward also names it as a.out), lse, shape and softmax constants.
+static AttnArgs attn_args(const void* q, const void* k, const void* v, const void* o, const void* lse, const long* qs,
+                          const long* ks, const long* vs, const long* os, int Sq, int Sk, int H, float scale,
+                          int causal, int q_offset) {
   AttnArgs a = {};
-  a.oacc = (float*)oacc;
-  a.acc_mode = acc_mode;
-  if (oas) {
-    a.oa_sb = oas[0]; a.oa_ss = oas[1]; a.oa_sh = oas[2];
-  }
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.out = (bf16_t*)o;
+  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
   a.lse = (float*)lse;
   a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
   a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
@@ -2398,6 +2342,24 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, v
   a.Sq = Sq; a.Sk = Sk; a.H = H;
   a.scale = scale; a.scale_log2 = scale * LOG2E;
   a.causal = causal; a.q_offset = q_offset;
+  return a;
+}
+// one output (AttnArgs out / out2 / out3) and its (batch, seq, head) strides
+static void attn_out(bf16_t*& out, long& sb, long& ss, long& sh, void* p, const long* st) {
+  out = (bf16_t*)p; sb = st[0]; ss = st[1]; sh = st[2];
+}
+
+// strides are in elements, ordered (batch, seq, head); head_dim must be 64 and contiguous.
+static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
+                         int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
+                         int causal, int q_offset, void* oacc, const long* oas, int acc_mode, hipStream_t stream) {
+  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, q_offset);
+  a.out = (bf16_t*)o;   // (addressed with the o strides)
+  a.oacc = (float*)oacc;
+  a.acc_mode = acc_mode;
+  if (oas) {
+    a.oa_sb = oas[0]; a.oa_ss = oas[1]; a.oa_sh = oas[2];
+  }
   a.vst = g_vst && vst_ok(o, os);
   if (g_fwd_res > 0 && Sk <= FKR && (long)(Sk - 1) * (ks[1] > vs[1] ? ks[1] : vs[1]) * 2 + 128 < (1L << 31)) {
     // 8 waves x 16 queries per block leave CUs idle below 256 blocks (B*H = 64 at the
@@ -2475,18 +2437,10 @@ LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void
                          const long* qs, const long* ks, const long* vs, const long* os, const long* dos,
                          const long* dqs, const long* dks, const long* dvs, float scale, int causal, int q_offset,
                          hipStream_t stream) {
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
+  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, q_offset);
   a.dout = (const bf16_t*)dout;
-  a.lse = (float*)lse; a.delta = (const float*)delta;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
+  a.delta = (const float*)delta;
   a.do_sb = dos[0]; a.do_ss = dos[1]; a.do_sh = dos[2];
-  a.Sq = Sq; a.Sk = Sk; a.H = H;
-  a.scale = scale; a.scale_log2 = scale * LOG2E;
-  a.causal = causal; a.q_offset = q_offset;
   // 2 = automatic: the fused kernel runs one workgroup per (batch, head), so below ~half a
   // workgroup per CU (B*H < 128: the reference's B = 8 x 8 heads) the split kernels' per-query-
   // block grids fill the chip better (measured: 0.1218 vs 0.1248 ms/step at B = 8, equal at 16,
@@ -2494,9 +2448,9 @@ LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void
   const bool fused = g_bwd_fused == 1 || (g_bwd_fused == 2 && (long)B * H >= 128);
   if (fused && Sk <= FK) {
     AttnArgs f = a;
-    f.out = (bf16_t*)dk; f.out_sb = dks[0]; f.out_ss = dks[1]; f.out_sh = dks[2];
-    f.out2 = (bf16_t*)dv; f.out2_sb = dvs[0]; f.out2_ss = dvs[1]; f.out2_sh = dvs[2];
-    f.out3 = (bf16_t*)dq; f.out3_sb = dqs[0]; f.out3_ss = dqs[1]; f.out3_sh = dqs[2];
+    attn_out(f.out, f.out_sb, f.out_ss, f.out_sh, dk, dks);
+    attn_out(f.out2, f.out2_sb, f.out2_ss, f.out2_sh, dv, dvs);
+    attn_out(f.out3, f.out3_sb, f.out3_ss, f.out3_sh, dq, dqs);
     f.vst = vst_ok(dk, dks) && vst_ok(dv, dvs) && vst_ok(dq, dqs) ? g_vst : 0;
     f.trace = g_attn_trace;
     // 2 = automatic: the DMA form when a block sweeps at most two query blocks (the 2-D mesh's
@@ -2516,11 +2470,11 @@ LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void
     return (int)hipGetLastError();
   }
   AttnArgs c = a;
-  c.out = (bf16_t*)dq; c.out_sb = dqs[0]; c.out_ss = dqs[1]; c.out_sh = dqs[2];
+  attn_out(c.out, c.out_sb, c.out_ss, c.out_sh, dq, dqs);
   c.vst = g_vst && vst_ok(dq, dqs);  // (the 128-query dQ blocks use it)
   AttnArgs b = a;
-  b.out = (bf16_t*)dk; b.out_sb = dks[0]; b.out_ss = dks[1]; b.out_sh = dks[2];
-  b.out2 = (bf16_t*)dv; b.out2_sb = dvs[0]; b.out2_ss = dvs[1]; b.out2_sh = dvs[2];
+  attn_out(b.out, b.out_sb, b.out_ss, b.out_sh, dk, dks);
+  attn_out(b.out2, b.out2_sb, b.out2_ss, b.out2_sh, dv, dvs);
   b.vst = g_vst && vst_ok(dk, dks) && vst_ok(dv, dvs);  // (the 128-key dK/dV blocks use it)
   const long nq = (Sq + BLK - 1) / BLK, nk = (Sk + BLK - 1) / BLK;
   if (g_dkv32 && (nq + (Sk + 127) / 128) * H * B < (1L << 30)) {
@@ -2576,18 +2530,10 @@ LJS_API int ljs_attn_bwd_proj(const void* q, const void* k, const void* v, const
       !dq || !dk || !dv || !vst_ok(dq, dqs) || !vst_ok(dk, dks) || !vst_ok(dv, dvs) ||
       !ljs_attn_bwd_proj_enabled(B, H))
     return (int)hipErrorInvalidValue;
-  AttnArgs a = {};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
-  a.lse = (float*)lse;
-  a.q_sb = qs[0]; a.q_ss = qs[1]; a.q_sh = qs[2];
-  a.k_sb = ks[0]; a.k_ss = ks[1]; a.k_sh = ks[2];
-  a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
-  a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
-  a.out = (bf16_t*)dk; a.out_sb = dks[0]; a.out_ss = dks[1]; a.out_sh = dks[2];
-  a.out2 = (bf16_t*)dv; a.out2_sb = dvs[0]; a.out2_ss = dvs[1]; a.out2_sh = dvs[2];
-  a.out3 = (bf16_t*)dq; a.out3_sb = dqs[0]; a.out3_ss = dqs[1]; a.out3_sh = dqs[2];
-  a.Sq = Sq; a.Sk = Sk; a.H = H;
-  a.scale = scale; a.scale_log2 = scale * LOG2E;
+  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, 0);
+  attn_out(a.out, a.out_sb, a.out_ss, a.out_sh, dk, dks);
+  attn_out(a.out2, a.out2_sb, a.out2_ss, a.out2_sh, dv, dvs);
+  attn_out(a.out3, a.out3_sb, a.out3_ss, a.out3_sh, dq, dqs);
   a.vst = 1;
   a.trace = g_attn_trace;
   BwdProjArgs pj;

@@ -175,17 +175,25 @@ __device__ __forceinline__ u32x4 rsrc_u4(const void* base, long bytes) {
   r[3] = 0x00020000u;
   return r;
 }
-// 64 lanes x 16 B from rsrc + voff (per lane) to LDS [lds, lds + 1 KiB), lane-contiguous
-__device__ __forceinline__ void dma_lds_x4(const u32x4& rs, int voff, const void* lds) {
-  const unsigned m = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(LDS_PTR(const void))lds);
+// 64 lanes x 16 B from rsrc + voff (per lane) to LDS, lane-contiguous: 1 KiB from the block's LDS
+// byte address lds_byte (the _at forms: a kernel that chooses among images at run time passes the
+// destination as a number) or from the pointer lds
+__device__ __forceinline__ void dma_lds_x4_at(const u32x4& rs, int voff, unsigned lds_byte) {
+  const unsigned m = __builtin_amdgcn_readfirstlane(lds_byte);
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
                :: "v"(voff), "s"(rs), "s"(m) : "memory", "m0");
 }
-// 64 lanes x 4 B to LDS [lds, lds + 256 B)
-__device__ __forceinline__ void dma_lds_x1(const u32x4& rs, int voff, const void* lds) {
-  const unsigned m = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(LDS_PTR(const void))lds);
+__device__ __forceinline__ void dma_lds_x4(const u32x4& rs, int voff, const void* lds) {
+  dma_lds_x4_at(rs, voff, (unsigned)(uintptr_t)(LDS_PTR(const void))lds);
+}
+// 64 lanes x 4 B to LDS: 256 B
+__device__ __forceinline__ void dma_lds_x1_at(const u32x4& rs, int voff, unsigned lds_byte) {
+  const unsigned m = __builtin_amdgcn_readfirstlane(lds_byte);
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %0, %1, 0 offen lds"
                :: "v"(voff), "s"(rs), "s"(m) : "memory", "m0");
+}
+__device__ __forceinline__ void dma_lds_x1(const u32x4& rs, int voff, const void* lds) {
+  dma_lds_x1_at(rs, voff, (unsigned)(uintptr_t)(LDS_PTR(const void))lds);
 }
 
 // ---- in-launch "last arriver" hand-off (cdna_hip_programming.md §6 Guideline 16, valid form:
