@@ -42,6 +42,53 @@ struct GemmArgs {
   unsigned long long* trace;  // LJS_GEMM_TRACE builds only: per-wave timestamps (see gemm_trace)
 };
 
+// Transposed fragment reads as asm statements, for a K-loop that keeps LDS-DMA pieces in flight
+// across its barrier.  The compiler knows nothing about what ds_read_tr16_b64 (the builtin) reads,
+// so with a DMA outstanding it puts s_waitcnt vmcnt(0) in front of every group of them: every
+// m/n-contiguous LDS-DMA kernel drains its ring right after the barrier, whatever its counted wait
+// said (the k-contiguous kernels' plain ds_read_b128 are not treated so).  An asm read is not
+// counted by the compiler at all, so these come with their own lgkmcnt waits:
+//   tr_read5_wait   5 fragments, valid when the statement ends (it waits lgkmcnt(0) itself);
+//   tr_read3 / 4    fragments that are NOT valid until a tr_wait* statement naming them ("+v", so
+//                   nothing that uses them can be scheduled above it) -- join the halves into an
+//                   MFMA operand only after that, so that a register copy the join may need reads
+//                   landed data.
+// A fragment is two reads 4 k-rows (1024 B at 128-wide rows) apart from one address; ad: LDS byte
+// addresses (frag_tr_addr below).
+#define LJS_TR2(l, h, a) "ds_read_b64_tr_b16 %" #l ", %" #a "\n\tds_read_b64_tr_b16 %" #h ", %" #a " offset:1024\n\t"
+__device__ __forceinline__ void tr_read5_wait(s16x4* lo, s16x4* hi, const unsigned* ad) {
+  asm volatile(LJS_TR2(0, 1, 10) LJS_TR2(2, 3, 11) LJS_TR2(4, 5, 12) LJS_TR2(6, 7, 13) LJS_TR2(8, 9, 14)
+               "s_waitcnt lgkmcnt(0)"
+               : "=&v"(lo[0]), "=&v"(hi[0]), "=&v"(lo[1]), "=&v"(hi[1]), "=&v"(lo[2]), "=&v"(hi[2]), "=&v"(lo[3]),
+                 "=&v"(hi[3]), "=&v"(lo[4]), "=&v"(hi[4])
+               : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3]), "v"(ad[4])
+               : "memory");
+}
+__device__ __forceinline__ void tr_read3(s16x4* lo, s16x4* hi, const unsigned* ad) {
+  asm volatile(LJS_TR2(0, 1, 6) LJS_TR2(2, 3, 7) LJS_TR2(4, 5, 8)
+               : "=&v"(lo[0]), "=&v"(hi[0]), "=&v"(lo[1]), "=&v"(hi[1]), "=&v"(lo[2]), "=&v"(hi[2])
+               : "v"(ad[0]), "v"(ad[1]), "v"(ad[2])
+               : "memory");
+}
+__device__ __forceinline__ void tr_read4(s16x4* lo, s16x4* hi, const unsigned* ad) {
+  asm volatile(LJS_TR2(0, 1, 8) LJS_TR2(2, 3, 9) LJS_TR2(4, 5, 10) LJS_TR2(6, 7, 11)
+               : "=&v"(lo[0]), "=&v"(hi[0]), "=&v"(lo[1]), "=&v"(hi[1]), "=&v"(lo[2]), "=&v"(hi[2]), "=&v"(lo[3]),
+                 "=&v"(hi[3])
+               : "v"(ad[0]), "v"(ad[1]), "v"(ad[2]), "v"(ad[3])
+               : "memory");
+}
+#undef LJS_TR2
+#define LJS_TRW(x, i) "+v"(x##lo[i]), "+v"(x##hi[i])
+// every read issued so far has landed: the 3 fragments of a (tr_read3) and the 8 of b (2 x tr_read4)
+__device__ __forceinline__ void tr_wait3_8(s16x4* alo, s16x4* ahi, s16x4* blo, s16x4* bhi) {
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : LJS_TRW(a, 0), LJS_TRW(a, 1), LJS_TRW(a, 2), LJS_TRW(b, 0), LJS_TRW(b, 1), LJS_TRW(b, 2),
+                 LJS_TRW(b, 3), LJS_TRW(b, 4), LJS_TRW(b, 5), LJS_TRW(b, 6), LJS_TRW(b, 7)
+               :
+               : "memory");
+}
+#undef LJS_TRW
+
 // Timeline instrumentation of the LDS-DMA kernel (compiled in with -DLJS_GEMM_TRACE only, a
 // variant library for scripts/gemm_trace.py): per wave, kTraceSlots core-clock stamps (s_memtime)
 // written by lane 0 with vector stores -- kernel start, then per K-tile wait: before the counted
@@ -165,6 +212,14 @@ __device__ __forceinline__ bf16x8 frag(const bf16_t* lds, int rb, int ks, int la
     s16x4 hi = lds_read_tr16(lds + kr1 * R + swz_mn<R>(kr1, c8) * 4);
     return join_bf16x8(lo, hi);
   }
+}
+
+// LDS byte address of the first read of frag<128, false>(lds, rb, 0, lane), for the tr_read* statements
+__device__ __forceinline__ unsigned frag_tr_addr(const bf16_t* lds, int rb, int lane) {
+  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
+  const int kr0 = 8 * g + q;
+  const int c8 = (rb >> 2) + p;
+  return (unsigned)(unsigned long)(LDS_PTR(const bf16_t))(lds + kr0 * 128 + swz_mn<128>(kr0, c8) * 4);
 }
 
 template <int BM, int BN, bool A_KC, bool B_KC, bool OUT_F32>
@@ -422,6 +477,17 @@ struct DmaTile {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (LDS_PTR(void))(lds + (wave + NW * i) * 512), 16, voff[i], soff,
                                                0, 0);
   }
+
+  // half H of the tile (its k-rows 32 H .. 32 H + 31 -- an m/n-contiguous wave's pieces 2 H and
+  // 2 H + 1 when every piece is 4 k-rows and 4 waves share the tile) into a half-tile image at lds
+  template <int H>
+  __device__ __forceinline__ void issue_half(__amdgpu_buffer_rsrc_t rs, bf16_t* lds, int soff, int wave) const {
+    static_assert(!KC && PER_WAVE == 4 && R == 128, "pieces i and i + 2 are 32 k-rows apart");
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (LDS_PTR(void))(lds + (wave + NW * i) * 512), 16, voff[2 * H + i],
+                                               soff, 0, 0);
+  }
 };
 
 struct WorkItem {
@@ -481,7 +547,16 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
   static_assert(OUT_F32 || TN % 2 == 0, "column blocks pair up for 16-byte stores");
   constexpr int S_EPI = TM * TN / 2;
   static_assert(L * (NST - 1) + S_EPI + 1 <= 63, "vmcnt immediate range");
-  __shared__ __attribute__((aligned(16))) bf16_t smem[NST * STAGE];
+  // RING: the 4-wave 128x128 weight-gradient slab instance (tile code 1282) keeps its LDS as FIVE
+  // HALF-tile slots (32 k-rows of A, then of B: 16 KiB each, 80 KiB -- still two blocks per CU)
+  // instead of two whole stages, so halves stay in flight across every barrier.  NST = 2 then only
+  // says "two whole stages' worth": it stays in the template arguments (and the launch record's
+  // name) and sizes nothing here.  The schedule is at ring_wait below.
+  constexpr bool RING = NST == 2 && BM == 128 && BN == 128 && NW == 4 && !A_KC && !B_KC && OUT_F32 && RES == 3;
+  constexpr int HALF = STAGE / 2, A_HALF = A_TILE / 2, RING_SLOTS = 5;
+  constexpr int E_RING = TM * TN;   // an item's direct f32 stores per lane (one per accumulator block)
+  static_assert(!RING || 4 * L / 2 + E_RING + 1 <= 63, "vmcnt immediate range");
+  __shared__ __attribute__((aligned(16))) bf16_t smem[RING ? RING_SLOTS * HALF : NST * STAGE];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -508,9 +583,16 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
       if (lane == 0) trc[kTraceSlots - 1] = t;
     }
   };
+  // stamp(), and whether it stored: a stamp is one more entry of the wave's vmcnt queue
+  auto stamp_st = [&]() {
+    const int st = trc && trn < kTraceSlots - 1;
+    stamp();
+    return st;
+  };
 #else
   auto stamp = [&]() {};
   auto stamp_end = [&]() {};
+  auto stamp_st = [&]() { return 0; };
 #endif
   stamp();
 
@@ -569,9 +651,43 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // RING: the halves of the flattened (item, K-tile) sequence are numbered h = 0, 1, 2, ... (tile f
+  // is halves 2 f and 2 f + 1) and issued strictly in that order, half h into slot h mod 5: the
+  // write slot just rotates.  A half is 2 A pieces and 2 B pieces per wave (L / 2 = 4 instructions).
+  int ring_w = 0, ring_r = 0;   // element offsets of the next half's slot / of tile f's first half
+  auto ring_adv = [](int so, int n) {
+    so += n * HALF;
+    return so >= RING_SLOTS * HALF ? so - RING_SLOTS * HALF : so;
+  };
+  auto ring_issue0 = [&]() {   // k-rows 0-31 of the cursor's tile
+    if constexpr (RING) {
+      if (is_kt == 0) load_item(is_item);
+      ta.template issue_half<0>(ra, smem + ring_w, a_off, wave);
+      tb.template issue_half<0>(rb, smem + ring_w + A_HALF, b_off, wave);
+      ring_w = ring_adv(ring_w, 1);
+    }
+  };
+  auto ring_issue1 = [&]() {   // k-rows 32-63, and the cursor moves on
+    if constexpr (RING) {
+      ta.template issue_half<1>(ra, smem + ring_w, a_off, wave);
+      tb.template issue_half<1>(rb, smem + ring_w + A_HALF, b_off, wave);
+      ring_w = ring_adv(ring_w, 1);
+      a_off += a_step;
+      b_off += b_step;
+      if (++is_kt == nk) { is_kt = 0; ++is_item; }
+    }
+  };
+
+  if constexpr (RING) {
+    // prologue: up to five halves (tiles 0 and 1 and the first half of tile 2)
+    if (total > 0) { ring_issue0(); ring_issue1(); }
+    if (total > 1) { ring_issue0(); ring_issue1(); }
+    if (total > 2) ring_issue0();
+  } else {
 #pragma unroll
-  for (int s = 0; s < NST - 1; ++s)
-    if (s < total) issue_next(s);
+    for (int s = 0; s < NST - 1; ++s)
+      if (s < total) issue_next(s);
+  }
 
   // RES 3 (PLAIN): alpha 1, no bias / ReLU / fused sum -- a compile-time epilogue, so the kernel
   // carries one store loop with nothing but the pair exchange, the bf16 packing and the stores;
@@ -612,6 +728,51 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     after_epi = false;
+    stamp();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    stamp();
+  };
+  // ---- RING schedule (one barrier per K-tile, as before; what changes is what is in flight).
+  //   prologue        halves 0 .. 4                                   (as many as exist)
+  //   top of tile f   counted vmcnt: halves 2 f and 2 f + 1 landed;  lgkmcnt(0);  s_barrier
+  //   after it        (f >= 1) halves 2 f + 3 and 2 f + 4 into the slots of tile f - 1's halves
+  //                   2 f - 2 and 2 f - 1, which every wave finished reading (lgkmcnt(0)) before
+  //                   it entered this barrier; the other three slots hold 2 f, 2 f + 1 (read now)
+  //                   and 2 f + 2 (in flight)
+  //   then            k-step 0 from half 2 f's slot, k-step 1 from half 2 f + 1's: the fragments
+  //                   and, per output element, the MFMA order of the two-stage loop (the reads
+  //                   themselves are the tr_read* statements: see there)
+  // So half 2 f + 2 is asked for two K-tiles before its wait and half 2 f + 3 one K-tile before
+  // (the two-stage loop: about one and about one half), and a tile's reads come one barrier after
+  // the wait that retired its halves, never in the same phase.
+  // The count.  Halves are issued in order and vmcnt retires in order, so "halves 2 f, 2 f + 1
+  // landed" is vmcnt(4 n + e) with n = the halves issued after 2 f + 1 so far and e = the younger
+  // non-DMA entries of the queue.  Before the top of tile f the halves issued are 0 .. 4 (f = 0)
+  // or 0 .. 2 f + 2 (f >= 1), cut off at the sequence's last half 2 total - 1:
+  //   f = 0:  n = 3, or 2 total - 2 when total <= 2 (nk = 1 or 2 on a one-item block: 0 or 2 -- the
+  //           ring never wraps, every half has its own slot);
+  //   f >= 1: n = 1, or 0 on the last tile (the tail: nothing left to issue, so the last tile
+  //           waits vmcnt(0)).  Inside the loop of a longer sequence the count is never 0.
+  // Item change (a persistent block): the sequence is flat, so the halves above are the NEXT item's
+  // and stay in flight across the epilogue; f >= 1 there.  The epilogue's stores are younger than
+  // every half issued so far: with one 16-byte buffer store per accumulator block from every lane
+  // (rows / columns past M / N leave through an out-of-range offset, as in the bf16 kernels) they
+  // are exactly e = E_RING entries.  When the stores are not that uniform (unaligned C, N % 4) e
+  // stays 0: a count that is too small only waits for more.  A timeline stamp before the wait is
+  // one more entry.  The block's last item is followed by nothing: its tile waited vmcnt(0) and
+  // passed a barrier, which is what staging the slab through the (whole) ring needs.
+  int ring_epi = 0;   // E_RING when the previous item's stores were counted
+  auto ring_wait = [&](int f) {
+    const int st = stamp_st();
+    const int n = f == 0 ? (total > 2 ? 3 : 2 * total - 2) : (f + 1 < total ? 1 : 0);
+    if (n == 1 && !ring_epi) {   // steady state
+      if (st) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else {
+      wait_vm_n(4 * n + ring_epi + st);
+    }
+    ring_epi = 0;
     stamp();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -677,6 +838,53 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
 
   for (int it = 0, f = 0; it < my_items; ++it) {
   for (int kk = 0; kk < nk; ++kk, ++f) {
+    if constexpr (RING) {
+      const bf16_t* h0 = smem + ring_r;
+      const bf16_t* h1 = smem + ring_adv(ring_r, 1);
+      ring_r = ring_adv(ring_r, 2);
+      // fragment reads as asm statements (tr_read*: the compiler must not see them, or it drains
+      // the ring).  Raw halves r[0] = A row block 0, r[1..4] = B column blocks 0..3 -- what the
+      // first four MFMAs need, valid when tr_read5_wait ends -- and r[5..7] = A row blocks 1..3,
+      // in flight until tr_wait3_8 below.
+      auto addr_half = [&](const bf16_t* hs, unsigned* ad) {
+        ad[0] = frag_tr_addr(hs, wr * (BM / WM), lane);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) ad[1 + j] = frag_tr_addr(hs + A_HALF, wc * (BN / WN) + j * 16, lane);
+#pragma unroll
+        for (int ii = 1; ii < TM; ++ii) ad[4 + ii] = frag_tr_addr(hs, wr * (BM / WM) + ii * 16, lane);
+      };
+      auto row0 = [&](const s16x4* lo, const s16x4* hi) {
+        const bf16x8 a0 = join_bf16x8(lo[0], hi[0]);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[0][j] = mfma16x16x32(join_bf16x8(lo[1 + j], hi[1 + j]), a0, acc[0][j]);
+      };
+      auto rows123 = [&](const s16x4* lo, const s16x4* hi) {
+#pragma unroll
+        for (int ii = 1; ii < TM; ++ii) {
+          const bf16x8 a = join_bf16x8(lo[4 + ii], hi[4 + ii]);
+#pragma unroll
+          for (int j = 0; j < TN; ++j) acc[ii][j] = mfma16x16x32(join_bf16x8(lo[1 + j], hi[1 + j]), a, acc[ii][j]);
+        }
+      };
+      static_assert(TM == 4 && TN == 4 && SWAP, "the tr_read* groups are written for 4 x 4 fragments");
+      unsigned ad0[8], ad1[8];
+      s16x4 r0lo[8], r0hi[8], r1lo[8], r1hi[8];
+      addr_half(h0, ad0);
+      addr_half(h1, ad1);
+      ring_wait(f);
+      tr_read5_wait(r0lo, r0hi, ad0);                    // k-step 0: A 0, B 0..3
+      tr_read3(r0lo + 5, r0hi + 5, ad0 + 5);             // k-step 0: A 1..3
+      tr_read4(r1lo, r1hi, ad1);                         // k-step 1: A 0, B 0..2
+      tr_read4(r1lo + 4, r1hi + 4, ad1 + 4);             // k-step 1: B 3, A 1..3
+      if (f >= 1 && f + 1 < total) ring_issue1();        // half 2 f + 3 into half 2 f - 2's slot
+      if (f >= 1 && f + 2 < total) ring_issue0();        // half 2 f + 4 into half 2 f - 1's slot
+      row0(r0lo, r0hi);
+      tr_wait3_8(r0lo + 5, r0hi + 5, r1lo, r1hi);        // (long landed: the issues above took longer)
+      rows123(r0lo, r0hi);
+      row0(r1lo, r1hi);
+      rows123(r1lo, r1hi);
+      continue;
+    }
     if constexpr (!PIPE) {
       // barrier for tile f, then per k-step: fragment reads, half of tile f + NST - 1's DMA
       // pieces (their issue time overlaps the LDS latency), MFMAs
@@ -823,6 +1031,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
     } else {
       // lane holds C[16 ii + (lane & 15)][16 j + 4 g + 0..3]
       const bool vec = (p.ldc & 3) == 0 && (p.sC & 3) == 0 && ((((uintptr_t)p.C) & 15) == 0);
+      [[maybe_unused]] const bool ring_exact = RING && vec && (p.N & 3) == 0;
       if constexpr (BN / WN == 64 && WM * WN * (BM / WM) * 256 <= NST * STAGE * 2) {
         if (slabs && vec && (p.flags & kSlabVst) && it + 1 == my_items && !has_bias && !relu && !accumulate) {
           // no DMA is in flight after the block's last item: once every wave's last fragment reads
@@ -882,6 +1091,16 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
             if (relu) v[e] = fmaxf(v[e], 0.f);
           }
           acc[ii][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if constexpr (RING) {
+            if (ring_exact) {   // every lane stores: the next wait counts these E_RING entries
+              const bool ok = row < p.M && col < p.N;   // N % 4 == 0: chunks are whole
+              const int off = ok ? (int)((cb + (long)row * p.ldc + col) * 4) : 0x7ffffff0;
+              const u32x4 bits = __builtin_bit_cast(u32x4, v);
+              if (st_sc1) __builtin_amdgcn_raw_buffer_store_b128(bits, rc, off, 0, kSC1);
+              else __builtin_amdgcn_raw_buffer_store_b128(bits, rc, off, 0, 0);
+              continue;
+            }
+          }
           if (row >= p.M || col >= p.N) continue;
           float* C = reinterpret_cast<float*>(p.C) + cb + (long)row * p.ldc + col;
           if (p.splitk > 1 && !slabs) {
@@ -903,7 +1122,9 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
       }
       // drain before the next item's counted waits; after the block's last item the wave just
       // ends (its stores complete on their own and the CU is free for the next block sooner)
-      if (it + 1 < my_items) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      // (RING: no drain -- the next item's halves are in flight and the next wait counts the stores)
+      if constexpr (RING) ring_epi = ring_exact ? E_RING : 0;
+      else if (it + 1 < my_items) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     // the next item's first tile (f): its barrier, k-step 0 fragments and the DMA of tile
     // f + NST - 1 (the stage of tile f - 1, read by every wave before this barrier)

@@ -11,7 +11,7 @@ after it, after the barrier) and at its end.  Printed per case, averaged over al
   DMA issue, epilogues)
 * ``tail`` cycles from the last wait to the end (last MFMAs + the last epilogue)
 
-    python scripts/gemm_trace.py [case ...]      cases: qkv out dh dwqkv dwo (default: all)
+    python scripts/gemm_trace.py [case ...]      cases: qkv out dh dwqkv dwqkv6 dwo (default: all but dwqkv6)
 """
 import os
 import sys
@@ -49,6 +49,8 @@ def cases():
     s24 = hip.slab_count(nkt, 24)
     sl8 = torch.empty(s8, 3, 640, 512, device=dev)
     sl24 = torch.empty(s24, 512, 640, device=dev)
+    s6 = hip.slab_count(nkt, 6)
+    sl6 = torch.empty(s6, 3, 640, 512, device=dev)
     return {
         "qkv": (lambda tile: hip.gemm(x, wqkv, qkv, T, 512, 640, 640, 640, 1536, True, True, batch=3, sA=0,
                                       sB=512 * 640, sC=512, tile=tile), 2561),
@@ -56,6 +58,9 @@ def cases():
         "dh": (lambda tile: hip.gemm(dy, won, dh, T, 512, 640, 640, 640, 512, True, True, tile=tile), 1282),
         "dwqkv": (lambda tile: hip.gemm(x, dq[0], sl8, 640, 512, T, 640, 512, 512, False, False, batch=3, sA=0,
                                         sC=640 * 512, splitk=s8, tile=tile, slabs=True, b_list=dq), 1282),
+        # the headline pair's own split: 6 x 43 K-tiles (the stamps hold the first 42 waits)
+        "dwqkv6": (lambda tile: hip.gemm(x, dq[0], sl6, 640, 512, T, 640, 512, 512, False, False, batch=3, sA=0,
+                                         sC=640 * 512, splitk=s6, tile=tile, slabs=True, b_list=dq), 1282),
         "dwo": (lambda tile: hip.gemm(h, dy, sl24, 512, 640, T, 512, 640, 640, False, False, sC=512 * 640,
                                       splitk=s24, tile=tile, slabs=True), 1282),
     }
