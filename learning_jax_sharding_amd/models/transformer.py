@@ -4,15 +4,16 @@ The reference declares the FF layer in comments only (``case6_attention.py:36-40
 ``y = Relu(Win x) Wout``) and maps its ``hidden`` logical axis to ``model``
 (``case6_attention.py:186``).  This layer is the case6 attention block followed
 by that FF block, each with a residual connection; ``fp8=True`` runs the FF
-GEMMs on CDNA4's e4m3 MFMA path.
+GEMMs on CDNA4's e4m3 MFMA path.  ``norm='layer'`` / ``'rms'`` makes it a pre-norm
+layer (``h = x + attn(norm1(x))``, ``y = h + ff(norm2(h))``) that can be stacked.
 """
 from __future__ import annotations
 
-from typing import Any
+from typing import Any, Optional
 
 import torch
 
-from ..nn.layers import FeedForward
+from ..nn.layers import FeedForward, LayerNorm, RMSNorm
 from ..nn.module import Module
 from ..ops import core
 from .attention import MultiHeadAttention, attention_block_flops
@@ -27,12 +28,26 @@ class TransformerLayer(Module):
     ff_dim: int = 2560
     dtype: Any = torch.bfloat16
     fp8: bool = False
+    norm: Optional[str] = None   # None (no normalisation), "layer" or "rms": pre-norm
 
     def setup(self):
         self.attn = MultiHeadAttention(self.query_dim, self.heads, self.dim_head, dtype=self.dtype, name="attn")
         self.ff = FeedForward(self.ff_dim, dtype=self.dtype, fp8=self.fp8, name="ff")
+        if self.norm is not None:
+            if self.norm not in ("layer", "rms"):
+                raise ValueError(f"TransformerLayer norm must be None, 'layer' or 'rms', got {self.norm!r}")
+            # the norms write the compute dtype: their output is the projections' operand as it is
+            cls = LayerNorm if self.norm == "layer" else RMSNorm
+            self.norm1 = cls(dtype=self.dtype, name="norm1")
+            self.norm2 = cls(dtype=self.dtype, name="norm2")
 
     def __call__(self, x):
+        if self.norm is not None:
+            # pre-norm: the skips carry the un-normalised stream.  The attention's stays in its
+            # out-projection's epilogue; the FF's residual is not its input, so it takes
+            # FeedForward's general path
+            h = self.attn(self.norm1(x), residual=x)
+            return self.ff(self.norm2(h), residual=h)
         # h = x + attn(x); y = h + ff(h), both skip connections fused into the output GEMMs'
         # epilogues (x is read in f32 and rounded to the compute dtype there, as convert(x) would)
         h = self.attn(x, residual=x)
@@ -40,6 +55,8 @@ class TransformerLayer(Module):
 
 
 def transformer_layer_flops(batch, seq, dim, heads, dim_head, ff_dim, train: bool) -> float:
+    """Matmul FLOPs of one layer step (the project's convention: the memory-bound norms of a
+    pre-norm layer are not counted)."""
     att = attention_block_flops(batch, seq, dim, heads, dim_head, train)
     ff = 2 * 2 * batch * seq * dim * ff_dim
     return att + (3 * ff if train else ff)

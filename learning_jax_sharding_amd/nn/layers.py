@@ -18,7 +18,8 @@ from . import initializers as init
 from .module import Module, compact
 from .partitioning import with_logical_constraint, with_logical_partitioning
 
-__all__ = ["Dense", "DenseGeneral", "Dropout", "FeedForward", "relu", "gelu", "softmax", "Embed", "LayerNorm"]
+__all__ = ["Dense", "DenseGeneral", "Dropout", "FeedForward", "relu", "gelu", "softmax", "Embed", "LayerNorm",
+           "RMSNorm"]
 
 
 def relu(x):
@@ -194,6 +195,16 @@ class Embed(Module):
                             sharding_from_tile(tile, like=[ids.sharding]), loc)
 
 
+def _fused_norm(x: ShardedArray, scale, bias, epsilon: float, kind: str, dtype) -> Optional[ShardedArray]:
+    """The fused norm (:func:`ops.core.layer_norm`: one HIP kernel per shard forward, one backward)
+    when every local shard is a GPU tensor and the feature dim is whole on each device; else None
+    (host devices, ``eval_shape``'s meta tensors, sharded features, ``LJS_FUSED_NORM=0``)."""
+    from ..ops import kernels as K
+    if not x.local or not all(t.is_cuda for t in x.local.values()) or not K.fused_norm_enabled():
+        return None
+    return core.layer_norm(x, scale, bias, epsilon, kind, dtype)
+
+
 class LayerNorm(Module):
     epsilon: float = 1e-6
     dtype: Any = None
@@ -204,6 +215,9 @@ class LayerNorm(Module):
         d = x.shape[-1]
         scale = self.param("scale", init.ones, (d,), torch.float32) if self.use_scale else None
         bias = self.param("bias", init.zeros, (d,), torch.float32) if self.use_bias else None
+        y = _fused_norm(x, scale, bias, self.epsilon, "layer", _dt.canonicalize(self.dtype) or x.dtype)
+        if y is not None:
+            return y
         xf = core.convert(x, torch.float32)
         mean = core.reduce_mean(xf, -1, keepdims=True)
         xc = core.binary("sub", xf, mean)
@@ -213,4 +227,26 @@ class LayerNorm(Module):
             y = core.binary("mul", y, scale)
         if bias is not None:
             y = core.binary("add", y, bias)
+        return core.convert(y, _dt.canonicalize(self.dtype) or x.dtype)
+
+
+class RMSNorm(Module):
+    """``x * rsqrt(mean(x^2) + epsilon) * scale`` over the last dim, statistics in f32 (no centring,
+    no bias).  On GPU shards with whole features one fused HIP kernel, like :class:`LayerNorm`."""
+
+    epsilon: float = 1e-6
+    dtype: Any = None
+    use_scale: bool = True
+
+    def __call__(self, x: ShardedArray) -> ShardedArray:
+        d = x.shape[-1]
+        scale = self.param("scale", init.ones, (d,), torch.float32) if self.use_scale else None
+        y = _fused_norm(x, scale, None, self.epsilon, "rms", _dt.canonicalize(self.dtype) or x.dtype)
+        if y is not None:
+            return y
+        xf = core.convert(x, torch.float32)
+        ms = core.reduce_mean(core.binary("mul", xf, xf), -1, keepdims=True)
+        y = core.binary("mul", xf, core.unary("rsqrt", core.binary("add", ms, self.epsilon)))
+        if scale is not None:
+            y = core.binary("mul", y, scale)
         return core.convert(y, _dt.canonicalize(self.dtype) or x.dtype)

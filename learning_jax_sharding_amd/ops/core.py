@@ -37,6 +37,7 @@ __all__ = [
     "binary", "unary", "convert", "reshape", "transpose", "reduce_sum", "reduce_mean", "reduce_max",
     "getitem", "dot_general", "dot", "matmul", "einsum", "softmax", "dot_product_attention", "dense",
     "with_sharding_constraint", "asarray_like", "broadcast_to", "where", "concatenate", "mse_loss",
+    "layer_norm",
 ]
 
 
@@ -639,6 +640,34 @@ def einsum(subscripts: str, *operands, preferred_element_type=None, precision=No
 
 def _last_out(a, b, out, rest):
     return "".join(dict.fromkeys(ch for ch in a + b if ch in out or any(ch in s for s in rest)))
+
+
+# ----------------------------------------------------------------------------- layer / rms norm
+def layer_norm(x: ShardedArray, scale: Optional[ShardedArray] = None, bias: Optional[ShardedArray] = None,
+               epsilon: float = 1e-6, kind: str = "layer", dtype=None) -> Optional[ShardedArray]:
+    """LayerNorm (``kind='layer'``) / RMSNorm (``'rms'``) over the last dim, one fused kernel per shard
+    (:func:`.kernels.layer_norm`).  The last dim has to be whole on every device: ``scale`` / ``bias``
+    are replicated onto ``x``'s devices (the transpose of that reshard sums their per-shard gradients)
+    and the output keeps ``x``'s sharding.  With the last dim sharded the row statistics would need an
+    all-reduce of partial sums: returns None, and the caller composes the norm from reductions."""
+    if kind not in ("layer", "rms"):
+        raise ValueError(f"layer_norm kind must be 'layer' or 'rms', got {kind!r}")
+    if x.ndim == 0 or x.tile.tile_shape[-1] > 1:
+        return None
+    out_dtype = _dt.canonicalize(dtype) or x.dtype
+    params = []
+    for name, p in (("scale", scale), ("bias", bias if kind == "layer" else None)):
+        if p is not None:
+            if tuple(p.shape) != (x.shape[-1],):
+                raise ValueError(f"layer_norm: {name} shape {p.shape} != ({x.shape[-1]},)")
+            tgt = _target_for(x.tile, x.shape, p.shape)
+            p = reshard_tile(p, tgt, note=f"norm.{name}") if tgt != p.tile else p
+        params.append(p)
+    s2, b2 = params
+    _plan.record("layer_norm", norm=kind, tiles=x.tile.tile_shape)
+    loc = {d: K.layer_norm(t, s2.local[d] if s2 is not None else None, b2.local[d] if b2 is not None else None,
+                           float(epsilon), kind, out_dtype) for d, t in x.local.items()}
+    return ShardedArray(x.shape, out_dtype, x.sharding, loc)
 
 
 # ----------------------------------------------------------------------------- softmax / attention

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
-           "adam", "rng_fill", "colsum", "supports_cast"]
+           "adam", "rng_fill", "colsum", "supports_cast", "norm"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -85,6 +85,11 @@ _SIGS = {
     "ljs_rng_fill": [c_void_p, c_int, c_int, _LP, _LP, _LP, c_uint, c_uint, c_int, c_float, c_float, c_float,
                      c_float, c_void_p],
     "ljs_dropout": [c_void_p, c_void_p, c_int, c_int, _LP, _LP, _LP, c_uint, c_uint, c_float, c_void_p],
+    "ljs_norm_fwd": [c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_int,
+                     c_int, c_float, c_int, c_void_p],
+    "ljs_norm_bwd": [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                     c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ljs_norm_bwd_ws_bytes": [c_int, c_int],
     "ljs_launch_count": [],
     "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
     "ljs_attn_set_cus": [c_int],
@@ -106,6 +111,7 @@ def lib():
                     fn.argtypes = argt
                     fn.restype = c_int
                 L.ljs_mse_colsum_ws_bytes.restype = c_long
+                L.ljs_norm_bwd_ws_bytes.restype = c_long
                 L.ljs_launch_count.restype = c_long
                 _LIB = L
     return _LIB
@@ -1077,6 +1083,115 @@ class _Softmax(torch.autograd.Function):
 
 def softmax_lastdim(x: torch.Tensor) -> torch.Tensor:
     return _Softmax.apply(x)
+
+
+# ============================================================================ layer / rms norm
+_NORM_KINDS = {"layer": 0, "rms": 1}
+_NORM_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def norm_supported(D: int, dtype: torch.dtype) -> bool:
+    """Whether the fused norm kernels (csrc/kernels/norm.hip) take rows of ``D`` features of ``dtype``."""
+    return D % 8 == 0 and 8 <= D <= 8192 and dtype in _NORM_DTYPES
+
+
+def _norm_in_place(t: torch.Tensor) -> bool:
+    """Whether the kernels can take ``t`` as it is: dense (rows of ``t.shape[-1]`` contiguous elements
+    with no gaps, in any row order - a seq-major activation) and 16-byte aligned."""
+    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and storage_order(t) is not None
+
+
+def _norm_param(p: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if p is None:
+        return None
+    p = p.detach()
+    if p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16:
+        p = p.float().contiguous().clone()
+    return p
+
+
+def _norm_ws(t: torch.Tensor, nbytes: int) -> torch.Tensor:
+    """The backward's ticket / partial-row workspace: one per device, stream and size, so launches
+    that could overlap (two streams) never share ticket words; virtual devices that share a GPU
+    issue on one stream, in order.  A capture takes the device's ``graph`` workspace: captures are
+    made on fresh streams, and a workspace first made inside one would replay its zero-fill.  Never
+    regrown: a captured graph keeps the address it recorded."""
+    tag = "graph" if torch.cuda.is_current_stream_capturing() else str(_stream(t))
+    return _workspace(t.device, f"norm/{tag}/{nbytes}", nbytes)
+
+
+class _Norm(torch.autograd.Function):
+    """LayerNorm / RMSNorm of one shard over its last dim: one HIP launch forward (y, and the rows'
+    mean / rstd for the backward), one backward (dx, d(scale), d(bias); whichever are not needed are
+    skipped).  Rows are independent, so a dense shard is processed in storage order, whatever its
+    row order, and ``y`` / ``dx`` take ``x``'s strides."""
+
+    @staticmethod
+    def forward(ctx, x, scale, bias, eps, kind, out_dtype):
+        D = x.shape[-1]
+        if not _norm_in_place(x):
+            x = x.contiguous()
+        R = x.numel() // D
+        y = torch.empty_strided(x.shape, x.stride(), dtype=out_dtype, device=x.device)
+        layer = kind == "layer"
+        rstd = torch.empty((R,), dtype=torch.float32, device=x.device)
+        mean = torch.empty((R,), dtype=torch.float32, device=x.device) if layer else None
+        sc, bi = _norm_param(scale), _norm_param(bias) if layer else None
+        rc = lib().ljs_norm_fwd(_p(x), int(x.dtype == torch.bfloat16), D, _p(sc), _p(bi), _p(y),
+                                int(out_dtype == torch.bfloat16), D, _p(mean), _p(rstd), R, D, float(eps),
+                                _NORM_KINDS[kind], _stream(x))
+        _ck(rc, "norm_fwd")
+        ctx.save_for_backward(x, sc, mean, rstd)
+        ctx.meta = (kind, R, out_dtype, scale.dtype if scale is not None else None,
+                    bias.dtype if bias is not None else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, sc, mean, rstd = ctx.saved_tensors
+        kind, R, out_dtype, sdt, bdt = ctx.meta
+        D = x.shape[-1]
+        need_dx = ctx.needs_input_grad[0]
+        need_ds = sdt is not None and ctx.needs_input_grad[1]
+        need_db = bdt is not None and kind == "layer" and ctx.needs_input_grad[2]
+        zero_db = bdt is not None and kind != "layer" and ctx.needs_input_grad[2]
+        if g.dtype != out_dtype or g.stride() != x.stride() or g.data_ptr() % 16:
+            # the cotangent in y's dtype and row order
+            g = torch.empty_strided(x.shape, x.stride(), dtype=out_dtype, device=x.device).copy_(g)
+        dx = ds = db = None
+        if need_dx:
+            dx = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
+        if need_ds:
+            ds = torch.empty((D,), dtype=torch.float32, device=x.device)
+        if need_db:
+            db = torch.empty((D,), dtype=torch.float32, device=x.device)
+        if need_dx or need_ds or need_db:
+            ws = _norm_ws(x, lib().ljs_norm_bwd_ws_bytes(R, D)) if need_ds or need_db else None
+            rc = lib().ljs_norm_bwd(_p(x), int(x.dtype == torch.bfloat16), D, _p(g),
+                                    int(out_dtype == torch.bfloat16), D, _p(sc), _p(mean), _p(rstd), _p(dx), D, R, D,
+                                    _NORM_KINDS[kind], _p(ws), _p(ds), _p(db), _stream(x))
+            _ck(rc, "norm_bwd")
+        if ds is not None and sdt != torch.float32:
+            ds = ds.to(sdt)
+        if db is not None and bdt != torch.float32:
+            db = db.to(bdt)
+        if zero_db:
+            db = torch.zeros((D,), dtype=bdt, device=x.device)
+        return dx, ds, db, None, None, None
+
+
+def norm(x: torch.Tensor, scale: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+         kind: str = "layer", out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``kind`` = ``layer``: ``(x - mean) rsqrt(var + eps) scale + bias``; ``rms``: ``x rsqrt(mean(x^2) + eps)
+    scale`` (``bias`` ignored) over the last dim of one shard, statistics in f32; ``x`` and the result f32 or
+    bf16 independently, ``scale`` / ``bias`` ``[D]`` or None."""
+    out_dtype = out_dtype or x.dtype
+    if kind not in _NORM_KINDS:
+        raise ValueError(f"norm kind must be 'layer' or 'rms', got {kind!r}")
+    if not norm_supported(x.shape[-1], x.dtype) or out_dtype not in _NORM_DTYPES:
+        raise NotImplementedError(f"norm kernel: f32 / bf16 rows of 8..8192 features (a multiple of 8), got "
+                                  f"{x.dtype} -> {out_dtype}, D = {x.shape[-1]}")
+    return _Norm.apply(x, scale, bias, float(eps), kind, out_dtype)
 
 
 # ============================================================================ dense / linear

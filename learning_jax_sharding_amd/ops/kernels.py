@@ -56,6 +56,58 @@ def mse_loss(y: torch.Tensor, t: torch.Tensor, scale: float) -> torch.Tensor:
     return ((y.float() - t.float()) ** 2).sum() * scale
 
 
+# ----------------------------------------------------------------------------- layer / rms norm
+def norm_reference(x: torch.Tensor, scale: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+                   kind: str = "layer", out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Plain torch LayerNorm (``kind='layer'``) / RMSNorm (``'rms'``, no bias) over the last dim:
+    f32 statistics, the variance from the centred values."""
+    xc = x.float()
+    if kind == "layer":
+        xc = xc - xc.mean(-1, keepdim=True)
+    y = xc * torch.rsqrt((xc * xc).mean(-1, keepdim=True) + eps)
+    if scale is not None:
+        y = y * scale.float()
+    if bias is not None and kind == "layer":
+        y = y + bias.float()
+    return y.to(out_dtype or x.dtype)
+
+
+_WARNED_NORM_D = set()
+_NORM_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def fused_norm_enabled() -> bool:
+    # LJS_FUSED_NORM=0: LayerNorm / RMSNorm on GPU shards as the composite of elementwise and
+    # reduction ops instead of the fused HIP kernels (A/B timing; escape hatch)
+    return os.environ.get("LJS_FUSED_NORM", "1") != "0"
+
+
+def _hip_norm(x: torch.Tensor, out_dtype: torch.dtype) -> bool:
+    """Whether the fused HIP norm kernels take this shard: a GPU tensor, f32 or bf16 in and out, a
+    feature count that is a multiple of 8 in 8..8192.  Another feature count on a GPU runs the
+    torch formulation there, with a one-time warning per count."""
+    if not use_hip(x) or not fused_norm_enabled():
+        return False
+    D = x.shape[-1] if x.dim() else 0
+    if not (D % 8 == 0 and 8 <= D <= 8192):
+        if D not in _WARNED_NORM_D:
+            _WARNED_NORM_D.add(D)
+            import warnings
+            warnings.warn(f"HIP norm kernels take 8..8192 features in multiples of 8; {D} features run the torch "
+                          "formulation on the GPU")
+        return False
+    return x.dtype in _NORM_DTYPES and out_dtype in _NORM_DTYPES and x.numel() > 0
+
+
+def layer_norm(x: torch.Tensor, scale: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+               kind: str = "layer", out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """LayerNorm / RMSNorm of one shard over its last dim (``scale`` / ``bias``: ``[D]`` or None)."""
+    out_dtype = out_dtype or x.dtype
+    if _hip_norm(x, out_dtype):
+        return _hip().norm(x, scale, bias, eps, kind, out_dtype)
+    return norm_reference(x, scale, bias, eps, kind, out_dtype)
+
+
 # ----------------------------------------------------------------------------- matmuls
 def _to_bmk(a: torch.Tensor, batch, free, contract):
     perm = list(batch) + list(free) + list(contract)
