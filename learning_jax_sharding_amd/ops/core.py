@@ -37,7 +37,7 @@ __all__ = [
     "binary", "unary", "convert", "reshape", "transpose", "reduce_sum", "reduce_mean", "reduce_max",
     "getitem", "dot_general", "dot", "matmul", "einsum", "softmax", "dot_product_attention", "dense",
     "with_sharding_constraint", "asarray_like", "broadcast_to", "where", "concatenate", "mse_loss",
-    "layer_norm",
+    "layer_norm", "softmax_cross_entropy",
 ]
 
 
@@ -668,6 +668,55 @@ def layer_norm(x: ShardedArray, scale: Optional[ShardedArray] = None, bias: Opti
     loc = {d: K.layer_norm(t, s2.local[d] if s2 is not None else None, b2.local[d] if b2 is not None else None,
                            float(epsilon), kind, out_dtype) for d, t in x.local.items()}
     return ShardedArray(x.shape, out_dtype, x.sharding, loc)
+
+
+# ----------------------------------------------------------------------------- softmax cross-entropy
+def softmax_cross_entropy(logits: ShardedArray, labels: ShardedArray) -> ShardedArray:
+    """Softmax cross-entropy with integer labels over the last dim: ``logsumexp(logits) - logits[label]``
+    per row, f32 of shape ``logits.shape[:-1]``.  A label < 0 marks an ignored row (loss 0, zero gradient).
+
+    ``labels`` are resharded onto the logits' row tiling.  With the last dim whole on every device
+    one fused kernel per shard (:func:`.kernels.softmax_xent`) gives the loss rows, which keep the
+    row sharding.  With the last dim sharded (a vocab-parallel LM head) every shard gives its rows'
+    ``(m_i, log s_i, t_i)`` (:func:`.kernels.softmax_xent_stats`: the shard's maximum, sum-exp around
+    it, and target logit minus maximum where it owns the label); the ``[3, rows]`` statistics are
+    all-gathered over the vocabulary group and merged on every member,
+
+        M = max m_i,   S = sum s_i e^(m_i - M),   loss = log S - sum own_i (t_i + m_i - M),
+
+    so the result is replicated over the vocabulary axis.  Autograd through the merge and the
+    gather's transpose hands each shard's backward kernel its two row coefficients,
+    ``g s_i e^(m_i - M) / S`` and ``g own_i``; the maximum and the sum stay two values throughout."""
+    nd = logits.ndim
+    if nd < 1 or tuple(labels.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"softmax_cross_entropy: labels shape {tuple(labels.shape)} != logits shape "
+                         f"{tuple(logits.shape)} without its last dim")
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"softmax_cross_entropy: labels must be int32 or int64, got {labels.dtype}")
+    rows = logits.tile.project(list(range(nd - 1)))
+    lab = reshard_tile(labels, rows, note="xent.labels") if labels.tile != rows else labels
+    nv = logits.tile.tile_shape[-1]
+    _plan.record("softmax_xent", vocab_shards=nv)
+    sh = sharding_from_tile(rows, like=[logits.sharding])
+    if nv == 1:
+        loc = {d: K.softmax_xent(t, lab.local[d]) for d, t in logits.local.items()}
+        return ShardedArray(tuple(logits.shape[:-1]), torch.float32, sh, loc)
+    vl = logits.tile.shard_shape(logits.shape)[-1]
+    stats = {}
+    for d, t in logits.local.items():
+        m, ls, tt = K.softmax_xent_stats(t, lab.local[d], logits.tile.coords[d][-1] * vl)
+        stats[d] = torch.stack([m.float(), ls.float(), tt.float()]).unsqueeze(0)
+    gathered = C.all_gather(stats, logits.tile.groups_along([nd - 1]), 0, note="xent.stats")
+    loc = {}
+    for d, st in gathered.items():
+        l = lab.local[d]
+        mi, ls, ti = st[:, 0].detach(), st[:, 1], st[:, 2]
+        rel = mi - mi.amax(0)                                                   # m_i - M
+        lo = (torch.arange(nv, device=l.device) * vl).view((nv,) + (1,) * l.dim())
+        own = ((l >= lo) & (l < lo + vl)).to(st.dtype)
+        loss = torch.log((torch.exp(ls) * torch.exp(rel)).sum(0)) - (own * (ti + rel)).sum(0)
+        loc[d] = torch.where(l >= 0, loss, torch.zeros_like(loss))
+    return ShardedArray(tuple(logits.shape[:-1]), torch.float32, sh, loc)
 
 
 # ----------------------------------------------------------------------------- softmax / attention

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
-           "adam", "rng_fill", "colsum", "supports_cast", "norm"]
+           "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -90,6 +90,11 @@ _SIGS = {
     "ljs_norm_bwd": [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
                      c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "ljs_norm_bwd_ws_bytes": [c_int, c_int],
+    "ljs_xent_fwd": [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                     c_int, c_void_p],
+    "ljs_xent_bwd": [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                     c_long, c_long, c_int, c_void_p],
+    "ljs_xent_wave_max_v": [],
     "ljs_launch_count": [],
     "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
     "ljs_attn_set_cus": [c_int],
@@ -1192,6 +1197,133 @@ def norm(x: torch.Tensor, scale: Optional[torch.Tensor], bias: Optional[torch.Te
         raise NotImplementedError(f"norm kernel: f32 / bf16 rows of 8..8192 features (a multiple of 8), got "
                                   f"{x.dtype} -> {out_dtype}, D = {x.shape[-1]}")
     return _Norm.apply(x, scale, bias, float(eps), kind, out_dtype)
+
+
+# ============================================================================ softmax cross-entropy
+_XENT_DTYPES = (torch.float32, torch.bfloat16)
+_XENT_LABELS = (torch.int32, torch.int64)
+
+
+def __getattr__(name):
+    # XENT_WAVE_MAX_V: the widest row (elements) that takes the one-wave-per-row mapping of the
+    # cross-entropy kernels; wider rows take one block each.  Read from the library, not repeated.
+    if name == "XENT_WAVE_MAX_V":
+        return int(lib().ljs_xent_wave_max_v())
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def xent_supported(logits: torch.Tensor, labels: torch.Tensor) -> bool:
+    """Whether the fused cross-entropy kernels (csrc/kernels/xent.hip) take these: f32 or bf16 logits
+    of any vocabulary size >= 1, int32 or int64 labels of the logits' leading shape, not empty."""
+    return (logits.dim() >= 1 and logits.dtype in _XENT_DTYPES and labels.dtype in _XENT_LABELS
+            and tuple(labels.shape) == tuple(logits.shape[:-1]) and 1 <= logits.shape[-1] < 2 ** 31
+            and logits.numel() > 0)
+
+
+def _xent_rows(x: torch.Tensor):
+    """``x`` as rows of its last dim for the kernels: (tensor kept alive, row count, row stride).
+    A matrix whose rows are contiguous is taken as it is, whatever its row stride; anything else
+    as its contiguous copy."""
+    V = x.shape[-1]
+    if x.dim() == 2 and x.stride(1) == 1 and (x.stride(0) >= V or x.shape[0] == 1):
+        return x, x.shape[0], max(x.stride(0), V)
+    x = x.contiguous()
+    return x, x.numel() // V, V
+
+
+def _xent_fwd(x: torch.Tensor, labels: torch.Tensor, vocab_offset: int, want_loss: bool):
+    xr, R, ld = _xent_rows(x.detach())
+    V = x.shape[-1]
+    lab = labels.detach().reshape(-1).contiguous()
+    m, s, t = (torch.empty((R,), dtype=torch.float32, device=x.device) for _ in range(3))
+    loss = torch.empty((R,), dtype=torch.float32, device=x.device) if want_loss else None
+    rc = lib().ljs_xent_fwd(_p(xr), int(xr.dtype == torch.bfloat16), ld, _p(lab), int(lab.dtype == torch.int64),
+                            int(vocab_offset), _p(m), _p(s), _p(t), _p(loss), R, V, _stream(x))
+    _ck(rc, "xent_fwd")
+    return xr, ld, lab, m, s, t, loss
+
+
+def _xent_bwd(xr: torch.Tensor, ld: int, lab: torch.Tensor, vocab_offset: int, m, s, a, b, shape) -> torch.Tensor:
+    """dx = a exp(x - m) / s - b onehot(label), a fresh contiguous tensor of ``shape`` in x's dtype."""
+    V = shape[-1]
+    R = lab.numel()
+    dx = torch.empty(shape, dtype=xr.dtype, device=xr.device)
+    a = a.detach().reshape(-1).to(torch.float32).contiguous()
+    b = b.detach().reshape(-1).to(torch.float32).contiguous()
+    rc = lib().ljs_xent_bwd(_p(xr), int(xr.dtype == torch.bfloat16), ld, _p(lab), int(lab.dtype == torch.int64),
+                            int(vocab_offset), _p(m), _p(s), _p(a), _p(b), _p(dx), V, R, V, _stream(xr))
+    _ck(rc, "xent_bwd")
+    return dx
+
+
+class _Xent(torch.autograd.Function):
+    """Softmax cross-entropy rows of one shard that holds the whole vocabulary: one HIP launch
+    forward (the loss rows, and the rows' max / sum-exp for the backward), one backward (dx in the
+    logits' dtype from the logits, the two statistics and the loss rows' cotangent)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        xr, ld, lab, m, s, _, loss = _xent_fwd(logits, labels, 0, True)
+        ctx.save_for_backward(xr, lab, m, s)
+        ctx.meta = (ld, tuple(logits.shape))
+        return loss.view(logits.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        xr, lab, m, s = ctx.saved_tensors
+        ld, shape = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return _xent_bwd(xr, ld, lab, 0, m, s, g, g, shape), None
+
+
+class _XentStats(torch.autograd.Function):
+    """The statistics of one vocabulary shard: ``(m, log s, t)`` per row, ``m`` the shard's row maximum
+    (not differentiable: the loss does not depend on it), ``s = sum exp(x - m)``, ``t = x[label] - m`` where
+    the shard owns the label, else 0.  With ``m`` held constant d(log s)/dx = exp(x - m) / s and
+    dt/dx = onehot(label), so the cotangents of ``log s`` and ``t`` are the backward kernel's two
+    row coefficients."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, vocab_offset):
+        xr, ld, lab, m, s, t, _ = _xent_fwd(logits, labels, vocab_offset, False)
+        ctx.save_for_backward(xr, lab, m, s)
+        ctx.meta = (ld, tuple(logits.shape), int(vocab_offset))
+        lead = logits.shape[:-1]
+        m = m.view(lead)
+        ctx.mark_non_differentiable(m)
+        return m, torch.log(s).view(lead), t.view(lead)
+
+    @staticmethod
+    def backward(ctx, gm, gls, gt):
+        xr, lab, m, s = ctx.saved_tensors
+        ld, shape, vocab_offset = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        a = gls if gls is not None else torch.zeros_like(m)
+        b = -gt if gt is not None else torch.zeros_like(m)
+        return _xent_bwd(xr, ld, lab, vocab_offset, m, s, a, b, shape), None, None
+
+
+def _xent_check(logits: torch.Tensor, labels: torch.Tensor):
+    if not xent_supported(logits, labels):
+        raise NotImplementedError(f"xent kernels: f32 / bf16 logits [..., V >= 1] with int32 / int64 labels [...], got "
+                                  f"{logits.dtype} {tuple(logits.shape)} and {labels.dtype} {tuple(labels.shape)}")
+
+
+def xent(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """``logsumexp(logits) - logits[label]`` per row over the last dim (the whole vocabulary), f32 of shape
+    ``logits.shape[:-1]``; a label < 0 marks an ignored row (loss 0, zero gradient row)."""
+    _xent_check(logits, labels)
+    return _Xent.apply(logits, labels)
+
+
+def xent_stats(logits: torch.Tensor, labels: torch.Tensor, vocab_offset: int = 0):
+    """``(m, log s, t)`` of one vocabulary shard whose column 0 is global column ``vocab_offset`` (see
+    :class:`_XentStats`); shards merge with ``M = max m_i``, ``S = sum s_i e^(m_i - M)``,
+    ``loss = log S - sum own_i (t_i + m_i - M)``."""
+    _xent_check(logits, labels)
+    return _XentStats.apply(logits, labels, int(vocab_offset))
 
 
 # ============================================================================ dense / linear

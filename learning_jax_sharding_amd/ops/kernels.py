@@ -108,6 +108,53 @@ def layer_norm(x: torch.Tensor, scale: Optional[torch.Tensor], bias: Optional[to
     return norm_reference(x, scale, bias, eps, kind, out_dtype)
 
 
+# ----------------------------------------------------------------------------- softmax cross-entropy
+def fused_xent_enabled() -> bool:
+    # LJS_FUSED_XENT=0: softmax cross-entropy on GPU shards as the torch formulation below instead
+    # of the fused HIP kernels of csrc/kernels/xent.hip (A/B timing; escape hatch)
+    return os.environ.get("LJS_FUSED_XENT", "1") != "0"
+
+
+def _hip_xent(logits: torch.Tensor, labels: torch.Tensor) -> bool:
+    return use_hip(logits) and fused_xent_enabled() and _hip().xent_supported(logits, labels)
+
+
+def xent_stats_reference(logits: torch.Tensor, labels: torch.Tensor, vocab_offset: int = 0):
+    """Plain torch ``(m, log s, t)`` of one vocabulary shard over its last dim, in f64 for f64 logits
+    (the oracle) and f32 otherwise: ``m`` the row maximum (a constant to autograd), ``s = sum exp(x - m)``,
+    ``t = x[label] - m`` where ``vocab_offset <= label < vocab_offset + V``, else 0."""
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    V = x.shape[-1]
+    m = x.detach().amax(-1)
+    s = torch.exp(x - m.unsqueeze(-1)).sum(-1)
+    col = labels.long() - int(vocab_offset)
+    own = (labels >= 0) & (col >= 0) & (col < V)
+    xl = torch.gather(x, -1, col.clamp(0, V - 1).unsqueeze(-1)).squeeze(-1)
+    t = torch.where(own, xl - m, torch.zeros_like(m))
+    return m, torch.log(s), t
+
+
+def softmax_xent_reference(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """Plain torch ``log(sum exp(x - m)) - (x[label] - m)`` per row, 0 where the label is negative."""
+    m, ls, t = xent_stats_reference(logits, labels, 0)
+    return torch.where(labels >= 0, ls - t, torch.zeros_like(ls))
+
+
+def softmax_xent(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """Softmax cross-entropy rows of one shard that holds the whole vocabulary: f32 of shape
+    ``logits.shape[:-1]``; a label < 0 marks an ignored row (loss 0, zero gradient)."""
+    if _hip_xent(logits, labels):
+        return _hip().xent(logits, labels)
+    return softmax_xent_reference(logits, labels)
+
+
+def softmax_xent_stats(logits: torch.Tensor, labels: torch.Tensor, vocab_offset: int = 0):
+    """``(m, log s, t)`` of one vocabulary shard whose column 0 is global column ``vocab_offset``."""
+    if _hip_xent(logits, labels):
+        return _hip().xent_stats(logits, labels, vocab_offset)
+    return xent_stats_reference(logits, labels, vocab_offset)
+
+
 # ----------------------------------------------------------------------------- matmuls
 def _to_bmk(a: torch.Tensor, batch, free, contract):
     perm = list(batch) + list(free) + list(contract)
