@@ -27,12 +27,19 @@ def _sources(sub):
     return sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith((".hip", ".cpp")))
 
 
+def _headers():
+    d = os.path.join(HERE, "kernels")
+    return sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith(".h"))
+
+
 def _digest(files):
+    """Of the sources and of every kernel header (name and bytes): an edit to any of them, or a new
+    header, makes the stamp of a built library stale."""
     h = hashlib.sha256()
-    for f in files + [os.path.join(HERE, "kernels", "common.h")]:
-        if os.path.exists(f):
-            with open(f, "rb") as fh:
-                h.update(fh.read())
+    for f in files + _headers():
+        h.update(os.path.basename(f).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
     h.update(" ".join(FLAGS).encode())
     return h.hexdigest()[:16]
 

@@ -1,7 +1,7 @@
 // Memory-bound kernels: casts (optionally transposing), reductions, softmax, fused Adam,
 // Philox RNG.  All vectorised to 16 bytes per lane (CDNA Guideline 13); grid-stride loops
 // capped at 2048 workgroups so one launch fills the 256 CUs without oversubscription.
-#include "common.h"
+#include "rowwise.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <algorithm>
@@ -21,14 +21,9 @@ __global__ void cast_f32_bf16(const float* __restrict__ in, bf16_t* __restrict__
   long i8 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
   long stride = (long)gridDim.x * blockDim.x * 8;
   for (; i8 + 8 <= n; i8 += stride) {
-    f32x4 a = *reinterpret_cast<const f32x4*>(in + i8);
-    f32x4 b = *reinterpret_cast<const f32x4*>(in + i8 + 4);
-    u32x4 o;
-    o[0] = pack_bf16x2(a[0], a[1]);
-    o[1] = pack_bf16x2(a[2], a[3]);
-    o[2] = pack_bf16x2(b[0], b[1]);
-    o[3] = pack_bf16x2(b[2], b[3]);
-    *reinterpret_cast<u32x4*>(out + i8) = o;
+    float v[8];
+    load_chunk8(in + i8, v);
+    store_chunk(out + i8, v);
   }
   if (i8 < n) for (long j = i8; j < n; ++j) out[j] = f2bf(in[j]);
 }
@@ -41,10 +36,10 @@ __global__ void cast_bf16_f32(const bf16_t* __restrict__ in, float* __restrict__
     f32x4 a, b;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      a[2 * k] = __uint_as_float(v[k] << 16);
-      a[2 * k + 1] = __uint_as_float(v[k] & 0xffff0000u);
-      b[2 * k] = __uint_as_float(v[k + 2] << 16);
-      b[2 * k + 1] = __uint_as_float(v[k + 2] & 0xffff0000u);
+      a[2 * k] = bf16_lo(v[k]);
+      a[2 * k + 1] = bf16_hi(v[k]);
+      b[2 * k] = bf16_lo(v[k + 2]);
+      b[2 * k + 1] = bf16_hi(v[k + 2]);
     }
     *reinterpret_cast<f32x4*>(out + i8) = a;
     *reinterpret_cast<f32x4*>(out + i8 + 4) = b;
@@ -93,18 +88,11 @@ __global__ __launch_bounds__(256) void cast_transpose_f32_bf16(const float* __re
 
 // ------------------------------------------------------------------ reductions
 template <typename T>
-__device__ __forceinline__ float ldv(const T* p, long i);
-template <>
-__device__ __forceinline__ float ldv<float>(const float* p, long i) { return p[i]; }
-template <>
-__device__ __forceinline__ float ldv<bf16_t>(const bf16_t* p, long i) { return bf2f(p[i]); }
-
-template <typename T>
 __global__ void sum_all_kernel(const T* __restrict__ in, long n, float* __restrict__ out) {
   float s = 0.f;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) s += ldv<T>(in, i);
+  for (; i < n; i += stride) s += load1(in + i);
   s = warp_sum64(s);
   __shared__ float part[16];
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -114,6 +102,18 @@ __global__ void sum_all_kernel(const T* __restrict__ in, long n, float* __restri
     float t = 0.f;
     for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += part[k];
     atomicAdd(out, t);
+  }
+}
+
+// s += the E elements of one 16-byte chunk: pairwise for bf16 (each word's two halves first)
+template <typename T>
+__device__ __forceinline__ void add_chunk(float& s, const u32x4& v) {
+  if constexpr (sizeof(T) == 2) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += bf16_lo(v[k]) + bf16_hi(v[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += __uint_as_float(v[k]);
   }
 }
 
@@ -125,18 +125,9 @@ __global__ void sum_all_vec_kernel(const T* __restrict__ in, long n, float* __re
   long nv = n / V;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < nv; i += stride) {
-    u32x4 v = *reinterpret_cast<const u32x4*>(in + i * V);
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s += __uint_as_float(v[k] << 16) + __uint_as_float(v[k] & 0xffff0000u);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s += __uint_as_float(v[k]);
-    }
-  }
+  for (; i < nv; i += stride) add_chunk<T>(s, *reinterpret_cast<const u32x4*>(in + i * V));
   if (blockIdx.x == 0)
-    for (long j = nv * V + threadIdx.x; j < n; j += blockDim.x) s += ldv<T>(in, j);
+    for (long j = nv * V + threadIdx.x; j < n; j += blockDim.x) s += load1(in + j);
   s = warp_sum64(s);
   __shared__ float part[16];
   int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -149,7 +140,12 @@ __global__ void sum_all_vec_kernel(const T* __restrict__ in, long n, float* __re
   }
 }
 
-constexpr int kGroup = 32, kMaxSumBlocks = 1024;  // sum_all: ticket group size, max grid
+// sum_all: the largest grid, and its persistent workspace in 4-byte words: one f32 partial per
+// block from 0, one per ticket group from kSumGroupPart, then the two-level ticket words
+constexpr int kMaxSumBlocks = 1024, kSumGroups = kMaxSumBlocks / (int)kTicketGroup;
+constexpr int kSumGroupPart = kMaxSumBlocks, kSumTickets = kSumGroupPart + kSumGroups;
+constexpr int kSumWsWords = kSumTickets + 1 + kSumGroups;
+static_assert(kSumWsWords == 1089, "ops/hip.py allocates the sum_all workspace by this size");
 
 // Whole-array sum with the in-launch last-arriver reduction: no memset, no second kernel, and
 // the result is written directly in the output dtype (f32 or bf16).
@@ -162,56 +158,37 @@ __global__ void sum_all_ticket_kernel(const T* __restrict__ in, long n, float* _
   float s = 0.f;
   const long nv = n / V;
   const long stride = (long)gridDim.x * blockDim.x;
-  auto acc = [&](const u32x4& v) {
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s += __uint_as_float(v[k] << 16) + __uint_as_float(v[k] & 0xffff0000u);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s += __uint_as_float(v[k]);
-    }
-  };
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + (U - 1) * stride < nv; i += U * stride) {
     u32x4 v[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) v[u] = *reinterpret_cast<const u32x4*>(in + (i + u * stride) * V);
 #pragma unroll
-    for (int u = 0; u < U; ++u) acc(v[u]);
+    for (int u = 0; u < U; ++u) add_chunk<T>(s, v[u]);
   }
-  for (; i < nv; i += stride) acc(*reinterpret_cast<const u32x4*>(in + i * V));
+  for (; i < nv; i += stride) add_chunk<T>(s, *reinterpret_cast<const u32x4*>(in + i * V));
   if (blockIdx.x == 0)
-    for (long j = nv * V + threadIdx.x; j < n; j += blockDim.x) s += ldv<T>(in, j);
+    for (long j = nv * V + threadIdx.x; j < n; j += blockDim.x) s += load1(in + j);
   s = warp_sum64(s);
   __shared__ float part[16];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) part[w] = s;
   __syncthreads();
   if (w == 0) {
-    // two-level last-arriver: one ticket word per group of kGroup blocks, then one top ticket
-    // over the groups (a single word retires only ~88 arrivals/us, so 1024 arrivals on one
-    // word would serialise for ~12 us)
-    const int G = (int)gridDim.x, grp = blockIdx.x / kGroup, ngrp = (G + kGroup - 1) / kGroup;
-    const int in_grp = min(kGroup, G - grp * kGroup);
+    // the two ticket levels drawn one by one: a group's last arriver sums the group's partials
+    // in between, so the overall last arriver reads one value per group
+    const TicketGroup tg = ticket_group(blockIdx.x, gridDim.x);
     if (lane == 0) {
       float t = 0.f;
       for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += part[k];
       sc1_store(partials + blockIdx.x, t);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int last = 0;
-    if (lane == 0) last = ticket_last(ticket + 1 + grp, in_grp);
-    last = __shfl(last, 0, 64);
-    if (!last) return;
-    float v = lane < in_grp ? sc1_load(partials + grp * kGroup + lane) : 0.f;
+    if (!wave_last(ticket + 1 + tg.grp, tg.in_grp)) return;
+    float v = (unsigned)lane < tg.in_grp ? sc1_load(partials + tg.grp * kTicketGroup + lane) : 0.f;
     v = warp_sum64(v);
-    if (lane == 0) sc1_store(partials + kMaxSumBlocks + grp, v);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = 0;
-    if (lane == 0) last = ticket_last(ticket, ngrp);
-    last = __shfl(last, 0, 64);
-    if (!last) return;
-    v = lane < ngrp ? sc1_load(partials + kMaxSumBlocks + lane) : 0.f;
+    if (lane == 0) sc1_store(partials + kSumGroupPart + tg.grp, v);
+    if (!wave_last(ticket, tg.ngrp)) return;
+    v = (unsigned)lane < tg.ngrp ? sc1_load(partials + kSumGroupPart + lane) : 0.f;
     v = warp_sum64(v);
     if (lane == 0) {
       if (out_bf16) *reinterpret_cast<bf16_t*>(out) = f2bf(v);
@@ -248,8 +225,8 @@ __global__ void colsum_ticket_kernel(const bf16_t* __restrict__ in, int R, int C
   auto add = [&](const u32x4& v) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      acc[2 * k] += __uint_as_float(v[k] << 16);
-      acc[2 * k + 1] += __uint_as_float(v[k] & 0xffff0000u);
+      acc[2 * k] += bf16_lo(v[k]);
+      acc[2 * k + 1] += bf16_hi(v[k]);
     }
   };
   if (c0 < C && mask) {
@@ -296,8 +273,8 @@ __global__ void colsum_ticket_kernel(const bf16_t* __restrict__ in, int R, int C
     float s = 0.f;
     for (int r = 0; r < 32; ++r) s += red[r][lane];
     if (c < C) sc1_store(partials + (long)blockIdx.y * C + c, s);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) last_s = ticket_last(tickets + blockIdx.x, gridDim.y);
+    const bool last = lane0_last(tickets + blockIdx.x, gridDim.y);
+    if (lane == 0) last_s = last;
   }
   __syncthreads();
   if (!last_s) return;
@@ -349,8 +326,7 @@ __device__ __forceinline__ f32x4 ld_slab4(const ST* __restrict__ p, long e) {
     return *(const __attribute__((address_space(1))) f32x4*)(reinterpret_cast<const float*>(p) + e);
   } else {
     const u32x2 r = *(const __attribute__((address_space(1))) u32x2*)(reinterpret_cast<const bf16_t*>(p) + e);
-    return f32x4{__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16),
-                 __uint_as_float(r[1] & 0xffff0000u)};
+    return unpack_bf16x4(r);
   }
 }
 
@@ -441,8 +417,8 @@ __global__ void colsum_vec_kernel(const bf16_t* __restrict__ in, int R, int C, l
       u32x4 v = *reinterpret_cast<const u32x4*>(in + (long)r * ld + c0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        acc[2 * k] += __uint_as_float(v[k] << 16);
-        acc[2 * k + 1] += __uint_as_float(v[k] & 0xffff0000u);
+        acc[2 * k] += bf16_lo(v[k]);
+        acc[2 * k + 1] += bf16_hi(v[k]);
       }
     }
   }
@@ -466,7 +442,7 @@ __global__ void colsum_kernel(const T* __restrict__ in, int R, int C, long ld, f
   int rows_per = (R + gridDim.y - 1) / gridDim.y;
   int r0 = blockIdx.y * rows_per, r1 = min(R, r0 + rows_per);
   float s = 0.f;
-  for (int r = r0; r < r1; ++r) s += ldv<T>(in, (long)r * ld + c);
+  for (int r = r0; r < r1; ++r) s += load1(in + (long)r * ld + c);
   atomicAdd(out + c, s);
 }
 
@@ -507,7 +483,7 @@ __global__ void adam_kernel(const float* __restrict__ p, const G* __restrict__ g
       f32x4 vv = *reinterpret_cast<const f32x4*>(v + i);
       f32x4 gg;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) gg[k] = ldv<G>(g, i + k);
+      for (int k = 0; k < 4; ++k) gg[k] = load1(g + i + k);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
@@ -520,7 +496,7 @@ __global__ void adam_kernel(const float* __restrict__ p, const G* __restrict__ g
       *reinterpret_cast<f32x4*>(vo + i) = vv;
     } else {
       for (long j = i; j < n; ++j) {
-        float gg = ldv<G>(g, j);
+        float gg = load1(g + j);
         float mm = b1 * m[j] + (1.f - b1) * gg;
         float vv = b2 * v[j] + (1.f - b2) * gg * gg;
         float u = (mm * inv_bc1) / (sqrtf(vv) * inv_sqrt_bc2 + eps) + wd * p[j];
@@ -605,14 +581,9 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamBatch batch, i
     long i8 = ((long)cb * kThreads + threadIdx.x) * 8;
     const long stride = (long)ncb * kThreads * 8;
     for (; i8 + 8 <= cast.n; i8 += stride) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(cast.src + i8);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(cast.src + i8 + 4);
-      u32x4 o;
-      o[0] = pack_bf16x2(a[0], a[1]);
-      o[1] = pack_bf16x2(a[2], a[3]);
-      o[2] = pack_bf16x2(c[0], c[1]);
-      o[3] = pack_bf16x2(c[2], c[3]);
-      *reinterpret_cast<u32x4*>(cast.dst + i8) = o;
+      float v[8];
+      load_chunk8(cast.src + i8, v);
+      store_chunk(cast.dst + i8, v);
     }
     if (i8 < cast.n)
       for (long j = i8; j < cast.n; ++j) cast.dst[j] = f2bf(cast.src[j]);
@@ -743,8 +714,7 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamBatch batch, i
         gv[q] = f32x4{c, c, c, c};
       } else if (T.g_bf16) {
         const u32x2 raw = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(T.g) + gi);
-        gv[q] = f32x4{__uint_as_float(raw[0] << 16), __uint_as_float(raw[0] & 0xffff0000u),
-                      __uint_as_float(raw[1] << 16), __uint_as_float(raw[1] & 0xffff0000u)};
+        gv[q] = unpack_bf16x4(raw);
       } else {
         gv[q] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(T.g) + gi);
       }
@@ -968,12 +938,9 @@ __global__ void swap01_bf16_kernel(const T* __restrict__ in, bf16_t* __restrict_
     const long i = ((long)b * S + s) * K8 + k8;
     u32x4 w;
     if constexpr (sizeof(T) == 4) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(in + i * 8);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(in + i * 8 + 4);
-      w[0] = pack_bf16x2(a[0], a[1]);
-      w[1] = pack_bf16x2(a[2], a[3]);
-      w[2] = pack_bf16x2(c[0], c[1]);
-      w[3] = pack_bf16x2(c[2], c[3]);
+      float v[8];
+      load_chunk8(in + i * 8, v);
+      w = pack_bf16x8(v);
     } else {
       w = *reinterpret_cast<const u32x4*>(in + i * 8);
     }
@@ -1065,8 +1032,8 @@ __global__ void sum_n_kernel(SumPtrs sp, int n, long count, T* __restrict__ out)
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            acc[2 * e] += __uint_as_float(v[u][e] << 16);
-            acc[2 * e + 1] += __uint_as_float(v[u][e] & 0xffff0000u);
+            acc[2 * e] += bf16_lo(v[u][e]);
+            acc[2 * e + 1] += bf16_hi(v[u][e]);
           }
         }
       }
@@ -1186,11 +1153,10 @@ LJS_API int ljs_cast_transpose_f32_bf16(const void* in, void* out, int R, int C,
 }
 
 // out (scalar, f32 or bf16 per out_bf16) = sum(in); in is f32 (is_bf16=0) or bf16.
-// ws: persistent workspace of >= 1089 floats whose ticket words are zero at rest.
+// ws: persistent workspace of >= kSumWsWords (1089) floats whose ticket words are zero at rest.
 LJS_API int ljs_sum_all(const void* in, int is_bf16, long n, void* out, int out_bf16, void* ws, hipStream_t s) {
-  // ws layout: [partials: kMaxSumBlocks][group partials: 32][top ticket][group tickets: 32]
   float* partials = (float*)ws;
-  unsigned* ticket = (unsigned*)ws + kMaxSumBlocks + 32;
+  unsigned* ticket = (unsigned*)ws + kSumTickets;
   const bool aligned = (((uintptr_t)in) & 15) == 0;
   if (aligned) {
     // one batch of U = 16 independent 16-byte loads per thread covers the array (21 MB of the

@@ -5,7 +5,8 @@
 // the backward of the loss costs no kernel of its own and y / t are read once.  The scalar is
 // reduced in-launch by the last-arriving workgroup (two-level ticket, no memset, no second
 // kernel).  16-byte loads, 8 elements per lane per iteration, several iterations in flight.
-#include "common.h"
+#include "rowwise.h"
+#include <type_traits>
 
 namespace {
 
@@ -20,38 +21,21 @@ __global__ void __launch_bounds__(256) mse_kernel(const bf16_t* __restrict__ y, 
   const long stride = (long)gridDim.x * blockDim.x;
   const float g2 = 2.f * scale;
   float s = 0.f;
+  using TT = std::conditional_t<kTgtBf16, bf16_t, float>;
+  const TT* t = reinterpret_cast<const TT*>(tgt);
   auto step = [&](long i) {
-    const u32x4 yv = *reinterpret_cast<const u32x4*>(y + i * 8);
-    float tv[8];
-    if constexpr (kTgtBf16) {
-      const u32x4 t = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(tgt) + i * 8);
+    const u32x4 yraw = *reinterpret_cast<const u32x4*>(y + i * 8);
+    float tv[8], d[8];
+    load_chunk8(t + i * 8, tv);
+    unpack_bf16x8(yraw, d);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        tv[2 * k] = __uint_as_float(t[k] << 16);
-        tv[2 * k + 1] = __uint_as_float(t[k] & 0xffff0000u);
-      }
-    } else {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(tgt) + i * 8);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(tgt) + i * 8 + 4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        tv[k] = a[k];
-        tv[4 + k] = b[k];
-      }
-    }
-    float d[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      d[2 * k] = __uint_as_float(yv[k] << 16) - tv[2 * k];
-      d[2 * k + 1] = __uint_as_float(yv[k] & 0xffff0000u) - tv[2 * k + 1];
-    }
+    for (int k = 0; k < 8; ++k) d[k] -= tv[k];
 #pragma unroll
     for (int k = 0; k < 8; ++k) s = fmaf(d[k], d[k], s);
     if constexpr (kWantDy) {
-      u32x4 o;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = pack_bf16x2(g2 * d[2 * k], g2 * d[2 * k + 1]);
-      *reinterpret_cast<u32x4*>(dy + i * 8) = o;
+      for (int k = 0; k < 8; ++k) d[k] *= g2;
+      store_chunk(dy + i * 8, d);
     }
   };
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -64,8 +48,8 @@ __global__ void __launch_bounds__(256) mse_kernel(const bf16_t* __restrict__ y, 
   for (; i < nv; i += stride) step(i);
   if (blockIdx.x == 0) {
     for (long j = nv * 8 + threadIdx.x; j < n; j += blockDim.x) {
-      const float t = kTgtBf16 ? bf2f(reinterpret_cast<const bf16_t*>(tgt)[j]) : reinterpret_cast<const float*>(tgt)[j];
-      const float d = bf2f(y[j]) - t;
+      const float tj = load1(t + j);
+      const float d = bf2f(y[j]) - tj;
       s = fmaf(d, d, s);
       if constexpr (kWantDy) dy[j] = f2bf(g2 * d);
     }
@@ -77,11 +61,7 @@ __global__ void __launch_bounds__(256) mse_kernel(const bf16_t* __restrict__ y, 
   __syncthreads();
   if (w != 0) return;
   if (lane == 0) sc1_store(partials + blockIdx.x, part[0] + part[1] + part[2] + part[3]);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  int last = 0;
-  if (lane == 0) last = ticket_last_2lvl(ticket, blockIdx.x, gridDim.x);
-  last = __shfl(last, 0, 64);
-  if (!last) return;
+  if (!wave_last_2lvl(ticket, blockIdx.x, gridDim.x)) return;
   // the last arriver sums the partials with 4 independent loads in flight per lane
   float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
   const int G = (int)gridDim.x;
@@ -115,13 +95,13 @@ __global__ void __launch_bounds__(256) mse_colsum_kernel(const bf16_t* __restric
   const float g2 = 2.f * scale;
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float s = 0.f;
-  auto one = [&](long r, const u32x4& yv, const float (&tv)[8]) {
+  using TT = std::conditional_t<kTgtBf16, bf16_t, float>;
+  const TT* t = reinterpret_cast<const TT*>(tgt);
+  auto one = [&](long r, const u32x4& yraw, const float (&tv)[8]) {
     float d[8];
+    unpack_bf16x8(yraw, d);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      d[2 * k] = __uint_as_float(yv[k] << 16) - tv[2 * k];
-      d[2 * k + 1] = __uint_as_float(yv[k] & 0xffff0000u) - tv[2 * k + 1];
-    }
+    for (int k = 0; k < 8; ++k) d[k] -= tv[k];
     u32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -129,29 +109,12 @@ __global__ void __launch_bounds__(256) mse_colsum_kernel(const bf16_t* __restric
       s = fmaf(d[2 * k + 1], d[2 * k + 1], s);
       o[k] = pack_bf16x2(g2 * d[2 * k], g2 * d[2 * k + 1]);
       // the bias gradient sums the bf16 values the GEMMs read
-      acc[2 * k] += __uint_as_float(o[k] << 16);
-      acc[2 * k + 1] += __uint_as_float(o[k] & 0xffff0000u);
+      acc[2 * k] += bf16_lo(o[k]);
+      acc[2 * k + 1] += bf16_hi(o[k]);
     }
     *reinterpret_cast<u32x4*>(dy + r * C + c0) = o;
   };
-  auto load_t = [&](long r, float (&tv)[8]) {
-    if constexpr (kTgtBf16) {
-      const u32x4 t = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(tgt) + r * C + c0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        tv[2 * k] = __uint_as_float(t[k] << 16);
-        tv[2 * k + 1] = __uint_as_float(t[k] & 0xffff0000u);
-      }
-    } else {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(tgt) + r * C + c0);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(tgt) + r * C + c0 + 4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        tv[k] = a[k];
-        tv[4 + k] = b[k];
-      }
-    }
-  };
+  auto load_t = [&](long r, float (&tv)[8]) { load_chunk8(t + r * C + c0, tv); };
   if (c0 < C) {
     int r = r0 + rl;
     for (; r + 64 < r1; r += 96) {  // 3 rows in flight per thread
@@ -190,11 +153,10 @@ __global__ void __launch_bounds__(256) mse_colsum_kernel(const bf16_t* __restric
     for (int r = 0; r < 32; ++r) cs += red[r][lane];
     if (c < C) sc1_store(col_part + (long)blockIdx.y * C + c, cs);
     if (lane == 0) sc1_store(loss_part + bid, lred[0] + lred[1] + lred[2] + lred[3]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) {
-      last_col = ticket_last(col_tickets + blockIdx.x, gridDim.y);
-      last_all = ticket_last_2lvl(loss_tickets, bid, nblk);
-    }
+    const bool lc = lane0_last(col_tickets + blockIdx.x, gridDim.y);
+    if (lane == 0) last_col = lc;
+    const bool la = lane0_last_2lvl(loss_tickets, bid, nblk);
+    if (lane == 0) last_all = la;
   }
   __syncthreads();
   // the last row block of this column block sums its column partials: 4 waves x row slices,
@@ -260,39 +222,46 @@ LJS_API int ljs_mse_ws_bytes() { return (kMseMaxBlocks + 33) * 4; }
 
 // Fused loss + dY + dY's column sums over [R][C] (C % 64 == 0, 16-byte aligned rows).  ws: at
 // least ljs_mse_colsum_ws_bytes(R, C) zeroed bytes (tickets re-armed by the kernel).
-static void mse_colsum_geom(int R, int C, int* cb, int* gy, int* rpb) {
-  *cb = C / 64;
-  int want = 1024 / (*cb > 0 ? *cb : 1);         // ~1024 blocks over the whole array
+namespace {
+// grid (cb column blocks x gy row blocks of rpb rows) and the workspace in 4-byte words: ticket
+// words (one per column block, then the two-level loss ticket over all blocks, padded), the column
+// partials [gy][C] from col_part, the loss partials [nblk] from loss_part, words in all
+struct MseColsumPlan {
+  int cb, gy, rpb;
+  long col_part, loss_part, words;
+};
+MseColsumPlan mse_colsum_plan(int R, int C) {
+  MseColsumPlan p;
+  p.cb = C / 64;
+  int want = 1024 / (p.cb > 0 ? p.cb : 1);        // ~1024 blocks over the whole array
   if (want < 1) want = 1;
   int r = (R + want - 1) / want;
   r = ((r + 95) / 96) * 96;                       // whole 3-row groups per row lane
   if (r < 96) r = 96;
-  *rpb = r;
-  *gy = (R + r - 1) / r;
+  p.rpb = r;
+  p.gy = (R + r - 1) / r;
+  const long nblk = (long)p.cb * p.gy;
+  p.col_part = p.cb + 1 + (nblk + 31) / 32 + 64;
+  p.loss_part = p.col_part + (long)p.gy * C;
+  p.words = p.loss_part + nblk + 64;
+  return p;
 }
+}  // namespace
 
-LJS_API long ljs_mse_colsum_ws_bytes(int R, int C) {
-  int cb, gy, rpb;
-  mse_colsum_geom(R, C, &cb, &gy, &rpb);
-  const long nblk = (long)cb * gy;
-  return 4L * (cb + 1 + (nblk + 31) / 32 + 64) + 4L * ((long)gy * C + nblk + 64);
-}
+LJS_API long ljs_mse_colsum_ws_bytes(int R, int C) { return 4 * mse_colsum_plan(R, C).words; }
 
 LJS_API int ljs_mse_colsum(const void* y, const void* tgt, int tgt_bf16, int R, int C, float scale, void* dy,
                            void* colsum, void* out, void* ws, hipStream_t s) {
   if (C % 64 || (((uintptr_t)y) | ((uintptr_t)tgt) | ((uintptr_t)dy)) & 15) return (int)hipErrorInvalidValue;
-  int cb, gy, rpb;
-  mse_colsum_geom(R, C, &cb, &gy, &rpb);
-  const long nblk = (long)cb * gy;
+  const MseColsumPlan p = mse_colsum_plan(R, C);
   unsigned* tickets = (unsigned*)ws;
-  const long nt = cb + 1 + (nblk + 31) / 32 + 64;
-  float* col_part = (float*)ws + nt;
-  float* loss_part = col_part + (long)gy * C;
+  float* col_part = (float*)ws + p.col_part;
+  float* loss_part = (float*)ws + p.loss_part;
   if (tgt_bf16)
-    hipLaunchKernelGGL(mse_colsum_kernel<true>, dim3(cb, gy), dim3(256), 0, s, (const bf16_t*)y, tgt, R, C, rpb,
+    hipLaunchKernelGGL(mse_colsum_kernel<true>, dim3(p.cb, p.gy), dim3(256), 0, s, (const bf16_t*)y, tgt, R, C, p.rpb,
                        scale, (bf16_t*)dy, col_part, loss_part, tickets, (float*)colsum, (float*)out);
   else
-    hipLaunchKernelGGL(mse_colsum_kernel<false>, dim3(cb, gy), dim3(256), 0, s, (const bf16_t*)y, tgt, R, C, rpb,
+    hipLaunchKernelGGL(mse_colsum_kernel<false>, dim3(p.cb, p.gy), dim3(256), 0, s, (const bf16_t*)y, tgt, R, C, p.rpb,
                        scale, (bf16_t*)dy, col_part, loss_part, tickets, (float*)colsum, (float*)out);
   return (int)hipGetLastError();
 }

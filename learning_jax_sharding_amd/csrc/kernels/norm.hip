@@ -20,11 +20,11 @@
 // Backward: dx per row as above; d(gamma) = sum_rows g xhat and d(beta) = sum_rows g are kept per
 // thread over the rows it visits, combined over the block's waves in wave order, written as one
 // f32 partial row per block with write-through stores, and summed in block order by the last
-// arriver of each group of 32 blocks, then in group order by the last group (sc1_store / sc1_load /
-// ticket_last of common.h, as colsum_ticket_kernel).  No memset, no float atomics; the order of
+// arriver of each group of 32 blocks, then in group order by the last group (the block form of
+// rowwise.h's last-arriver hand-off).  No memset, no float atomics; the order of
 // every sum is fixed by (R, D), so the result is the same bits on every run, and the tickets are
 // zero again when the launch ends (a replayed graph finds them armed).
-#include "common.h"
+#include "rowwise.h"
 #include <type_traits>
 
 namespace {
@@ -33,39 +33,9 @@ constexpr int kWaveMaxD = 1024;     // widest row of the wave mapping
 constexpr int kMaxD = 8192;
 constexpr int kFwdWaves = 4;        // wave mapping: waves (= rows in flight) per forward block
 constexpr int kBwdWaves = 8;        //               per backward block
-constexpr int kBlockThreads = 256;  // block mapping
 constexpr int kFwdMaxBlocks = 2048;
 constexpr int kBwdMaxBlocks = 512;  // = partial rows of the parameter gradients
-constexpr int kGroup = 32;          // blocks per first-level ticket
-constexpr int kMaxGroups = kBwdMaxBlocks / kGroup;
-constexpr int kTicketWords = 64;    // 1 + kMaxGroups, padded
-
-__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { v[k] = a[k]; v[4 + k] = b[k]; }
-}
-__device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
-  const u32x4 a = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[2 * k] = __uint_as_float(a[k] << 16);
-    v[2 * k + 1] = __uint_as_float(a[k] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
-  f32x4 a, b;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { a[k] = v[k]; b[k] = v[4 + k]; }
-  *reinterpret_cast<f32x4*>(p) = a;
-  *reinterpret_cast<f32x4*>(p + 4) = b;
-}
-__device__ __forceinline__ void store8(bf16_t* p, const float (&v)[8]) {
-  u32x4 a;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
-  *reinterpret_cast<u32x4*>(p) = a;
-}
+constexpr int kTicketWords = 64;    // 1 + kBwdMaxBlocks / kTicketGroup, padded
 
 // sums of a and b over the row: over the wave, or (BLOCK) over the block's four waves through
 // red[2][4].  The caller gives every sum of a row its own red array and alternates between two
@@ -105,16 +75,8 @@ __device__ __forceinline__ float partial_rows_sum(const float* p, unsigned cnt, 
   return partial_rows_step<1>(p, cnt, n, s);
 }
 
-template <bool BLOCK, int WAVES>
-struct RowMap {
-  static constexpr int W = BLOCK ? kBlockThreads : 64;  // chunk stride between a thread's chunks
-  __device__ static int slot() { return BLOCK ? threadIdx.x : threadIdx.x & 63; }
-  __device__ static long first() { return BLOCK ? blockIdx.x : (long)blockIdx.x * WAVES + (threadIdx.x >> 6); }
-  __device__ static long step() { return BLOCK ? gridDim.x : (long)gridDim.x * WAVES; }
-};
-
 template <bool LAYER, typename TX, typename TY, int NV, int U, bool BLOCK>
-__global__ __launch_bounds__(BLOCK ? kBlockThreads : 64 * kFwdWaves)
+__global__ __launch_bounds__(BLOCK ? kRowBlockThreads : 64 * kFwdWaves)
 void norm_fwd_kernel(const TX* __restrict__ x, long ldx, const float* __restrict__ gamma,
                      const float* __restrict__ beta, TY* __restrict__ y, long ldy, float* __restrict__ mean,
                      float* __restrict__ rstd, int R, int D, float eps) {
@@ -133,8 +95,8 @@ void norm_fwd_kernel(const TX* __restrict__ x, long ldx, const float* __restrict
     cv[i] = col[i] < D;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { gam[i][k] = 1.f; bet[i][k] = 0.f; }
-    if (cv[i] && gamma) load8(gamma + col[i], gam[i]);
-    if (cv[i] && beta) load8(beta + col[i], bet[i]);
+    if (cv[i] && gamma) load_chunk8(gamma + col[i], gam[i]);
+    if (cv[i] && beta) load_chunk8(beta + col[i], bet[i]);
   }
   int par = 0;
   for (long r0 = M::first(); r0 < R; r0 += step * U, par ^= 1) {
@@ -145,7 +107,7 @@ void norm_fwd_kernel(const TX* __restrict__ x, long ldx, const float* __restrict
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         if (row < R && cv[i]) {
-          load8(x + row * ldx + col[i], v[u][i]);
+          load_chunk8(x + row * ldx + col[i], v[u][i]);
         } else {
 #pragma unroll
           for (int k = 0; k < 8; ++k) v[u][i][k] = 0.f;
@@ -198,7 +160,7 @@ void norm_fwd_kernel(const TX* __restrict__ x, long ldx, const float* __restrict
           float o[8];
 #pragma unroll
           for (int k = 0; k < 8; ++k) o[k] = v[u][i][k] * r * gam[i][k] + bet[i][k];
-          store8(y + row * ldy + col[i], o);
+          store_chunk8(y + row * ldy + col[i], o);
         }
       if (slot == 0) {
         rstd[row] = r;
@@ -209,7 +171,7 @@ void norm_fwd_kernel(const TX* __restrict__ x, long ldx, const float* __restrict
 }
 
 template <bool LAYER, typename TX, typename TG, int NV, int U, bool BLOCK>
-__global__ __launch_bounds__(BLOCK ? kBlockThreads : 64 * kBwdWaves)
+__global__ __launch_bounds__(BLOCK ? kRowBlockThreads : 64 * kBwdWaves)
 void norm_bwd_kernel(const TX* __restrict__ x, long ldx, const TG* __restrict__ g, long ldg,
                      const float* __restrict__ gamma, const float* __restrict__ mean,
                      const float* __restrict__ rstd, TX* __restrict__ dx, long lddx, int R, int D,
@@ -232,7 +194,7 @@ void norm_bwd_kernel(const TX* __restrict__ x, long ldx, const TG* __restrict__ 
     cv[i] = col[i] < D;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { gam[i][k] = 1.f; dgam[i][k] = 0.f; dbet[i][k] = 0.f; }
-    if (cv[i] && gamma) load8(gamma + col[i], gam[i]);
+    if (cv[i] && gamma) load_chunk8(gamma + col[i], gam[i]);
   }
   int par = 0;
   for (long r0 = M::first(); r0 < R; r0 += step * U, par ^= 1) {
@@ -243,8 +205,8 @@ void norm_bwd_kernel(const TX* __restrict__ x, long ldx, const TG* __restrict__ 
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         if (row < R && cv[i]) {
-          load8(x + row * ldx + col[i], xv[u][i]);
-          load8(g + row * ldg + col[i], gv[u][i]);
+          load_chunk8(x + row * ldx + col[i], xv[u][i]);
+          load_chunk8(g + row * ldg + col[i], gv[u][i]);
         } else {
 #pragma unroll
           for (int k = 0; k < 8; ++k) { xv[u][i][k] = 0.f; gv[u][i][k] = 0.f; }
@@ -284,7 +246,7 @@ void norm_bwd_kernel(const TX* __restrict__ x, long ldx, const TG* __restrict__ 
             float o[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] = r * (gv[u][i][k] * gam[i][k] - m1 - xv[u][i][k] * m2);
-            store8(dx + row * lddx + col[i], o);
+            store_chunk8(dx + row * lddx + col[i], o);
           }
       }
     }
@@ -328,31 +290,21 @@ void norm_bwd_kernel(const TX* __restrict__ x, long ldx, const TG* __restrict__ 
       if constexpr (LAYER) sc1_store(mine + D + c, acc[1][c]);
     }
   }
-  // every storing wave drains its stores, then one lane draws the group's ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const unsigned nb = gridDim.x, grp = blockIdx.x / kGroup, ngrp = (nb + kGroup - 1) / kGroup;
-  const unsigned in_grp = nb - grp * kGroup < (unsigned)kGroup ? nb - grp * kGroup : (unsigned)kGroup;
-  if (threadIdx.x == 0) last_s = ticket_last(tickets + 1 + grp, in_grp);
-  __syncthreads();
-  if (!last_s) return;
+  const TicketGroup tg = ticket_group(blockIdx.x, gridDim.x);
+  if (!block_last(tickets + 1 + tg.grp, tg.in_grp, &last_s)) return;
 
   // ---- last block of its group: the group's partial rows summed in block order
   const int n = NQ * D;
-  const float* gbase = part + (long)grp * kGroup * n;
+  const float* gbase = part + (long)tg.grp * kTicketGroup * n;
   for (int c = threadIdx.x; c < n; c += blockDim.x) {
-    const float s = partial_rows_sum(gbase + c, in_grp, n);
-    sc1_store(gpart + (long)grp * n + c, s);
+    const float s = partial_rows_sum(gbase + c, tg.in_grp, n);
+    sc1_store(gpart + (long)tg.grp * n + c, s);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();  // (also: every thread has read last_s)
-  if (threadIdx.x == 0) last_s = ticket_last(tickets, ngrp);
-  __syncthreads();
-  if (!last_s) return;
+  if (!block_last(tickets, tg.ngrp, &last_s)) return;
 
   // ---- last group: the group sums in group order
   for (int c = threadIdx.x; c < n; c += blockDim.x) {
-    const float s = partial_rows_sum(gpart + c, ngrp, n);
+    const float s = partial_rows_sum(gpart + c, tg.ngrp, n);
     if (c < D) {
       if (dgamma) dgamma[c] = s;
     } else if (dbeta) {
@@ -385,7 +337,7 @@ int launch_fwd(const char* wave_name, const char* block_name, const void* x, lon
                hipStream_t s) {
   const int cfg = norm_cfg(D);
   const dim3 grid(fwd_grid(R, cfg));
-  const unsigned block = cfg == 2 ? kBlockThreads : 64 * kFwdWaves;
+  const unsigned block = cfg == 2 ? kRowBlockThreads : 64 * kFwdWaves;
 #define LJS_NORM_FWD(NV, U, BLOCK)                                                                              \
   hipLaunchKernelGGL((norm_fwd_kernel<LAYER, TX, TY, NV, U, BLOCK>), grid, dim3(block), 0, s, (const TX*)x, ldx, \
                      (const float*)gamma, (const float*)beta, (TY*)y, ldy, (float*)mean, (float*)rstd, R, D, eps)
@@ -404,7 +356,7 @@ int launch_bwd(const char* wave_name, const char* block_name, const void* x, lon
   const int cfg = norm_cfg(D);
   const int nb = bwd_grid(R, cfg);
   const dim3 grid(nb);
-  const unsigned block = cfg == 2 ? kBlockThreads : 64 * kBwdWaves;
+  const unsigned block = cfg == 2 ? kRowBlockThreads : 64 * kBwdWaves;
   const long n = (LAYER ? 2 : 1) * (long)D;
   unsigned* tickets = (unsigned*)ws;
   float* part = (float*)ws + kTicketWords;
@@ -431,7 +383,7 @@ inline bool shape_ok(int R, int D) { return R >= 1 && D >= 8 && D <= kMaxD && D 
 LJS_API long ljs_norm_bwd_ws_bytes(int R, int D) {
   if (!shape_ok(R, D)) return 0;
   const long nb = bwd_grid(R, norm_cfg(D));
-  const long ngrp = (nb + kGroup - 1) / kGroup;
+  const long ngrp = (nb + kTicketGroup - 1) / kTicketGroup;
   return 4 * (kTicketWords + (nb + ngrp) * 2L * D);
 }
 

@@ -35,7 +35,7 @@
 //   block (V  > 2048): one 256-thread block per row; the four waves' pairs meet in 8 floats of LDS.
 // A row is never split over blocks.  Every output is per row: no atomics, no workspace, no memset,
 // the same bits on every run, nothing to re-arm for a graph replay.  Row offsets are 64-bit.
-#include "common.h"
+#include "rowwise.h"
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -44,47 +44,13 @@ namespace {
 
 constexpr int kWaveMaxV = 2048;     // widest row of the wave mapping
 constexpr int kWaves = 4;           // wave mapping: waves (= rows in flight) per block
-constexpr int kBlockThreads = 256;
+constexpr int kBlockThreads = kRowBlockThreads;  // both mappings
 constexpr int kMaxBlocks = 2048;    // rows beyond the grid are taken by a grid-stride loop
 constexpr int kU = 4;               // 16-byte chunks in flight per thread
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kNegInf = -__builtin_inff();
 
 __device__ __forceinline__ float raw_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ float load1(const float* p) { return *p; }
-__device__ __forceinline__ float load1(const bf16_t* p) { return bf2f(*p); }
-__device__ __forceinline__ void store1(float* p, float v) { *p = v; }
-__device__ __forceinline__ void store1(bf16_t* p, float v) { *p = f2bf(v); }
-
-// one 16-byte chunk: 4 f32 or 8 bf16, at element alignment (memcpy: no 16-byte promise made)
-__device__ __forceinline__ void load_chunk(const float* p, float* v) {
-  f32x4 a;
-  __builtin_memcpy(&a, p, 16);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = a[k];
-}
-__device__ __forceinline__ void load_chunk(const bf16_t* p, float* v) {
-  u32x4 a;
-  __builtin_memcpy(&a, p, 16);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[2 * k] = __uint_as_float(a[k] << 16);
-    v[2 * k + 1] = __uint_as_float(a[k] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void store_chunk(float* p, const float* v) {
-  f32x4 a;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a[k] = v[k];
-  __builtin_memcpy(p, &a, 16);
-}
-__device__ __forceinline__ void store_chunk(bf16_t* p, const float* v) {
-  u32x4 a;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
-  __builtin_memcpy(p, &a, 16);
-}
 
 // running maximum m, nm = -fl(m log2e), dl = m log2e + nm, and s = sum exp(x - m) of the elements
 // seen.  Before the first finite element m = -inf with nm = dl = 0: an element of -inf then adds
@@ -128,13 +94,13 @@ __global__ __launch_bounds__(kBlockThreads)
 void xent_fwd_kernel(const T* __restrict__ x, long ld, const L* __restrict__ labels, long vocab_offset,
                      float* __restrict__ m_out, float* __restrict__ s_out, float* __restrict__ t_out,
                      float* __restrict__ loss, long R, int V) {
-  constexpr int E = 16 / (int)sizeof(T);
-  constexpr int W = BLOCK ? kBlockThreads : 64;  // chunk stride between a thread's chunks
-  __shared__ float red[2][2][4];                 // [row parity][m, s][wave]
-  const int slot = BLOCK ? threadIdx.x : threadIdx.x & 63;
-  const long step = BLOCK ? (long)gridDim.x : (long)gridDim.x * kWaves;
-  long row = BLOCK ? (long)blockIdx.x : (long)blockIdx.x * kWaves + (threadIdx.x >> 6);
-  for (int par = 0; row < R; row += step, par ^= 1) {
+  using M = RowMap<BLOCK, kWaves>;
+  constexpr int E = 16 / (int)sizeof(T), W = M::W;
+  __shared__ float red[2][2][4];  // [row parity][m, s][wave]
+  const int slot = M::slot();
+  const long step = M::step();
+  int par = 0;
+  for (long row = M::first(); row < R; row += step, par ^= 1) {
     const T* p = x + row * ld;
     const long lab = (long)labels[row];
     const long c = lab - vocab_offset;
@@ -148,7 +114,7 @@ void xent_fwd_kernel(const T* __restrict__ x, long ld, const L* __restrict__ lab
       for (int u = 0; u < kU; ++u) {
         const int i = i0 + u * W;
         if (i < nvec) {
-          load_chunk(p + (long)i * E, v + u * E);
+          load_chunk<kElemAligned>(p + (long)i * E, v + u * E);
         } else {
 #pragma unroll
           for (int k = 0; k < E; ++k) v[u * E + k] = kNegInf;  // adds exp2(-inf) = 0
@@ -189,11 +155,11 @@ __global__ __launch_bounds__(kBlockThreads)
 void xent_bwd_kernel(const T* __restrict__ x, long ld, const L* __restrict__ labels, long vocab_offset,
                      const float* __restrict__ m_in, const float* __restrict__ s_in, const float* __restrict__ a_in,
                      const float* __restrict__ b_in, T* __restrict__ dx, long lddx, long R, int V) {
-  constexpr int E = 16 / (int)sizeof(T);
-  constexpr int W = BLOCK ? kBlockThreads : 64;
-  const int slot = BLOCK ? threadIdx.x : threadIdx.x & 63;
-  const long step = BLOCK ? (long)gridDim.x : (long)gridDim.x * kWaves;
-  long row = BLOCK ? (long)blockIdx.x : (long)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  using M = RowMap<BLOCK, kWaves>;
+  constexpr int E = 16 / (int)sizeof(T), W = M::W;
+  const int slot = M::slot();
+  const long step = M::step();
+  long row = M::first();
   for (; row < R; row += step) {
     const T* p = x + row * ld;
     T* q = dx + row * lddx;
@@ -203,7 +169,7 @@ void xent_bwd_kernel(const T* __restrict__ x, long ld, const L* __restrict__ lab
       float z[E];
 #pragma unroll
       for (int k = 0; k < E; ++k) z[k] = 0.f;
-      for (int i = slot; i < nvec; i += W) store_chunk(q + (long)i * E, z);
+      for (int i = slot; i < nvec; i += W) store_chunk<kElemAligned>(q + (long)i * E, z);
       if (te < V) store1(q + te, 0.f);
       continue;
     }
@@ -218,7 +184,7 @@ void xent_bwd_kernel(const T* __restrict__ x, long ld, const L* __restrict__ lab
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const int i = i0 + u * W;
-        if (i < nvec) load_chunk(p + (long)i * E, v + u * E);
+        if (i < nvec) load_chunk<kElemAligned>(p + (long)i * E, v + u * E);
       }
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
@@ -232,7 +198,7 @@ void xent_bwd_kernel(const T* __restrict__ x, long ld, const L* __restrict__ lab
 #pragma unroll
             for (int k = 0; k < E; ++k) o[k] -= c0 + k == cl ? b : 0.f;
           }
-          store_chunk(q + (long)i * E, o);
+          store_chunk<kElemAligned>(q + (long)i * E, o);
         }
       }
     }

@@ -51,3 +51,26 @@ def test_gfx950_code_object(built):
     """The kernel library carries gfx950 machine code (not a generic/other-arch target)."""
     blob = open(built[0], "rb").read()
     assert b"amdgcn-amd-amdhsa--gfx950" in blob
+
+
+def test_build_digest_covers_every_kernel_header(tmp_path, monkeypatch):
+    """The stamp that lets build_lib() skip a rebuild hashes the sources and EVERY header under
+    csrc/kernels: a stale library behind a matching stamp would hide an edit to a shared header."""
+    from learning_jax_sharding_amd.csrc import build
+    k = tmp_path / "kernels"
+    k.mkdir()
+    (k / "a.hip").write_text('#include "two.h"\n')
+    (k / "one.h").write_text("// one\n")
+    (k / "two.h").write_text("// two\n")
+    monkeypatch.setattr(build, "HERE", str(tmp_path))
+    srcs = build._sources("kernels")
+    assert [os.path.basename(s) for s in srcs] == ["a.hip"]
+    d0 = build._digest(srcs)
+    assert build._digest(srcs) == d0                 # stable
+    (k / "two.h").write_text("// two, edited\n")
+    d1 = build._digest(srcs)
+    assert d1 != d0                                  # a second header's bytes
+    (k / "three.h").write_text("")
+    d2 = build._digest(srcs)
+    assert d2 not in (d0, d1)                        # a header added (even an empty one)
+    assert build._digest(build._sources("kernels")) == d2
