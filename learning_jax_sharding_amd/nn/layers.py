@@ -177,22 +177,20 @@ class FeedForward(Module):
 
 
 class Embed(Module):
+    """Rows of a ``(num_embeddings, features)`` table by integer id (:func:`..ops.core.embed`: one fused
+    HIP gather per shard on GPU, a deterministic scatter-sum backward).  ``dtype``: the output's
+    (None: the table's); an id outside the table gives a row of zeros.  The table's logical axes are
+    ``("vocab", "embed")``: a rule that maps ``vocab`` to a mesh axis makes the lookup vocab-parallel."""
+
     num_embeddings: int
     features: int
+    dtype: Any = None
     param_dtype: Any = torch.float32
 
     def __call__(self, ids: ShardedArray) -> ShardedArray:
-        table = self.param("embedding", init.normal(1.0), (self.num_embeddings, self.features),
-                           _dt.canonicalize(self.param_dtype))
-        # rows gathered locally: the table is replicated onto the ids' devices first
-        from ..sharding.tile import TileAssignment
-        from ..spmd.reshard import reshard_tile
-        tab = reshard_tile(table, TileAssignment.replicated(ids.tile.device_ids, 2))
-        loc = {d: tab.local[d][ids.local[d].long()] for d in ids.local}
-        tile = ids.tile.insert_dims(list(range(ids.ndim)), ids.ndim + 1)
-        from ..sharding.shardings import sharding_from_tile
-        return ShardedArray(tuple(ids.shape) + (self.features,), table.dtype,
-                            sharding_from_tile(tile, like=[ids.sharding]), loc)
+        table = self.param("embedding", with_logical_partitioning(init.normal(1.0), ("vocab", "embed")),
+                           (self.num_embeddings, self.features), _dt.canonicalize(self.param_dtype))
+        return core.embed(table, ids, self.dtype)
 
 
 def _fused_norm(x: ShardedArray, scale, bias, epsilon: float, kind: str, dtype) -> Optional[ShardedArray]:

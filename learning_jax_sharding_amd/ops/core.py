@@ -37,7 +37,7 @@ __all__ = [
     "binary", "unary", "convert", "reshape", "transpose", "reduce_sum", "reduce_mean", "reduce_max",
     "getitem", "dot_general", "dot", "matmul", "einsum", "softmax", "dot_product_attention", "dense",
     "with_sharding_constraint", "asarray_like", "broadcast_to", "where", "concatenate", "mse_loss",
-    "layer_norm", "softmax_cross_entropy",
+    "layer_norm", "softmax_cross_entropy", "embed",
 ]
 
 
@@ -717,6 +717,51 @@ def softmax_cross_entropy(logits: ShardedArray, labels: ShardedArray) -> Sharded
         loss = torch.log((torch.exp(ls) * torch.exp(rel)).sum(0)) - (own * (ti + rel)).sum(0)
         loc[d] = torch.where(l >= 0, loss, torch.zeros_like(loss))
     return ShardedArray(tuple(logits.shape[:-1]), torch.float32, sh, loc)
+
+
+# ----------------------------------------------------------------------------- embedding lookup
+def embed(table: ShardedArray, ids: ShardedArray, dtype=None) -> ShardedArray:
+    """Rows of ``table`` (``[V, D]``) by integer ``ids`` (any shape): ``[*ids.shape, D]`` in ``dtype`` (default:
+    the table's).  An id outside ``[0, V)`` gives a row of zeros and no gradient (the negative label of
+    :func:`softmax_cross_entropy`, for ids).  One fused kernel per shard (:func:`.kernels.embed`).
+
+    The table may stay sharded over device axes the ids are replicated on.  Sharded rows are the
+    vocab-parallel case: every device looks its ids up in its own rows (``vocab_offset`` = its first
+    row) and writes zeros for the ids of other shards, and the partial outputs, exactly one non-zero
+    contributor per row, are all-reduced over the vocabulary group: T x D activations move, no table
+    bytes.  Sharded columns shard the output's last dim, with no collective.  Over the axes the ids
+    are sharded on the table has to be whole on every device; a table laid out otherwise is
+    replicated first, and the transpose of that reshard (or, for a table already replicated, the
+    replica-gradient sum) adds the per-device table gradients."""
+    if not isinstance(table, ShardedArray) or not isinstance(ids, ShardedArray):
+        raise TypeError("embed: table and ids must be ShardedArrays")
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"embed: ids must be int32 or int64, got {ids.dtype}")
+    if table.ndim != 2:
+        raise ValueError(f"embed: the table must be [vocab, features], got shape {tuple(table.shape)}")
+    out_dtype = _dt.canonicalize(dtype) or table.dtype
+    n, it = ids.ndim, ids.tile
+
+    def joint(tt: TileAssignment) -> Optional[TileAssignment]:
+        # ids tiles x table tiles: a tile assignment only when every pair is held equally often
+        if set(tt.device_ids) != set(it.device_ids):
+            return None
+        return TileAssignment.from_coords({d: it.coords[d] + tt.coords[d] for d in it.device_ids},
+                                          it.tile_shape + tt.tile_shape)
+
+    tab, jt = table, joint(table.tile)
+    if jt is None:
+        tab = reshard_tile(table, TileAssignment.replicated(it.device_ids, 2), note="embed.table")
+        jt = joint(tab.tile)
+    nv, nf = tab.tile.tile_shape
+    vl = tab.tile.shard_shape(tab.shape)[0]
+    _plan.record("embed", vocab_shards=nv, feature_shards=nf)
+    loc = {d: K.embed(tab.local[d], t, tab.tile.coords[d][0] * vl, out_dtype) for d, t in ids.local.items()}
+    if nv > 1:
+        loc = C.all_reduce(loc, jt.groups_along([n]), note="embed.out")
+    tile = jt.project(list(range(n)) + [n + 1])
+    sh = sharding_from_tile(tile, like=[ids.sharding, table.sharding])
+    return ShardedArray(tuple(ids.shape) + (table.shape[1],), out_dtype, sh, loc)
 
 
 # ----------------------------------------------------------------------------- softmax / attention

@@ -18,7 +18,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
-           "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats"]
+           "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
+           "embed_grad"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -95,6 +96,15 @@ _SIGS = {
     "ljs_xent_bwd": [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_long, c_long, c_int, c_void_p],
     "ljs_xent_wave_max_v": [],
+    "ljs_embed_fwd": [c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_void_p, c_int, c_long, c_int, c_int, c_void_p],
+    "ljs_embed_index": [c_void_p, c_int, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                        c_void_p],
+    "ljs_embed_scan": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "ljs_embed_bwd": [c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                      c_void_p],
+    "ljs_embed_chunk": [],
+    "ljs_embed_allpairs_max_tokens": [],
+    "ljs_embed_work_cap": [c_long],
     "ljs_launch_count": [],
     "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
     "ljs_attn_set_cus": [c_int],
@@ -1209,6 +1219,13 @@ def __getattr__(name):
     # cross-entropy kernels; wider rows take one block each.  Read from the library, not repeated.
     if name == "XENT_WAVE_MAX_V":
         return int(lib().ljs_xent_wave_max_v())
+    # EMBED_CHUNK: tokens of one table row's list that one wave of the embedding backward sums (a
+    # longer list is cut into chunks of this many); EMBED_ALLPAIRS_MAX_TOKENS: most tokens whose
+    # inverted index the all-pairs rank kernel builds (above: a stable torch.sort).
+    if name == "EMBED_CHUNK":
+        return int(lib().ljs_embed_chunk())
+    if name == "EMBED_ALLPAIRS_MAX_TOKENS":
+        return int(lib().ljs_embed_allpairs_max_tokens())
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -1324,6 +1341,137 @@ def xent_stats(logits: torch.Tensor, labels: torch.Tensor, vocab_offset: int = 0
     ``loss = log S - sum own_i (t_i + m_i - M)``."""
     _xent_check(logits, labels)
     return _XentStats.apply(logits, labels, int(vocab_offset))
+
+
+# ============================================================================ embedding lookup
+_EMBED_DTYPES = (torch.float32, torch.bfloat16)
+_EMBED_IDS = (torch.int32, torch.int64)
+
+
+def embed_supported(table: torch.Tensor, ids: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> bool:
+    """Whether the fused embedding kernels (csrc/kernels/embed.hip) take these: an f32 or bf16 table
+    ``[V, D]`` with D a multiple of 8 in 8..8192 (the norm kernels' rule), int32 or int64 ids of any
+    shape, not empty, an f32 or bf16 output."""
+    if table.dim() != 2 or table.dtype not in _EMBED_DTYPES or ids.dtype not in _EMBED_IDS:
+        return False
+    V, D = table.shape
+    return ((out_dtype or table.dtype) in _EMBED_DTYPES and D % 8 == 0 and 8 <= D <= 8192 and 1 <= V < 2 ** 31
+            and 0 < ids.numel() < 2 ** 31 - 1024)
+
+
+def _embed_ws(t: torch.Tensor, nbytes: int) -> torch.Tensor:
+    """The index build's histogram: zero between launches (the scan kernel re-zeroes it), under the
+    rules of :func:`_norm_ws`: one per device, stream and size, a ``graph`` one under capture,
+    never regrown."""
+    tag = "graph" if torch.cuda.is_current_stream_capturing() else str(_stream(t))
+    return _workspace(t.device, f"embed/{tag}/{nbytes}", nbytes)
+
+
+def _embed_index(ids: torch.Tensor, vocab_offset: int, V: int):
+    """The inverted index of flat ``ids`` over table rows ``vocab_offset .. vocab_offset + V``:
+    (start ``[V + 1]``, list ``[T]``, work list, its capacity), all int32.  Up to
+    ``EMBED_ALLPAIRS_MAX_TOKENS`` tokens by the rank / scan / fill kernels; above, the list is the
+    permutation of a stable ``torch.sort`` and only the scan kernel runs.  Either way each row's
+    tokens come out in ascending order."""
+    T, dev = ids.numel(), ids.device
+    cap = int(lib().ljs_embed_work_cap(T))
+    i32 = dict(dtype=torch.int32, device=dev)
+    start, work = torch.empty(V + 1, **i32), torch.empty(2 + 2 * cap, **i32)
+    vpad = (V + 3) // 4 * 4
+    if T <= int(lib().ljs_embed_allpairs_max_tokens()):
+        lst, rank = torch.empty(T, **i32), torch.empty(T, **i32)
+        hist = _embed_ws(ids, vpad * 4)
+        rc = lib().ljs_embed_index(_p(ids), int(ids.dtype == torch.int64), int(vocab_offset), T, V, _p(hist),
+                                   _p(rank), _p(start), _p(lst), _p(work), cap, _stream(ids))
+        _ck(rc, "embed_index")
+        return start, lst, work, cap
+    loc = ids.long() - int(vocab_offset)
+    loc = torch.where((loc >= 0) & (loc < V), loc, torch.full_like(loc, V))  # unowned tokens sort last
+    lst = torch.sort(loc, stable=True)[1].to(torch.int32)
+    hist = torch.zeros(vpad + 4, **i32)
+    hist.index_add_(0, loc, torch.ones(T, **i32))  # integer adds: the counts do not depend on their order
+    hist[V:].zero_()
+    rc = lib().ljs_embed_scan(_p(hist), V, _p(start), _p(work), cap, _stream(ids))
+    _ck(rc, "embed_scan")
+    return start, lst, work, cap
+
+
+def embed_grad(dy: torch.Tensor, ids: torch.Tensor, num_rows: int, vocab_offset: int = 0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The table gradient of :func:`embed`: f32 ``[num_rows, D]`` with row ``v`` the sum of the ``dy`` rows
+    (f32 or bf16, ``[*ids.shape, D]``) of the tokens whose id is ``vocab_offset + v``, added in f32 in
+    ascending token order (lists longer than ``EMBED_CHUNK`` per chunk, then the chunks in order).
+    No float atomics; every row of ``out`` (given, or fresh) is written, unchosen rows as zeros."""
+    D = dy.shape[-1]
+    ids = ids.detach().reshape(-1).contiguous()
+    T = ids.numel()
+    dy = dy.detach().reshape(T, D)
+    if dy.dtype not in _EMBED_DTYPES:
+        dy = dy.float()
+    if not dy.is_contiguous() or dy.data_ptr() % 16:
+        dy = dy.contiguous().clone() if dy.is_contiguous() else dy.contiguous()
+    if out is None:
+        out = torch.empty((num_rows, D), dtype=torch.float32, device=dy.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (num_rows, D) or not out.is_contiguous():
+        raise ValueError(f"embed_grad: out must be a contiguous f32 [{num_rows}, {D}] tensor")
+    start, lst, work, cap = _embed_index(ids, vocab_offset, num_rows)
+    partial = torch.empty((cap, D), dtype=torch.float32, device=dy.device) if cap else None
+    rc = lib().ljs_embed_bwd(_p(dy), int(dy.dtype == torch.bfloat16), T, D, num_rows, _p(start), _p(lst), _p(work),
+                             cap, _p(partial), _p(out), _stream(dy))
+    _ck(rc, "embed_bwd")
+    return out
+
+
+class _Embed(torch.autograd.Function):
+    """Rows of one table shard by id: one HIP launch forward; backward the inverted index of the ids
+    (three launches) and the sum pass (one, and one more that adds the chunks of long lists), or
+    with ``fused_bwd`` off torch's ``index_add_`` (float atomics: the sum order is not fixed)."""
+
+    @staticmethod
+    def forward(ctx, table, ids, vocab_offset, out_dtype, fused_bwd):
+        V, D = table.shape
+        tab = table.detach()
+        es = tab.element_size()
+        if tab.stride(1) != 1 or tab.stride(0) < D or (tab.stride(0) * es) % 16 or tab.data_ptr() % 16:
+            tab = tab.contiguous()
+        idf = ids.detach().reshape(-1).contiguous()
+        out = torch.empty(tuple(ids.shape) + (D,), dtype=out_dtype, device=table.device)
+        rc = lib().ljs_embed_fwd(_p(tab), int(tab.dtype == torch.bfloat16), tab.stride(0), _p(idf),
+                                 int(idf.dtype == torch.int64), int(vocab_offset), _p(out),
+                                 int(out_dtype == torch.bfloat16), idf.numel(), V, D, _stream(table))
+        _ck(rc, "embed_fwd")
+        ctx.save_for_backward(idf)
+        ctx.meta = (V, D, table.dtype, int(vocab_offset), bool(fused_bwd))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (idf,) = ctx.saved_tensors
+        V, D, tdt, vocab_offset, fused_bwd = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        if fused_bwd:
+            dt = embed_grad(g, idf, V, vocab_offset)
+        else:
+            loc = idf.long() - vocab_offset
+            own = (loc >= 0) & (loc < V)
+            gf = torch.where(own.unsqueeze(-1), g.detach().reshape(-1, D).float(), g.new_zeros((), dtype=torch.float32))
+            dt = torch.zeros((V, D), dtype=torch.float32, device=g.device).index_add_(0, loc.clamp(0, V - 1), gf)
+        return (dt if tdt == torch.float32 else dt.to(tdt)), None, None, None, None
+
+
+def embed(table: torch.Tensor, ids: torch.Tensor, vocab_offset: int = 0, out_dtype: Optional[torch.dtype] = None,
+          fused_bwd: bool = True) -> torch.Tensor:
+    """``table[ids - vocab_offset]`` as ``[*ids.shape, D]`` in ``out_dtype`` (default: the table's), a row of
+    zeros (and no gradient) for an id outside ``vocab_offset .. vocab_offset + V``: a negative id, one
+    past the vocabulary, one that another vocabulary shard owns.  The table's gradient is f32 sums in
+    a fixed order (:func:`embed_grad`), cast to the table's dtype."""
+    out_dtype = out_dtype or table.dtype
+    if not embed_supported(table, ids, out_dtype):
+        raise NotImplementedError(f"embed kernels: an f32 / bf16 table [V, D] with D a multiple of 8 in 8..8192, "
+                                  f"int32 / int64 ids, f32 / bf16 out; got {table.dtype} {tuple(table.shape)}, "
+                                  f"{ids.dtype} {tuple(ids.shape)} -> {out_dtype}")
+    return _Embed.apply(table, ids, int(vocab_offset), out_dtype, bool(fused_bwd))
 
 
 # ============================================================================ dense / linear

@@ -155,6 +155,52 @@ def softmax_xent_stats(logits: torch.Tensor, labels: torch.Tensor, vocab_offset:
     return xent_stats_reference(logits, labels, vocab_offset)
 
 
+# ----------------------------------------------------------------------------- embedding lookup
+# whether LJS_FUSED_EMBED=1 (the default) includes the deterministic fused backward, or only the
+# forward with torch's index_add_ behind it (profiles/PERF_NOTES.md "Fused embedding")
+_EMBED_BWD_BY_DEFAULT = True
+
+
+def fused_embed_mode() -> int:
+    # LJS_FUSED_EMBED=0: the embedding lookup on GPU shards as the torch formulation below instead of
+    # the fused HIP kernels of csrc/kernels/embed.hip (A/B timing; escape hatch); 1 (default): the
+    # fused kernels; 2: the fused forward and the deterministic fused backward whatever the default
+    v = os.environ.get("LJS_FUSED_EMBED", "1")
+    return 0 if v == "0" else (2 if v == "2" else 1)
+
+
+def fused_embed_enabled() -> bool:
+    return fused_embed_mode() != 0
+
+
+def _hip_embed(table: torch.Tensor, ids: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> bool:
+    return (use_hip(table) and use_hip(ids) and fused_embed_enabled()
+            and _hip().embed_supported(table, ids, out_dtype))
+
+
+def embed_reference(table: torch.Tensor, ids: torch.Tensor, vocab_offset: int = 0,
+                    out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Plain torch ``table[ids - vocab_offset]`` as ``[*ids.shape, D]``: a row of zeros where ``ids -
+    vocab_offset`` is outside ``[0, V)`` (a mask, a clamped index and ``where``), in the table's dtype
+    (f64 for an f64 table: the oracle) cast to ``out_dtype``; the backward is torch's."""
+    V = table.shape[0]
+    loc = ids.long() - int(vocab_offset)
+    own = (loc >= 0) & (loc < V)
+    rows = table[loc.clamp(0, V - 1)]
+    rows = torch.where(own.unsqueeze(-1), rows, torch.zeros((), dtype=rows.dtype, device=rows.device))
+    return rows if out_dtype is None or out_dtype == rows.dtype else rows.to(out_dtype)
+
+
+def embed(table: torch.Tensor, ids: torch.Tensor, vocab_offset: int = 0,
+          out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Rows of one table shard (``[V, D]``, its row 0 global id ``vocab_offset``) by id; an id the shard
+    does not hold gives a row of zeros and no gradient."""
+    if _hip_embed(table, ids, out_dtype):
+        mode = fused_embed_mode()
+        return _hip().embed(table, ids, vocab_offset, out_dtype, fused_bwd=mode == 2 or _EMBED_BWD_BY_DEFAULT)
+    return embed_reference(table, ids, vocab_offset, out_dtype)
+
+
 # ----------------------------------------------------------------------------- matmuls
 def _to_bmk(a: torch.Tensor, batch, free, contract):
     perm = list(batch) + list(free) + list(contract)

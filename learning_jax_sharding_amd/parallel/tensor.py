@@ -32,8 +32,8 @@ from ..mesh import Mesh, current_mesh
 from ..ops import core
 from ..sharding import NamedSharding, PartitionSpec as P
 
-__all__ = ["REFERENCE_RULES", "FSDP_RULES", "GSPMD2D_RULES", "MEGATRON_RULES", "DP_RULES", "PRESETS", "rules", "column_parallel",
-           "row_parallel"]
+__all__ = ["REFERENCE_RULES", "FSDP_RULES", "GSPMD2D_RULES", "MEGATRON_RULES", "VOCAB_PARALLEL_RULES", "DP_RULES", "PRESETS",
+           "rules", "column_parallel", "row_parallel"]
 
 Rules = Tuple[Tuple[str, Optional[str]], ...]
 
@@ -46,11 +46,15 @@ GSPMD2D_RULES: Rules = (("batch", "data"), ("embed", "data"), ("heads", "model")
 # heads / FF hidden over model, batch over data, embed replicated
 MEGATRON_RULES: Rules = (("batch", "data"), ("heads", "model"), ("hidden", "model"), ("embed", None),
                          ("kv", None), ("length", None))
+# the Megatron rules with the vocabulary over model too: the embedding table's rows and the LM
+# head's columns (nn.Embed, models/lm.py), met by the vocab-parallel lookup and loss
+VOCAB_PARALLEL_RULES: Rules = MEGATRON_RULES + (("vocab", "model"),)
 # pure data parallelism (every weight replicated)
 DP_RULES: Rules = (("batch", "data"),)
 
 PRESETS = {"reference": REFERENCE_RULES, "case6": REFERENCE_RULES, "fsdp": FSDP_RULES, "case5": FSDP_RULES,
-           "gspmd2d": GSPMD2D_RULES, "megatron": MEGATRON_RULES, "dp": DP_RULES}
+           "gspmd2d": GSPMD2D_RULES, "megatron": MEGATRON_RULES, "vocab_parallel": VOCAB_PARALLEL_RULES,
+           "dp": DP_RULES}
 
 
 def rules(name: str) -> Rules:
