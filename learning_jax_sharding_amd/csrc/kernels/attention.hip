@@ -2278,7 +2278,7 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
 // Kernel-variant switches.  The defaults are the measured winners (profiles/PERF_NOTES.md); the
 // setters (ops/hip.py set_attention_*) exist so the GPU tests can run every variant and check it
 // bit-exact against the default -- they are not environment knobs.  (ljs_attn_set_cus, the grid of
-// the fused projection + forward, is one of them: it sits with g_attn_cus below.)
+// the fused projection + forward, is one of them.)
 //  * split backward as ONE launch of dQ and dK/dV blocks (attn_bwd_pair_kernel), else two launches
 static int g_bwd_pair = 1;
 LJS_API void ljs_attn_set_bwd_pair(int v) { g_bwd_pair = v < 0 ? 1 : v; }
@@ -2296,9 +2296,8 @@ LJS_API void ljs_attn_set_vst(int v) { g_vst = v < 0 ? 1 : v; }
 static bool vst_ok(const void* p, const long* st) {
   return (((uintptr_t)p) & 15) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0;
 }
-static int g_attn_cus = 0;   // CUs of the current device (the fused projection's grid)
 //  * the fused projection + forward's grid: n > 0 blocks instead of one per CU (the tests run many
-//    items per block on small shapes this way); <= 0 = the device's CU count again
+//    items per block on small shapes this way); <= 0 = the device's CU count (ljs_device_cus) again
 static int g_attn_cus_forced = 0;
 LJS_API void ljs_attn_set_cus(int v) { g_attn_cus_forced = v > 0 ? v : 0; }
 //  * K/V-resident forward for Sk <= 256: 8 (or 4) waves per block; 0 = the tiled kernel
@@ -2412,19 +2411,13 @@ LJS_API int ljs_qkv_attn_fwd(const void* x, long ldx, const void* w, void* qkv, 
       (((uintptr_t)x | (uintptr_t)w | (uintptr_t)qkv | (uintptr_t)o) & 15) ||
       (long)T * ldx * 2 >= (1L << 31) || 3L * N * K * 2 >= (1L << 31))
     return (int)hipErrorInvalidValue;
-  if (!g_attn_cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_attn_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_attn_cus <= 0) g_attn_cus = 256;
-  }
   QkvAttnArgs a;
   a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.qkv = (bf16_t*)qkv; a.o = (bf16_t*)o; a.lse = (float*)lse;
   a.T = T; a.K = K; a.N = N; a.H = H; a.ldx = (int)ldx;
   a.scale_log2 = scale * LOG2E;
   a.trace = (unsigned long long*)trace;
   const int items = T / QA_S * H;
-  const int cus = g_attn_cus_forced > 0 ? g_attn_cus_forced : g_attn_cus;
+  const int cus = g_attn_cus_forced > 0 ? g_attn_cus_forced : ljs_device_cus();
   const int grid = items < cus ? items : cus;   // one 8-wave block per CU, items dealt round-robin
   ljs_launch_rec("qkv_attn_fwd", dim3(grid), 512);
   hipLaunchKernelGGL(qkv_attn_fwd_kernel, dim3(grid), dim3(512), 0, stream, a);

@@ -43,6 +43,18 @@ inline void ljs_launch_rec(const char* name, dim3 grid, unsigned block, int acc_
   ljs_launch_push(r);
 }
 
+// compute units of the current device, 256 if unknown (asked once per process: the launchers size
+// persistent grids by it)
+inline int ljs_device_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+  }();
+  return cus;
+}
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;

@@ -1424,178 +1424,384 @@ gemm_lean_kernel(GemmArgs p) {
 }
 
 
+// ============================================================================ host side
+// The LDS-DMA tile table: everything a tile code stands for, stated once.  The explicit
+// instantiations, the instance names, the dispatch, the demotion chain and the psum geometry
+// below all come from these lines.
+//   code, BM x BN block tile, WM x WN waves, NST ring stages, then what the tile has:
+//   KK    k-contiguous operands, bf16 output: 0 nothing; 1 the RES 0 instance; 5 the epilogue
+//         instances RES 0-4; 3 the same five instantiated, but a call with an epilogue operand
+//         (RES 1 / 2) demotes the tile
+//   KKF   k-contiguous operands, f32 output
+//   MIX   the other five layout / output pairs (one operand m/n-contiguous, or both with bf16 output)
+//   MN    m/n-contiguous operands, f32 output (weight gradients): 1 the RES 0 instance; 2 also
+//         the plain split-K slab instance (RES 3) and the grouped-pair kernel
+//   LEAN  a lean K-loop twin of the KK instances: 1 only when forced (code + 100000: the general
+//         kernel measured 14.4 vs 14.8 us at 128x160, one item per block), 2 by default
+//   DEMOTE  the code a call falls to when the tile has no instance for it, or the operands do not
+//         meet the LDS-DMA kernels' conditions; every chain ends at a register-staged tile
+//   UNFOLD  0: batches run as they are; else the tile runs a batch only folded into one GEMM
+//         over N * batch columns, and this is the code of a batch that cannot be folded
+// 64x64: the small-M GEMMs of the reference shape (2048 tokens), where 128x128 tiles leave most
+// CUs idle.  128x160 (4 waves stacked along M): N = 640 is 4 column tiles, so a [16384, 640]
+// output is exactly one round of 2 blocks/CU.  256x192 (8 waves of 64x96, 112 KiB): 7 DMA pieces
+// and 20 fragment reads per wave per 48 MFMAs (256x128: 6 and 16 per 32).  256x128 / 128x256
+// weight-gradient tiles: 48 KiB of operands per K-tile for twice the MFMA work of 128x128.
+// 128x128 with 8 waves (2 x 4): two waves per SIMD at one block per CU, so a deep ring does not
+// cost MFMA/LDS overlap.
+#define LJS_GEMM_TILES(X)                                       \
+  /* code    BM   BN  WM WN NST KK KKF MIX MN LEAN DEMOTE UNFOLD */ \
+  X(643,     64,  64, 2, 2, 3,  1, 1,  1,  1, 0,   64,    0)    \
+  X(644,     64,  64, 2, 2, 4,  3, 1,  1,  1, 2,   64,    0)    \
+  X(1282,   128, 128, 2, 2, 2,  5, 1,  1,  2, 2,   128,   0)    \
+  X(1284,   128, 128, 2, 2, 4,  5, 1,  1,  1, 2,   128,   0)    \
+  X(1602,   128, 160, 4, 1, 2,  5, 0,  0,  0, 1,   1282,  0)    \
+  X(2561,   256, 128, 4, 2, 3,  5, 1,  0,  0, 2,   1284,  0)    \
+  X(2562,   256, 192, 4, 2, 2,  3, 0,  0,  0, 2,   1282,  2561) \
+  X(2563,   256, 128, 4, 2, 3,  0, 0,  0,  1, 0,   1282,  0)    \
+  X(12856,  128, 256, 2, 4, 3,  0, 0,  0,  1, 0,   1282,  0)    \
+  X(12883,  128, 128, 2, 4, 3,  5, 1,  0,  2, 2,   1282,  0)    \
+  X(12884,  128, 128, 2, 4, 4,  5, 1,  0,  2, 2,   1282,  0)
+// code + kForceLean runs a tile's lean K-loop kernel where it has one, + 2 * kForceLean the
+// general one (A/B timing and the bit-exact tests)
+constexpr int kForceLean = 100000;
+
 // explicit instantiations: hipcc (ROCm 7.2) otherwise leaves some of these kernels' host stubs
-// undefined when they are only named inside launch_dma's instantiations
-#define LJS_DMA_INST(BM, BN, WM, WN, NST, AK, BKc, OF) \
-  template __global__ void gemm_dma_kernel<BM, BN, WM, WN, NST, AK, BKc, OF>(GemmArgs);
-#define LJS_DMA_INST_LAYOUTS(NST)                                                                           \
-  LJS_DMA_INST(128, 128, 2, 2, NST, true, true, false) LJS_DMA_INST(128, 128, 2, 2, NST, true, true, true)     \
-  LJS_DMA_INST(128, 128, 2, 2, NST, false, false, false) LJS_DMA_INST(128, 128, 2, 2, NST, false, false, true) \
-  LJS_DMA_INST(128, 128, 2, 2, NST, true, false, false) LJS_DMA_INST(128, 128, 2, 2, NST, true, false, true)   \
-  LJS_DMA_INST(128, 128, 2, 2, NST, false, true, false) LJS_DMA_INST(128, 128, 2, 2, NST, false, true, true)
-LJS_DMA_INST_LAYOUTS(2)
-LJS_DMA_INST_LAYOUTS(4)
-// f32 split-K slab kernels with the compile-time plain epilogue (weight gradients: m/n-contiguous)
-template __global__ void gemm_dma_kernel<128, 128, 2, 2, 2, false, false, true, 3>(GemmArgs);
-template __global__ void gemm_dma_group2_kernel<128, 128, 2, 2, 2, false, false, true, 3>(GemmArgs, GemmArgs, int);
-template __global__ void gemm_dma_group2_kernel<128, 128, 2, 4, 4, false, false, true, 3>(GemmArgs, GemmArgs, int);
-template __global__ void gemm_dma_group2_kernel<128, 128, 2, 4, 3, false, false, true, 3>(GemmArgs, GemmArgs, int);
-template __global__ void gemm_dma_kernel<128, 128, 2, 4, 4, false, false, true, 3>(GemmArgs);
-template __global__ void gemm_dma_kernel<128, 128, 2, 4, 3, false, false, true, 3>(GemmArgs);
-// 64x64 tiles (4 waves of 32x32, 3 or 4 stages): the small-M GEMMs of the reference shape
-// (2048 tokens), where 128x128 tiles leave most CUs idle
-#define LJS_DMA_INST_64(NST)                                                                               \
-  LJS_DMA_INST(64, 64, 2, 2, NST, true, true, false) LJS_DMA_INST(64, 64, 2, 2, NST, true, true, true)     \
-  LJS_DMA_INST(64, 64, 2, 2, NST, false, false, false) LJS_DMA_INST(64, 64, 2, 2, NST, false, false, true) \
-  LJS_DMA_INST(64, 64, 2, 2, NST, true, false, false) LJS_DMA_INST(64, 64, 2, 2, NST, true, false, true)   \
-  LJS_DMA_INST(64, 64, 2, 2, NST, false, true, false) LJS_DMA_INST(64, 64, 2, 2, NST, false, true, true)
-LJS_DMA_INST_64(3)
-LJS_DMA_INST_64(4)
-#undef LJS_DMA_INST_64
-LJS_DMA_INST(256, 128, 4, 2, 3, true, true, false)
-LJS_DMA_INST(256, 128, 4, 2, 3, true, true, true)
-// 256x192, 8 waves of 64x96, 2 stages (112 KiB): 7 DMA pieces and 20 fragment reads per wave per
-// 48 MFMAs (256x128: 6 and 16 per 32); [T][1536] outputs are 2 items per block
-LJS_DMA_INST(256, 192, 4, 2, 2, true, true, false)
-// weight gradients (m/n-contiguous operands, f32 slabs): 256-wide tiles, 8 waves, 3 stages, one
-// block per CU -- 48 KiB of operands per 64-deep K-tile for twice the MFMA work of 128x128
-LJS_DMA_INST(256, 128, 4, 2, 3, false, false, true)
-LJS_DMA_INST(128, 256, 2, 4, 3, false, false, true)
-// 128x160 with 4 waves stacked along M (32x160 each): N = 640 splits into 4 column tiles, so a
-// [16384, 640] output is exactly 512 items = one round of 2 blocks/CU (128x128: 640 items, 1.25)
-LJS_DMA_INST(128, 160, 4, 1, 2, true, true, false)
-// 128x128 with 8 waves (2 x 4, 64x32 each): two waves per SIMD at one block per CU, so a
-// deep (3-4 stage) ring does not cost MFMA/LDS overlap
-#define LJS_DMA_INST_8W(NST)                                                                                \
-  LJS_DMA_INST(128, 128, 2, 4, NST, false, false, true) LJS_DMA_INST(128, 128, 2, 4, NST, true, true, false) \
-  LJS_DMA_INST(128, 128, 2, 4, NST, true, true, true)
-LJS_DMA_INST_8W(3)
-LJS_DMA_INST_8W(4)
-#undef LJS_DMA_INST_8W
-// epilogue-operand variants (bf16 output, k-contiguous operands: forward and dX GEMMs)
-#define LJS_DMA_INST_RES(BM, BN, WM, WN, NST) \
-  template __global__ void gemm_dma_kernel<BM, BN, WM, WN, NST, true, true, false, 1>(GemmArgs); \
-  template __global__ void gemm_dma_kernel<BM, BN, WM, WN, NST, true, true, false, 2>(GemmArgs); \
-  template __global__ void gemm_dma_kernel<BM, BN, WM, WN, NST, true, true, false, 3>(GemmArgs); \
-  template __global__ void gemm_dma_kernel<BM, BN, WM, WN, NST, true, true, false, 4>(GemmArgs);
-LJS_DMA_INST_RES(128, 160, 4, 1, 2)
-LJS_DMA_INST_RES(256, 192, 4, 2, 2)
-LJS_DMA_INST_RES(64, 64, 2, 2, 4)
-LJS_DMA_INST_RES(256, 128, 4, 2, 3)
-LJS_DMA_INST_RES(128, 128, 2, 2, 2)
-LJS_DMA_INST_RES(128, 128, 2, 2, 4)
-LJS_DMA_INST_RES(128, 128, 2, 4, 3)
-LJS_DMA_INST_RES(128, 128, 2, 4, 4)
-#undef LJS_DMA_INST_RES
-// lean K-loop kernels (k-contiguous, bf16 output; every epilogue instance)
-#define LJS_LEAN_INST(BM, BN, WM, WN, NST)                                  \
-  template __global__ void gemm_lean_kernel<BM, BN, WM, WN, NST, 0>(GemmArgs); \
-  template __global__ void gemm_lean_kernel<BM, BN, WM, WN, NST, 1>(GemmArgs); \
-  template __global__ void gemm_lean_kernel<BM, BN, WM, WN, NST, 2>(GemmArgs); \
-  template __global__ void gemm_lean_kernel<BM, BN, WM, WN, NST, 3>(GemmArgs); \
-  template __global__ void gemm_lean_kernel<BM, BN, WM, WN, NST, 4>(GemmArgs);
-LJS_LEAN_INST(256, 128, 4, 2, 3)
-LJS_LEAN_INST(256, 192, 4, 2, 2)
-LJS_LEAN_INST(128, 160, 4, 1, 2)
-LJS_LEAN_INST(128, 128, 2, 2, 2)
-LJS_LEAN_INST(128, 128, 2, 2, 4)
-LJS_LEAN_INST(128, 128, 2, 4, 3)
-LJS_LEAN_INST(128, 128, 2, 4, 4)
-LJS_LEAN_INST(64, 64, 2, 2, 4)
+// undefined when they are only named inside the dispatch's templates
+#define LJS_DMA_INST(BM, BN, WM, WN, NST, AK, BKc, OF, RES) \
+  template __global__ void gemm_dma_kernel<BM, BN, WM, WN, NST, AK, BKc, OF, RES>(GemmArgs);
+#define LJS_LEAN_INST(BM, BN, WM, WN, NST, RES) \
+  template __global__ void gemm_lean_kernel<BM, BN, WM, WN, NST, RES>(GemmArgs);
+#define LJS_INST_KK_0(...)
+#define LJS_INST_KK_1(...) LJS_DMA_INST(__VA_ARGS__, true, true, false, 0)
+#define LJS_INST_KK_5(...)                                                                 \
+  LJS_INST_KK_1(__VA_ARGS__) LJS_DMA_INST(__VA_ARGS__, true, true, false, 1)               \
+  LJS_DMA_INST(__VA_ARGS__, true, true, false, 2) LJS_DMA_INST(__VA_ARGS__, true, true, false, 3) \
+  LJS_DMA_INST(__VA_ARGS__, true, true, false, 4)
+#define LJS_INST_KK_3(...) LJS_INST_KK_5(__VA_ARGS__)
+#define LJS_INST_KKF_0(...)
+#define LJS_INST_KKF_1(...) LJS_DMA_INST(__VA_ARGS__, true, true, true, 0)
+#define LJS_INST_MIX_0(...)
+#define LJS_INST_MIX_1(...)                                                                      \
+  LJS_DMA_INST(__VA_ARGS__, false, false, false, 0) LJS_DMA_INST(__VA_ARGS__, true, false, false, 0) \
+  LJS_DMA_INST(__VA_ARGS__, true, false, true, 0) LJS_DMA_INST(__VA_ARGS__, false, true, false, 0)   \
+  LJS_DMA_INST(__VA_ARGS__, false, true, true, 0)
+#define LJS_INST_MN_0(...)
+#define LJS_INST_MN_1(...) LJS_DMA_INST(__VA_ARGS__, false, false, true, 0)
+#define LJS_INST_MN_2(...)                                                          \
+  LJS_INST_MN_1(__VA_ARGS__) LJS_DMA_INST(__VA_ARGS__, false, false, true, 3)       \
+  template __global__ void gemm_dma_group2_kernel<__VA_ARGS__, false, false, true, 3>(GemmArgs, GemmArgs, int);
+#define LJS_INST_LEAN_0(...)
+#define LJS_INST_LEAN_1(...)                                                                        \
+  LJS_LEAN_INST(__VA_ARGS__, 0) LJS_LEAN_INST(__VA_ARGS__, 1) LJS_LEAN_INST(__VA_ARGS__, 2)         \
+  LJS_LEAN_INST(__VA_ARGS__, 3) LJS_LEAN_INST(__VA_ARGS__, 4)
+#define LJS_INST_LEAN_2(...) LJS_INST_LEAN_1(__VA_ARGS__)
+#define LJS_INST_TILE(CODE, BM, BN, WM, WN, NST, KK, KKF, MIX, MN, LEAN, DEMOTE, UNFOLD)        \
+  LJS_INST_KK_##KK(BM, BN, WM, WN, NST) LJS_INST_KKF_##KKF(BM, BN, WM, WN, NST)                  \
+  LJS_INST_MIX_##MIX(BM, BN, WM, WN, NST) LJS_INST_MN_##MN(BM, BN, WM, WN, NST)                  \
+  LJS_INST_LEAN_##LEAN(BM, BN, WM, WN, NST)
+LJS_GEMM_TILES(LJS_INST_TILE)
+#undef LJS_INST_TILE
 #undef LJS_LEAN_INST
-#undef LJS_DMA_INST_LAYOUTS
 #undef LJS_DMA_INST
 
-int g_cus = 0;
 unsigned long long* g_gemm_trace = nullptr;  // LJS_GEMM_TRACE builds: the next LDS-DMA launches' stamps
-
-// Launch record (common.h): the tile code ljs_gemm_bf16 was asked for and the one it resolved it
-// to, for the launch sites below (a grouped GEMM carries its own in its GroupRec).
-thread_local int g_req_tile = -1, g_res_tile = -1;
 
 // instance names, formatted once per instantiation: "gemm_dma<128,128,2,2,4,kc,kc,bf16>"
 struct LaunchName { char s[64]; };
+#define LJS_NAME_ONCE(...)                  \
+  static const LaunchName n = [] {          \
+    LaunchName x;                           \
+    snprintf(x.s, sizeof x.s, __VA_ARGS__); \
+    return x;                               \
+  }();                                      \
+  return n.s;
 template <int BM, int BN, int WM, int WN, int NST, bool AK, bool BKc, bool OF, bool GROUP2>
 const char* dma_name() {
-  static const LaunchName n = [] {
-    LaunchName x;
-    snprintf(x.s, sizeof x.s, "%s<%d,%d,%d,%d,%d,%s,%s,%s>", GROUP2 ? "gemm_dma_group2" : "gemm_dma", BM, BN, WM, WN,
-             NST, AK ? "kc" : "mn", BKc ? "kc" : "mn", OF ? "f32" : "bf16");
-    return x;
-  }();
-  return n.s;
+  LJS_NAME_ONCE("%s<%d,%d,%d,%d,%d,%s,%s,%s>", GROUP2 ? "gemm_dma_group2" : "gemm_dma", BM, BN, WM, WN, NST,
+                AK ? "kc" : "mn", BKc ? "kc" : "mn", OF ? "f32" : "bf16")
 }
 template <int BM, int BN, int WM, int WN, int NST>
 const char* lean_name() {
-  static const LaunchName n = [] {
-    LaunchName x;
-    snprintf(x.s, sizeof x.s, "gemm_lean<%d,%d,%d,%d,%d>", BM, BN, WM, WN, NST);
-    return x;
-  }();
-  return n.s;
+  LJS_NAME_ONCE("gemm_lean<%d,%d,%d,%d,%d>", BM, BN, WM, WN, NST)
 }
 template <int BM, int BN, bool AK, bool BKc, bool OF>
 const char* reg_name() {
-  static const LaunchName n = [] {
-    LaunchName x;
-    snprintf(x.s, sizeof x.s, "gemm_bf16<%d,%d,%s,%s,%s>", BM, BN, AK ? "kc" : "mn", BKc ? "kc" : "mn",
-             OF ? "f32" : "bf16");
-    return x;
-  }();
-  return n.s;
+  LJS_NAME_ONCE("gemm_bf16<%d,%d,%s,%s,%s>", BM, BN, AK ? "kc" : "mn", BKc ? "kc" : "mn", OF ? "f32" : "bf16")
 }
-inline void gemm_rec(const char* name, dim3 grid, unsigned block, int splitk, int variant, int splitk1 = -1) {
-  LjsLaunchRec r = ljs_launch_make(name, grid, block);
-  r.req_tile = g_req_tile; r.res_tile = g_res_tile;
-  r.splitk = splitk; r.splitk1 = splitk1; r.variant = variant;
+#undef LJS_NAME_ONCE
+
+// ---------------------------------------------------------------------------- plan
+// What one ljs_gemm_bf16 call launches, worked out from the call's numbers alone: gemm_plan
+// dereferences nothing and calls no HIP function, so it answers on a machine without a GPU too
+// (ljs_gemm_plan).
+enum GemmFamily { kFamReg = 0, kFamDma = 1, kFamLean = 2, kFamSlab = 3 };  // kFamSlab: a groupable plain slab GEMM
+using GemmKernel = void (*)(GemmArgs);
+using GemmGroup2 = void (*)(GemmArgs, GemmArgs, int);
+
+struct GemmPlan {
+  hipError_t err;
+  int tile;                         // the resolved tile code
+  int family;
+  int BM, BN, WM, WN, NST;          // the instance (register-staged: 4 waves, 2 buffers)
+  bool a_kc, b_kc, out_f32;
+  int variant;                      // RES of the LDS-DMA / lean instance, else -1
+  int splitk, kt_per_split;
+  int N, batch;                     // as launched: a folded batch is one GEMM over N * batch columns
+  int items;                        // LDS-DMA / lean work items (tiles x batch x splits)
+  unsigned gx, gy, block;
+  bool psum, mfast;                 // the kernel writes the fused output sums; kMFast item order
+  int psum_count;
+  const char* name;
+  GemmKernel kernel;
+  GemmGroup2 group2;                // kFamSlab: the grouped-pair kernel of the same instance
+  const char* group2_name;
+};
+
+template <int BM, int BN, int WM, int WN, int NST, bool AK, bool BKc, bool OF, int RES = 0>
+void set_dma(GemmPlan& p) {
+  p.family = kFamDma;
+  p.variant = RES;
+  p.kernel = gemm_dma_kernel<BM, BN, WM, WN, NST, AK, BKc, OF, RES>;
+  p.name = dma_name<BM, BN, WM, WN, NST, AK, BKc, OF, false>();
+}
+
+// the epilogue instance of a k-contiguous bf16-output call, general and lean kernel alike (bf16
+// outputs never split)
+inline int epilogue_variant(const GemmArgs& a, bool psum) {
+  if (a.flags & (kResAdd | kResMask)) return (a.flags & kResF32) ? 2 : 1;
+  // plain epilogue (RES 3: compile-time instance, PERF_NOTES r4 "plain instance")
+  if (a.alpha == 1.f && !(a.flags & 3) && !psum) return 3;
+  // bias (f32) + optional fused sum, alpha 1, no ReLU (RES 4)
+  if (a.alpha == 1.f && (a.flags & 7) == 6) return 4;
+  return 0;
+}
+
+#define LJS_BY_RES(v, X) \
+  switch (v) { case 1: X(1); break; case 2: X(2); break; case 3: X(3); break; case 4: X(4); break; default: X(0); }
+#define LJS_SET_LEAN(RES) p.kernel = gemm_lean_kernel<BM, BN, WM, WN, NST, RES>
+#define LJS_SET_DMA(RES) set_dma<BM, BN, WM, WN, NST, true, true, false, RES>(p)
+// The tile's instance for the call p describes (layout, output type, a's flags); false when the
+// tile has none.  (Plain if/else and switch, not ?:, between kernel instances -- see the
+// explicit-instantiation note above.)
+template <int BM, int BN, int WM, int WN, int NST, int KK, bool KKF, bool MIX, int MN, int LEAN>
+bool dma_instance(const GemmArgs& a, bool lean_req, bool gen_req, GemmPlan& p) {
+  p.BM = BM; p.BN = BN; p.WM = WM; p.WN = WN; p.NST = NST;
+  p.block = WM * WN * 64;
+  p.group2 = nullptr;
+  // fused output sums: bf16 output; the caller's buffer holds 8 partials per 128x128 of output
+  // (ops/hip.py psum_slots), which a tile under 128x128 would overrun
+  p.psum = a.psum && !p.out_f32 && BM >= 128 && BN >= 128;
+  const bool res = a.flags & (kResAdd | kResMask);
+  if (p.a_kc && p.b_kc && !p.out_f32) {
+    if constexpr (KK == 0) {
+      return false;
+    } else if constexpr (KK == 1) {
+      if (res) return false;
+      set_dma<BM, BN, WM, WN, NST, true, true, false>(p);
+    } else {
+      if (res && KK < 5) return false;
+      const int v = epilogue_variant(a, p.psum);
+      if (!gen_req && LEAN >= (lean_req ? 1 : 2)) {
+        if constexpr (LEAN > 0) {
+          p.family = kFamLean;
+          p.variant = v;
+          p.name = lean_name<BM, BN, WM, WN, NST>();
+          LJS_BY_RES(v, LJS_SET_LEAN)
+        }
+        return true;
+      }
+      LJS_BY_RES(v, LJS_SET_DMA)
+    }
+    return true;
+  }
+  if (res) return false;  // the epilogue operand is in the k-contiguous bf16 instances only
+  if (p.a_kc && p.b_kc) {
+    if constexpr (KKF) set_dma<BM, BN, WM, WN, NST, true, true, true>(p);
+    return KKF;
+  }
+  if (!p.a_kc && !p.b_kc && p.out_f32) {
+    // weight gradients: the plain split-K slab instance (RES 3) when the slabs are f32 and
+    // nothing else is asked for
+    if constexpr (MN == 2) {
+      if ((a.flags & kSlabs) && !(a.flags & (1 | 2 | 8 | 16)) && a.alpha == 1.f) {
+        set_dma<BM, BN, WM, WN, NST, false, false, true, 3>(p);
+        p.family = kFamSlab;
+        p.group2 = gemm_dma_group2_kernel<BM, BN, WM, WN, NST, false, false, true, 3>;
+        p.group2_name = dma_name<BM, BN, WM, WN, NST, false, false, true, true>();
+        return true;
+      }
+    }
+    if constexpr (MN > 0) set_dma<BM, BN, WM, WN, NST, false, false, true>(p);
+    return MN > 0;
+  }
+  if constexpr (MIX) {
+    if (!p.a_kc && !p.b_kc) set_dma<BM, BN, WM, WN, NST, false, false, false>(p);
+    else if (p.a_kc && !p.out_f32) set_dma<BM, BN, WM, WN, NST, true, false, false>(p);
+    else if (p.a_kc) set_dma<BM, BN, WM, WN, NST, true, false, true>(p);
+    else if (!p.out_f32) set_dma<BM, BN, WM, WN, NST, false, true, false>(p);
+    else set_dma<BM, BN, WM, WN, NST, false, true, true>(p);
+  }
+  return MIX;
+}
+#undef LJS_SET_DMA
+#undef LJS_SET_LEAN
+#undef LJS_BY_RES
+
+struct TileEntry { int code, demote, unfold; };
+inline const TileEntry* find_tile(int code) {
+#define LJS_ENTRY(CODE, BM, BN, WM, WN, NST, KK, KKF, MIX, MN, LEAN, DEMOTE, UNFOLD) {CODE, DEMOTE, UNFOLD},
+  static const TileEntry table[] = {LJS_GEMM_TILES(LJS_ENTRY)};
+#undef LJS_ENTRY
+  for (const TileEntry& t : table)
+    if (t.code == code) return &t;
+  return nullptr;
+}
+inline bool tile_instance(int code, const GemmArgs& a, bool lean_req, bool gen_req, GemmPlan& p) {
+  switch (code) {
+#define LJS_CASE(CODE, BM, BN, WM, WN, NST, KK, KKF, MIX, MN, LEAN, DEMOTE, UNFOLD) \
+  case CODE: return dma_instance<BM, BN, WM, WN, NST, KK, KKF, MIX, MN, LEAN>(a, lean_req, gen_req, p);
+    LJS_GEMM_TILES(LJS_CASE)
+#undef LJS_CASE
+  }
+  return false;
+}
+
+// the register-staged tiles (64, 128): the terminal fallbacks, every layout and output type
+template <int BM, int BN>
+void reg_instance(GemmPlan& p) {
+  p.family = kFamReg;
+  p.BM = BM; p.BN = BN; p.WM = 2; p.WN = 2; p.NST = 2;
+  p.block = 256;
+  p.variant = -1;
+  p.psum = false;
+  p.group2 = nullptr;
+#define LJS_CASE(AK, BK_, OF)                                   \
+  if (p.a_kc == AK && p.b_kc == BK_ && p.out_f32 == OF) {       \
+    p.kernel = gemm_bf16_kernel<BM, BN, AK, BK_, OF>;           \
+    p.name = reg_name<BM, BN, AK, BK_, OF>();                   \
+  }
+  LJS_CASE(1, 1, 0) LJS_CASE(1, 1, 1) LJS_CASE(0, 0, 0) LJS_CASE(0, 0, 1)
+  LJS_CASE(1, 0, 0) LJS_CASE(1, 0, 1) LJS_CASE(0, 1, 0) LJS_CASE(0, 1, 1)
+#undef LJS_CASE
+}
+
+// The LDS-DMA and lean kernels' grid: persistent when the items fill whole rounds of the resident
+// slots -- each block then walks `rounds` items with the next item's first K-tiles in flight
+// during the current item's epilogue (measured at T = 16384: QKV projection 43.8 -> 39.9 us on
+// 128x128 x 2/CU).  Otherwise one block per item, which lets the dispatcher balance a ragged last
+// round (measured best at the bench shapes).
+inline int dma_grid(const GemmPlan& p, int cus) {
+  const int lds_bytes = p.NST * (p.BM + p.BN) * BK * 2;
+  const int slots = cus * ((p.WM * p.WN == 4 && lds_bytes <= 80 * 1024) ? 2 : 1);  // resident blocks
+  return (p.items > slots && p.items % slots == 0) ? slots : p.items;
+}
+
+// a: the call as ljs_gemm_bf16 received it (a.psum: the caller's psum buffer; a.splitk and
+// a.kt_per_split are not read).  Preconditions checked here (the Python wrapper checks them too):
+// K % 8 == 0; for an m/n-contiguous operand its M (or N) % 8 == 0; leading dimensions that are
+// multiples of 8 elements.
+GemmPlan gemm_plan(const GemmArgs& a, bool a_kc, bool b_kc, bool out_f32, int splitk, int tile, int cus) {
+  GemmPlan p{};
+  p.err = hipErrorInvalidValue;
+  p.a_kc = a_kc; p.b_kc = b_kc; p.out_f32 = out_f32;
+  p.N = a.N; p.batch = a.batch;
+  const int M = a.M, N = a.N, K = a.K, flags = a.flags;
+  const bool res = flags & (kResAdd | kResMask), slabs = flags & kSlabs;
+  if (K % 8 || (!a_kc && M % 8) || (!b_kc && N % 8) || a.lda % 8 || a.ldb % 8) return p;
+  if (splitk > 1 && !out_f32) return p;
+  // the epilogue operand applies to bf16 outputs (its 16-byte loads need aligned 8-column chunks)
+  if (res && (out_f32 || !a.res || (a.ldr % 8) || (a.sR % 8) || (N % 8) || (((uintptr_t)a.res) & 15))) return p;
+  // B as a host array of `batch` (<= 4) device pointers: slab mode only
+  if ((flags & kBPtrs) && (a.batch < 1 || a.batch > 4 || !slabs)) return p;
+  // zeroing C first (split-K accumulates with atomics) needs C to be one dense block
+  if ((flags & 16) && a.batch > 1 && a.sC != (long)M * a.ldc) return p;
+  const bool gen_req = tile >= 2 * kForceLean;
+  if (gen_req) tile -= 2 * kForceLean;
+  const bool lean_req = tile >= kForceLean;
+  if (lean_req) tile -= kForceLean;
+  const int nkt = (K + BK - 1) / BK;
+  if (splitk < 1) splitk = 1;
+  if (splitk > nkt) splitk = nkt;
+  p.kt_per_split = (nkt + splitk - 1) / splitk;
+  p.splitk = (nkt + p.kt_per_split - 1) / p.kt_per_split;
+  // The LDS-DMA kernels need K % 64 == 0, a split that divides the K-tiles (slab mode: the last
+  // split may run past K), operands addressable with 32-bit byte offsets and, for a bf16 output,
+  // whole aligned 16-byte chunks of C.
+  const long k_ext = slabs ? (long)p.splitk * p.kt_per_split * BK : K;  // K-rows the splits address
+  const bool dma_ok = K % BK == 0 && (slabs || (K / BK) % p.splitk == 0) &&
+                      (a_kc ? (long)M * a.lda : k_ext * a.lda) < (1L << 30) &&
+                      (b_kc ? (long)N * a.ldb : k_ext * a.ldb) < (1L << 30);
+  const bool dma_store_ok = out_f32 || (N % 8 == 0 && a.ldc % 8 == 0 && (a.sC % 8 == 0 || a.batch == 1) &&
+                                        (((uintptr_t)a.C) & 15) == 0);
+  // slab mode: f32 slabs of an LDS-DMA tile over m/n-contiguous operands, and the caller's slab
+  // count must be the launched split count
+  if (slabs && (!out_f32 || a_kc || b_kc || (flags & (8 | 16)) || p.splitk != splitk || !find_tile(tile) || !dma_ok))
+    return p;
+  // walk the demotion chain to the first tile that has an instance for this call
+  while (const TileEntry* t = find_tile(tile)) {
+    if (!(dma_ok && dma_store_ok) || !tile_instance(tile, a, lean_req, gen_req, p)) {
+      tile = t->demote;
+    } else if (t->unfold && a.batch > 1) {
+      // weight-major batches side by side in C over contiguous B (the fused Q/K/V projection):
+      // one GEMM over N * batch columns (the folded B still addressable by 32-bit offsets)
+      if (a.sA == 0 && a.sB == (long)N * a.ldb && a.sC == N && a.ldc == (long)N * a.batch && !a.bias &&
+          (long)N * a.batch * a.ldb < (1L << 30)) {
+        p.N = N * a.batch;
+        p.batch = 1;
+        break;
+      }
+      tile = t->unfold;
+    } else {
+      break;
+    }
+  }
+  const bool dma = find_tile(tile);
+  if (!dma) {
+    tile = tile == 64 ? 64 : 128;
+    if (tile == 64) reg_instance<64, 64>(p);
+    else reg_instance<128, 128>(p);
+  }
+  const int ntm = (M + p.BM - 1) / p.BM, ntn = (p.N + p.BN - 1) / p.BN;
+  if (!dma) {
+    p.gx = ntm * ntn;
+    p.gy = p.batch * p.splitk;
+  } else {
+    p.items = ntm * ntn * p.batch * p.splitk;
+    p.mfast = ntm < ntn;  // narrow dimension fastest: tiles sharing a panel run together
+    p.gx = dma_grid(p, cus);
+    p.gy = 1;
+    if (p.psum) p.psum_count = p.items * p.WM * p.WN;  // one float per (item, wave)
+  }
+  p.tile = tile;
+  p.err = hipSuccess;
+  return p;
+}
+
+// ---------------------------------------------------------------------------- launch
+inline void gemm_rec(const GemmPlan& p, int req_tile, const char* name, unsigned grid_x, int splitk1 = -1) {
+  LjsLaunchRec r = ljs_launch_make(name, dim3(grid_x, p.gy), p.block);
+  r.req_tile = req_tile; r.res_tile = p.tile;
+  r.splitk = p.splitk; r.splitk1 = splitk1; r.variant = p.variant;
   ljs_launch_push(r);
 }
 
-template <int BM, int BN, int WM, int WN, int NST, bool AK, bool BKc, bool OF, int RES = 0>
-hipError_t launch_dma(const GemmArgs& a, hipStream_t s, int blocks_per_cu) {
-  if (!g_cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_cus <= 0) g_cus = 256;
-  }
-  const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-  const int items = ntm * ntn * a.batch * a.splitk;
-  GemmArgs a2 = a;
-  a2.trace = g_gemm_trace;
-  if (ntm < ntn) a2.flags |= kMFast;   // narrow dimension fastest: tiles sharing a panel run together
-  // blocks_per_cu 0 = one block per work item (measured best at the bench shapes: the
-  // dispatcher balances), else a persistent grid of blocks_per_cu x CUs
-  int bpc = blocks_per_cu;
-  // Persistent grid when the items fill whole rounds of the resident slots: each block then
-  // walks `rounds` items with the next item's first K-tiles in flight during the current
-  // item's epilogue (measured at T = 16384: QKV projection 43.8 -> 39.9 us on 128x128 x 2/CU).
-  // Otherwise one block per item, which lets the dispatcher balance a ragged last round.
-  constexpr int kLdsBytes = NST * (BM + BN) * BK * 2;
-  constexpr int kNatural = (WM * WN == 4 && kLdsBytes <= 80 * 1024) ? 2 : 1;  // resident blocks / CU
-  if (bpc == 0 && items > g_cus * kNatural && items % (g_cus * kNatural) == 0) bpc = kNatural;
-  int grid = bpc > 0 ? g_cus * bpc : items;
-  if (grid > items) grid = items;
-  gemm_rec(dma_name<BM, BN, WM, WN, NST, AK, BKc, OF, false>(), dim3(grid), WM * WN * 64, a.splitk, RES);
-  hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, NST, AK, BKc, OF, RES>), dim3(grid), dim3(WM * WN * 64), 0,
-                     s, a2);
-  return hipGetLastError();
+// the call's arguments as its plan launches them
+inline void apply_plan(const GemmPlan& p, GemmArgs& a) {
+  a.N = p.N;
+  a.batch = p.batch;
+  a.splitk = p.splitk;
+  a.kt_per_split = p.kt_per_split;
+  if (!p.psum) a.psum = nullptr;
+  if (p.mfast) a.flags |= kMFast;
 }
 
-// bf16-output k-contiguous launch with the epilogue operand variant the flags ask for
-template <int BM, int BN, int WM, int WN, int NST>
-hipError_t launch_dma_kk(const GemmArgs& a, hipStream_t s) {
-  if (a.flags & (kResAdd | kResMask)) {
-    if (a.flags & kResF32) return launch_dma<BM, BN, WM, WN, NST, true, true, false, 2>(a, s, 0);
-    return launch_dma<BM, BN, WM, WN, NST, true, true, false, 1>(a, s, 0);
-  }
-  // plain epilogue (RES 3: compile-time instance, PERF_NOTES r4 "plain instance")
-  if (a.alpha == 1.f && !(a.flags & 3) && !a.psum)
-    return launch_dma<BM, BN, WM, WN, NST, true, true, false, 3>(a, s, 0);
-  // bias (f32) + optional fused sum, alpha 1, no ReLU (RES 4)
-  if (a.alpha == 1.f && (a.flags & 7) == 6 && a.splitk == 1)
-    return launch_dma<BM, BN, WM, WN, NST, true, true, false, 4>(a, s, 0);
-  return launch_dma<BM, BN, WM, WN, NST, true, true, false, 0>(a, s, 0);
+hipError_t launch_plan(const GemmPlan& p, GemmArgs a, int req_tile, hipStream_t s) {
+  if (p.family == kFamDma || p.family == kFamSlab) a.trace = g_gemm_trace;
+  gemm_rec(p, req_tile, p.name, p.gx);
+  void* args[] = {&a};
+  (void)hipLaunchKernel((const void*)p.kernel, dim3(p.gx, p.gy), dim3(p.block), args, 0, s);
+  return hipGetLastError();
 }
 
 // Grouped weight-gradient launches (ljs_gemm_group_begin / _end): while a group is open, plain f32
@@ -1604,129 +1810,39 @@ hipError_t launch_dma_kk(const GemmArgs& a, hipStream_t s) {
 // one by one.  Same kernel body per item: bit-identical to separate launches.
 struct GroupRec {
   GemmArgs a;
-  int req_tile, res_tile;   // for the launch record, as ljs_gemm_bf16 saw them
-  int kind;   // 1: 128x128 2x2 waves 2 stages, 2: 128x128 2x4 4 stages, 3: 128x128 2x4 3 stages
+  GemmPlan p;
+  int req_tile;   // for the launch record, as ljs_gemm_bf16 saw it
 };
 // (per host thread: another thread's GEMMs are never recorded into this thread's open group)
 static thread_local bool g_group_on = false;
 static thread_local GroupRec g_group[2];
 static thread_local int g_group_n = 0;
 
-template <int BM, int BN>
-GemmArgs group_prep(const GemmArgs& a, int* items) {
-  const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-  *items = ntm * ntn * a.batch * a.splitk;
-  GemmArgs a2 = a;
-  a2.trace = nullptr;
-  if (ntm < ntn) a2.flags |= kMFast;
-  return a2;
-}
-
-// weight-gradient (m/n-contiguous, f32 output) launch: the plain split-K slab instance (RES 3)
-// when the slabs are f32 and nothing else is asked for
-template <int BM, int BN, int WM, int WN, int NST>
-hipError_t launch_slab(const GemmArgs& a, hipStream_t s) {
-  if ((a.flags & kSlabs) && !(a.flags & (1 | 2 | 8 | 16)) && a.alpha == 1.f) {
-    constexpr int kind = (BM == 128 && BN == 128 && WM == 2 && WN == 2 && NST == 2)   ? 1
-                         : (BM == 128 && BN == 128 && WM == 2 && WN == 4 && NST == 4) ? 2
-                         : (BM == 128 && BN == 128 && WM == 2 && WN == 4 && NST == 3) ? 3
-                                                                                      : 0;
-    if (kind && g_group_on && g_group_n < 2) {
-      g_group[g_group_n].a = a;
-      g_group[g_group_n].kind = kind;
-      g_group[g_group_n].req_tile = g_req_tile;
-      g_group[g_group_n].res_tile = g_res_tile;
-      ++g_group_n;
-      return hipSuccess;
-    }
-    return launch_dma<BM, BN, WM, WN, NST, false, false, true, 3>(a, s, 0);
-  }
-  return launch_dma<BM, BN, WM, WN, NST, false, false, true, 0>(a, s, 0);
-}
-
-template <int WN, int NST>
-hipError_t launch_group_kind(const GroupRec* r, int n, hipStream_t s) {
-  g_req_tile = r[0].req_tile;
-  g_res_tile = r[0].res_tile;
-  if (n == 2) {
-    int i0 = 0, i1 = 0;
-    const GemmArgs a0 = group_prep<128, 128>(r[0].a, &i0), a1 = group_prep<128, 128>(r[1].a, &i1);
-    gemm_rec(dma_name<128, 128, 2, WN, NST, false, false, true, true>(), dim3(i0 + i1), 2 * WN * 64, a0.splitk, 3,
-             a1.splitk);
-    hipLaunchKernelGGL((gemm_dma_group2_kernel<128, 128, 2, WN, NST, false, false, true, 3>), dim3(i0 + i1),
-                       dim3(2 * WN * 64), 0, s, a0, a1, i0);
-    return hipGetLastError();
-  }
-  return launch_dma<128, 128, 2, WN, NST, false, false, true, 3>(r[0].a, s, 0);
-}
-
-hipError_t launch_rec(const GroupRec* r, int n, hipStream_t s) {
-  if (r[0].kind == 1) return launch_group_kind<2, 2>(r, n, s);
-  if (r[0].kind == 2) return launch_group_kind<4, 4>(r, n, s);
-  return launch_group_kind<4, 3>(r, n, s);
-}
-
-// the lean K-loop kernel (k-contiguous, bf16 output, no split): same grid choice as launch_dma
-template <int BM, int BN, int WM, int WN, int NST, int RES>
-hipError_t launch_lean(const GemmArgs& a, hipStream_t s) {
-  if (!g_cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (g_cus <= 0) g_cus = 256;
-  }
-  const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-  const int items = ntm * ntn * a.batch;
-  GemmArgs a2 = a;
-  if (ntm < ntn) a2.flags |= kMFast;
-  constexpr int kLdsBytes = NST * (BM + BN) * BK * 2;
-  constexpr int kNatural = (WM * WN == 4 && kLdsBytes <= 80 * 1024) ? 2 : 1;
-  int grid = items;
-  if (items > g_cus * kNatural && items % (g_cus * kNatural) == 0) grid = g_cus * kNatural;
-  gemm_rec(lean_name<BM, BN, WM, WN, NST>(), dim3(grid), WM * WN * 64, a.splitk, RES);
-  hipLaunchKernelGGL((gemm_lean_kernel<BM, BN, WM, WN, NST, RES>), dim3(grid), dim3(WM * WN * 64), 0, s, a2);
+hipError_t launch_group2(GroupRec* r, hipStream_t s) {
+  const GemmPlan& p = r[0].p;
+  const unsigned grid = r[0].p.items + r[1].p.items;
+  gemm_rec(p, r[0].req_tile, p.group2_name, grid, r[1].p.splitk);
+  void* args[] = {&r[0].a, &r[1].a, &r[0].p.items};
+  (void)hipLaunchKernel((const void*)p.group2, dim3(grid), dim3(p.block), args, 0, s);
   return hipGetLastError();
 }
 
-template <int BM, int BN, int WM, int WN, int NST>
-hipError_t launch_lean_kk(const GemmArgs& a, hipStream_t s) {
-  if (a.flags & (kResAdd | kResMask)) {
-    if (a.flags & kResF32) return launch_lean<BM, BN, WM, WN, NST, 2>(a, s);
-    return launch_lean<BM, BN, WM, WN, NST, 1>(a, s);
-  }
-  if (a.alpha == 1.f && !(a.flags & 3) && !a.psum) return launch_lean<BM, BN, WM, WN, NST, 3>(a, s);
-  if (a.alpha == 1.f && (a.flags & 7) == 6) return launch_lean<BM, BN, WM, WN, NST, 4>(a, s);
-  return launch_lean<BM, BN, WM, WN, NST, 0>(a, s);
-}
-
-template <int BM, int BN, bool AK, bool BKc, bool OF>
-hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
-  int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-  dim3 grid(ntm * ntn, a.batch * a.splitk);
-  gemm_rec(reg_name<BM, BN, AK, BKc, OF>(), grid, 256, a.splitk, -1);
-  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, AK, BKc, OF>), grid, dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-template <int BM, int BN>
-hipError_t dispatch_layout(const GemmArgs& a, int a_kc, int b_kc, int out_f32, hipStream_t s) {
-#define LJS_CASE(AK, BK_, OF) \
-  if (a_kc == AK && b_kc == BK_ && out_f32 == OF) return launch_t<BM, BN, AK, BK_, OF>(a, s);
-  LJS_CASE(1, 1, 0) LJS_CASE(1, 1, 1) LJS_CASE(0, 0, 0) LJS_CASE(0, 0, 1)
-  LJS_CASE(1, 0, 0) LJS_CASE(1, 0, 1) LJS_CASE(0, 1, 0) LJS_CASE(0, 1, 1)
-#undef LJS_CASE
-  return hipErrorInvalidValue;
+GemmArgs make_args(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, long lda, long ldb,
+                   long ldc, long sA, long sB, long sC, long sBias, int batch, int flags, float alpha, void* psum,
+                   const void* res, long ldr, long sR) {
+  GemmArgs a{};  // (bptr, trace: null)
+  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.bias = bias;
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.sA = sA; a.sB = sB; a.sC = sC; a.sBias = sBias;
+  a.M = M; a.N = N; a.K = K; a.batch = batch;
+  a.alpha = alpha; a.flags = flags;
+  a.psum = (float*)psum;
+  a.res = res; a.ldr = ldr; a.sR = sR;
+  return a;
 }
 
 }  // namespace
 
-// Returns 0 on success.  Preconditions checked here (the Python wrapper checks them too):
-// K % 8 == 0; for an m/n-contiguous operand its M (or N) % 8 == 0; 16-byte aligned bases
-// and leading dimensions that are multiples of 8 elements.
-
-// LJS_GEMM_TRACE builds: the LDS-DMA launches that follow write their per-wave timelines to
-// `buf` (blocks x waves x kTraceSlots u64, zeroed by the caller); null turns it off.  Returns
-// kTraceSlots, or 0 in a library built without the instrumentation.
 LJS_API void ljs_gemm_group_begin() {
   g_group_on = true;
   g_group_n = 0;
@@ -1737,15 +1853,17 @@ LJS_API int ljs_gemm_group_end(hipStream_t stream) {
   g_group_on = false;
   const int n = g_group_n;
   g_group_n = 0;
-  if (n == 0) return 0;
-  if (n == 2 && g_group[0].kind == g_group[1].kind) return (int)launch_rec(g_group, 2, stream);
+  if (n == 2 && g_group[0].p.kernel == g_group[1].p.kernel) return (int)launch_group2(g_group, stream);
   for (int i = 0; i < n; ++i) {
-    const hipError_t e = launch_rec(&g_group[i], 1, stream);
+    const hipError_t e = launch_plan(g_group[i].p, g_group[i].a, g_group[i].req_tile, stream);
     if (e != hipSuccess) return (int)e;
   }
   return 0;
 }
 
+// LJS_GEMM_TRACE builds: the LDS-DMA launches that follow write their per-wave timelines to
+// `buf` (blocks x waves x kTraceSlots u64, zeroed by the caller); null turns it off.  Returns
+// kTraceSlots, or 0 in a library built without the instrumentation.
 LJS_API int ljs_gemm_set_trace(void* buf) {
 #ifdef LJS_GEMM_TRACE
   g_gemm_trace = (unsigned long long*)buf;
@@ -1756,186 +1874,56 @@ LJS_API int ljs_gemm_set_trace(void* buf) {
 #endif
 }
 
+// Returns 0 on success.  A call the plan rejects returns hipErrorInvalidValue with nothing done:
+// C is not zeroed (flags & 16) and nothing is launched or recorded.
 LJS_API int ljs_gemm_bf16(const void* A, const void* B, void* C, const void* bias, int M, int N, int K,
                           long lda, long ldb, long ldc, long sA, long sB, long sC, long sBias, int batch,
                           int a_kc, int b_kc, int out_f32, int flags, float alpha, int splitk, int tile,
                           void* psum, int* psum_count, const void* res, long ldr, long sR, hipStream_t stream) {
-  if (K % 8 || (!a_kc && M % 8) || (!b_kc && N % 8) || lda % 8 || ldb % 8) return (int)hipErrorInvalidValue;
-  if (splitk > 1 && !out_f32) return (int)hipErrorInvalidValue;
-  // the epilogue operand applies to bf16 outputs (its 16-byte loads need aligned 8-column chunks)
-  if ((flags & (kResAdd | kResMask)) &&
-      (out_f32 || !res || (ldr % 8) || (sR % 8) || (N % 8) || (((uintptr_t)res) & 15)))
-    return (int)hipErrorInvalidValue;
-  GemmArgs a;
-  a.A = (const bf16_t*)A;
-  a.B = (const bf16_t*)B;
-  a.C = C;
-  a.bias = bias;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-  a.sA = sA; a.sB = sB; a.sC = sC; a.sBias = sBias;
-  a.M = M; a.N = N; a.K = K;
-  a.batch = batch;
-  a.alpha = alpha;
-  a.flags = flags;
-  a.psum = nullptr;
-  a.res = res;
-  a.ldr = ldr;
-  a.sR = sR;
-  a.trace = nullptr;
+  GemmArgs a = make_args(A, B, C, bias, M, N, K, lda, ldb, ldc, sA, sB, sC, sBias, batch, flags, alpha, psum, res,
+                         ldr, sR);
+  const GemmPlan p = gemm_plan(a, a_kc, b_kc, out_f32, splitk, tile, ljs_device_cus());
+  if (p.err != hipSuccess) return (int)p.err;
+  if (psum_count) *psum_count = p.psum_count;
+  if (flags & 16) {  // zero C first (split-K accumulates with atomics)
+    const size_t es = out_f32 ? 4 : 2;
+    const size_t bytes = ((size_t)(batch - 1) * sC + (size_t)(M - 1) * ldc + N) * es;
+    const hipError_t me = hipMemsetAsync(C, 0, bytes, stream);
+    if (me != hipSuccess) return (int)me;
+  }
   if (flags & kBPtrs) {
-    // B is a HOST array of `batch` (<= 4) device pointers, one B operand per batch
-    if (batch < 1 || batch > 4 || !(flags & kSlabs)) return (int)hipErrorInvalidValue;
+    // B is a HOST array of `batch` device pointers, one B operand per batch
     const void* const* bp = (const void* const*)B;
     for (int i = 0; i < 4; ++i) a.bptr[i] = (const bf16_t*)(i < batch ? bp[i] : bp[0]);
     a.B = a.bptr[0];
-  } else {
-    for (int i = 0; i < 4; ++i) a.bptr[i] = nullptr;
   }
-  if (psum_count) *psum_count = 0;
-  // A/B: tile code + 100000 forces the lean K-loop kernel where it applies, + 200000 the general one
-  g_req_tile = tile;
-  const bool gen_req = tile >= 200000;
-  if (gen_req) tile -= 200000;
-  const bool lean_req = tile >= 100000;
-  if (lean_req) tile -= 100000;
-  int nkt = (K + BK - 1) / BK;
-  if (splitk < 1) splitk = 1;
-  if (splitk > nkt) splitk = nkt;
-  a.kt_per_split = (nkt + splitk - 1) / splitk;
-  a.splitk = (nkt + a.kt_per_split - 1) / a.kt_per_split;
-  if (flags & 16) {  // zero C first (split-K accumulates with atomics); C must be one dense block
-    if (batch > 1 && sC != (long)M * ldc) return (int)hipErrorInvalidValue;
-    size_t es = out_f32 ? 4 : 2;
-    size_t bytes = ((size_t)(batch - 1) * sC + (size_t)(M - 1) * ldc + N) * es;
-    hipError_t me = hipMemsetAsync(C, 0, bytes, stream);
-    if (me != hipSuccess) return (int)me;
+  apply_plan(p, a);
+  if (p.family == kFamSlab && g_group_on && g_group_n < 2) {
+    g_group[g_group_n++] = GroupRec{a, p, tile};
+    return 0;
   }
-  hipError_t e;
-  // Persistent LDS-DMA kernels (tile codes): 2561 = 256x128, 8 waves, 3 stages, 1 block/CU
-  // (k-contiguous operands only); 1284 = 128x128, 4 waves, 4 stages, 1 block/CU; 1282 =
-  // 128x128, 4 waves, 2 stages, 2 blocks/CU.  They need K % 64 == 0, a split that divides the
-  // K-tiles and operands addressable with 32-bit byte offsets.
-  const int nkt64 = K / BK;
-  const bool slabs = flags & kSlabs;
-  if (slabs && (!out_f32 || a_kc || b_kc || (flags & (8 | 16)) || K % BK ||
-                a.splitk != splitk || !(tile > 1000 || tile == 643 || tile == 644)))
-    return (int)hipErrorInvalidValue;  // the caller's slab count must be the launched split count
-  const long k_ext = slabs ? (long)a.splitk * a.kt_per_split * BK : K;  // K-rows the splits address
-  const bool dma_ok = K % BK == 0 && (slabs || nkt64 % a.splitk == 0) &&
-                      (a_kc ? (long)M * lda : k_ext * lda) < (1L << 30) &&
-                      (b_kc ? (long)N * ldb : k_ext * ldb) < (1L << 30);
-  if (slabs && !dma_ok) return (int)hipErrorInvalidValue;
-  const bool dma_store_ok = out_f32 || (N % 8 == 0 && ldc % 8 == 0 && (sC % 8 == 0 || batch == 1) &&
-                                        (((uintptr_t)C) & 15) == 0);
-  if (tile > 1000 && !(dma_ok && dma_store_ok)) tile = 128;
-  // the LDS-DMA kernels carry the epilogue operand in their k-contiguous bf16 variants only
-  if ((flags & (kResAdd | kResMask)) && tile > 1000 && !(a_kc && b_kc)) tile = 128;
-  if ((flags & (kResAdd | kResMask)) && (tile == 643 || tile == 644)) tile = 64;
-  if ((tile == 643 || tile == 644) && !(dma_ok && dma_store_ok)) tile = 64;
-  if ((tile == 2563 || tile == 12856) && !(!a_kc && !b_kc && out_f32)) tile = 1282;
-  if (tile == 2561 && !(a_kc && b_kc)) tile = 1284;
-  if (tile == 2562 && !(a_kc && b_kc && !out_f32 && !(flags & (kResAdd | kResMask)))) tile = 1282;
-  if (tile == 2562 && batch > 1) {
-    // weight-major batches side by side in C over contiguous B (the fused Q/K/V projection):
-    // one GEMM over N * batch columns
-    if (sA == 0 && sB == (long)N * ldb && sC == N && ldc == (long)N * batch && !bias &&
-        (long)N * batch * ldb < (1L << 30)) {   // (the folded B still addressable by 32-bit offsets)
-      a.N = N * batch;
-      a.batch = 1;
-      N = a.N;
-      batch = 1;
-    } else {
-      tile = 2561;
-    }
-  }
-  if (tile == 1602 && !(a_kc && b_kc && !out_f32 && a.splitk == 1)) tile = 1282;
-  if ((tile == 12883 || tile == 12884) && !((!a_kc && !b_kc && out_f32) || (a_kc && b_kc))) tile = 1282;
-  g_res_tile = tile;
-  // fused output sum (psum): LDS-DMA kernels with bf16 output only; one float per (item, wave)
-  if (psum && !out_f32 && tile > 1000) {
-    const int bm = (tile == 2561 || tile == 2562) ? 256 : 128;
-    const int nw = (tile == 2561 || tile == 2562 || tile == 12883 || tile == 12884) ? 8 : 4;
-    const int bn = tile == 1602 ? 160 : tile == 2562 ? 192 : 128;
-    a.psum = (float*)psum;
-    if (psum_count) *psum_count = ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * batch * a.splitk * nw;
-  }
-  // the lean K-loop kernel for the k-contiguous bf16-output LDS-DMA tiles without split-K
-  // (tile code + 100000 forces the lean one, + 200000 the general one: A/B and bit-exact tests)
-  if (!gen_req && a_kc && b_kc && !out_f32 && a.splitk == 1 && !(flags & kBPtrs) && dma_ok &&
-      dma_store_ok) {
-    if (tile == 2561) return (int)launch_lean_kk<256, 128, 4, 2, 3>(a, stream);
-    if (tile == 2562) return (int)launch_lean_kk<256, 192, 4, 2, 2>(a, stream);
-    // (128x160, one item per block: the general kernel measured 14.4 vs 14.8 us, gpurun_out/r5i)
-    if (tile == 1602 && lean_req) return (int)launch_lean_kk<128, 160, 4, 1, 2>(a, stream);
-    if (tile == 1282) return (int)launch_lean_kk<128, 128, 2, 2, 2>(a, stream);
-    if (tile == 1284) return (int)launch_lean_kk<128, 128, 2, 2, 4>(a, stream);
-    if (tile == 12883) return (int)launch_lean_kk<128, 128, 2, 4, 3>(a, stream);
-    if (tile == 12884) return (int)launch_lean_kk<128, 128, 2, 4, 4>(a, stream);
-    if (tile == 644 && !(flags & (kResAdd | kResMask))) return (int)launch_lean_kk<64, 64, 2, 2, 4>(a, stream);
-  }
-  if (tile == 2563) {
-    e = launch_dma<256, 128, 4, 2, 3, false, false, true>(a, stream, 0);
-  } else if (tile == 12856) {
-    e = launch_dma<128, 256, 2, 4, 3, false, false, true>(a, stream, 0);
+  return (int)launch_plan(p, a, tile, stream);
+}
 
-  } else if (tile == 1602) {
-    e = launch_dma_kk<128, 160, 4, 1, 2>(a, stream);
-  } else if (tile == 2562) {
-    e = launch_dma_kk<256, 192, 4, 2, 2>(a, stream);
-  } else if (tile == 2561) {
-    if (out_f32) e = launch_dma<256, 128, 4, 2, 3, true, true, true>(a, stream, 0);
-    else e = launch_dma_kk<256, 128, 4, 2, 3>(a, stream);
-  } else if (tile == 12883 || tile == 12884) {
-    // 128x128, 8 waves, 3 / 4 stages (weight-grad MN x MN f32, or k-contiguous operands)
-    const bool d4 = tile == 12884;
-    if (!a_kc) {
-      if (d4) e = launch_slab<128, 128, 2, 4, 4>(a, stream);
-      else e = launch_slab<128, 128, 2, 4, 3>(a, stream);
-    } else if (out_f32) {
-      if (d4) e = launch_dma<128, 128, 2, 4, 4, true, true, true>(a, stream, 0);
-      else e = launch_dma<128, 128, 2, 4, 3, true, true, true>(a, stream, 0);
-    } else {
-      if (d4) e = launch_dma_kk<128, 128, 2, 4, 4>(a, stream);
-      else e = launch_dma_kk<128, 128, 2, 4, 3>(a, stream);
-    }
-  } else if (tile == 643 || tile == 644) {
-    if (a_kc && b_kc && !out_f32 && (flags & (kResAdd | kResMask))) {
-      e = hipErrorInvalidValue;  // no epilogue-operand variant at 64x64: use the register-staged tile
-    } else {
-      // k-contiguous bf16 output: the compile-time epilogue instances (plain / bias + sum)
-      if (tile == 644 && a_kc && b_kc && !out_f32) return (int)launch_dma_kk<64, 64, 2, 2, 4>(a, stream);
-#define LJS_DMA(AK, BK_, OF)                                                                   \
-  if (a_kc == AK && b_kc == BK_ && out_f32 == OF) {                                            \
-    if (tile == 644) return (int)launch_dma<64, 64, 2, 2, 4, AK, BK_, OF>(a, stream, 0);       \
-    return (int)launch_dma<64, 64, 2, 2, 3, AK, BK_, OF>(a, stream, 0);                        \
-  }
-      LJS_DMA(1, 1, 0) LJS_DMA(1, 1, 1) LJS_DMA(0, 0, 0) LJS_DMA(0, 0, 1)
-      LJS_DMA(1, 0, 0) LJS_DMA(1, 0, 1) LJS_DMA(0, 1, 0) LJS_DMA(0, 1, 1)
-#undef LJS_DMA
-      e = hipErrorInvalidValue;
-    }
-  } else if (tile == 1284 || tile == 1282) {
-    if (tile == 1282 && !a_kc && !b_kc && out_f32) return (int)launch_slab<128, 128, 2, 2, 2>(a, stream);
-    // (plain if/else, not ?: -- see the explicit-instantiation note above)
-    if (a_kc && b_kc && !out_f32) {
-      if (tile == 1284) return (int)launch_dma_kk<128, 128, 2, 2, 4>(a, stream);
-      return (int)launch_dma_kk<128, 128, 2, 2, 2>(a, stream);
-    }
-#define LJS_DMA(AK, BK_, OF)                                                              \
-  if (a_kc == AK && b_kc == BK_ && out_f32 == OF) {                                       \
-    if (tile == 1284) return (int)launch_dma<128, 128, 2, 2, 4, AK, BK_, OF>(a, stream, 0); \
-    return (int)launch_dma<128, 128, 2, 2, 2, AK, BK_, OF>(a, stream, 0);                  \
-  }
-    LJS_DMA(1, 1, 0) LJS_DMA(1, 1, 1) LJS_DMA(0, 0, 0) LJS_DMA(0, 0, 1)
-    LJS_DMA(1, 0, 0) LJS_DMA(1, 0, 1) LJS_DMA(0, 1, 0) LJS_DMA(0, 1, 1)
-#undef LJS_DMA
-    e = hipErrorInvalidValue;
-  } else if (tile == 64) {
-    e = dispatch_layout<64, 64>(a, a_kc, b_kc, out_f32, stream);
-  } else {
-    e = dispatch_layout<128, 128>(a, a_kc, b_kc, out_f32, stream);
-  }
-  return (int)e;
+// The plan of the same call on a device of `cus` compute units, without a GPU: nothing is
+// dereferenced or launched (C and res are read as addresses, for their alignment).  out[0..20]:
+// error, resolved tile, family (0 register-staged, 1 LDS-DMA, 2 lean, 3 groupable slab), BM, BN, WM,
+// WN, NST, a_kc, b_kc, out_f32, variant, splitk, kt_per_split, launched N, launched batch, grid x,
+// grid y, block, psum partials, kMFast; name: the kernel instance.  Returns the error.
+LJS_API int ljs_gemm_plan(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, long lda,
+                          long ldb, long ldc, long sA, long sB, long sC, long sBias, int batch, int a_kc, int b_kc,
+                          int out_f32, int flags, float alpha, int splitk, int tile, void* psum, int* psum_count,
+                          const void* res, long ldr, long sR, int cus, int* out, char* name, int name_cap) {
+  const GemmPlan p = gemm_plan(make_args(A, B, C, bias, M, N, K, lda, ldb, ldc, sA, sB, sC, sBias, batch, flags, alpha,
+                                         psum, res, ldr, sR),
+                               a_kc, b_kc, out_f32, splitk, tile, cus);
+  if (psum_count) *psum_count = p.psum_count;
+  const int v[21] = {(int)p.err, p.tile, p.family, p.BM, p.BN, p.WM, p.WN, p.NST, p.a_kc, p.b_kc, p.out_f32,
+                     p.variant, p.splitk, p.kt_per_split, p.N, p.batch, (int)p.gx, (int)p.gy, (int)p.block,
+                     p.psum_count, p.mfast};
+  for (int i = 0; i < 21; ++i) out[i] = v[i];
+  if (name && name_cap > 0) snprintf(name, (size_t)name_cap, "%s", p.err == hipSuccess ? p.name : "");
+  return (int)p.err;
 }
 
 // ============================================================================ launch record

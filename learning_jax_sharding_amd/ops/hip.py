@@ -36,6 +36,10 @@ _SIGS = {
     "ljs_gemm_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long, c_long,
                       c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p,
                       ctypes.POINTER(c_int), c_void_p, c_long, c_long, c_void_p],
+    "ljs_gemm_plan": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long, c_long,
+                      c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p,
+                      ctypes.POINTER(c_int), c_void_p, c_long, c_long, c_int, ctypes.POINTER(c_int), ctypes.c_char_p,
+                      c_int],
     "ljs_sum_partials": [c_void_p, c_int, c_void_p, c_int, c_void_p],
     "ljs_mse_colsum_ws_bytes": [c_int, c_int],
     "ljs_gemm_f32": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long,
@@ -328,9 +332,17 @@ def _longs(vals) -> ctypes.Array:
 
 
 # ============================================================================ GEMM
-# output stores with sc1 (drop the written lines from L2 so the output stream does not evict the
-# operand panels that neighbouring blocks re-read)
-_GEMM_SC1 = True
+def _gemm_flags(relu, bias_dtype, accumulate, zero_c, slabs, res_dtype, res_mode) -> int:
+    """ljs_gemm_bf16's flag word (gemm.hip GemmArgs).  32: output stores with sc1, always on (they
+    drop the written lines from L2, so the output stream does not evict the operand panels that
+    neighbouring blocks re-read)."""
+    flags = (1 if relu else 0) | (2 if bias_dtype is not None else 0) | (4 if bias_dtype == torch.float32 else 0) | \
+        (8 if accumulate else 0) | (16 if zero_c else 0) | 32 | (512 if slabs else 0) | \
+        (8192 if (slabs and _SLAB_VST) else 0)
+    if res_dtype is not None:
+        assert res_dtype in (torch.bfloat16, torch.float32), res_dtype
+        flags |= (64 if res_mode == "add" else 128) | (256 if res_dtype == torch.float32 else 0)
+    return flags
 
 
 def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int, K: int, lda: int, ldb: int, ldc: int,
@@ -359,18 +371,11 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int, K: i
     assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16, (A.dtype, B.dtype)
     assert not slabs or C.dtype == torch.float32, "split-K slabs are f32"
     out_f32 = C.dtype == torch.float32
+    assert res is None or not out_f32, (C.dtype, res.dtype)
     if tile is None:
-        tile = pick_tile(M, N, K, batch, a_kc, b_kc, out_f32, splitk, ldc, A.dtype, bias, sBias, relu, accumulate,
-                         zero_c, psum, res, slabs, sA, sB, sC, ldb)
-    flags = (1 if relu else 0) | (2 if bias is not None else 0) | \
-        (4 if (bias is not None and bias.dtype == torch.float32) else 0) | (8 if accumulate else 0) | \
-        (16 if zero_c else 0) | (32 if _GEMM_SC1 else 0) | (512 if slabs else 0) | \
-        (8192 if (slabs and _SLAB_VST) else 0)
-    if res is not None:
-        assert not out_f32 and res.dtype in (torch.bfloat16, torch.float32), (C.dtype, res.dtype)
-        flags |= (64 if res_mode == "add" else 128) | (256 if res.dtype == torch.float32 else 0)
-    if tile is None:
-        tile = pick_tile(M, N, K, batch, a_kc, b_kc, out_f32, splitk, ldc)
+        tile = pick_tile(M, N, K, batch, a_kc, b_kc, out_f32, splitk, ldc, bias, res, sA, sB, sC, ldb)
+    flags = _gemm_flags(relu, None if bias is None else bias.dtype, accumulate, zero_c, slabs,
+                        None if res is None else res.dtype, res_mode)
     eA = A.element_size()
     cnt = c_int(0)
     b_arg = ctypes.c_void_p(B.data_ptr() + b_off * eA)
@@ -388,6 +393,36 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int, K: i
     return cnt.value
 
 
+_PLAN_FIELDS = ("err", "resolved_tile", "family", "BM", "BN", "WM", "WN", "NST", "a_kc", "b_kc", "out_f32", "variant",
+                "splitk", "kt_per_split", "N", "batch", "grid_x", "grid_y", "block", "psum_count", "mfast")
+_PLAN_FAMILIES = ("register-staged", "lds-dma", "lean", "slab")
+
+
+def gemm_plan(M: int, N: int, K: int, lda: int, ldb: int, ldc: int, a_kc: bool, b_kc: bool, out_f32: bool,
+              batch: int = 1, sA: int = 0, sB: int = 0, sC: int = 0, bias_dtype=None, relu: bool = False,
+              alpha: float = 1.0, accumulate: bool = False, splitk: int = 1, tile: int = 128, zero_c: bool = False,
+              psum: bool = False, res_dtype=None, res_ld: int = 0, res_mode: str = "add", sR: int = 0,
+              slabs: bool = False, c_addr: int = 4096, res_addr: int = 4096, cus: int = 256) -> dict:
+    """What :func:`gemm` would launch for these arguments on a device of ``cus`` compute units
+    (``ljs_gemm_plan``: the launcher's own plan step; needs the library, not a GPU).  Tensors are
+    given by what the plan reads of them: dtypes, and the addresses of C and ``res`` for their
+    alignment.  Returns the fields of a launch record (``name``, ``grid``, ``blocks``, ``block``,
+    ``resolved_tile``, ``splitk``, ``variant``) plus ``family``, the instance's ``BM`` ... ``NST``,
+    ``kt_per_split``, the launched ``N`` and ``batch`` (a folded batch is one GEMM), ``psum_count``
+    and ``mfast``; ``err`` is the launcher's error code (0: it would launch)."""
+    flags = _gemm_flags(relu, bias_dtype, accumulate, zero_c, slabs, res_dtype, res_mode)
+    out, cnt, name = (c_int * len(_PLAN_FIELDS))(), c_int(0), ctypes.create_string_buffer(64)
+    fake = c_void_p(4096)   # operand addresses the plan never reads
+    res = c_void_p(res_addr) if res_dtype is not None else None
+    lib().ljs_gemm_plan(fake, fake, c_void_p(c_addr), fake if bias_dtype is not None else None, M, N, K, lda, ldb, ldc,
+                        sA, sB, sC, 0, batch, int(a_kc), int(b_kc), int(out_f32), flags, alpha, splitk, tile,
+                        fake if psum else None, ctypes.byref(cnt), res, res_ld, sR, cus, out, name, len(name))
+    plan = dict(zip(_PLAN_FIELDS, out))
+    plan.update(name=name.value.decode(), family=_PLAN_FAMILIES[plan["family"]], grid=(out[16], out[17], 1),
+                blocks=out[16] * out[17], variant=None if out[11] < 0 else out[11])
+    return plan
+
+
 def gemm_group_begin():
     """Open a grouped launch: the plain f32 slab GEMMs (weight gradients) that :func:`gemm` is
     asked for until :func:`gemm_group_end` are recorded instead of launched."""
@@ -403,10 +438,6 @@ def gemm_group_end(dev_tensor: torch.Tensor):
     item, so bit-identical to separate launches), anything else one by one."""
     rc = lib().ljs_gemm_group_end(_stream(dev_tensor))
     _ck(rc, "ljs_gemm_group_end")
-
-
-_LEAN_REQ = 100000  # tile code + _LEAN_REQ: force the lean K-loop kernel (gemm.hip gemm_lean_kernel; A/B),
-                    # + 2 * _LEAN_REQ: force the general LDS-DMA kernel
 
 
 def psum_slots(M: int, N: int, batch: int = 1) -> int:
@@ -441,42 +472,33 @@ def _psum_for(t: torch.Tensor):
     return partials, count
 
 
-# 256x128 tile for large k-contiguous bf16 GEMMs: with the DMA pieces issued after each k-step's
-# fragment reads it beats the 128x128 x 2/CU kernel at the QKV projection (37.9 vs 40.4 us) and
-# the FF up-projection (60.7 vs 65.2 us; scripts/gemm_tiles_out.py)
-_TILE_2561 = True
-# 256x192 tile (8 waves of 64x96, 2 stages; a weight-major batch folded into one GEMM): fewer DMA
-# pieces and fragment reads per MFMA than 256x128, one stage less in flight.  On by default with the
-# lean K-loop kernel (round 5: QKV 33.5 vs 39.2 us isolated, B=64 step 0.2124 / 0.2159 vs 0.2250 /
-# 0.2189 ms, gpurun_out/r5g)
-_TILE_2562 = True
 # slab-mode GEMMs: the last item's f32 tile leaves through LDS as whole rows (kSlabVst; the GPU
 # tests switch it off to check the per-lane form bit-exact)
 _SLAB_VST = True
 
 
-# 128x160 tiles when they (and not 128x128 tiles) fill whole rounds of 512 resident blocks
-_TILE_1602 = True
-
-
 def pick_tile(M: int, N: int, K: int, batch: int, a_kc: bool, b_kc: bool, out_f32: bool, splitk: int = 1,
-              ldc: int = 0, a_dtype=None, bias=None, sBias: int = 0, relu: bool = False, accumulate: bool = False,
-              zero_c: bool = False, psum=None, res=None, slabs: bool = False, sA: int = 0, sB: int = 0,
-              sC: int = 0, ldb: int = 0) -> int:
+              ldc: int = 0, bias=None, res=None, sA: int = 0, sB: int = 0, sC: int = 0, ldb: int = 0) -> int:
     """Kernel/tile choice (measured on MI355X at the bench shapes, ``scripts/gemm_one.py``): the
     LDS-DMA kernels (codes 2562 = 256x192 8 waves, 2561 = 256x128 8 waves, 1602 = 128x160 4 waves,
     1282 = 128x128 4 waves x 2 blocks/CU, ...; the k-contiguous ones run the lean K-loop kernel)
     whenever K is a multiple of 64, else the register-staged 128/64 tiles."""
     tiles128 = -(-M // 128) * -(-N // 128) * batch * max(1, splitk)
-    if (_TILE_1602 and K % 64 == 0 and a_kc and b_kc and not out_f32 and splitk <= 1 and N % 160 == 0
+    # 128x160 tiles when they (and not 128x128 tiles) fill whole rounds of 512 resident blocks
+    if (K % 64 == 0 and a_kc and b_kc and not out_f32 and splitk <= 1 and N % 160 == 0
             and ldc % 8 == 0 and tiles128 % 512 and (-(-M // 128) * (N // 160) * batch) % 512 == 0):
         return 1602
     if K % 64 == 0 and tiles128 >= 96 and (out_f32 or (N % 8 == 0 and ldc % 8 == 0)):
-        if (_TILE_2562 and a_kc and b_kc and not out_f32 and res is None and M >= 4096 and splitk <= 1
+        # 256x192 (8 waves of 64x96, 2 stages; a weight-major batch folded into one GEMM): fewer DMA
+        # pieces and fragment reads per MFMA than 256x128, one stage less in flight (lean K-loop
+        # kernel: QKV 33.5 vs 39.2 us isolated, B=64 step 0.2124 / 0.2159 vs 0.2250 / 0.2189 ms)
+        if (a_kc and b_kc and not out_f32 and res is None and M >= 4096 and splitk <= 1
                 and (N * batch) % 192 == 0 and (batch == 1 or (bias is None and sA == 0 and sB == N * ldb
                                                                 and sC == N and ldc == N * batch))):
             return 2562
-        if _TILE_2561 and a_kc and b_kc and not out_f32 and M >= 4096 and N * batch >= 1024 and N % 128 == 0:
+        # 256x128 for large k-contiguous bf16 GEMMs: beats 128x128 x 2/CU at the QKV projection (37.9
+        # vs 40.4 us) and the FF up-projection (60.7 vs 65.2 us; scripts/gemm_tiles_out.py)
+        if a_kc and b_kc and not out_f32 and M >= 4096 and N * batch >= 1024 and N % 128 == 0:
             return 2561
         if a_kc and b_kc and not out_f32 and tiles128 < 256 and splitk <= 1:
             # under one round of 128x128 blocks (the 2048-token QKV projection: 192 tiles): the

@@ -1,7 +1,7 @@
 """The headline step's GEMM shapes (T = 16384 tokens) with their candidate tiles, timed in
 interleaved rounds in one process (the case table scripts/gemm_ab.py times per library build).
 
-    python scripts/gemm_cases.py [case ...]     cases: qkv qkv32 out dh dwqkv dwo (default: all)
+    python scripts/gemm_cases.py [case ...]     cases: qkv out dh dwqkv dwo (default: all)
 """
 import os
 import sys
@@ -56,18 +56,6 @@ def cases():
         return lambda: hip.gemm(x, wqkv, qkv, T, 512, 640, 640, 640, 1536, True, True, batch=3, sA=0, sB=512 * 640,
                                 sC=512, tile=tile)
     out["qkv"] = (qkv_fn, [2561, 2562], 2 * T * 640 * 1536)
-
-    x32 = torch.randn(T, 640, device=dev)
-    xb = torch.empty(T, 640, device=dev).bfloat16()
-
-    def qkv32_fn(tile):
-        if tile == "cast":   # the separate cast pass + the bf16 ping-pong GEMM
-            return lambda: (hip.cast_into(x32, xb) if hasattr(hip, "cast_into") else xb.copy_(x32),
-                            hip.gemm(xb, wqkv, qkv, T, 512, 640, 640, 640, 1536, True, True, batch=3, sA=0,
-                                     sB=512 * 640, sC=512, tile=2561))
-        return lambda: hip.gemm(x32, wqkv, qkv, T, 512, 640, 640, 640, 1536, True, True, batch=3, sA=0,
-                                sB=512 * 640, sC=512, acopy=xb, tile=tile)
-    out["qkv32"] = (qkv32_fn, [2561, "cast"], 2 * T * 640 * 1536)
 
     h = torch.randn(T, 512, device=dev).bfloat16()
     wo = torch.randn(640, 512, device=dev).bfloat16()
@@ -161,7 +149,7 @@ _GRAPH_CASES = {"dwgroup", "dwgroup_big", "dwgroup_8w", "dwqkv_ring", "dwo_ring"
 
 
 def main():
-    want = sys.argv[1:] or ["qkv", "qkv32", "out", "dh", "dwqkv", "dwo"]
+    want = sys.argv[1:] or ["qkv", "out", "dh", "dwqkv", "dwo"]
     cs = cases()
     for name in want:
         mk, tiles, flops = cs[name]

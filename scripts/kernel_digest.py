@@ -1,9 +1,13 @@
-"""SHA-256 of what the streaming kernels (norm, xent, loss, elementwise) compute on a fixed list of
-small seeded cases, one ``case-name sha256`` line per output tensor: two builds of the library
-compute the same bits exactly when their lines are equal.
+"""SHA-256 of what the streaming kernels (norm, xent, loss, elementwise) and the bf16 GEMMs compute on
+a fixed list of small seeded cases, one ``case-name sha256`` line per output tensor: two builds of
+the library compute the same bits exactly when their lines are equal.  The ``gemm`` group also
+prints each case's launch record, so equal lines mean the same kernels on the same grids too.
 
     python scripts/kernel_digest.py [--json out.json] [--grep norm]
     LJS_KERNELS_LIB=path/to/libljs_kernels.so python scripts/kernel_digest.py    # another build
+
+(Another build has to export every function ops/hip.py binds; to compare with a commit whose library
+does not, copy this script into a checkout of that commit and run it there.)
 
 Every kernel here fixes the order of its sums by the shape alone, so a run is comparable with any
 other run by digest; one process per library.  Inputs are made on the CPU from a generator seeded
@@ -65,6 +69,12 @@ class Out:
         t = t.detach().contiguous().cpu()
         h = hashlib.sha256(t.reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()
         self.lines.append((f"{name}[{_N.get(t.dtype, t.dtype)}{list(t.shape)}]", h))
+        print(*self.lines[-1], flush=True)
+
+    def record(self, name):
+        """The last launch's record (ops/hip.py last_launch) as a line of its own."""
+        rec = hip.last_launch()
+        self.lines.append((name + "/record", ",".join(f"{k}={rec[k]}" for k in sorted(rec)).replace(" ", "")))
         print(*self.lines[-1], flush=True)
 
 
@@ -194,7 +204,84 @@ def misc_cases(out):
         out.add(f"adam_f32/{k}", t)
 
 
-GROUPS = {"norm": norm_cases, "xent": xent_cases, "sum": sum_cases, "colsum": colsum_cases, "mse": mse_cases,
+def _gemm(out, name, tile, a_kc, b_kc, out_f32, M, N, K, hashed=True, **kw):
+    """One bf16 GEMM from seeded operands in the asked layouts: C, the fused output sums where the
+    kernel wrote any, and the launch record (which kernel instance, grid, tile, split, variant)."""
+    g = _gen(name)
+    A, B = _randn(g, (M, K), BF16), _randn(g, (K, N), BF16)
+    As, lda = (A, K) if a_kc else (A.t().contiguous(), M)
+    Bs, ldb = (B.t().contiguous(), K) if b_kc else (B, N)
+    C = torch.full((M, N), float("nan"), dtype=F32 if out_f32 else BF16, device=DEV)
+    if kw.pop("bias", False):
+        kw["bias"] = _randn(g, (N,), F32)
+    if "res" in kw:
+        kw.update(res=_randn(g, (M, N), kw["res"]), res_ld=N)
+    psum = torch.zeros(hip.psum_slots(M, N), dtype=F32, device=DEV) if kw.pop("psum", False) else None
+    cnt = hip.gemm(As, Bs, C, M, N, K, lda, ldb, N, bool(a_kc), bool(b_kc), tile=tile, psum=psum, **kw)
+    out.record(name)
+    if hashed:
+        out.add(name + "/C", C)
+        if cnt:
+            out.add(name + "/psum", psum[:cnt])
+
+
+def gemm_cases(out):
+    """gemm.hip's bf16 launcher: every tile and kernel family at one ragged block (the instance
+    lists of tests/test_kernel_variants_gpu.py), the epilogue instances, slabs alone and as a
+    grouped pair, the folded batch, a persistent grid.  Atomics split-K has no fixed sum order: its
+    record is printed, its output is not hashed."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_kernel_variants_gpu as tv
+    kk = tv._LEAN + tv._DMA_KK
+    for tile, M, N, K, _ in kk:
+        _gemm(out, f"gemm/kk/{tile}/{M}x{N}x{K}", tile, 1, 1, 0, M, N, K)
+    for tile, M, N, K in ((643, 72, 40, 128), (1284, 136, 72, 128)):          # test_gemm_dma_layout_instances
+        for a_kc, b_kc, of in ((a, b, o) for a in (1, 0) for b in (1, 0) for o in (0, 1)):
+            forced = 200000 if (tile == 1284 and a_kc and b_kc and not of) else 0
+            _gemm(out, f"gemm/layout/{tile}/{a_kc}{b_kc}{of}/{M}x{N}x{K}", tile + forced, a_kc, b_kc, of, M, N, K)
+    for tile in (64, 128, 644, 1282):                 # register-staged, asked for and by demotion (K % 64)
+        for a_kc, b_kc, of in ((1, 1, 0), (0, 0, 1), (1, 0, 0), (0, 1, 1)):
+            _gemm(out, f"gemm/reg/{tile}/{a_kc}{b_kc}{of}/136x72x40", tile, a_kc, b_kc, of, 136, 72, 40)
+    epilogues = {"plain": {}, "bias-psum": dict(bias=True, psum=True), "res-bf16": dict(res=BF16),
+                 "res-f32": dict(res=F32), "mask": dict(res=BF16, res_mode="mask"),
+                 "relu-alpha": dict(bias=True, relu=True, alpha=0.5)}
+    for tile, (ename, kw) in ((t, e) for t in sorted({c[0] for c in kk}) for e in epilogues.items()):
+        _gemm(out, f"gemm/epilogue/{tile}/{ename}/136x72x128", tile, 1, 1, 0, 136, 72, 128, **kw)
+    T, K, N, S = 448, 136, 72, 3                      # test_gemm_slab_instance: 7 K-tiles as 3 + 3 + 1
+
+    def slab_gemm(name, tile, K, N, S):
+        g = _gen(name)
+        x, dy = _randn(g, (T, K), BF16), _randn(g, (T, N), BF16)
+        slabs = torch.full((S, K, N), float("nan"), dtype=F32, device=DEV)
+        hip.gemm(x, dy, slabs, K, N, T, K, N, N, False, False, sC=K * N, splitk=S, tile=tile, slabs=True)
+        return slabs
+    for tile in (1282, 12883, 12884):
+        name = f"gemm/slab/{tile}/{K}x{N}x{T}s{S}"
+        slabs = slab_gemm(name, tile, K, N, S)
+        out.record(name)
+        out.add(name + "/slabs", slabs)
+    hip.gemm_group_begin()                            # test_gemm_grouped_pair_instance
+    pair = [slab_gemm(f"gemm/group/{i}", 1282, k, n, s) for i, (k, n, s) in enumerate(((136, 72, 3), (72, 200, 2)))]
+    hip.gemm_group_end(pair[0])
+    out.record("gemm/group")
+    for i, slabs in enumerate(pair):
+        out.add(f"gemm/group/{i}/slabs", slabs)
+    # the fused projection's weight-major 3-batch, folded into one 256x192 GEMM
+    name, (M, N, K) = "gemm/fold/2562/1000x512x640b3", (1000, 512, 640)
+    g = _gen(name)
+    x, wt = _randn(g, (M, K), BF16), _randn(g, (3, N, K), BF16, 0.05)
+    C = torch.full((M, 3 * N), float("nan"), dtype=BF16, device=DEV)
+    psum = torch.zeros(hip.psum_slots(M, N, 3), dtype=F32, device=DEV)
+    cnt = hip.gemm(x, wt, C, M, N, K, K, K, 3 * N, True, True, batch=3, sA=0, sB=N * K, sC=N, tile=2562, psum=psum)
+    out.record(name)
+    out.add(name + "/C", C)
+    out.add(name + "/psum", psum[:cnt])
+    # whole rounds of 2 blocks per CU on 256 CUs: the persistent grid
+    _gemm(out, "gemm/persistent/1282/4096x4096x64", 1282, 1, 1, 0, 4096, 4096, 64)
+    _gemm(out, "gemm/atomics/1282/320x128x2048s4", 1282, 0, 0, 1, 320, 128, 2048, hashed=False, splitk=4, zero_c=True)
+
+
+GROUPS = {"gemm": gemm_cases, "norm": norm_cases, "xent": xent_cases, "sum": sum_cases, "colsum": colsum_cases, "mse": mse_cases,
           "misc": misc_cases}
 
 

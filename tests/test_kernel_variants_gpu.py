@@ -39,43 +39,44 @@ def _stored(mat, kc_rowmajor: bool):
 def resolved_tile(tile, a_kc, b_kc, out_f32, M, N, K, lda=None, ldb=None, ldc=None, batch=1, splitk=1, sA=0, sB=0,
                   sC=0, res=False, bias=False, slabs=False, c_aligned=True):
     """The tile code ljs_gemm_bf16 launches for a requested one: its demotion rules in the order the
-    launcher applies them (csrc/kernels/gemm.hip, line of each rule in the comments).  Pure Python;
+    launcher applies them, stated here independently of csrc/kernels/gemm.hip's tile table (whose
+    plan step tests/test_gemm_picks.py checks against this function).  Pure Python;
     ``res``: an epilogue operand (residual add / mask) is passed, ``bias``: a bias is passed."""
     a_kc, b_kc, out_f32 = bool(a_kc), bool(b_kc), bool(out_f32)
     lda = (K if a_kc else M) if lda is None else lda
     ldb = (K if b_kc else N) if ldb is None else ldb
     ldc = N if ldc is None else ldc
-    tile %= 100000                                    # :1576-1579 the + 100000 / + 200000 forcing codes
-    nkt = -(-K // 64)                                 # :1580-1584 the launched split count
+    tile %= 100000                                    # the + 100000 / + 200000 forcing codes
+    nkt = -(-K // 64)                                 # the launched split count: ceil-sized splits
     splitk = min(max(1, splitk), nkt)
     kps = -(-nkt // splitk)
     splitk = -(-nkt // kps)
-    k_ext = splitk * kps * 64 if slabs else K         # :1602
-    dma_ok = (K % 64 == 0 and (slabs or (K // 64) % splitk == 0)               # :1603-1605
+    k_ext = splitk * kps * 64 if slabs else K         # K-rows the splits address
+    dma_ok = (K % 64 == 0 and (slabs or (K // 64) % splitk == 0)  # whole K-tiles, 32-bit offsets
               and (M * lda if a_kc else k_ext * lda) < (1 << 30)
               and (N * ldb if b_kc else k_ext * ldb) < (1 << 30))
-    dma_store_ok = out_f32 or (N % 8 == 0 and ldc % 8 == 0 and (sC % 8 == 0 or batch == 1) and c_aligned)  # :1607
-    if tile > 1000 and not (dma_ok and dma_store_ok):                          # :1609
+    dma_store_ok = out_f32 or (N % 8 == 0 and ldc % 8 == 0 and (sC % 8 == 0 or batch == 1) and c_aligned)  # 16-byte stores
+    if tile > 1000 and not (dma_ok and dma_store_ok):                          # LDS-DMA conditions unmet
         tile = 128
-    if res and tile > 1000 and not (a_kc and b_kc):                            # :1611
+    if res and tile > 1000 and not (a_kc and b_kc):                            # epilogue operand: k-contiguous
         tile = 128
-    if res and tile in (643, 644):                                             # :1612
+    if res and tile in (643, 644):                                             # ... and none at 64x64
         tile = 64
-    if tile in (643, 644) and not (dma_ok and dma_store_ok):                   # :1613
+    if tile in (643, 644) and not (dma_ok and dma_store_ok):                   # LDS-DMA conditions unmet
         tile = 64
-    if tile in (2563, 12856) and not (not a_kc and not b_kc and out_f32):      # :1614
+    if tile in (2563, 12856) and not (not a_kc and not b_kc and out_f32):      # weight-gradient tiles only
         tile = 1282
-    if tile == 2561 and not (a_kc and b_kc):                                   # :1615
+    if tile == 2561 and not (a_kc and b_kc):                                   # k-contiguous only
         tile = 1284
-    if tile == 2562 and not (a_kc and b_kc and not out_f32 and not res):       # :1616
+    if tile == 2562 and not (a_kc and b_kc and not out_f32 and not res):       # ... bf16, no epilogue operand
         tile = 1282
-    if tile == 2562 and batch > 1:                                             # :1617-1629 folded or 256x128
+    if tile == 2562 and batch > 1:                                             # a batch: folded, or 256x128
         if not (sA == 0 and sB == N * ldb and sC == N and ldc == N * batch and not bias
                 and N * batch * ldb < (1 << 30)):
             tile = 2561
-    if tile == 1602 and not (a_kc and b_kc and not out_f32 and splitk == 1):   # :1630
+    if tile == 1602 and not (a_kc and b_kc and not out_f32 and splitk == 1):   # ... bf16, unsplit
         tile = 1282
-    if tile in (12883, 12884) and not ((not a_kc and not b_kc and out_f32) or (a_kc and b_kc)):   # :1631
+    if tile in (12883, 12884) and not ((not a_kc and not b_kc and out_f32) or (a_kc and b_kc)):   # no mixed layouts
         tile = 1282
     return tile
 
