@@ -2275,50 +2275,54 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
 
 }  // namespace
 
-// Kernel-variant switches.  The defaults are the measured winners (profiles/PERF_NOTES.md); the
-// setters (ops/hip.py set_attention_*) exist so the GPU tests can run every variant and check it
-// bit-exact against the default -- they are not environment knobs.  (ljs_attn_set_cus, the grid of
-// the fused projection + forward, is one of them.)
-//  * split backward as ONE launch of dQ and dK/dV blocks (attn_bwd_pair_kernel), else two launches
-static int g_bwd_pair = 1;
-LJS_API void ljs_attn_set_bwd_pair(int v) { g_bwd_pair = v < 0 ? 1 : v; }
-//  * 128-key dK/dV blocks in the split backward (S = 4096 step 1.50 -> 1.04 ms; B = 8, 256 keys:
-//    0.0861-0.0873 -> 0.0852 ms), else 64-key blocks
-static int g_dkv32 = 1;
-LJS_API void ljs_attn_set_dkv32(int v) { g_dkv32 = v != 0; }
-//  * 128-query dQ blocks beside the 128-key dK/dV blocks, else 64-query ones
-static int g_dq32 = 1;
-LJS_API void ljs_attn_set_dq32(int v) { g_dq32 = v != 0; }
-//  * row tiles stored through LDS as whole 128-byte rows (1), per-lane 8-byte stores (0), or dK / dV
-//    staged with per-lane dQ (2)
-static int g_vst = 1;
-LJS_API void ljs_attn_set_vst(int v) { g_vst = v < 0 ? 1 : v; }
-static bool vst_ok(const void* p, const long* st) {
-  return (((uintptr_t)p) & 15) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0;
+// ---------------------------------------------------------------------------- switches
+// Kernel-variant switches, X(name, default).  The defaults are the measured winners
+// (profiles/PERF_NOTES.md); ljs_attn_set (ops/hip.py set_attention_*) exists so the GPU tests can
+// run every variant and check it bit-exact against the default -- they are not environment knobs.
+// One rule for all: v < 0 restores the default.  The row order is the `which` of ljs_attn_set /
+// ljs_attn_get (ops/hip.py _ATTN_SWITCHES).
+#define LJS_ATTN_SWITCHES(X)                                                                                  \
+  /* split backward as ONE launch of dQ and dK/dV blocks (attn_bwd_pair_kernel), else two launches */        \
+  X(bwd_pair, 1)                                                                                              \
+  /* 128-key dK/dV blocks in the split backward (S = 4096 step 1.50 -> 1.04 ms; B = 8, 256 keys:             \
+     0.0861-0.0873 -> 0.0852 ms), else (0) 64-key blocks */                                                   \
+  X(dkv32, 1)                                                                                                 \
+  /* 128-query dQ blocks beside the 128-key dK/dV blocks, else (0) 64-query ones */                           \
+  X(dq32, 1)                                                                                                  \
+  /* row tiles stored through LDS as whole 128-byte rows (1), per-lane 8-byte stores (0), or dK / dV         \
+     staged with per-lane dQ (2) */                                                                           \
+  X(vst, 1)                                                                                                   \
+  /* the fused projection + forward's grid: n > 0 blocks instead of one per CU (the tests run many           \
+     items per block on small shapes this way); 0 = the device's CU count */                                  \
+  X(cus, 0)                                                                                                   \
+  /* K/V-resident forward for Sk <= 256: 8 (or 4) waves per block; 0 = the tiled kernel */                    \
+  X(fwd_res, 8)                                                                                               \
+  /* fused backward's K / V staging: 1 = LDS-DMA in flight with the first query block, 0 = register          \
+     copy, 2 = automatic (DMA for <= 128 queries per block) */                                                \
+  X(bwd_kv_dma, 2)                                                                                            \
+  /* backward for Sk <= 256: 1 = fused single-pass kernel, 0 = split dQ + dK/dV kernels, 2 = automatic       \
+     by grid size */                                                                                          \
+  X(bwd_fused, 2)                                                                                             \
+  /* the fused backward that computes its own dO from the out-projection's dY (ljs_attn_bwd_proj):           \
+     1 = whenever its gate holds, 0 = never, 2 = automatic: where the fused backward is chosen and           \
+     there are at least 192 (batch, head) pairs.  It measured ahead at every size tried (B = 16 / 24 /       \
+     32 / 64 x 8 heads: profiles/attn_bwd_proj_gate_lines.txt); the B H = 128 step keeps the two             \
+     kernels because tests/test_kernel_variants_gpu.py::test_production_picks_run_as_picked pins the         \
+     dX GEMM + attn_bwd_fused pair at exactly that size */                                                    \
+  X(bwd_proj, 2)
+#define X(name, def) kSw_##name,
+enum AttnSwitch { LJS_ATTN_SWITCHES(X) kSwCount };
+#undef X
+#define X(name, def) def,
+static const int kSwDefault[kSwCount] = {LJS_ATTN_SWITCHES(X)};
+static int g_sw[kSwCount] = {LJS_ATTN_SWITCHES(X)};
+#undef X
+LJS_API int ljs_attn_set(int which, int v) {
+  if (which < 0 || which >= kSwCount) return (int)hipErrorInvalidValue;
+  g_sw[which] = v < 0 ? kSwDefault[which] : v;
+  return 0;
 }
-//  * the fused projection + forward's grid: n > 0 blocks instead of one per CU (the tests run many
-//    items per block on small shapes this way); <= 0 = the device's CU count (ljs_device_cus) again
-static int g_attn_cus_forced = 0;
-LJS_API void ljs_attn_set_cus(int v) { g_attn_cus_forced = v > 0 ? v : 0; }
-//  * K/V-resident forward for Sk <= 256: 8 (or 4) waves per block; 0 = the tiled kernel
-static int g_fwd_res = 8;
-LJS_API void ljs_attn_set_fwd_res(int v) { g_fwd_res = v < 0 ? 8 : v; }
-//  * fused backward's K / V staging: 1 = LDS-DMA in flight with the first query block, 0 = register
-//    copy, 2 = automatic (DMA for <= 128 queries per block)
-static int g_bwd_kv_dma = 2;
-LJS_API void ljs_attn_set_bwd_kv_dma(int v) { g_bwd_kv_dma = v < 0 ? 2 : v; }
-//  * backward for Sk <= 256: 1 = fused single-pass kernel, 0 = split dQ + dK/dV kernels, 2 =
-//    automatic by grid size
-static int g_bwd_fused = 2;
-LJS_API void ljs_attn_set_bwd_fused(int v) { g_bwd_fused = v < 0 ? 2 : v; }
-//  * the fused backward that computes its own dO from the out-projection's dY (ljs_attn_bwd_proj):
-//    1 = whenever its gate holds, 0 = never, 2 = automatic: where the fused backward is chosen and
-//    there are at least 192 (batch, head) pairs.  It measured ahead at every size tried (B = 16 / 24 /
-//    32 / 64 x 8 heads: profiles/attn_bwd_proj_gate_lines.txt); the B H = 128 step keeps the two
-//    kernels because tests/test_kernel_variants_gpu.py::test_production_picks_run_as_picked pins the
-//    dX GEMM + attn_bwd_fused pair at exactly that size
-static int g_bwd_proj = 2;
-LJS_API void ljs_attn_set_bwd_proj(int v) { g_bwd_proj = v < 0 ? 2 : v; }
+LJS_API int ljs_attn_get(int which) { return which < 0 || which >= kSwCount ? -1 : g_sw[which]; }
 //  * (diagnostic) the fused backward's phase-stamp buffer (LJS_ATTN_BWD_TRACE builds): [B][H][waves][8]
 static unsigned long long* g_attn_trace = nullptr;
 LJS_API void ljs_attn_set_trace(void* p) { g_attn_trace = (unsigned long long*)p; }
@@ -2343,15 +2347,226 @@ static AttnArgs attn_args(const void* q, const void* k, const void* v, const voi
   a.causal = causal; a.q_offset = q_offset;
   return a;
 }
-// one output (AttnArgs out / out2 / out3) and its (batch, seq, head) strides
-static void attn_out(bf16_t*& out, long& sb, long& ss, long& sh, void* p, const long* st) {
-  out = (bf16_t*)p; sb = st[0]; ss = st[1]; sh = st[2];
+// a with its outputs (out / out2 / out3; null: none) and their (batch, seq, head) strides
+static AttnArgs attn_outs(AttnArgs a, void* o1, const long* s1, void* o2 = nullptr, const long* s2 = nullptr,
+                          void* o3 = nullptr, const long* s3 = nullptr) {
+  a.out = (bf16_t*)o1; a.out_sb = s1[0]; a.out_ss = s1[1]; a.out_sh = s1[2];
+  if (o2) { a.out2 = (bf16_t*)o2; a.out2_sb = s2[0]; a.out2_ss = s2[1]; a.out2_sh = s2[2]; }
+  if (o3) { a.out3 = (bf16_t*)o3; a.out3_sb = s3[0]; a.out3_ss = s3[1]; a.out3_sh = s3[2]; }
+  return a;
+}
+static bool none_null(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (!p) return false;
+  return true;
+}
+static bool vst_ok(const void* p, long sb, long ss, long sh) {
+  return (((uintptr_t)p) & 15) == 0 && sb % 8 == 0 && ss % 8 == 0 && sh % 8 == 0;
 }
 
+// ---------------------------------------------------------------------------- instances and plan
+// The launchable kernel instances, X(id, launch-record name, block threads).  The four fused
+// instances stay in (dma, sw) order: attn_bwd_plan indexes them as kBwdFused00 + 2 dma + sw.
+#define LJS_ATTN_INSTANCES(X)                    \
+  X(kFwdRes8, "attn_fwd_res<8>", 512)            \
+  X(kFwdRes4, "attn_fwd_res<4>", 256)            \
+  X(kFwdTiled, "attn_fwd_tiled<1>", 256)         \
+  X(kBwdFused00, "attn_bwd_fused<dma=0,sw=0>", FT) \
+  X(kBwdFused01, "attn_bwd_fused<dma=0,sw=1>", FT) \
+  X(kBwdFused10, "attn_bwd_fused<dma=1,sw=0>", FT) \
+  X(kBwdFused11, "attn_bwd_fused<dma=1,sw=1>", FT) \
+  X(kBwdPair32Dq0, "attn_bwd_pair32<dq32=0>", 256) \
+  X(kBwdPair32Dq1, "attn_bwd_pair32<dq32=1>", 256) \
+  X(kBwdPair, "attn_bwd_pair", 256)              \
+  X(kBwdDq, "attn_bwd_dq", 256)                  \
+  X(kBwdDkv, "attn_bwd_dkv", 256)                \
+  X(kBwdProj, "attn_bwd_proj", FT)               \
+  X(kQkvFwd, "qkv_attn_fwd", 512)
+#define X(id, name, block) id,
+enum AttnInst { LJS_ATTN_INSTANCES(X) kInstCount };
+#undef X
+#define X(id, name, block) {name, block},
+static const struct { const char* name; unsigned block; } kAttnInst[kInstCount] = {LJS_ATTN_INSTANCES(X)};
+#undef X
+
+// What one entry-point call launches, worked out from the call's numbers alone: the plan functions
+// read shapes, strides, operand addresses (for their alignment), acc_mode, the switches and a CU
+// count; they dereference nothing and call no HIP function, so they answer on a machine without a
+// GPU too (ljs_attn_plan).
+struct AttnLaunch {
+  AttnInst inst;
+  unsigned gx, gy, block;
+};
+struct AttnPlan {
+  hipError_t err;
+  int n;             // launches (0 with err)
+  AttnLaunch l[2];
+  int vst[2];        // AttnArgs::vst: of the one argument struct, or of the split backward's dQ and dK/dV ones
+  int flags32;       // AttnArgs::flags32 of the dQ one
+  int nw, nqb;       // forward: waves per block (0: the tiled kernel) and query blocks per (batch, head)
+  int acc_mode;      // the launch record's: the forward's acc_mode, else -1
+};
+static AttnPlan attn_reject() {
+  AttnPlan p = {};
+  p.err = hipErrorInvalidValue;
+  p.acc_mode = -1;
+  return p;
+}
+// one more launch; a grid from 2^30 blocks up makes the whole plan an error
+static bool attn_add(AttnPlan& p, AttnInst inst, long gx, long gy = 1) {
+  if (gx * gy >= (1L << 30)) {
+    p = attn_reject();
+    return false;
+  }
+  p.l[p.n++] = AttnLaunch{inst, (unsigned)gx, (unsigned)gy, kAttnInst[inst].block};
+  return true;
+}
+
+// a: as attn_fwd_impl fills it (out = o).  acc: ljs_attn_fwd_acc's call (acc_mode 1 / 2 / 3)
+static AttnPlan attn_fwd_plan(const AttnArgs& a, int B, bool acc) {
+  if (!none_null({a.q, a.k, a.v, a.lse}) || (!a.out && (a.acc_mode == 0 || a.acc_mode == 3))) return attn_reject();
+  if (acc && (a.acc_mode < 1 || a.acc_mode > 3 || !a.oacc || (((uintptr_t)a.oacc) & 15) || a.oa_ss % 4 ||
+              a.oa_sh % 4 || a.oa_sb % 4))
+    return attn_reject();
+  AttnPlan p = {};
+  p.acc_mode = a.acc_mode;
+  p.vst[0] = g_sw[kSw_vst] && vst_ok(a.out, a.o_sb, a.o_ss, a.o_sh);
+  const int res = g_sw[kSw_fwd_res];
+  if (res > 0 && a.Sk <= FKR && (long)(a.Sk - 1) * (a.k_ss > a.v_ss ? a.k_ss : a.v_ss) * 2 + 128 < (1L << 31)) {
+    // 8 waves x 16 queries per block leave CUs idle below 256 blocks (B*H = 64 at the
+    // reference shape): 4-wave blocks there (B=8: step 0.1069 -> 0.1057 ms).  (16-wave blocks,
+    // a persistent double-buffered form, per-key-tile waits and two query sub-tiles per wave all
+    // measured slower and were removed: PERF_NOTES rounds 2-5)
+    p.nw = res == 4 ? 4 : 8;
+    if (p.nw == 8 && (long)((a.Sq + 127) / 128) * a.H * B < 256) p.nw = 4;
+    p.nqb = (a.Sq + 16 * p.nw - 1) / (16 * p.nw);
+    attn_add(p, p.nw == 8 ? kFwdRes8 : kFwdRes4, (long)p.nqb * a.H * B);
+  } else {
+    p.nqb = (a.Sq + BLK - 1) / BLK;
+    attn_add(p, kFwdTiled, (long)p.nqb * a.H * B);
+  }
+  return p;
+}
+
+// a: out = dK, out2 = dV, out3 = dQ (the fused kernel's layout)
+static AttnPlan attn_bwd_plan(const AttnArgs& a, int B) {
+  if (!none_null({a.q, a.k, a.v, a.o, a.dout, a.lse, a.delta, a.out, a.out2, a.out3})) return attn_reject();
+  AttnPlan p = {};
+  p.acc_mode = -1;
+  const int vst = g_sw[kSw_vst], fsw = g_sw[kSw_bwd_fused], dma = g_sw[kSw_bwd_kv_dma];
+  const bool dq_ok = vst_ok(a.out3, a.out3_sb, a.out3_ss, a.out3_sh);
+  const bool dkv_ok = vst_ok(a.out, a.out_sb, a.out_ss, a.out_sh) && vst_ok(a.out2, a.out2_sb, a.out2_ss, a.out2_sh);
+  // 2 = automatic: the fused kernel runs one workgroup per (batch, head), so below ~half a
+  // workgroup per CU (B*H < 128: the reference's B = 8 x 8 heads) the split kernels' per-query-
+  // block grids fill the chip better (measured: 0.1218 vs 0.1248 ms/step at B = 8, equal at 16,
+  // fused far ahead from 32)
+  const bool fused = fsw == 1 || (fsw == 2 && (long)B * a.H >= 128);
+  if (fused && a.Sk <= FK) {
+    p.vst[0] = dkv_ok && dq_ok ? vst : 0;
+    // 2 = automatic: the DMA form when a block sweeps at most two query blocks (the 2-D mesh's
+    // 128 local queries against 256 gathered keys: the K / V prologue is a third of the block's
+    // time there, and overlapping it with the first query block's loads measured 58.8 -> 57.1 us,
+    // 2-D rehearsal step 0.2963 -> 0.2937 ms median, gpurun_out/r4ab); at 256 queries it is
+    // neutral (0.2194 vs 0.2196 ms), so the register copy stays there
+    const bool kv_dma = dma == 1 || (dma == 2 && a.Sq <= 2 * BLK);
+    const bool sw1 = p.vst[0] == 1 && a.Sq % BLK == 0 && a.Sk == FK && !a.causal;
+    attn_add(p, (AttnInst)(kBwdFused00 + 2 * kv_dma + sw1), a.H, B);
+    return p;
+  }
+  p.vst[0] = vst && dq_ok;    // (the 128-query dQ blocks use it)
+  p.vst[1] = vst && dkv_ok;   // (the 128-key dK/dV blocks use it)
+  const long nq = (a.Sq + BLK - 1) / BLK, nk = (a.Sk + BLK - 1) / BLK, nk128 = (a.Sk + 127) / 128, HB = (long)a.H * B;
+  if (g_sw[kSw_dkv32] && (nq + nk128) * HB < (1L << 30)) {
+    p.flags32 = g_sw[kSw_dq32] != 0;
+    attn_add(p, p.flags32 ? kBwdPair32Dq1 : kBwdPair32Dq0, ((p.flags32 ? (a.Sq + 127) / 128 : nq) + nk128) * HB);
+  } else if (g_sw[kSw_bwd_pair] && (nq + nk) * HB < (1L << 30)) {
+    // one launch: dQ blocks and dK/dV blocks (which form delta themselves) side by side
+    attn_add(p, kBwdPair, (nq + nk) * HB);
+  } else if (attn_add(p, kBwdDq, nq * HB)) {
+    // dQ first: it also computes delta, which the dK/dV kernel consumes (stream order)
+    attn_add(p, kBwdDkv, nk * HB);
+  }
+  return p;
+}
+
+static bool bwd_proj_enabled(long BH) {
+  const int proj = g_sw[kSw_bwd_proj], fsw = g_sw[kSw_bwd_fused];
+  if (proj == 0 || g_sw[kSw_vst] != 1) return false;
+  return proj == 1 || ((fsw == 1 || fsw == 2) && BH >= 192);
+}
+// Whether the switches let ljs_attn_bwd_proj run a (B, H) grid (the shape gate is attn_bwd_proj_plan's)
+LJS_API int ljs_attn_bwd_proj_enabled(int B, int H) { return bwd_proj_enabled((long)B * H); }
+
+// a: as attn_bwd_plan's, without dout / delta.  Exactly the fused backward's common case: Sq == Sk ==
+// 256, not causal, 16-byte aligned operands and outputs with row strides % 8 == 0
+static AttnPlan attn_bwd_proj_plan(const AttnArgs& a, int B, const BwdProjArgs& pj) {
+  const long lim = 0x7ffffff0L;
+  auto in_ok = [&](const void* p, long sb, long ss, long sh) {
+    return p && vst_ok(p, sb, ss, sh) && ss >= 0 && 2 * ((long)(FK - 1) * ss + D) < lim;
+  };
+  auto out_ok = [&](const void* p, long sb, long ss, long sh) { return p && vst_ok(p, sb, ss, sh); };
+  if (B <= 0 || a.H <= 0 || (long)B * a.H >= (1L << 30) || a.Sq != FK || a.Sk != FK || a.causal || pj.M <= 0 ||
+      pj.M % PJ_BK || !(pj.dy_ld == 0 || (pj.dy_ld >= pj.M && pj.dy_ld % 8 == 0)) || !pj.dy || !pj.w || !a.lse ||
+      (((uintptr_t)pj.dy | (uintptr_t)pj.w) & 15) || (((uintptr_t)a.lse) & 3) ||
+      2 * ((long)(FK - 1) * pj.dy_ld + pj.M) >= lim || 2L * D * pj.M >= lim ||
+      !in_ok(a.q, a.q_sb, a.q_ss, a.q_sh) || !in_ok(a.k, a.k_sb, a.k_ss, a.k_sh) ||
+      !in_ok(a.v, a.v_sb, a.v_ss, a.v_sh) || !in_ok(a.o, a.o_sb, a.o_ss, a.o_sh) ||
+      !out_ok(a.out3, a.out3_sb, a.out3_ss, a.out3_sh) || !out_ok(a.out, a.out_sb, a.out_ss, a.out_sh) ||
+      !out_ok(a.out2, a.out2_sb, a.out2_ss, a.out2_sh) || !bwd_proj_enabled((long)B * a.H))
+    return attn_reject();
+  AttnPlan p = {};
+  p.acc_mode = -1;
+  p.vst[0] = 1;
+  attn_add(p, kBwdProj, (long)B * a.H);
+  return p;
+}
+
+// ldx: the call's row stride (a.ldx is its narrowed copy); cus: the device's compute units
+static AttnPlan qkv_attn_fwd_plan(const QkvAttnArgs& a, long ldx, int cus) {
+  if (a.T <= 0 || a.T % QA_S || a.K < 2 * QA_BK || a.K % (2 * QA_BK) || a.N != a.H * D || a.H <= 0 || ldx < a.K ||
+      ldx % 8 || (((uintptr_t)a.x | (uintptr_t)a.w | (uintptr_t)a.qkv | (uintptr_t)a.o) & 15) ||
+      (long)a.T * ldx * 2 >= (1L << 31) || 3L * a.N * a.K * 2 >= (1L << 31))
+    return attn_reject();
+  AttnPlan p = {};
+  p.acc_mode = -1;
+  const int items = a.T / QA_S * a.H;
+  if (g_sw[kSw_cus] > 0) cus = g_sw[kSw_cus];
+  attn_add(p, kQkvFwd, items < cus ? items : cus);   // one 8-wave block per CU, items dealt round-robin
+  return p;
+}
+
+// record and launch one planned instance of the AttnArgs kernels (b: the pair kernels' dK/dV half)
+static void attn_launch(const AttnLaunch& l, hipStream_t stream, const AttnArgs& a, const AttnArgs* b = nullptr,
+                        int acc_mode = -1) {
+  const dim3 grid(l.gx, l.gy), block(l.block);
+  ljs_launch_rec(kAttnInst[l.inst].name, grid, l.block, acc_mode);
+  switch (l.inst) {
+    case kFwdRes8: hipLaunchKernelGGL(attn_fwd_res_kernel<8>, grid, block, 0, stream, a); break;
+    case kFwdRes4: hipLaunchKernelGGL(attn_fwd_res_kernel<4>, grid, block, 0, stream, a); break;
+    case kFwdTiled: hipLaunchKernelGGL(attn_fwd_kernel<1>, grid, block, 0, stream, a); break;
+    case kBwdFused00: hipLaunchKernelGGL((attn_bwd_fused_kernel<false, 0>), grid, block, 0, stream, a); break;
+    case kBwdFused01: hipLaunchKernelGGL((attn_bwd_fused_kernel<false, 1>), grid, block, 0, stream, a); break;
+    case kBwdFused10: hipLaunchKernelGGL((attn_bwd_fused_kernel<true, 0>), grid, block, 0, stream, a); break;
+    case kBwdFused11: hipLaunchKernelGGL((attn_bwd_fused_kernel<true, 1>), grid, block, 0, stream, a); break;
+    case kBwdPair32Dq0:
+    case kBwdPair32Dq1: hipLaunchKernelGGL(attn_bwd_pair32_kernel, grid, block, 0, stream, a, *b); break;
+    case kBwdPair: hipLaunchKernelGGL(attn_bwd_pair_kernel, grid, block, 0, stream, a, *b); break;
+    case kBwdDq: hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, stream, a); break;
+    case kBwdDkv: hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, block, 0, stream, a); break;
+    default: break;   // (attn_bwd_proj and qkv_attn_fwd take other arguments: launched by their entry points)
+  }
+}
+
+// ---------------------------------------------------------------------------- entry points
+// Each builds its arguments, asks the plan, and records and launches what the plan says; a call the
+// plan rejects returns hipErrorInvalidValue with nothing launched or recorded.  With `plan` set they
+// stop after the plan step (ljs_attn_plan).
 // strides are in elements, ordered (batch, seq, head); head_dim must be 64 and contiguous.
 static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
                          int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
-                         int causal, int q_offset, void* oacc, const long* oas, int acc_mode, hipStream_t stream) {
+                         int causal, int q_offset, void* oacc, const long* oas, int acc_mode, bool acc,
+                         hipStream_t stream, AttnPlan* plan = nullptr) {
+  if (!none_null({qs, ks, vs, os}) || (acc && !oas)) return (int)hipErrorInvalidValue;
   AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, q_offset);
   a.out = (bf16_t*)o;   // (addressed with the o strides)
   a.oacc = (float*)oacc;
@@ -2359,25 +2574,15 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, v
   if (oas) {
     a.oa_sb = oas[0]; a.oa_ss = oas[1]; a.oa_sh = oas[2];
   }
-  a.vst = g_vst && vst_ok(o, os);
-  if (g_fwd_res > 0 && Sk <= FKR && (long)(Sk - 1) * (ks[1] > vs[1] ? ks[1] : vs[1]) * 2 + 128 < (1L << 31)) {
-    // 8 waves x 16 queries per block leave CUs idle below 256 blocks (B*H = 64 at the
-    // reference shape): 4-wave blocks there (B=8: step 0.1069 -> 0.1057 ms).  (16-wave blocks,
-    // a persistent double-buffered form, per-key-tile waits and two query sub-tiles per wave all
-    // measured slower and were removed: PERF_NOTES rounds 2-5)
-    int nw = g_fwd_res == 4 ? 4 : 8;
-    if (nw == 8 && (Sq + 127) / 128 * H * B < 256) nw = 4;
-    const int nqb = (Sq + 16 * nw - 1) / (16 * nw);
-    a.fd_nx = make_fastdiv(nqb);
+  const AttnPlan p = attn_fwd_plan(a, B, acc);
+  if (plan) *plan = p;
+  if (plan || p.err != hipSuccess) return (int)p.err;
+  a.vst = p.vst[0];
+  if (p.nw) {
+    a.fd_nx = make_fastdiv(p.nqb);
     a.fd_h = make_fastdiv(H);
-    ljs_launch_rec(nw == 8 ? "attn_fwd_res<8>" : "attn_fwd_res<4>", dim3(nqb * H * B), 64 * nw, acc_mode);
-    if (nw == 8) hipLaunchKernelGGL(attn_fwd_res_kernel<8>, dim3(nqb * H * B), dim3(512), 0, stream, a);
-    else hipLaunchKernelGGL(attn_fwd_res_kernel<4>, dim3(nqb * H * B), dim3(256), 0, stream, a);
-    return (int)hipGetLastError();
   }
-  const int nqb = (Sq + BLK - 1) / BLK;
-  ljs_launch_rec("attn_fwd_tiled<1>", dim3(nqb * H * B), 256, acc_mode);
-  hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3(nqb * H * B), dim3(256), 0, stream, a);
+  attn_launch(p.l[0], stream, a, nullptr, p.acc_mode);
   return (int)hipGetLastError();
 }
 
@@ -2385,7 +2590,7 @@ LJS_API int ljs_attn_fwd(const void* q, const void* k, const void* v, void* o, v
                          int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
                          int causal, int q_offset, hipStream_t stream) {
   return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, qs, ks, vs, os, scale, causal, q_offset, nullptr, nullptr, 0,
-                       stream);
+                       false, stream);
 }
 
 // blockwise forward with the running-output merge (ring attention's hop): acc_mode 1 / 2 / 3 (see
@@ -2393,11 +2598,8 @@ LJS_API int ljs_attn_fwd(const void* q, const void* k, const void* v, void* o, v
 LJS_API int ljs_attn_fwd_acc(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
                              int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
                              int causal, int q_offset, void* oacc, const long* oas, int acc_mode, hipStream_t stream) {
-  if (acc_mode < 1 || acc_mode > 3 || !oacc || !lse || (((uintptr_t)oacc) & 15) || oas[1] % 4 || oas[2] % 4 ||
-      oas[0] % 4)
-    return (int)hipErrorInvalidValue;
   return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, qs, ks, vs, os, scale, causal, q_offset, oacc, oas, acc_mode,
-                       stream);
+                       true, stream);
 }
 
 
@@ -2405,134 +2607,129 @@ LJS_API int ljs_attn_fwd_acc(const void* q, const void* k, const void* v, void* 
 // ldx), w [3][N][K] bf16 (the stacked transposed Q/K/V weights), N = H * 64, T = B * 256 tokens
 // (sequence 256, batch-major rows); writes qkv [T][3N], o [T][N] ([B][256][H][64]) and lse
 // [B][H][256] (log2 domain, as ljs_attn_fwd).  scale: the softmax scale.
-LJS_API int ljs_qkv_attn_fwd(const void* x, long ldx, const void* w, void* qkv, void* o, void* lse, int T, int K, int N,
-                             int H, float scale, void* trace, hipStream_t stream) {
-  if (T <= 0 || T % QA_S || K < 2 * QA_BK || K % (2 * QA_BK) || N != H * D || H <= 0 || ldx < K || ldx % 8 ||
-      (((uintptr_t)x | (uintptr_t)w | (uintptr_t)qkv | (uintptr_t)o) & 15) ||
-      (long)T * ldx * 2 >= (1L << 31) || 3L * N * K * 2 >= (1L << 31))
-    return (int)hipErrorInvalidValue;
+static int qkv_attn_fwd_impl(const void* x, long ldx, const void* w, void* qkv, void* o, void* lse, int T, int K, int N,
+                             int H, float scale, void* trace, int cus, hipStream_t stream, AttnPlan* plan = nullptr) {
   QkvAttnArgs a;
   a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.qkv = (bf16_t*)qkv; a.o = (bf16_t*)o; a.lse = (float*)lse;
   a.T = T; a.K = K; a.N = N; a.H = H; a.ldx = (int)ldx;
   a.scale_log2 = scale * LOG2E;
   a.trace = (unsigned long long*)trace;
-  const int items = T / QA_S * H;
-  const int cus = g_attn_cus_forced > 0 ? g_attn_cus_forced : ljs_device_cus();
-  const int grid = items < cus ? items : cus;   // one 8-wave block per CU, items dealt round-robin
-  ljs_launch_rec("qkv_attn_fwd", dim3(grid), 512);
-  hipLaunchKernelGGL(qkv_attn_fwd_kernel, dim3(grid), dim3(512), 0, stream, a);
+  const AttnPlan p = qkv_attn_fwd_plan(a, ldx, cus);
+  if (plan) *plan = p;
+  if (plan || p.err != hipSuccess) return (int)p.err;
+  ljs_launch_rec(kAttnInst[kQkvFwd].name, dim3(p.l[0].gx), p.l[0].block);
+  hipLaunchKernelGGL(qkv_attn_fwd_kernel, dim3(p.l[0].gx), dim3(p.l[0].block), 0, stream, a);
   return (int)hipGetLastError();
+}
+LJS_API int ljs_qkv_attn_fwd(const void* x, long ldx, const void* w, void* qkv, void* o, void* lse, int T, int K, int N,
+                             int H, float scale, void* trace, hipStream_t stream) {
+  return qkv_attn_fwd_impl(x, ldx, w, qkv, o, lse, T, K, N, H, scale, trace, ljs_device_cus(), stream);
 }
 
 // dq/dk/dv outputs get their own strides; delta is a [B][H][Sq] f32 workspace
+static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                         const void* lse, void* delta, void* dq, void* dk, void* dv, int B, int Sq, int Sk, int H,
+                         const long* qs, const long* ks, const long* vs, const long* os, const long* dos,
+                         const long* dqs, const long* dks, const long* dvs, float scale, int causal, int q_offset,
+                         hipStream_t stream, AttnPlan* plan = nullptr) {
+  if (!none_null({qs, ks, vs, os, dos, dqs, dks, dvs})) return (int)hipErrorInvalidValue;
+  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, q_offset);
+  a.dout = (const bf16_t*)dout;
+  a.delta = (const float*)delta;
+  a.do_sb = dos[0]; a.do_ss = dos[1]; a.do_sh = dos[2];
+  AttnArgs f = attn_outs(a, dk, dks, dv, dvs, dq, dqs);
+  const AttnPlan p = attn_bwd_plan(f, B);
+  if (plan) *plan = p;
+  if (plan || p.err != hipSuccess) return (int)p.err;
+  if (p.l[0].inst >= kBwdFused00 && p.l[0].inst <= kBwdFused11) {
+    f.vst = p.vst[0];
+    f.trace = g_attn_trace;
+    attn_launch(p.l[0], stream, f);
+    return (int)hipGetLastError();
+  }
+  AttnArgs c = attn_outs(a, dq, dqs), b = attn_outs(a, dk, dks, dv, dvs);
+  c.vst = p.vst[0];
+  c.flags32 = p.flags32;
+  b.vst = p.vst[1];
+  if (p.n == 1) {
+    attn_launch(p.l[0], stream, c, &b);
+  } else {
+    attn_launch(p.l[0], stream, c);
+    attn_launch(p.l[1], stream, b);
+  }
+  return (int)hipGetLastError();
+}
 LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
                          const void* lse, void* delta, void* dq, void* dk, void* dv, int B, int Sq, int Sk, int H,
                          const long* qs, const long* ks, const long* vs, const long* os, const long* dos,
                          const long* dqs, const long* dks, const long* dvs, float scale, int causal, int q_offset,
                          hipStream_t stream) {
-  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, q_offset);
-  a.dout = (const bf16_t*)dout;
-  a.delta = (const float*)delta;
-  a.do_sb = dos[0]; a.do_ss = dos[1]; a.do_sh = dos[2];
-  // 2 = automatic: the fused kernel runs one workgroup per (batch, head), so below ~half a
-  // workgroup per CU (B*H < 128: the reference's B = 8 x 8 heads) the split kernels' per-query-
-  // block grids fill the chip better (measured: 0.1218 vs 0.1248 ms/step at B = 8, equal at 16,
-  // fused far ahead from 32)
-  const bool fused = g_bwd_fused == 1 || (g_bwd_fused == 2 && (long)B * H >= 128);
-  if (fused && Sk <= FK) {
-    AttnArgs f = a;
-    attn_out(f.out, f.out_sb, f.out_ss, f.out_sh, dk, dks);
-    attn_out(f.out2, f.out2_sb, f.out2_ss, f.out2_sh, dv, dvs);
-    attn_out(f.out3, f.out3_sb, f.out3_ss, f.out3_sh, dq, dqs);
-    f.vst = vst_ok(dk, dks) && vst_ok(dv, dvs) && vst_ok(dq, dqs) ? g_vst : 0;
-    f.trace = g_attn_trace;
-    // 2 = automatic: the DMA form when a block sweeps at most two query blocks (the 2-D mesh's
-    // 128 local queries against 256 gathered keys: the K / V prologue is a third of the block's
-    // time there, and overlapping it with the first query block's loads measured 58.8 -> 57.1 us,
-    // 2-D rehearsal step 0.2963 -> 0.2937 ms median, gpurun_out/r4ab); at 256 queries it is
-    // neutral (0.2194 vs 0.2196 ms), so the register copy stays there
-    const bool kv_dma = g_bwd_kv_dma == 1 || (g_bwd_kv_dma == 2 && Sq <= 2 * BLK);
-    const bool sw1 = f.vst == 1 && Sq % BLK == 0 && Sk == FK && !causal;
-    ljs_launch_rec(kv_dma ? (sw1 ? "attn_bwd_fused<dma=1,sw=1>" : "attn_bwd_fused<dma=1,sw=0>")
-                          : (sw1 ? "attn_bwd_fused<dma=0,sw=1>" : "attn_bwd_fused<dma=0,sw=0>"),
-                   dim3(H, B), FT);
-    if (kv_dma && sw1) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, 1>), dim3(H, B), dim3(FT), 0, stream, f);
-    else if (kv_dma) hipLaunchKernelGGL((attn_bwd_fused_kernel<true, 0>), dim3(H, B), dim3(FT), 0, stream, f);
-    else if (sw1) hipLaunchKernelGGL((attn_bwd_fused_kernel<false, 1>), dim3(H, B), dim3(FT), 0, stream, f);
-    else hipLaunchKernelGGL((attn_bwd_fused_kernel<false, 0>), dim3(H, B), dim3(FT), 0, stream, f);
-    return (int)hipGetLastError();
-  }
-  AttnArgs c = a;
-  attn_out(c.out, c.out_sb, c.out_ss, c.out_sh, dq, dqs);
-  c.vst = g_vst && vst_ok(dq, dqs);  // (the 128-query dQ blocks use it)
-  AttnArgs b = a;
-  attn_out(b.out, b.out_sb, b.out_ss, b.out_sh, dk, dks);
-  attn_out(b.out2, b.out2_sb, b.out2_ss, b.out2_sh, dv, dvs);
-  b.vst = g_vst && vst_ok(dk, dks) && vst_ok(dv, dvs);  // (the 128-key dK/dV blocks use it)
-  const long nq = (Sq + BLK - 1) / BLK, nk = (Sk + BLK - 1) / BLK;
-  if (g_dkv32 && (nq + (Sk + 127) / 128) * H * B < (1L << 30)) {
-    const long nk128 = (Sk + 127) / 128;
-    c.flags32 = g_dq32;
-    const long nqb = c.flags32 ? (Sq + 127) / 128 : nq;
-    ljs_launch_rec(c.flags32 ? "attn_bwd_pair32<dq32=1>" : "attn_bwd_pair32<dq32=0>",
-                   dim3((unsigned)((nqb + nk128) * H * B)), 256);
-    hipLaunchKernelGGL(attn_bwd_pair32_kernel, dim3((unsigned)((nqb + nk128) * H * B)), dim3(256), 0, stream, c, b);
-    return (int)hipGetLastError();
-  }
-  if (g_bwd_pair && (nq + nk) * H * B < (1L << 30)) {
-    // one launch: dQ blocks and dK/dV blocks (which form delta themselves) side by side
-    ljs_launch_rec("attn_bwd_pair", dim3((unsigned)((nq + nk) * H * B)), 256);
-    hipLaunchKernelGGL(attn_bwd_pair_kernel, dim3((unsigned)((nq + nk) * H * B)), dim3(256), 0, stream, c, b);
-    return (int)hipGetLastError();
-  }
-  // dQ first: it also computes delta, which the dK/dV kernel consumes (stream order)
-  ljs_launch_rec("attn_bwd_dq", dim3(nq * H * B), 256);
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(nq * H * B), dim3(256), 0, stream, c);
-  ljs_launch_rec("attn_bwd_dkv", dim3(nk * H * B), 256);
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(nk * H * B), dim3(256), 0, stream, b);
-  return (int)hipGetLastError();
-}
-
-// Whether the switches let ljs_attn_bwd_proj run a (B, H) grid (the shape gate is the entry point's)
-LJS_API int ljs_attn_bwd_proj_enabled(int B, int H) {
-  if (g_bwd_proj == 0 || g_vst != 1) return 0;
-  if (g_bwd_proj == 1) return 1;
-  return (g_bwd_fused == 1 || g_bwd_fused == 2) && (long)B * H >= 192;
+  return attn_bwd_impl(q, k, v, o, dout, lse, delta, dq, dk, dv, B, Sq, Sk, H, qs, ks, vs, os, dos, dqs, dks, dvs,
+                       scale, causal, q_offset, stream);
 }
 
 // The fused backward with dO = dY . W^T formed per (batch, head) inside the kernel
 // (attn_bwd_proj_kernel): dy [B * Sq][M] bf16 with row stride dy_ld (0: one row broadcast), w
-// [H * 64][M] bf16 (the out-projection weight, k-contiguous).  Exactly the fused backward's common
-// case: Sq == Sk == 256, not causal, 16-byte aligned operands and outputs with row strides % 8 == 0;
-// anything else is hipErrorInvalidValue and launches nothing.
+// [H * 64][M] bf16 (the out-projection weight, k-contiguous).  What attn_bwd_proj_plan's gate does
+// not take is hipErrorInvalidValue and launches nothing.
+static int attn_bwd_proj_impl(const void* q, const void* k, const void* v, const void* o, const void* dy, long dy_ld,
+                              const void* w, int M, const void* lse, void* dq, void* dk, void* dv, int B, int Sq,
+                              int Sk, int H, const long* qs, const long* ks, const long* vs, const long* os,
+                              const long* dqs, const long* dks, const long* dvs, float scale, int causal,
+                              hipStream_t stream, AttnPlan* plan = nullptr) {
+  if (!none_null({qs, ks, vs, os, dqs, dks, dvs})) return (int)hipErrorInvalidValue;
+  AttnArgs a = attn_outs(attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, 0), dk, dks, dv, dvs,
+                         dq, dqs);
+  BwdProjArgs pj;
+  pj.dy = (const bf16_t*)dy; pj.w = (const bf16_t*)w; pj.dy_ld = dy_ld; pj.M = M;
+  pj.steps = g_attn_trace_steps;
+  const AttnPlan p = attn_bwd_proj_plan(a, B, pj);
+  if (plan) *plan = p;
+  if (plan || p.err != hipSuccess) return (int)p.err;
+  a.vst = p.vst[0];
+  a.trace = g_attn_trace;
+  ljs_launch_rec(kAttnInst[kBwdProj].name, dim3(p.l[0].gx), p.l[0].block);
+  hipLaunchKernelGGL(attn_bwd_proj_kernel, dim3(p.l[0].gx), dim3(p.l[0].block), 0, stream, a, pj);
+  return (int)hipGetLastError();
+}
 LJS_API int ljs_attn_bwd_proj(const void* q, const void* k, const void* v, const void* o, const void* dy, long dy_ld,
                               const void* w, int M, const void* lse, void* dq, void* dk, void* dv, int B, int Sq,
                               int Sk, int H, const long* qs, const long* ks, const long* vs, const long* os,
                               const long* dqs, const long* dks, const long* dvs, float scale, int causal,
                               hipStream_t stream) {
-  const long lim = 0x7ffffff0L;
-  auto in_ok = [&](const void* p, const long* st) {
-    return p && (((uintptr_t)p) & 15) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0 && st[1] >= 0 &&
-           2 * ((long)(FK - 1) * st[1] + D) < lim;
-  };
-  if (B <= 0 || H <= 0 || (long)B * H >= (1L << 30) || Sq != FK || Sk != FK || causal || M <= 0 || M % PJ_BK ||
-      !(dy_ld == 0 || (dy_ld >= M && dy_ld % 8 == 0)) || !dy || !w || !lse ||
-      (((uintptr_t)dy | (uintptr_t)w) & 15) || (((uintptr_t)lse) & 3) ||
-      2 * ((long)(FK - 1) * dy_ld + M) >= lim || 2L * D * M >= lim ||
-      !in_ok(q, qs) || !in_ok(k, ks) || !in_ok(v, vs) || !in_ok(o, os) ||
-      !dq || !dk || !dv || !vst_ok(dq, dqs) || !vst_ok(dk, dks) || !vst_ok(dv, dvs) ||
-      !ljs_attn_bwd_proj_enabled(B, H))
-    return (int)hipErrorInvalidValue;
-  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, 0);
-  attn_out(a.out, a.out_sb, a.out_ss, a.out_sh, dk, dks);
-  attn_out(a.out2, a.out2_sb, a.out2_ss, a.out2_sh, dv, dvs);
-  attn_out(a.out3, a.out3_sb, a.out3_ss, a.out3_sh, dq, dqs);
-  a.vst = 1;
-  a.trace = g_attn_trace;
-  BwdProjArgs pj;
-  pj.dy = (const bf16_t*)dy; pj.w = (const bf16_t*)w; pj.dy_ld = dy_ld; pj.M = M;
-  pj.steps = g_attn_trace_steps;
-  ljs_launch_rec("attn_bwd_proj", dim3((unsigned)(B * H)), FT);
-  hipLaunchKernelGGL(attn_bwd_proj_kernel, dim3((unsigned)(B * H)), dim3(FT), 0, stream, a, pj);
-  return (int)hipGetLastError();
+  return attn_bwd_proj_impl(q, k, v, o, dy, dy_ld, w, M, lse, dq, dk, dv, B, Sq, Sk, H, qs, ks, vs, os, dqs, dks, dvs,
+                            scale, causal, stream);
+}
+
+// The plan of one entry point's call on a device of `cus` compute units, without a GPU: nothing is
+// dereferenced or launched.  kind: 0 ljs_attn_fwd, 1 ljs_attn_fwd_acc, 2 ljs_attn_bwd, 3
+// ljs_attn_bwd_proj, 4 ljs_qkv_attn_fwd.  addr: q, k, v, o, lse, dout, delta, oacc, dq, dk, dv, dy, w
+// (kind 4: x, w, qkv, o, lse); st: the (batch, seq, head) strides of q, k, v, o, dout, oacc, dq, dk,
+// dv; M, ld: the projection's columns and dy's row stride (kind 4: N and ldx, with T = B * Sq rows);
+// K: kind 4's.  out[0..15]: error, launches, (instance, grid x, grid y, block) of each of two, vst
+// of the two argument structs, flags32, nw, nqb, the record's acc_mode; names: the launches' record
+// names, separated by a space.  Returns the error.
+LJS_API int ljs_attn_plan(int kind, int B, int Sq, int Sk, int H, int causal, int acc_mode, void* const* addr,
+                          const long* st, int M, long ld, int K, int cus, int* out, char* names, int cap) {
+  void* const* p = addr;
+  AttnPlan pl = attn_reject();
+  if (kind == 0 || kind == 1)
+    attn_fwd_impl(p[0], p[1], p[2], p[3], p[4], B, Sq, Sk, H, st, st + 3, st + 6, st + 9, 1.f, causal, 0, p[7],
+                  kind ? st + 15 : nullptr, acc_mode, kind == 1, nullptr, &pl);
+  else if (kind == 2)
+    attn_bwd_impl(p[0], p[1], p[2], p[3], p[5], p[4], p[6], p[8], p[9], p[10], B, Sq, Sk, H, st, st + 3, st + 6, st + 9,
+                  st + 12, st + 18, st + 21, st + 24, 1.f, causal, 0, nullptr, &pl);
+  else if (kind == 3)
+    attn_bwd_proj_impl(p[0], p[1], p[2], p[3], p[11], ld, p[12], M, p[4], p[8], p[9], p[10], B, Sq, Sk, H, st, st + 3,
+                       st + 6, st + 9, st + 18, st + 21, st + 24, 1.f, causal, nullptr, &pl);
+  else if (kind == 4)
+    qkv_attn_fwd_impl(p[0], ld, p[1], p[2], p[3], p[4], B * Sq, K, M, H, 1.f, nullptr, cus, nullptr, &pl);
+  const int v[16] = {(int)pl.err, pl.n, pl.l[0].inst, (int)pl.l[0].gx, (int)pl.l[0].gy, (int)pl.l[0].block,
+                     pl.l[1].inst, (int)pl.l[1].gx, (int)pl.l[1].gy, (int)pl.l[1].block, pl.vst[0], pl.vst[1],
+                     pl.flags32, pl.nw, pl.nqb, pl.acc_mode};
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
+  if (names && cap > 0)
+    snprintf(names, (size_t)cap, "%s%s%s", pl.n > 0 ? kAttnInst[pl.l[0].inst].name : "", pl.n > 1 ? " " : "",
+             pl.n > 1 ? kAttnInst[pl.l[1].inst].name : "");
+  return (int)pl.err;
 }

@@ -111,7 +111,10 @@ _SIGS = {
     "ljs_embed_work_cap": [c_long],
     "ljs_launch_count": [],
     "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
-    "ljs_attn_set_cus": [c_int],
+    "ljs_attn_set": [c_int, c_int],
+    "ljs_attn_get": [c_int],
+    "ljs_attn_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p), _LP, c_int, c_long,
+                      c_int, c_int, ctypes.POINTER(c_int), ctypes.c_char_p, c_int],
 }
 
 
@@ -195,88 +198,72 @@ def launch_log():
         log.extend(r for r in (_launch_at(i) for i in range(max(start, end - 32), end)) if r is not None)
 
 
+# the `which` of ljs_attn_set / ljs_attn_get: the rows of LJS_ATTN_SWITCHES (csrc/kernels/attention.hip)
+_ATTN_SWITCHES = ("bwd_pair", "dkv32", "dq32", "vst", "cus", "fwd_res", "bwd_kv_dma", "bwd_fused", "bwd_proj")
+
+
+def _attn_set(which: str, value, flag: bool = True):
+    """One kernel-variant switch of attention.hip: None restores the library's default (as any
+    negative number does), ``flag`` switches take True / False, the others a number."""
+    lib().ljs_attn_set(_ATTN_SWITCHES.index(which), -1 if value is None else int(bool(value) if flag else value))
+
+
 def set_attention_cus(n: Optional[int]):
     """Grid of the fused Q/K/V projection + attention forward: ``n`` blocks instead of one per CU
     (tests: many items per block on small shapes); None or <= 0 = the device's CU count."""
-    fn = lib().ljs_attn_set_cus
-    fn.restype = None
-    fn(0 if n is None else int(n))
+    _attn_set("cus", n, flag=False)
 
 
 def set_attention_fwd_resident(waves: int):
     """Forward kernel for key lengths <= 256: 0 = tiled (K/V tiles through registers), 4 or 8 =
     K/V-resident (whole K/V of a head in LDS by one LDS-DMA burst; waves x 16 queries per block),
     -1 = the default (8, or 4 below 256 blocks)."""
-    fn = lib().ljs_attn_set_fwd_res
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(int(waves))
+    _attn_set("fwd_res", waves, flag=False)
 
 
 def set_attention_bwd_kv_dma(enabled: Optional[bool]):
     """Fused short-key backward: K / V land in LDS by LDS-DMA in flight with the first query block
     (True) or through registers (False); None = automatic (LDS-DMA when a block sweeps at most
     128 queries).  Bit-identical either way."""
-    fn = lib().ljs_attn_set_bwd_kv_dma
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(-1 if enabled is None else int(bool(enabled)))
+    _attn_set("bwd_kv_dma", enabled)
 
 
 def set_attention_vst(enabled: Optional[bool]):
     """Attention output row tiles (forward O, backward dK / dV) stored through an LDS image as
     whole 128-byte rows with 16-byte stores (True, the default via None), or per lane as 8-byte
     pieces (False).  Bit-identical either way."""
-    fn = lib().ljs_attn_set_vst
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(-1 if enabled is None else int(bool(enabled)))
+    _attn_set("vst", enabled)
 
 
 def set_attention_bwd_fused(enabled: Optional[bool]):
     """Select the attention backward for key lengths <= 256: the single-pass fused kernel
     (True), the split dQ + dK/dV kernels (False; always used above 256 keys), or None for the
     automatic choice by grid size (the default)."""
-    fn = lib().ljs_attn_set_bwd_fused
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(2 if enabled is None else (1 if enabled else 0))
+    _attn_set("bwd_fused", enabled)
 
 
 def set_attention_bwd_proj(enabled: Optional[bool]):
     """The fused backward that forms its own dO from the out-projection's dY (``attn_bwd_proj``):
     whenever its shape gate holds (True), never (False), or None for the automatic choice: where the
     fused backward itself is chosen and there are at least 192 (batch, head) pairs."""
-    fn = lib().ljs_attn_set_bwd_proj
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(2 if enabled is None else (1 if enabled else 0))
+    _attn_set("bwd_proj", enabled)
 
 
 def set_attention_dkv32(enabled: Optional[bool]):
     """Split attention backward with 128-key dK/dV blocks (4 waves x 32 keys): True / None (the
     default) or False (64-key blocks)."""
-    fn = lib().ljs_attn_set_dkv32
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(-1 if enabled is None else (1 if enabled else 0))
+    _attn_set("dkv32", enabled)
 
 
 def set_attention_dq32(enabled: Optional[bool]):
     """With 128-key dK/dV blocks: 128-query dQ blocks (True / None, the default) or 64 (False)."""
-    fn = lib().ljs_attn_set_dq32
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(1 if enabled is None or enabled else 0)
+    _attn_set("dq32", enabled)
 
 
 def set_attention_bwd_pair(enabled: Optional[bool]):
     """Split attention backward as ONE launch of dQ and dK/dV blocks (True, the default via
     None) or as two launches ordered by the dQ kernel's delta output (False)."""
-    fn = lib().ljs_attn_set_bwd_pair
-    fn.argtypes = [c_int]
-    fn.restype = None
-    fn(1 if enabled is None or enabled else 0)
+    _attn_set("bwd_pair", enabled)
 
 
 def available() -> bool:
@@ -1874,6 +1861,39 @@ def _bs_like(shape, ref: torch.Tensor) -> torch.Tensor:
     return torch.empty(shape, dtype=torch.bfloat16, device=ref.device)
 
 
+# ---------------------------------------------------------------------------- the launcher's plan
+_ATTN_KINDS = ("fwd", "fwd_acc", "bwd", "bwd_proj", "qkv_fwd")     # ljs_attn_plan's `kind`
+_ATTN_ADDRS = ("q", "k", "v", "o", "lse", "dout", "delta", "oacc", "dq", "dk", "dv", "dy", "w")
+_ATTN_STRIDES = ("q", "k", "v", "o", "dout", "oacc", "dq", "dk", "dv")
+
+
+def attn_plan(kind: str, B: int, Sq: int, Sk: int, H: int, *, causal: bool = False, q_offset: int = 0,
+              acc_mode: int = 0, strides=None, addrs=None, M: int = 0, dy_ld: int = 0, K: int = 0, N=None, ldx=None,
+              cus: int = 256) -> dict:
+    """What the attention entry point ``kind`` (fwd, fwd_acc, bwd, bwd_proj, qkv_fwd) would launch
+    for a call under the current switches, on a device of ``cus`` compute units (``ljs_attn_plan``:
+    the launcher's own plan step; needs the library, not a GPU).  ``strides`` / ``addrs``: dicts of
+    (batch, seq, head) strides and addresses by operand name (q, k, v, o, lse, dout, delta, oacc, dq,
+    dk, dv, dy, w; qkv_fwd: x, w, qkv, o, lse), the rest dense and 16-byte aligned; ``M`` / ``dy_ld``:
+    bwd_proj's; qkv_fwd takes T = B * Sq rows, ``K``, ``N`` (64 H) and ``ldx`` (K).  No rule reads
+    ``q_offset``.  Returns ``err``, ``launches`` (the :func:`last_launch` keys name, grid, blocks,
+    block, acc_mode of each), ``vst`` (of the argument structs), ``flags32``, ``nw`` and ``nqb``."""
+    strides, addrs, order = strides or {}, addrs or {}, _ATTN_ADDRS
+    if kind == "qkv_fwd":
+        M, dy_ld, order = 64 * H if N is None else N, K if ldx is None else ldx, ("x", "w", "qkv", "o", "lse")
+    rows = {"k": Sk, "v": Sk, "dk": Sk, "dv": Sk}
+    st = [s for n in _ATTN_STRIDES for s in strides.get(n) or (rows.get(n, Sq) * H * 64, H * 64, 64)]
+    ad = (c_void_p * len(order))(*[addrs.get(n, 4096) for n in order])
+    out, names = (c_int * 16)(), ctypes.create_string_buffer(96)
+    lib().ljs_attn_plan(_ATTN_KINDS.index(kind), B, Sq, Sk, H, int(causal), acc_mode, ad, _longs(st), M, dy_ld, K,
+                        cus, out, names, len(names))
+    launches = [{"name": n, "grid": (out[3 + 4 * i], out[4 + 4 * i], 1), "blocks": out[3 + 4 * i] * out[4 + 4 * i],
+                 "block": out[5 + 4 * i], "acc_mode": None if out[15] < 0 else out[15]}
+                for i, n in enumerate(names.value.decode().split())]
+    return {"err": out[0], "launches": launches, "vst": (out[10], out[11]), "flags32": out[12], "nw": out[13],
+            "nqb": out[14]}
+
+
 # ---------------------------------------------------------------------------- fused projection
 # The Q/K/V projection GEMM of a self-attention block with a 256-token sequence can run the
 # attention forward of each (batch, head) in the same kernel (ljs_qkv_attn_fwd): ops/linear.py
@@ -1952,26 +1972,24 @@ ATTN_BWD_PROJ_STATS = {"taken": 0, "materialised": 0}
 
 
 def proj_shape_ok(B: int, Sq: int, Sk: int, H: int, D: int, M: int, dy_ld: int, causal: bool) -> bool:
-    """The shape half of ljs_attn_bwd_proj's gate (alignment and the switches are checked apart)."""
-    return (B > 0 and H > 0 and D == 64 and Sq == 256 and Sk == 256 and not causal and M > 0 and M % 32 == 0
-            and (dy_ld == 0 or (dy_ld >= M and dy_ld % 8 == 0)))
+    """ljs_attn_bwd_proj's gate for dense, aligned operands of this shape under the current switches
+    (the head_dim is fixed in the library, so that one test is made here)."""
+    return D == 64 and attn_plan("bwd_proj", B, Sq, Sk, H, causal=causal, M=M, dy_ld=dy_ld)["err"] == 0
 
 
-def _proj_strides_ok(t: torch.Tensor) -> bool:
-    st = _strides3(t)
-    return (t.dtype == torch.bfloat16 and t.stride(3) == 1 and t.data_ptr() % 16 == 0
-            and all(x % 8 == 0 for x in st) and st[1] >= 0 and 2 * (255 * st[1] + 64) < 0x7ffffff0)
-
-
-def attn_bwd_proj_ok(q, k, v, o, dy: torch.Tensor, dy_ld: int, w: torch.Tensor, causal: bool) -> bool:
-    """Whether ljs_attn_bwd_proj accepts these operands (its whole gate, the switches included)."""
+def attn_bwd_proj_ok(q, k, v, o, dy: torch.Tensor, dy_ld: int, w: torch.Tensor, causal: bool, outs=None) -> bool:
+    """Whether ljs_attn_bwd_proj accepts these operands (and the outputs ``outs`` = (dq, dk, dv), else
+    dense ones): the entry point's own gate (attn_bwd_proj_plan, the switches included) asked through
+    the plan, and here only what the library cannot see -- dtypes, a contiguous head_dim and weight."""
     B, Sq, H, D = q.shape
-    M = w.shape[1]
-    return (proj_shape_ok(B, Sq, k.shape[1], H, D, M, dy_ld, causal) and w.shape[0] == H * D
-            and all(_proj_strides_ok(t) for t in (q, k, v, o))
-            and dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.is_contiguous()
-            and dy.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and 2 * (255 * dy_ld + M) < 0x7ffffff0
-            and bool(lib().ljs_attn_bwd_proj_enabled(B, H)))
+    ts = dict(zip(("q", "k", "v", "o", "dq", "dk", "dv"), (q, k, v, o) + tuple(outs or ())))
+    if not (D == 64 and w.shape[0] == H * D and dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and w.is_contiguous() and all(t.dtype == torch.bfloat16 and t.stride(3) == 1 for t in ts.values())):
+        return False
+    addrs = {n: t.data_ptr() for n, t in ts.items()}
+    addrs.update(dy=dy.data_ptr(), w=w.data_ptr())
+    return attn_plan("bwd_proj", B, Sq, k.shape[1], H, causal=causal, M=w.shape[1], dy_ld=dy_ld, addrs=addrs,
+                     strides={n: _strides3(t) for n, t in ts.items()})["err"] == 0
 
 
 def attn_bwd_proj_block(q, k, v, o, dy: torch.Tensor, dy_ld: int, w: torch.Tensor, lse, scale: float,
@@ -2020,8 +2038,7 @@ def _take_out_proj(do: torch.Tensor, q, k, v, o, outs, causal):
     dy, ld, wn, dx, launch = ent
     B, Sq, H, D = q.shape
     if (do.dtype == torch.bfloat16 and tuple(do.shape) == (B, Sq, H, D) and do.is_contiguous()
-            and dx.numel() == do.numel() and attn_bwd_proj_ok(q, k, v, o, dy, ld, wn, causal)
-            and all(_proj_strides_ok(t) for t in outs)):
+            and dx.numel() == do.numel() and attn_bwd_proj_ok(q, k, v, o, dy, ld, wn, causal, outs)):
         ATTN_BWD_PROJ_STATS["taken"] += 1
         return dy, ld, wn
     launch()
@@ -2029,21 +2046,43 @@ def _take_out_proj(do: torch.Tensor, q, k, v, o, outs, causal):
     return None
 
 
+def _attn_fwd_call(q, k, v, o, lse, scale, causal, q_offset):
+    """ljs_attn_fwd into ``o`` (bf16 [B, Sq, H, 64]) and ``lse`` (f32 [B, H, Sq]); returns both."""
+    B, Sq, H, _ = q.shape
+    _ck(lib().ljs_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, k.shape[1], H, _longs(_strides3(q)),
+                           _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)), scale, int(causal),
+                           q_offset, _stream(q)), "ljs_attn_fwd")
+    return o, lse
+
+
+def _lse_like(q: torch.Tensor) -> torch.Tensor:
+    return torch.empty((q.shape[0], q.shape[2], q.shape[1]), dtype=torch.float32, device=q.device)
+
+
+def _bf16_rows(do: torch.Tensor) -> torch.Tensor:
+    """The cotangent as the backward kernels read it: bf16 with a contiguous head_dim."""
+    do = do.to(torch.bfloat16)
+    return do if do.stride(3) == 1 else do.contiguous()
+
+
+def _attn_bwd_call(q, k, v, o, do, lse, dq, dk, dv, scale, causal, q_offset):
+    """ljs_attn_bwd into dq / dk / dv (``do`` as _bf16_rows gives it); allocates the delta workspace."""
+    B, Sq, H, _ = q.shape
+    delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    _ck(lib().ljs_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, Sq,
+                           k.shape[1], H, _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)),
+                           _longs(_strides3(o)), _longs(_strides3(do)), _longs(_strides3(dq)), _longs(_strides3(dk)),
+                           _longs(_strides3(dv)), scale, int(causal), q_offset, _stream(q)), "ljs_attn_bwd")
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, causal, q_offset):
-        B, Sq, H, D = q.shape
-        Sk = k.shape[1]
         pre = _take_fused_attention(q, k, v, scale, causal, q_offset)
         if pre is not None:
             o, lse = pre
         else:
-            o = _bs_like((B, Sq, H, D), q)
-            lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-            rc = lib().ljs_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, Sk, H, _longs(_strides3(q)),
-                                    _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)), scale,
-                                    int(causal), q_offset, _stream(q))
-            _ck(rc, "ljs_attn_fwd")
+            o, lse = _attn_fwd_call(q, k, v, _bs_like(q.shape, q), _lse_like(q), scale, causal, q_offset)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.args = (scale, causal, q_offset)
         return o
@@ -2054,9 +2093,7 @@ class _Attention(torch.autograd.Function):
         scale, causal, q_offset = ctx.args
         B, Sq, H, D = q.shape
         Sk = k.shape[1]
-        do = do.to(torch.bfloat16)
-        if do.stride(3) != 1:
-            do = do.contiguous()
+        do = _bf16_rows(do)
         st = q.stride()
         fused = (Sq == Sk and k.stride() == st and v.stride() == st and st[3] == 1 and st[2] == D
                  and k.data_ptr() - q.data_ptr() == H * D * 2 and v.data_ptr() - q.data_ptr() == 2 * H * D * 2
@@ -2073,29 +2110,16 @@ class _Attention(torch.autograd.Function):
         proj = _take_out_proj(do, q, k, v, o, (dq, dk, dv), causal) if _PROJ_PENDING else None
         if proj is not None:
             attn_bwd_proj_block(q, k, v, o, proj[0], proj[1], proj[2], lse, scale, causal, outs=(dq, dk, dv))
-            return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None
-        delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-        rc = lib().ljs_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, Sq,
-                                Sk, H, _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)),
-                                _longs(_strides3(o)), _longs(_strides3(do)), _longs(_strides3(dq)),
-                                _longs(_strides3(dk)), _longs(_strides3(dv)), scale, int(causal), q_offset,
-                                _stream(q))
-        _ck(rc, "ljs_attn_bwd")
+        else:
+            _attn_bwd_call(q, k, v, o, do, lse, dq, dk, dv, scale, causal, q_offset)
         return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None
 
 
 def attn_fwd_lse(q, k, v, scale: float, causal: bool = False, q_offset: int = 0):
     """Raw flash forward of one (q block, kv block) pair: (o bf16 [B,Sq,H,D], lse f32 [B,H,Sq]).
     lse is log2 of the scaled-score partition function; +inf marks rows with no unmasked key."""
-    B, Sq, H, D = q.shape
-    Sk = k.shape[1]
-    o = torch.empty((B, Sq, H, D), dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-    rc = lib().ljs_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, Sk, H, _longs(_strides3(q)),
-                            _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)), scale, int(causal),
-                            q_offset, _stream(q))
-    _ck(rc, "ljs_attn_fwd")
-    return o, lse
+    o = torch.empty(q.shape, dtype=torch.bfloat16, device=q.device)
+    return _attn_fwd_call(q, k, v, o, _lse_like(q), scale, causal, q_offset)
 
 
 def attn_fwd_acc(q, k, v, scale: float, causal: bool, q_offset: int, oacc: torch.Tensor, lse: torch.Tensor, mode: int,
@@ -2121,18 +2145,10 @@ def attn_bwd_block(q, k, v, o, do, lse, scale: float, causal: bool = False, q_of
     (blockwise-separable): returns this block's (dq, dk, dv) contributions in bf16."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
-    do = do.to(torch.bfloat16)
-    if do.stride(3) != 1:
-        do = do.contiguous()
     dq = torch.empty((B, Sq, H, D), dtype=torch.bfloat16, device=q.device)
     dk = torch.empty((B, Sk, H, D), dtype=torch.bfloat16, device=q.device)
     dv = torch.empty((B, Sk, H, D), dtype=torch.bfloat16, device=q.device)
-    delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-    rc = lib().ljs_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, Sq, Sk,
-                            H, _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)),
-                            _longs(_strides3(do)), _longs(_strides3(dq)), _longs(_strides3(dk)), _longs(_strides3(dv)),
-                            scale, int(causal), q_offset, _stream(q))
-    _ck(rc, "ljs_attn_bwd")
+    _attn_bwd_call(q, k, v, o, _bf16_rows(do), lse, dq, dk, dv, scale, causal, q_offset)
     return dq, dk, dv
 
 

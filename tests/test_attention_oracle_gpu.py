@@ -44,6 +44,18 @@ def _gpu(c, *names):
     return tuple(c[n].to(dev) for n in names)
 
 
+def _assert_planned(hip, kind, log, causal, q_off, **ts):
+    """The launcher's plan step (hip.attn_plan, under the switches now set) for the call on these
+    tensors -- their real addresses and strides -- against the launch log, entry for entry."""
+    q, k = ts["q"], ts["k"]
+    plan = hip.attn_plan(kind, q.shape[0], q.shape[1], k.shape[1], q.shape[2], causal=causal, q_offset=q_off,
+                         strides={n: hip._strides3(t) for n, t in ts.items()},
+                         addrs={n: t.data_ptr() for n, t in ts.items()})
+    keys = ("name", "grid", "block", "acc_mode")
+    assert plan["err"] == 0 and [[r[x] for x in keys] for r in plan["launches"]] == [[r[x] for x in keys] for r in log], \
+        (plan, list(log))
+
+
 # ============================================================================ forward: O and lse
 _FWD_RES = {"attn_fwd_tiled<1>": 0, "attn_fwd_res<4>": 4, "attn_fwd_res<8>": 8}
 
@@ -81,6 +93,7 @@ def test_forward_against_oracle(hip, kind, shape, inst):
         with hip.launch_log() as log:
             o, lse = hip.attn_fwd_lse(q, k, v, SCALE, causal, q_off)
         torch.cuda.synchronize()
+        _assert_planned(hip, "fwd", log, causal, q_off, q=q, k=k, v=v, o=o)
     finally:
         hip.set_attention_fwd_resident(-1)
     assert [(r["name"], r["acc_mode"]) for r in log] == [(inst, 0)], list(log)
@@ -171,6 +184,8 @@ def _run_bwd(hip, inst, shape, q, k, v, o, do, lse, q_off=None, names_shape=None
         with hip.launch_log() as log:
             got = hip.attn_bwd_block(q, k, v, o, do, lse, SCALE, causal, shape[5] if q_off is None else q_off)
         torch.cuda.synchronize()
+        _assert_planned(hip, "bwd", log, causal, shape[5] if q_off is None else q_off, q=q, k=k, v=v, o=o, dout=do,
+                        dq=got[0], dk=got[1], dv=got[2])
     assert [r["name"] for r in log] == _bwd_names(inst, names_shape or shape), list(log)
     return got
 

@@ -70,13 +70,23 @@ def test_linear_without_attention_is_unsafe():
 
 
 def test_shape_gate():
+    """ljs_attn_bwd_proj's own gate (hip.proj_shape_ok asks the launcher's plan step; the built
+    library answers without a GPU), with the switch forced on so that the shape alone decides."""
+    import os
+    if not os.path.exists(hip._LIBPATH):
+        from learning_jax_sharding_amd.csrc import build
+        build.build_all()
     ok = hip.proj_shape_ok
-    assert ok(64, 256, 256, 8, 64, 640, 0, False)
-    assert ok(1, 256, 256, 1, 64, 32, 32, False) and ok(1, 256, 256, 1, 64, 32, 40, False)
-    assert not ok(64, 256, 256, 8, 64, 40, 40, False)       # M % 32
-    assert not ok(64, 128, 256, 8, 64, 640, 640, False)     # the 2-D layout's 128 local queries
-    assert not ok(64, 256, 128, 8, 64, 640, 640, False)
-    assert not ok(64, 256, 256, 8, 32, 640, 640, False)     # head_dim
-    assert not ok(64, 256, 256, 8, 64, 640, 640, True)      # causal
-    assert not ok(64, 256, 256, 8, 64, 640, 636, False)     # rows shorter than M
-    assert not ok(64, 256, 256, 8, 64, 640, 644, False)     # row stride % 8
+    hip.set_attention_bwd_proj(True)
+    try:
+        assert ok(64, 256, 256, 8, 64, 640, 0, False)
+        assert ok(1, 256, 256, 1, 64, 32, 32, False) and ok(1, 256, 256, 1, 64, 32, 40, False)
+        assert not ok(64, 256, 256, 8, 64, 40, 40, False)       # M % 32
+        assert not ok(64, 128, 256, 8, 64, 640, 640, False)     # the 2-D layout's 128 local queries
+        assert not ok(64, 256, 128, 8, 64, 640, 640, False)
+        assert not ok(64, 256, 256, 8, 32, 640, 640, False)     # head_dim
+        assert not ok(64, 256, 256, 8, 64, 640, 640, True)      # causal
+        assert not ok(64, 256, 256, 8, 64, 640, 636, False)     # rows shorter than M
+        assert not ok(64, 256, 256, 8, 64, 640, 644, False)     # row stride % 8
+    finally:
+        hip.set_attention_bwd_proj(None)
