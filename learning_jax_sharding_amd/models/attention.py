@@ -15,6 +15,11 @@ MI355X design: the three projections run as ONE batched MFMA GEMM over the
 concatenated kernels (``fused_qkv``), and QKᵀ → scale → softmax → P·V is one
 flash-style HIP kernel (``impl="fused"``).  ``impl="einsum"`` runs the
 reference's literal einsum/softmax formulation (used by the parity tests).
+
+Beyond the reference: ``causal=True`` masks key positions after the query's (both formulations), and
+``rope_theta`` rotates q and k after the head split by their global positions (``ops.core.rope``:
+half-split pairs, ``y[i] = x[i] cos - x[i + h] sin``, ``y[i + h] = x[i + h] cos + x[i] sin`` with ``h =
+dim_head / 2`` and angle ``p theta^(-2 i / dim_head)``).  Both default to off.
 """
 from __future__ import annotations
 
@@ -46,8 +51,12 @@ class MultiHeadAttention(Module):
     kernel_axes_in: tuple = ("embed", "heads")
     kernel_axes_out: tuple = ("heads", "embed")
     verbose: bool = False
+    causal: bool = False                  # query position p attends to key positions <= p only
+    rope_theta: Optional[float] = None    # rotary position embedding of q and k with this base; None: none
 
     def setup(self):
+        if self.rope_theta is not None and self.dim_head % 2:
+            raise ValueError(f"MultiHeadAttention: rope_theta needs an even dim_head, got {self.dim_head}")
         inner_dim = self.dim_head * self.heads
         self.scale = self.dim_head ** -0.5
         qkv_init = with_logical_partitioning(init.lecun_normal(), self.kernel_axes_in)
@@ -100,6 +109,9 @@ class MultiHeadAttention(Module):
         ``residual + attention(...)`` in the compute dtype, the add fused into the output
         projection's GEMM epilogue when dropout is the identity."""
         self_attn = context is None
+        if self.rope_theta is not None and not self_attn:
+            raise ValueError("MultiHeadAttention: rope_theta with a context (cross-attention) is not defined: "
+                             "queries and keys would be rotated by positions of two different sequences")
         context = hidden_states if context is None else context
         self._log("context.shape: ", context.shape)
         dt = _dt.canonicalize(self.dtype)
@@ -126,7 +138,11 @@ class MultiHeadAttention(Module):
             # the attention forward rides in the projection kernel when every device holds whole
             # sequences and all heads (ops/linear.attention_next: single device / data parallel)
             from ..ops import linear as _lin
-            hint = (self.impl == "fused" and qkv_pf is None and hidden_states.ndim == 3
+            # (not for a causal or rotary layer: the fused projection + forward kernel is non-causal
+            # and consumes the un-rotated Q / K, so its launch would be wasted and its registry
+            # entry left stale)
+            hint = (self.impl == "fused" and not self.causal and self.rope_theta is None
+                    and qkv_pf is None and hidden_states.ndim == 3
                     and tuple(hidden_states.tile.tile_shape[1:]) == (1, 1)
                     and all(tuple(w.tile.tile_shape) == (1, 1) for w in (wq, wk, wv)))
             with (_lin.attention_next(self.heads, self.dim_head, self.scale) if hint else contextlib.nullcontext()):
@@ -153,13 +169,23 @@ class MultiHeadAttention(Module):
         v = with_logical_constraint(v, ("batch", "embed", None, None))
         self._log("query_states.shape: ", q.shape)
 
+        if self.rope_theta is not None:
+            # after the head split, before either attention formulation: q and k in one launch per device
+            q, k = core.rope(q, k, theta=self.rope_theta)
+
         if self.impl == "fused":
-            hidden = core.dot_product_attention(q, k, v, self.scale)
+            hidden = core.dot_product_attention(q, k, v, self.scale, causal=self.causal)
         else:
             qf = core.convert(q, torch.float32)
             kf = core.convert(k, torch.float32)
             scores = core.einsum("b t n h, b f n h -> b n f t", kf, qf)
             scores = core.binary("mul", scores, self.scale)
+            if self.causal:
+                # (f, t) = (query, key): -inf above the diagonal, before the softmax
+                nq, nk = q.shape[1], k.shape[1]
+                above = torch.arange(nk)[None, :] > torch.arange(nq)[:, None]
+                mask = torch.zeros(nq, nk).masked_fill_(above, float("-inf"))
+                scores = core.binary("add", scores, core.asarray_like(mask, scores))
             probs = core.softmax(scores, axis=-1)
             probs = core.convert(probs, dt)
             hidden = core.einsum("b n f t, b t n h -> b f n h", probs, v)

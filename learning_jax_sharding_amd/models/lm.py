@@ -1,6 +1,13 @@
-"""A small decoder-style language model from token ids to logits, through this project's kernels
-only: token (and optional learned position) :class:`~..nn.layers.Embed`, a stack of pre-norm
+"""A small language model from token ids to logits, through this project's kernels only: token (and
+optional learned position) :class:`~..nn.layers.Embed`, a stack of pre-norm
 :class:`~.transformer.TransformerLayer`, a final norm and a ``Dense(vocab_size)`` head.
+
+``causal=True`` makes it a decoder: the logits at position p depend on the tokens at positions <= p
+only, which is what :func:`lm_loss` on next-token labels needs.  With the default ``causal=False``
+every position attends to the whole sequence (an encoder; next-token labels would let the model read
+the tokens it is asked to predict).  Positions come from ``rope_theta`` (rotary embedding of q and k
+in every layer) or from ``max_len`` (a learned additive table), not both; with neither the model sees
+positions through the causal mask alone.
 
 The embedding table's logical axes are ``("vocab", "embed")`` and the head kernel's ``("embed",
 "vocab")``: under ``parallel.tensor.VOCAB_PARALLEL_RULES`` both ends of the model are vocab-parallel
@@ -46,16 +53,21 @@ class TransformerLM(Module):
     norm: str = "rms"
     dtype: Any = torch.bfloat16
     fp8: bool = False
+    causal: bool = False                  # causal self-attention in every layer
+    rope_theta: Optional[float] = None    # rotary position embedding with this base in every layer
 
     def setup(self):
         if self.norm not in ("layer", "rms"):
             raise ValueError(f"TransformerLM norm must be 'layer' or 'rms', got {self.norm!r}")
+        if self.rope_theta is not None and self.max_len is not None:
+            raise ValueError("TransformerLM: rope_theta and max_len are two position schemes; give one")
         self.embed = Embed(self.vocab_size, self.dim, dtype=self.dtype, name="embed")
         if self.max_len is not None:
             self.pos_embed = Embed(self.max_len, self.dim, dtype=self.dtype, name="pos_embed")
         ff = self.ff_dim if self.ff_dim is not None else 4 * self.dim
         self.blocks = [TransformerLayer(self.dim, heads=self.heads, dim_head=self.dim_head, ff_dim=ff,
-                                        dtype=self.dtype, fp8=self.fp8, norm=self.norm, name=f"layer_{i}")
+                                        dtype=self.dtype, fp8=self.fp8, norm=self.norm, causal=self.causal,
+                                        rope_theta=self.rope_theta, name=f"layer_{i}")
                        for i in range(self.layers)]
         cls = LayerNorm if self.norm == "layer" else RMSNorm
         self.final_norm = cls(dtype=self.dtype, name="final_norm")

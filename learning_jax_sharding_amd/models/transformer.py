@@ -29,9 +29,12 @@ class TransformerLayer(Module):
     dtype: Any = torch.bfloat16
     fp8: bool = False
     norm: Optional[str] = None   # None (no normalisation), "layer" or "rms": pre-norm
+    causal: bool = False                  # causal self-attention (MultiHeadAttention.causal)
+    rope_theta: Optional[float] = None    # rotary position embedding of q and k (MultiHeadAttention.rope_theta)
 
     def setup(self):
-        self.attn = MultiHeadAttention(self.query_dim, self.heads, self.dim_head, dtype=self.dtype, name="attn")
+        self.attn = MultiHeadAttention(self.query_dim, self.heads, self.dim_head, dtype=self.dtype,
+                                       causal=self.causal, rope_theta=self.rope_theta, name="attn")
         self.ff = FeedForward(self.ff_dim, dtype=self.dtype, fp8=self.fp8, name="ff")
         if self.norm is not None:
             if self.norm not in ("layer", "rms"):

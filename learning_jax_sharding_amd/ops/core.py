@@ -37,7 +37,7 @@ __all__ = [
     "binary", "unary", "convert", "reshape", "transpose", "reduce_sum", "reduce_mean", "reduce_max",
     "getitem", "dot_general", "dot", "matmul", "einsum", "softmax", "dot_product_attention", "dense",
     "with_sharding_constraint", "asarray_like", "broadcast_to", "where", "concatenate", "mse_loss",
-    "layer_norm", "softmax_cross_entropy", "embed",
+    "layer_norm", "softmax_cross_entropy", "embed", "rope",
 ]
 
 
@@ -762,6 +762,44 @@ def embed(table: ShardedArray, ids: ShardedArray, dtype=None) -> ShardedArray:
     tile = jt.project(list(range(n)) + [n + 1])
     sh = sharding_from_tile(tile, like=[ids.sharding, table.sharding])
     return ShardedArray(tuple(ids.shape) + (table.shape[1],), out_dtype, sh, loc)
+
+
+# ----------------------------------------------------------------------------- rotary embedding
+def rope(q: ShardedArray, k: Optional[ShardedArray] = None, theta: float = 10000.0, dtype=None):
+    """Rotary position embedding of ``(batch, length, heads, head_dim)`` arrays, half-split pairs (the
+    convention of :mod:`.kernels`): with ``h = head_dim / 2``, element ``i < h`` of the head vector at
+    global position ``p`` becomes ``x[i] cos(a) - x[i + h] sin(a)`` and element ``i + h`` becomes ``x[i + h]
+    cos(a) + x[i] sin(a)``, ``a = p theta^(-2 i / head_dim)``.  Returns ``q'``, or ``(q', k')`` with ``k``; q and
+    k that share a layout are rotated by one kernel launch per device (:func:`.kernels.rope`).
+
+    ``head_dim`` has to be whole on every device (an array laid out otherwise is resharded first);
+    batch, length and heads keep their sharding and there is no collective: every shard is rotated
+    by the positions of its own length region."""
+    arrs = [q] if k is None else [q, k]
+    for name, x in zip(("q", "k"), arrs):
+        if not isinstance(x, ShardedArray) or x.ndim != 4:
+            raise ValueError(f"rope: {name} must be a (batch, length, heads, head_dim) ShardedArray")
+        if x.shape[3] % 2:
+            raise ValueError(f"rope: head_dim must be even, got {x.shape[3]}")
+    arrs = [reshard_tile(x, x.tile.unshard([3]), note="rope.head_dim") if x.tile.tile_shape[3] > 1 else x
+            for x in arrs]
+    out_dtype = _dt.canonicalize(dtype)
+    joint = len(arrs) == 2 and arrs[0].tile == arrs[1].tile and tuple(arrs[0].shape) == tuple(arrs[1].shape) \
+        and arrs[0].dtype == arrs[1].dtype
+    _plan.record("rope", tiles=arrs[0].tile.tile_shape, tensors=len(arrs), joint=joint)
+
+    def offset(x, d):
+        return x.tile.region(d, x.shape)[1][0]
+
+    if joint:
+        q2, k2 = arrs
+        pairs = {d: K.rope(t, k2.local[d], offset(q2, d), float(theta), out_dtype) for d, t in q2.local.items()}
+        locs = [{d: p[0] for d, p in pairs.items()}, {d: p[1] for d, p in pairs.items()}]
+    else:
+        locs = [{d: K.rope(t, None, offset(x, d), float(theta), out_dtype)[0] for d, t in x.local.items()}
+                for x in arrs]
+    outs = [ShardedArray(x.shape, out_dtype or x.dtype, x.sharding, loc) for x, loc in zip(arrs, locs)]
+    return outs[0] if k is None else (outs[0], outs[1])
 
 
 # ----------------------------------------------------------------------------- softmax / attention

@@ -19,7 +19,7 @@ import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
-           "embed_grad"]
+           "embed_grad", "rope"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -109,6 +109,9 @@ _SIGS = {
     "ljs_embed_chunk": [],
     "ljs_embed_allpairs_max_tokens": [],
     "ljs_embed_work_cap": [c_long],
+    "ljs_rope": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP,
+                 c_void_p, c_void_p, c_long, c_long, c_int, c_void_p],
+    "ljs_rope_set_max_blocks": [c_int],
     "ljs_launch_count": [],
     "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
     "ljs_attn_set": [c_int, c_int],
@@ -160,7 +163,7 @@ def last_launch() -> dict:
     """The host-side record of the last GEMM / attention kernel the library launched:
 
     ``name`` (the kernel instance, e.g. ``gemm_lean<256,192,4,2,2>``, ``gemm_dma<128,128,2,2,4,kc,kc,bf16>``,
-    ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``),
+    ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``, ``rope<bf16,bf16>`` / ``rope<bf16,bf16,inv>``),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
     it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
@@ -1483,6 +1486,98 @@ def embed(table: torch.Tensor, ids: torch.Tensor, vocab_offset: int = 0, out_dty
     return _Embed.apply(table, ids, int(vocab_offset), out_dtype, bool(fused_bwd))
 
 
+# ============================================================================ rotary embedding
+_ROPE_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def set_rope_max_blocks(n: Optional[int]) -> None:
+    """Cap the rope kernel's grid at ``n`` blocks (tests: the grid-stride loop on small shapes);
+    None or <= 0 = the default, a fixed number of blocks per compute unit."""
+    lib().ljs_rope_set_max_blocks(-1 if n is None else int(n))
+
+
+def rope_supported(t: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> bool:
+    """Whether csrc/kernels/rope.hip takes ``t`` as it is: f32 / bf16 ``(B, S, H, D)``, D a multiple of
+    16 in 16..256 and contiguous, the base and the three outer strides 16-byte aligned."""
+    if t.dim() != 4 or t.dtype not in _ROPE_DTYPES or (out_dtype or t.dtype) not in _ROPE_DTYPES or not t.numel():
+        return False
+    D, es = t.shape[-1], t.element_size()
+    return (D % 16 == 0 and 16 <= D <= 256 and t.stride(-1) == 1 and t.data_ptr() % 16 == 0
+            and all((t.stride(i) * es) % 16 == 0 for i in range(3)))
+
+
+def rope_raw(q, k, q_out, k_out, cos, sin, pos_offset: int, inverse: bool = False) -> int:
+    """One ``ljs_rope`` launch on the tensors as they are; returns the launcher's code (non-zero:
+    rejected, nothing launched) instead of raising."""
+    B, S, H, D = q.shape
+    return lib().ljs_rope(_p(q), _p(k), _p(q_out), _p(k_out), int(q.dtype == torch.bfloat16),
+                          int(q_out.dtype == torch.bfloat16), B, S, H, D, _longs(_strides3(q)),
+                          _longs(_strides3(k)) if k is not None else None, _longs(_strides3(q_out)),
+                          _longs(_strides3(k_out)) if k_out is not None else None, _p(cos), _p(sin),
+                          cos.shape[0], int(pos_offset), int(bool(inverse)), _stream(q))
+
+
+def _rope_launch(q, k, pos_offset: int, theta: float, out_dtype: torch.dtype, inverse: bool):
+    """(q', k') of one launch; the outputs are fresh tensors stored like the inputs' (batch, seq)."""
+    from .kernels import rope_table
+    B, S, H, D = q.shape
+    cos, sin = rope_table(q.device, D, theta, pos_offset + S)
+    qo = _bs_like(q.shape, q, out_dtype)
+    ko = _bs_like(k.shape, k, out_dtype) if k is not None else None
+    _ck(rope_raw(q, k, qo, ko, cos, sin, pos_offset, inverse), "rope")
+    return qo, ko
+
+
+class _Rope(torch.autograd.Function):
+    """Rotary embedding of q and k (k may be None) in one HIP launch; the backward is the same
+    kernel with the inverse flag on (dq', dk').
+
+    The rotation is out of place even where q and k are column blocks of the fused QKV projection
+    buffer: they are two of the several output views of the dense Function, and autograd forbids
+    modifying one of a Function's multiple output views in place."""
+
+    @staticmethod
+    def forward(ctx, q, k, pos_offset, theta, out_dtype):
+        ctx.meta = (pos_offset, theta, q.dtype, tuple(q.shape))
+        qo, ko = _rope_launch(q.detach(), None if k is None else k.detach(), pos_offset, theta, out_dtype, False)
+        return qo, ko
+
+    @staticmethod
+    def backward(ctx, gq, gk):
+        pos_offset, theta, in_dtype, shape = ctx.meta
+        want_q, want_k = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and gk is not None
+
+        def ready(g):
+            # the kernel's cotangent: f32 / bf16 with D contiguous and aligned strides
+            g = g.detach()
+            if g.dtype not in _ROPE_DTYPES:
+                g = g.float()
+            return g if rope_supported(g) else g.contiguous().clone()
+
+        gs = [ready(g) for g, w in ((gq, want_q), (gk, want_k)) if w and g is not None]
+        if not gs:
+            return None, None, None, None, None
+        if len(gs) == 2 and gs[0].dtype != gs[1].dtype:
+            gs = [g.float() for g in gs]
+        outs = list(_rope_launch(gs[0], gs[1] if len(gs) == 2 else None, pos_offset, theta, in_dtype, True))
+        dq = outs.pop(0) if want_q and gq is not None else None
+        dk = outs.pop(0) if want_k else None
+        return dq, dk, None, None, None
+
+
+def rope(q: torch.Tensor, k: Optional[torch.Tensor] = None, pos_offset: int = 0, theta: float = 10000.0,
+         out_dtype: Optional[torch.dtype] = None):
+    """Rotary embedding (half-split pairs, see :mod:`.kernels`) of ``(B, S, H, D)`` shards whose first
+    position is ``pos_offset``: ``(q', k')`` in ``out_dtype`` (default: the inputs'), ``k'`` None without k."""
+    out_dtype = out_dtype or q.dtype
+    ts = [q] + ([k] if k is not None else [])
+    if any(t.shape != q.shape or t.dtype != q.dtype or not rope_supported(t, out_dtype) for t in ts):
+        raise NotImplementedError(f"rope kernel: f32 / bf16 (B, S, H, D) with D a multiple of 16 in 16..256, D "
+                                  f"contiguous, 16-byte aligned base and strides; got {q.dtype} {tuple(q.shape)} "
+                                  f"strides {q.stride()} -> {out_dtype}")
+    return _Rope.apply(q, k, int(pos_offset), float(theta), out_dtype)
+
+
 # ============================================================================ dense / linear
 def linear(x: torch.Tensor, ws: List[torch.Tensor], b: Optional[torch.Tensor], compute_dtype: torch.dtype,
            relu: bool, out_dtype: torch.dtype, residual: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
@@ -1851,14 +1946,14 @@ def _strides3(t: torch.Tensor):
     return [t.stride(0), t.stride(1), t.stride(2)]
 
 
-def _bs_like(shape, ref: torch.Tensor) -> torch.Tensor:
-    """Empty bf16 (B, S, H, D) stored like ``ref``'s (batch, seq) dims: seq-major when ref is
-    (the kernels take any batch / seq strides; the result then gathers / scatters over the
+def _bs_like(shape, ref: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Empty bf16 (or ``dtype``) (B, S, H, D) stored like ``ref``'s (batch, seq) dims: seq-major when
+    ref is (the kernels take any batch / seq strides; the result then gathers / scatters over the
     sequence as contiguous blocks)."""
     B, S, H, D = shape
     if B > 1 and S > 1 and ref.stride(1) > ref.stride(0):
-        return torch.empty((S, B, H, D), dtype=torch.bfloat16, device=ref.device).permute(1, 0, 2, 3)
-    return torch.empty(shape, dtype=torch.bfloat16, device=ref.device)
+        return torch.empty((S, B, H, D), dtype=dtype, device=ref.device).permute(1, 0, 2, 3)
+    return torch.empty(shape, dtype=dtype, device=ref.device)
 
 
 # ---------------------------------------------------------------------------- the launcher's plan

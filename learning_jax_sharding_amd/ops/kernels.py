@@ -201,6 +201,130 @@ def embed(table: torch.Tensor, ids: torch.Tensor, vocab_offset: int = 0,
     return embed_reference(table, ids, vocab_offset, out_dtype)
 
 
+# ----------------------------------------------------------------------------- rotary embedding
+# Convention (pinned by tests/test_rope.py): half-split pairs, as in MaxText and Llama-HF.  For a head
+# vector x[0:D] at global position p, with h = D / 2 and i in [0, h):
+#
+#     ang      = p * theta^(-2 i / D)
+#     y[i]     = x[i]     cos(ang) - x[i + h] sin(ang)
+#     y[i + h] = x[i + h] cos(ang) + x[i]     sin(ang)
+#
+# and the backward is the same map with -ang.  cos / sin come from a table: the angle and its cos /
+# sin in float64 on the host, rounded once to f32, [P][h] each.  (Evaluated in f32, p * inv_freq
+# alone would be off by about p * 2^-24 radians.)
+_ROPE_MIN_ROWS = 1024
+
+
+def rope_table_host(rows: int, D: int, theta: float, start: int = 0, dtype: torch.dtype = torch.float32):
+    """(cos, sin) of positions ``start .. start + rows``, ``[rows, D / 2]`` each: the angle ``p *
+    theta^(-2 i / D)`` and its cos / sin in float64, rounded once to ``dtype`` (float64: the oracle's
+    table).  Pure host arithmetic."""
+    if D < 2 or D % 2:
+        raise ValueError(f"rope: head_dim must be even, got {D}")
+    import numpy as np
+    inv_freq = np.power(np.float64(theta), -2.0 * np.arange(D // 2, dtype=np.float64) / D)
+    ang = np.arange(start, start + rows, dtype=np.float64)[:, None] * inv_freq[None, :]
+    return torch.from_numpy(np.cos(ang)).to(dtype), torch.from_numpy(np.sin(ang)).to(dtype)
+
+
+class RopeTableCache:
+    """The f32 tables per (device, D, theta).  A table grows by doubling; a superseded table stays
+    alive, because a captured graph holds its address.  A table is created only outside a graph
+    capture (``jit``'s warm-up call does that): a capture that needs more rows than exist raises."""
+
+    def __init__(self):
+        self.live = {}         # key -> (cos, sin)
+        self.superseded = []   # every table a longer one replaced
+
+    @staticmethod
+    def _key(device: torch.device, D: int, theta: float):
+        return (device.type, device.index, int(D), float(theta))
+
+    def get(self, device: torch.device, D: int, theta: float, rows: int):
+        """(cos, sin) on ``device`` with at least ``rows`` rows."""
+        key = self._key(device, D, theta)
+        cur = self.live.get(key)
+        if cur is not None and cur[0].shape[0] >= rows:
+            return cur
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(
+                f"rope: the cos/sin table for head_dim {D}, theta {theta} on {device} has "
+                f"{0 if cur is None else cur[0].shape[0]} rows and {rows} are needed, and a table cannot be "
+                "created during a graph capture: run the function once outside the capture first")
+        n = _ROPE_MIN_ROWS if cur is None else 2 * cur[0].shape[0]
+        while n < rows:
+            n *= 2
+        cos, sin = rope_table_host(n, D, theta)
+        new = (cos.to(device), sin.to(device))
+        if cur is not None:
+            self.superseded.append(cur)
+        self.live[key] = new
+        return new
+
+
+_ROPE_TABLES = RopeTableCache()
+
+
+def rope_table(device: torch.device, D: int, theta: float, rows: int):
+    return _ROPE_TABLES.get(device, D, theta, rows)
+
+
+def fused_rope_enabled() -> bool:
+    # LJS_FUSED_ROPE=0: the rotary embedding on GPU shards as the torch formulation below instead of
+    # the fused HIP kernel of csrc/kernels/rope.hip (A/B timing; escape hatch)
+    return os.environ.get("LJS_FUSED_ROPE", "1") != "0"
+
+
+def _rope_one(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    h = x.shape[-1] // 2
+    xf = x.float()
+    a, b = xf[..., :h], xf[..., h:]
+    return torch.cat([a * cos - b * sin, b * cos + a * sin], dim=-1).to(out_dtype)
+
+
+def rope_reference(q: torch.Tensor, k: Optional[torch.Tensor] = None, pos_offset: int = 0, theta: float = 10000.0,
+                   out_dtype: Optional[torch.dtype] = None):
+    """Plain torch rotary embedding of ``(B, S, H, D)`` shards whose first position is ``pos_offset``,
+    from the same f32 table as the HIP kernel and in f32 arithmetic: ``(q', k')`` (``k'`` None without
+    ``k``).  The backward is torch's: the rotation by ``-ang`` of the cotangent."""
+    S, D = q.shape[1], q.shape[-1]
+    cos, sin = rope_table(q.device, D, theta, pos_offset + S)
+    cos = cos[pos_offset:pos_offset + S].view(1, S, 1, D // 2)
+    sin = sin[pos_offset:pos_offset + S].view(1, S, 1, D // 2)
+    qo = _rope_one(q, cos, sin, out_dtype or q.dtype)
+    return qo, (None if k is None else _rope_one(k, cos, sin, out_dtype or k.dtype))
+
+
+_WARNED_ROPE_D = set()
+
+
+def _hip_rope(q: torch.Tensor, k: Optional[torch.Tensor], out_dtype: Optional[torch.dtype]) -> bool:
+    """Whether the fused HIP kernel takes these shards: GPU tensors ``(B, S, H, D)``, f32 or bf16 in
+    and out, D a multiple of 16 in 16..256 contiguous, bases and strides 16-byte aligned.  Anything
+    else on a GPU runs the torch formulation there, with a one-time warning per D."""
+    if not use_hip(q) or not fused_rope_enabled():
+        return False
+    ts = [q] + ([k] if k is not None else [])
+    D = q.shape[-1]
+    ok = all(t.shape == q.shape and t.dtype == q.dtype and _hip().rope_supported(t, out_dtype) for t in ts)
+    if not ok and D not in _WARNED_ROPE_D:
+        _WARNED_ROPE_D.add(D)
+        import warnings
+        warnings.warn(f"HIP rope kernel takes f32 / bf16 (B, S, H, D) shards with D a multiple of 16 in 16..256 and "
+                      f"16-byte aligned bases and strides; {q.dtype} {tuple(q.shape)} strides {q.stride()} runs the "
+                      "torch formulation on the GPU")
+    return ok
+
+
+def rope(q: torch.Tensor, k: Optional[torch.Tensor] = None, pos_offset: int = 0, theta: float = 10000.0,
+         out_dtype: Optional[torch.dtype] = None):
+    """Rotary embedding of one device's ``(B, S, H, D)`` shards of q and (optionally) k, whose first
+    position is ``pos_offset``: ``(q', k')``, one HIP launch for both on a GPU."""
+    if _hip_rope(q, k, out_dtype):
+        return _hip().rope(q, k, pos_offset, theta, out_dtype)
+    return rope_reference(q, k, pos_offset, theta, out_dtype)
+
+
 # ----------------------------------------------------------------------------- matmuls
 def _to_bmk(a: torch.Tensor, batch, free, contract):
     perm = list(batch) + list(free) + list(contract)
