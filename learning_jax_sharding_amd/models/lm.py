@@ -27,7 +27,7 @@ from ..nn.layers import Dense, Embed, LayerNorm, RMSNorm
 from ..nn.module import Module
 from ..nn.partitioning import with_logical_constraint, with_logical_partitioning
 from ..ops import core
-from .transformer import TransformerLayer
+from .transformer import TransformerLayer, check_ff_kind
 
 __all__ = ["TransformerLM", "lm_loss"]
 
@@ -48,13 +48,25 @@ class TransformerLM(Module):
     layers: int
     heads: int = 8
     dim_head: int = 64
-    ff_dim: Optional[int] = None   # None: 4 * dim
+    ff_dim: Optional[int] = None   # None: 4 * dim ("relu"); the multiple of 128 at or above 8 * dim / 3 ("swiglu")
     max_len: Optional[int] = None  # a learned position table of this many rows; None: no positions
     norm: str = "rms"
     dtype: Any = torch.bfloat16
     fp8: bool = False
     causal: bool = False                  # causal self-attention in every layer
     rope_theta: Optional[float] = None    # rotary position embedding with this base in every layer
+    ff: str = "relu"                      # "relu": FeedForward; "swiglu": GatedFeedForward (no fp8)
+
+    def default_ff_dim(self) -> int:
+        """``ff_dim=None``: 4 dim for the ReLU feed-forward; for the gated one, whose three matrices then
+        hold what the ReLU block's two do, the smallest multiple of 128 (the GEMM tiles) >= 8 dim / 3."""
+        if self.ff == "swiglu":
+            return -(-8 * self.dim // (3 * 128)) * 128
+        return 4 * self.dim
+
+    def __post_init__(self):
+        super().__post_init__()
+        check_ff_kind("TransformerLM", self.ff, self.fp8)
 
     def setup(self):
         if self.norm not in ("layer", "rms"):
@@ -64,10 +76,10 @@ class TransformerLM(Module):
         self.embed = Embed(self.vocab_size, self.dim, dtype=self.dtype, name="embed")
         if self.max_len is not None:
             self.pos_embed = Embed(self.max_len, self.dim, dtype=self.dtype, name="pos_embed")
-        ff = self.ff_dim if self.ff_dim is not None else 4 * self.dim
+        ff = self.ff_dim if self.ff_dim is not None else self.default_ff_dim()
         self.blocks = [TransformerLayer(self.dim, heads=self.heads, dim_head=self.dim_head, ff_dim=ff,
                                         dtype=self.dtype, fp8=self.fp8, norm=self.norm, causal=self.causal,
-                                        rope_theta=self.rope_theta, name=f"layer_{i}")
+                                        rope_theta=self.rope_theta, ff=self.ff, name=f"layer_{i}")
                        for i in range(self.layers)]
         cls = LayerNorm if self.norm == "layer" else RMSNorm
         self.final_norm = cls(dtype=self.dtype, name="final_norm")

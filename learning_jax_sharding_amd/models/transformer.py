@@ -13,12 +13,21 @@ from typing import Any, Optional
 
 import torch
 
-from ..nn.layers import FeedForward, LayerNorm, RMSNorm
+from ..nn.layers import FeedForward, GatedFeedForward, LayerNorm, RMSNorm
 from ..nn.module import Module
 from ..ops import core
 from .attention import MultiHeadAttention, attention_block_flops
 
 __all__ = ["TransformerLayer", "transformer_layer_flops"]
+
+
+def check_ff_kind(owner: str, kind, fp8: bool) -> None:
+    """The ``ff`` option of TransformerLayer / TransformerLM: "relu" or "swiglu", the latter without fp8."""
+    if kind not in ("relu", "swiglu"):
+        raise ValueError(f"{owner} ff must be 'relu' or 'swiglu', got {kind!r}")
+    if kind == "swiglu" and fp8:
+        raise ValueError(f"{owner}: ff='swiglu' has no fp8 path (GatedFeedForward is bf16 / f32 only); use "
+                         "fp8=False or ff='relu'")
 
 
 class TransformerLayer(Module):
@@ -31,11 +40,25 @@ class TransformerLayer(Module):
     norm: Optional[str] = None   # None (no normalisation), "layer" or "rms": pre-norm
     causal: bool = False                  # causal self-attention (MultiHeadAttention.causal)
     rope_theta: Optional[float] = None    # rotary position embedding of q and k (MultiHeadAttention.rope_theta)
+    ff: str = "relu"                      # "relu": FeedForward; "swiglu": GatedFeedForward (no fp8)
+
+    def __post_init__(self):
+        super().__post_init__()
+        check_ff_kind("TransformerLayer", self.ff, self.fp8)
 
     def setup(self):
         self.attn = MultiHeadAttention(self.query_dim, self.heads, self.dim_head, dtype=self.dtype,
                                        causal=self.causal, rope_theta=self.rope_theta, name="attn")
-        self.ff = FeedForward(self.ff_dim, dtype=self.dtype, fp8=self.fp8, name="ff")
+        # the field `ff` names the kind; on the bound module the submodule takes its place (callers
+        # reach the block as `layer.ff`, and its parameters sit under "ff" either way).  The kind is
+        # kept aside so that a copy of a module that is already set up builds its block again
+        kind = self.__dict__.get("_ff_kind") or self.ff
+        object.__setattr__(self, "_ff_kind", kind)
+        check_ff_kind("TransformerLayer", kind, self.fp8)
+        if kind == "relu":
+            self.ff = FeedForward(self.ff_dim, dtype=self.dtype, fp8=self.fp8, name="ff")
+        else:
+            self.ff = GatedFeedForward(self.ff_dim, dtype=self.dtype, name="ff")
         if self.norm is not None:
             if self.norm not in ("layer", "rms"):
                 raise ValueError(f"TransformerLayer norm must be None, 'layer' or 'rms', got {self.norm!r}")
@@ -57,9 +80,10 @@ class TransformerLayer(Module):
         return self.ff(h, residual=h)
 
 
-def transformer_layer_flops(batch, seq, dim, heads, dim_head, ff_dim, train: bool) -> float:
+def transformer_layer_flops(batch, seq, dim, heads, dim_head, ff_dim, train: bool, gated: bool = False) -> float:
     """Matmul FLOPs of one layer step (the project's convention: the memory-bound norms of a
-    pre-norm layer are not counted)."""
+    pre-norm layer and the activation are not counted).  ``gated``: a GatedFeedForward, three GEMMs
+    (gate, up, down) where the ReLU FeedForward has two."""
     att = attention_block_flops(batch, seq, dim, heads, dim_head, train)
-    ff = 2 * 2 * batch * seq * dim * ff_dim
+    ff = (3 if gated else 2) * 2 * batch * seq * dim * ff_dim
     return att + (3 * ff if train else ff)

@@ -18,8 +18,8 @@ from . import initializers as init
 from .module import Module, compact
 from .partitioning import with_logical_constraint, with_logical_partitioning
 
-__all__ = ["Dense", "DenseGeneral", "Dropout", "FeedForward", "relu", "gelu", "softmax", "Embed", "LayerNorm",
-           "RMSNorm"]
+__all__ = ["Dense", "DenseGeneral", "Dropout", "FeedForward", "GatedFeedForward", "relu", "gelu", "softmax", "swiglu",
+           "Embed", "LayerNorm", "RMSNorm"]
 
 
 def relu(x):
@@ -32,6 +32,11 @@ def gelu(x):
 
 def softmax(x, axis: int = -1):
     return core.softmax(x, axis)
+
+
+def swiglu(gate, up, dtype=None):
+    """``silu(gate) * up`` (:func:`..ops.core.swiglu`: one fused HIP kernel per shard on GPU)."""
+    return core.swiglu(gate, up, dtype)
 
 
 class Dense(Module):
@@ -174,6 +179,36 @@ class FeedForward(Module):
         if loc is None:
             return False
         return (loc.numel() // max(1, x.shape[-1]) * len(groups[0])) % 128 == 0
+
+
+class GatedFeedForward(Module):
+    """``y = (silu(x Wgate) * (x Wup)) Wout``, the gated (SwiGLU) feed-forward of Llama-shaped models.
+
+    The gate and up projections are one GEMM writing one ``[tokens][2 hidden]`` buffer
+    (:func:`..ops.core.dense` with two kernels), the activation is one fused kernel forward and one
+    backward (:func:`..ops.core.swiglu`), and the down projection takes ``residual`` in its epilogue.
+    Logical axes ``Wgate, Wup: ('embed','hidden')``, ``Wout: ('hidden','embed')``: the rule
+    ``('hidden','model')`` shards the hidden dim Megatron-style through the partitioner's dense path.
+    bf16 or f32 compute only; there is no fp8 variant.
+    """
+
+    hidden_dim: int
+    dtype: Any = torch.bfloat16
+
+    @compact
+    def __call__(self, x: ShardedArray, residual: Optional[ShardedArray] = None) -> ShardedArray:
+        d = x.shape[-1]
+        w_gate = self.param("w_gate", with_logical_partitioning(init.lecun_normal(), ("embed", "hidden")),
+                            (d, self.hidden_dim), torch.float32)
+        w_up = self.param("w_up", with_logical_partitioning(init.lecun_normal(), ("embed", "hidden")),
+                          (d, self.hidden_dim), torch.float32)
+        w_out = self.param("w_out", with_logical_partitioning(init.lecun_normal(), ("hidden", "embed")),
+                           (self.hidden_dim, d), torch.float32)
+        dt = _dt.canonicalize(self.dtype)
+        g, u = core.dense(x, [w_gate, w_up], None, compute_dtype=dt)
+        h = core.swiglu(g, u)
+        h = with_logical_constraint(h, ("batch", "length", "hidden"))
+        return core.dense(h, [w_out], None, compute_dtype=dt, residual=residual)[0]
 
 
 class Embed(Module):

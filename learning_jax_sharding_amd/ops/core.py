@@ -37,7 +37,7 @@ __all__ = [
     "binary", "unary", "convert", "reshape", "transpose", "reduce_sum", "reduce_mean", "reduce_max",
     "getitem", "dot_general", "dot", "matmul", "einsum", "softmax", "dot_product_attention", "dense",
     "with_sharding_constraint", "asarray_like", "broadcast_to", "where", "concatenate", "mse_loss",
-    "layer_norm", "softmax_cross_entropy", "embed", "rope",
+    "layer_norm", "softmax_cross_entropy", "embed", "rope", "swiglu",
 ]
 
 
@@ -800,6 +800,24 @@ def rope(q: ShardedArray, k: Optional[ShardedArray] = None, theta: float = 10000
                 for x in arrs]
     outs = [ShardedArray(x.shape, out_dtype or x.dtype, x.sharding, loc) for x, loc in zip(arrs, locs)]
     return outs[0] if k is None else (outs[0], outs[1])
+
+
+# ----------------------------------------------------------------------------- SwiGLU
+def swiglu(gate: ShardedArray, up: ShardedArray, dtype=None) -> ShardedArray:
+    """``silu(gate) * up``, the activation of a gated feed-forward, one fused kernel per shard forward
+    and one backward (:func:`.kernels.swiglu`).  Elementwise: the output keeps ``gate``'s sharding
+    whatever dims it shards, the feature dim included, and there is no collective; ``up`` is resharded
+    onto ``gate``'s tile if it is laid out otherwise."""
+    if not isinstance(gate, ShardedArray) or not isinstance(up, ShardedArray):
+        raise TypeError("swiglu: gate and up must be ShardedArrays")
+    if tuple(gate.shape) != tuple(up.shape):
+        raise ValueError(f"swiglu: gate shape {tuple(gate.shape)} != up shape {tuple(up.shape)}")
+    if up.tile != gate.tile:
+        up = reshard_tile(up, gate.tile, note="swiglu.up")
+    out_dtype = _dt.canonicalize(dtype) or gate.dtype
+    _plan.record("swiglu", tiles=gate.tile.tile_shape)
+    loc = {d: K.swiglu(t, up.local[d], out_dtype) for d, t in gate.local.items()}
+    return ShardedArray(gate.shape, out_dtype, gate.sharding, loc)
 
 
 # ----------------------------------------------------------------------------- softmax / attention

@@ -19,7 +19,7 @@ import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
-           "embed_grad", "rope"]
+           "embed_grad", "rope", "swiglu"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -112,6 +112,10 @@ _SIGS = {
     "ljs_rope": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP,
                  c_void_p, c_void_p, c_long, c_long, c_int, c_void_p],
     "ljs_rope_set_max_blocks": [c_int],
+    "ljs_swiglu": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP, _LP, c_void_p],
+    "ljs_swiglu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP,
+                       _LP, _LP, _LP, c_void_p],
+    "ljs_swiglu_set_max_blocks": [c_int],
     "ljs_launch_count": [],
     "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
     "ljs_attn_set": [c_int, c_int],
@@ -1576,6 +1580,132 @@ def rope(q: torch.Tensor, k: Optional[torch.Tensor] = None, pos_offset: int = 0,
                                   f"contiguous, 16-byte aligned base and strides; got {q.dtype} {tuple(q.shape)} "
                                   f"strides {q.stride()} -> {out_dtype}")
     return _Rope.apply(q, k, int(pos_offset), float(theta), out_dtype)
+
+
+# ============================================================================ SwiGLU
+_SWIGLU_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def set_swiglu_max_blocks(n: Optional[int]) -> None:
+    """Cap the swiglu kernels' grid at ``n`` blocks (tests: the grid-stride loop on small shapes);
+    None or <= 0 = the default, a fixed number of blocks per compute unit."""
+    lib().ljs_swiglu_set_max_blocks(-1 if n is None else int(n))
+
+
+def _bsf(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """``t`` as a (B, S, F) view (the kernels' shape), or None where its leading dims do not
+    collapse without a copy."""
+    if t.dim() == 3:
+        return t
+    if t.dim() < 3:
+        return t.reshape((1,) * (3 - t.dim()) + tuple(t.shape)) if t.dim() else None
+    try:
+        return t.view(-1, t.shape[-2], t.shape[-1])
+    except RuntimeError:
+        return None
+
+
+def _swiglu_operand(t: torch.Tensor) -> bool:
+    if t.dim() < 1 or t.dtype not in _SWIGLU_DTYPES or not t.numel():
+        return False
+    F, es = t.shape[-1], t.element_size()
+    if F < 8 or F % 8 or t.stride(-1) != 1 or t.data_ptr() % 16:
+        return False
+    t3 = _bsf(t)
+    return t3 is not None and all((t3.stride(i) * es) % 16 == 0 for i in range(2))
+
+
+def swiglu_supported(g: torch.Tensor, u: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> bool:
+    """Whether csrc/kernels/swiglu.hip takes ``g`` and ``u`` as they are: f32 / bf16 of one shape and
+    dtype, the last dim a multiple of 8 and contiguous, bases and outer strides 16-byte aligned."""
+    return (g.shape == u.shape and g.dtype == u.dtype and (out_dtype or g.dtype) in _SWIGLU_DTYPES
+            and _swiglu_operand(g) and _swiglu_operand(u))
+
+
+def _strides2(t: torch.Tensor):
+    return [t.stride(0), t.stride(1)]
+
+
+def _swiglu_raw_ok(g, u, *rest) -> bool:
+    # what the C entry cannot see: one (B, S, F) shape for all, F contiguous, one dtype for g and u
+    return (g.dim() == 3 and u.dtype == g.dtype and all(
+        t.shape == g.shape and t.stride(-1) == 1 and t.dtype in _SWIGLU_DTYPES for t in (g, u) + rest))
+
+
+def swiglu_raw(g, u, h) -> int:
+    """One ``ljs_swiglu`` launch on (B, S, F) tensors as they are; returns the launcher's code
+    (non-zero: rejected, nothing launched) instead of raising."""
+    if not _swiglu_raw_ok(g, u, h):
+        return 1
+    B, S, F = g.shape
+    return lib().ljs_swiglu(_p(g), _p(u), _p(h), int(g.dtype == torch.bfloat16), int(h.dtype == torch.bfloat16),
+                            B, S, F, _longs(_strides2(g)), _longs(_strides2(u)), _longs(_strides2(h)), _stream(g))
+
+
+def swiglu_bwd_raw(g, u, dh, dg, du) -> int:
+    """One ``ljs_swiglu_bwd`` launch on (B, S, F) tensors as they are; the launcher's code."""
+    if not _swiglu_raw_ok(g, u, dh, dg, du) or dg.dtype != g.dtype or du.dtype != g.dtype:
+        return 1
+    B, S, F = g.shape
+    return lib().ljs_swiglu_bwd(_p(g), _p(u), _p(dh), _p(dg), _p(du), int(g.dtype == torch.bfloat16),
+                                int(dh.dtype == torch.bfloat16), B, S, F, _longs(_strides2(g)),
+                                _longs(_strides2(u)), _longs(_strides2(dh)), _longs(_strides2(dg)),
+                                _longs(_strides2(du)), _stream(g))
+
+
+def _bsf_like(ref: torch.Tensor, F: int, dtype: torch.dtype) -> torch.Tensor:
+    """Empty (B, S, F) stored like ``ref``'s (batch, position) dims: seq-major when ref is."""
+    B, S = ref.shape[0], ref.shape[1]
+    if B > 1 and S > 1 and ref.stride(1) > ref.stride(0):
+        return torch.empty((S, B, F), dtype=dtype, device=ref.device).permute(1, 0, 2)
+    return torch.empty((B, S, F), dtype=dtype, device=ref.device)
+
+
+class _Swiglu(torch.autograd.Function):
+    """``silu(g) * u`` in one HIP launch; the backward is one launch that recomputes the sigmoid from
+    g and writes (dg, du).  Where g and u are the two adjacent column blocks of one [T][2F] buffer
+    (the fused gate / up projection's output), dg and du are the same column blocks of one fresh
+    buffer: the adjacency the projection's backward looks for (ops/linear.py _wgrads)."""
+
+    @staticmethod
+    def forward(ctx, g, u, out_dtype):
+        g3, u3 = _bsf(g.detach()), _bsf(u.detach())
+        h = _bsf_like(g3, g3.shape[-1], out_dtype)
+        _ck(swiglu_raw(g3, u3, h), "swiglu")
+        ctx.save_for_backward(g3, u3)
+        ctx.shape = tuple(g.shape)
+        return h.reshape(ctx.shape) if g.dim() != 3 else h
+
+    @staticmethod
+    def backward(ctx, dh):
+        g3, u3 = ctx.saved_tensors
+        F, es = g3.shape[-1], g3.element_size()
+        dh = dh.detach()
+        if dh.dtype not in _SWIGLU_DTYPES:
+            dh = dh.float()
+        dh3 = _bsf(dh) if _swiglu_operand(dh) else None
+        if dh3 is None:
+            dh3 = _bsf(dh.contiguous().clone() if dh.is_contiguous() else dh.contiguous())
+        if g3.stride() == u3.stride() and u3.data_ptr() == g3.data_ptr() + F * es:
+            both = _bsf_like(g3, 2 * F, g3.dtype)
+            dg, du = both[..., :F], both[..., F:]
+        else:
+            dg, du = _bsf_like(g3, F, g3.dtype), _bsf_like(g3, F, g3.dtype)
+        _ck(swiglu_bwd_raw(g3, u3, dh3, dg, du), "swiglu_bwd")
+        if len(ctx.shape) != 3:
+            dg, du = dg.reshape(ctx.shape), du.reshape(ctx.shape)
+        return (dg if ctx.needs_input_grad[0] else None), (du if ctx.needs_input_grad[1] else None), None
+
+
+def swiglu(g: torch.Tensor, u: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``silu(g) * u`` of one device's shards in ``out_dtype`` (default: the inputs')."""
+    out_dtype = out_dtype or g.dtype
+    if not swiglu_supported(g, u, out_dtype):
+        raise NotImplementedError(f"swiglu kernels: f32 / bf16 g and u of one shape and dtype, the last dim a "
+                                  f"contiguous multiple of 8, 16-byte aligned bases and strides; got {g.dtype} "
+                                  f"{tuple(g.shape)} strides {g.stride()} / {u.dtype} {tuple(u.shape)} strides "
+                                  f"{u.stride()} -> {out_dtype}")
+    return _Swiglu.apply(g, u, out_dtype)
 
 
 # ============================================================================ dense / linear

@@ -325,6 +325,79 @@ def rope(q: torch.Tensor, k: Optional[torch.Tensor] = None, pos_offset: int = 0,
     return rope_reference(q, k, pos_offset, theta, out_dtype)
 
 
+# ----------------------------------------------------------------------------- SwiGLU
+# h = silu(g) u = g sigma(g) u, the activation of a gated feed-forward.  With e = exp(-|g|) and
+# r = 1 / (1 + e): sigma = r for g >= 0 and e r below, c = 1 - sigma = e r for g >= 0 and r below: one exp
+# of a non-positive argument, and c never formed by subtraction (which loses it once sigma rounds
+# to 1).  The backward recomputes them from g: du = dh sigma g, dg = dh sigma u (1 + g c).
+def fused_swiglu_enabled() -> bool:
+    # LJS_FUSED_SWIGLU=0: the gated feed-forward's activation on GPU shards as the torch formulation
+    # below instead of the fused HIP kernels of csrc/kernels/swiglu.hip (A/B timing; escape hatch)
+    return os.environ.get("LJS_FUSED_SWIGLU", "1") != "0"
+
+
+def _sigmoid_pair(g: torch.Tensor):
+    e = torch.exp(-g.abs())
+    r = 1.0 / (1.0 + e)
+    er = e * r
+    pos = g >= 0
+    return torch.where(pos, r, er), torch.where(pos, er, r)
+
+
+class _SwigluReference(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, u, out_dtype):
+        ctx.save_for_backward(g, u)
+        gf, uf = (t if t.dtype == torch.float64 else t.float() for t in (g, u))
+        sg, _ = _sigmoid_pair(gf)
+        return (gf * sg * uf).to(out_dtype)
+
+    @staticmethod
+    def backward(ctx, dh):
+        g, u = ctx.saved_tensors
+        gf, uf, df = (t if t.dtype == torch.float64 else t.float() for t in (g, u, dh))
+        sg, c = _sigmoid_pair(gf)
+        ds = df * sg
+        dg = ds * uf * (1.0 + gf * c) if ctx.needs_input_grad[0] else None
+        du = ds * gf if ctx.needs_input_grad[1] else None
+        return (None if dg is None else dg.to(g.dtype)), (None if du is None else du.to(u.dtype)), None
+
+
+def swiglu_reference(g: torch.Tensor, u: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Plain torch ``silu(g) * u`` by the stable formulas above: f32 arithmetic (f64 for f64 inputs), one
+    rounding to ``out_dtype`` (default: g's), and an explicit backward by the same formulas (not the
+    autograd of a ``silu * u`` composite)."""
+    return _SwigluReference.apply(g, u, out_dtype or g.dtype)
+
+
+_WARNED_SWIGLU = set()
+
+
+def _hip_swiglu(g: torch.Tensor, u: torch.Tensor, out_dtype: Optional[torch.dtype]) -> bool:
+    """Whether the fused HIP kernels take these shards: GPU tensors of one shape, f32 or bf16 in and
+    out, the last dim a contiguous multiple of 8, bases and strides 16-byte aligned.  Anything else on
+    a GPU runs the torch formulation there, with a one-time warning per feature count."""
+    if not use_hip(g) or not use_hip(u) or not fused_swiglu_enabled():
+        return False
+    ok = _hip().swiglu_supported(g, u, out_dtype)
+    F = g.shape[-1] if g.dim() else 0
+    if not ok and F not in _WARNED_SWIGLU:
+        _WARNED_SWIGLU.add(F)
+        import warnings
+        warnings.warn(f"HIP swiglu kernels take f32 / bf16 shards whose last dim is a contiguous multiple of 8 with "
+                      f"16-byte aligned bases and strides; {g.dtype} {tuple(g.shape)} strides {g.stride()} (u "
+                      f"{u.dtype} strides {u.stride()}) runs the torch formulation on the GPU")
+    return ok
+
+
+def swiglu(g: torch.Tensor, u: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``silu(g) * u`` of one device's shards of the gate and up projections, in ``out_dtype`` (default:
+    g's): one HIP launch forward and one backward on a GPU."""
+    if _hip_swiglu(g, u, out_dtype):
+        return _hip().swiglu(g, u, out_dtype)
+    return swiglu_reference(g, u, out_dtype)
+
+
 # ----------------------------------------------------------------------------- matmuls
 def _to_bmk(a: torch.Tensor, batch, free, contract):
     perm = list(batch) + list(free) + list(contract)
