@@ -1725,6 +1725,9 @@ GemmPlan gemm_plan(const GemmArgs& a, bool a_kc, bool b_kc, bool out_f32, int sp
   if (splitk > nkt) splitk = nkt;
   p.kt_per_split = (nkt + splitk - 1) / splitk;
   p.splitk = (nkt + p.kt_per_split - 1) / p.kt_per_split;
+  // a split's partial is no output: the kernels would drop a bias (it is added when splitk == 1
+  // only) and apply a ReLU to every partial before the atomic add or in every slab
+  if ((p.splitk > 1 || slabs) && (flags & 3)) return p;
   // The LDS-DMA kernels need K % 64 == 0, a split that divides the K-tiles (slab mode: the last
   // split may run past K), operands addressable with 32-bit byte offsets and, for a bf16 output,
   // whole aligned 16-byte chunks of C.

@@ -346,7 +346,8 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int, K: i
          c_off: int = 0, zero_c: bool = False, psum: Optional[torch.Tensor] = None,
          res: Optional[torch.Tensor] = None, res_ld: int = 0, res_mode: str = "add", sR: int = 0,
          slabs: bool = False, b_list: Optional[Sequence[torch.Tensor]] = None) -> int:
-    """Raw launcher.  A/B bf16; C bf16 or f32 (split-K/accumulate need f32 C).
+    """Raw launcher.  A/B bf16; C bf16 or f32 (split-K/accumulate need f32 C; a split-K or slab
+    call with a bias or a ReLU is rejected: they apply to the sum, which no split holds).
 
     ``lda``/``ldb`` may be 0 for an operand that repeats one row (a broadcast gradient).
     ``zero_c`` zeroes C inside the launch sequence (needed before split-K accumulation).
@@ -366,6 +367,9 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int, K: i
     assert not slabs or C.dtype == torch.float32, "split-K slabs are f32"
     out_f32 = C.dtype == torch.float32
     assert res is None or not out_f32, (C.dtype, res.dtype)
+    # a split's partial is no output: the kernels drop the bias and would apply the ReLU per partial
+    assert not ((slabs or min(max(1, splitk), -(-K // 64)) > 1) and (relu or bias is not None)), \
+        "split-K / slab GEMMs take no bias and no ReLU"
     if tile is None:
         tile = pick_tile(M, N, K, batch, a_kc, b_kc, out_f32, splitk, ldc, bias, res, sA, sB, sC, ldb)
     flags = _gemm_flags(relu, None if bias is None else bias.dtype, accumulate, zero_c, slabs,

@@ -1,0 +1,157 @@
+"""The MX-fp8 GEMM kernels of csrc/kernels/fp8.hip against the exact-arithmetic oracle of
+tests/gemm_oracle.py (run on a real MI355X: -m gpu).  The operands are constructed, not quantized:
+payload bytes from integers in [-8, 8] and a scale byte 127 + e with e drawn independently per
+(row, 32-block) from {-1, 0, 1}, so every block scale is known and a mis-indexed scale operand of
+the block-scaled MFMA changes the answer.  Every partial sum is a multiple of 2^-2 far below 2^20:
+f32 outputs must equal the float64 product bit for bit, bf16 outputs its round-to-nearest-even, in
+guarded buffers.  (fp8.hip keeps no launch record: the tile code asked for is the one launched.)"""
+import pytest
+import torch
+
+import gemm_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+dev = torch.device("cuda", 0)
+
+_W4 = [1282, 1283, 2562, 2563]
+_W8 = [256256, 256128, 256160, 128320, 128256, 128128, 128160, 3128128, 3128160, 3128256, 3256128]
+
+
+def _bm_bn(tile):
+    if tile >= 10000:
+        return tile % 1000000 // 1000, tile % 1000
+    return (256 if tile // 10 >= 256 else 128), 128
+
+
+@pytest.fixture(scope="module")
+def F():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from learning_jax_sharding_amd.ops import fp8, hip
+    hip.lib()
+    return fp8
+
+
+def _run(F, c, M, N, K, out_dtype, tile, nsplit=1, **kw):
+    g = O.Guarded((nsplit, M, N), out_dtype, dev)
+    ops = [c[n].to(dev) for n in ("qa", "sa", "qb", "sb")]
+    bias = None if c["bias"] is None else c["bias"].to(dev)
+    res = None if c["res"] is None else c["res"].to(dev)
+    F.gemm_mx(*ops, M, N, K, g.view if nsplit > 1 else g.view[0], bias=bias, res=res, res_mode=c["res_mode"], tile=tile,
+              nsplit=nsplit, **kw)
+    torch.cuda.synchronize()
+    return g
+
+
+@pytest.mark.parametrize("K", [128, 384])
+@pytest.mark.parametrize("mode", ["f32", "bf16_bias_relu"])
+@pytest.mark.parametrize("tile", _W4 + _W8)
+def test_mx_gemm_tile_is_exact(F, tile, mode, K):
+    """Every tile code at one ragged block in each direction, one and three 128-wide K-tiles."""
+    bm, bn = _bm_bn(tile)
+    M, N = bm + 8, bn + 8
+    f32 = mode == "f32"
+    c = O.mx_case(M, N, K, bias=not f32, relu=not f32, out=torch.float32 if f32 else torch.bfloat16, seed=tile % 977 + K)
+    assert O.exactness(c) < 2 ** 20
+    g = _run(F, c, M, N, K, c["expected"].dtype, tile, relu=not f32)
+    O.assert_bits_equal(g.view, c["expected"], bm, bn)
+    g.check()
+
+
+_TWO = [1282, 256160]          # one 4-wave tile and one 8-wave tile
+
+
+@pytest.mark.parametrize("tile", _TWO)
+def test_mx_gemm_split_slabs_sum_exactly(F, tile):
+    bm, bn = _bm_bn(tile)
+    M, N, K = bm + 8, bn + 8, 384                       # 3 K-tiles over 2 splits: 2 + 1
+    c = O.mx_case(M, N, K, nsplit=2, seed=tile % 977)
+    g = _run(F, c, M, N, K, torch.float32, tile, nsplit=2)
+    O.assert_bits_equal(g.view, c["expected"], bm, bn)
+    g.check()
+    whole = O.mx_case(M, N, K, seed=tile % 977)
+    assert torch.equal(g.view.sum(0).cpu(), whole["expected"][0])
+
+
+@pytest.mark.parametrize("which", ["a_bcast", "b_bcast"])
+@pytest.mark.parametrize("tile", _TWO)
+def test_mx_gemm_broadcast_operand_is_exact(F, tile, which):
+    bm, bn = _bm_bn(tile)
+    M, N, K = bm + 8, bn + 8, 384
+    c = O.mx_case(M, N, K, seed=tile % 977 + 1, **{which: True})
+    g = _run(F, c, M, N, K, torch.float32, tile, **{which: True})
+    O.assert_bits_equal(g.view, c["expected"], bm, bn)
+    g.check()
+
+
+@pytest.mark.parametrize("res", [("add", "bf16"), ("mask", "bf16"), ("mask", "e4m3")])
+@pytest.mark.parametrize("tile", _TWO)
+def test_mx_gemm_residual_and_masks_are_exact(F, tile, res):
+    """bf16(bf16(y) + res); keep y where res > 0 and write +0 elsewhere, from a bf16 operand and from
+    e4m3 bytes."""
+    bm, bn = _bm_bn(tile)
+    M, N, K = bm + 8, bn + 8, 128
+    c = O.mx_case(M, N, K, bias=True, out=torch.bfloat16, res=res, seed=tile % 977 + 2)
+    g = _run(F, c, M, N, K, torch.bfloat16, tile)
+    O.assert_bits_equal(g.view, c["expected"], bm, bn)
+    g.check()
+
+
+@pytest.mark.parametrize("tile", _TWO)
+def test_mx_gemm_quantized_copies_are_exact(F, tile):
+    """qout / qtout: the MX copies of the bf16 output, rows and transposed.  The expected output is
+    known exactly, so its quantization (quantize_mx_ref) is fully determined."""
+    bm, bn = _bm_bn(tile)
+    M, N, K = bm + 32, bn + 32, 128
+    c = O.mx_case(M, N, K, bias=True, relu=True, out=torch.bfloat16, seed=tile % 977 + 3)
+    want = c["expected"][0]
+    outs = [torch.full(s, 0xAB, dtype=torch.uint8, device=dev) for s in ((M, N), (M, N // 32), (N, M), (N, M // 32))]
+    g = _run(F, c, M, N, K, torch.bfloat16, tile, relu=True, qout=(outs[0], outs[1]), qtout=(outs[2], outs[3]))
+    O.assert_bits_equal(g.view, c["expected"], bm, bn)
+    g.check()
+    for (q, s), ref, tag in (((outs[0], outs[1]), want, "rows"), ((outs[2], outs[3]), want.t().contiguous(), "transposed")):
+        q_ref, ex = F.quantize_mx_ref(ref)
+        assert (ex > -127).all()                                   # (no all-zero block: its scale byte is not pinned)
+        O.assert_bits_equal(s.cpu()[None], (ex + 127).to(torch.uint8)[None])
+        O.assert_bits_equal(q.cpu()[None], q_ref.view(torch.uint8)[None], bm if tag == "rows" else bn,
+                            bn if tag == "rows" else bm)
+
+
+def test_mx_gemm_fused_column_sums_are_exact(F):
+    """colsum (8-wave tiles): per row tile, the column sums of the bf16 values stored -- operands in
+    [-2, 2], so the sums are exact in any order."""
+    tile = 256160
+    bm, bn = _bm_bn(tile)
+    M, N, K = bm + 8, bn + 8, 128
+    c = O.mx_case(M, N, K, lo=-2, hi=2, out=torch.bfloat16, seed=7)
+    cs = torch.full((-(-M // bm), N), float("nan"), device=dev)
+    g = _run(F, c, M, N, K, torch.bfloat16, tile, colsum=cs)
+    O.assert_bits_equal(g.view, c["expected"], bm, bn)
+    g.check()
+    want = torch.stack([c["expected"][0, r:r + bm].double().sum(0) for r in range(0, M, bm)])
+    assert float(want.abs().max()) * 4 < 2 ** 24
+    O.assert_bits_equal(cs.cpu()[None], want.float()[None])
+
+
+@pytest.mark.parametrize("tile", _TWO)
+def test_mx_gemm_gaussian_inside_derived_bound(F, tile):
+    """N(0, 1) data quantized on the CPU (quantize_mx_ref), against the float64 product of the
+    dequantized operands: |got - oracle| <= (K + 2) 2^-24 sum_k |a_k b_k|, every element."""
+    bm, bn = _bm_bn(tile)
+    M, N, K = bm + 8, bn + 8, 384
+    gen = torch.Generator().manual_seed(tile % 977)
+    c = dict(bias=None, res=None, res_mode="add")
+    deq = []
+    for n, R in (("a", M), ("b", N)):
+        q, ex = F.quantize_mx_ref(torch.randn(R, K, generator=gen))
+        c["q" + n], c["s" + n] = q.view(torch.uint8), (ex + 127).to(torch.uint8)
+        deq.append(F.dequantize_mx_ref(q, ex).double())
+    oracle = deq[0] @ deq[1].t()
+    bound = (K + 2) * 2.0 ** -24 * (deq[0].abs() @ deq[1].abs().t())
+    g = _run(F, c, M, N, K, torch.float32, tile)
+    err = (g.view[0].double().cpu() - oracle).abs()
+    print(f"gemm-figures mx-gauss-{tile:<7d} M,N,K {M},{N},{K} max|err| {err.max().item():.3e} "
+          f"max err/bound {(err / bound).max().item():.3f}")
+    assert (err <= bound).all()
+    g.check()

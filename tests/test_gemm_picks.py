@@ -251,6 +251,21 @@ def test_plan_epilogue_variants_and_grid(planned):
     assert _plan(1282, 1, 1, 0, 128, 4096, 64)["mfast"] == 1                          # fewer tile rows than columns
 
 
+def test_plan_rejects_bias_and_relu_on_split_or_slab_calls(planned):
+    """A split's partial is no output: the kernels add a bias only when splitk == 1 and would apply
+    a ReLU to each partial, so the plan refuses both (after clamping the split count)."""
+    import torch
+    kw = dict(M=136, N=72, K=256, lda=136, ldb=72, ldc=72, a_kc=False, b_kc=False, out_f32=True, tile=1282)
+    assert hip.gemm_plan(**kw, splitk=2)["err"] == 0
+    for bad in (dict(relu=True), dict(bias_dtype=torch.float32), dict(bias_dtype=torch.bfloat16, relu=True)):
+        assert hip.gemm_plan(**kw, splitk=2, **bad)["err"] != 0
+        assert hip.gemm_plan(**kw, splitk=1, **bad)["err"] == 0
+        assert hip.gemm_plan(**kw, splitk=9, **bad)["err"] != 0          # clamped to 4 splits: still split
+        assert hip.gemm_plan(**kw, sC=136 * 72, splitk=2, slabs=True, **bad)["err"] != 0
+        assert hip.gemm_plan(**kw, sC=136 * 72, splitk=1, slabs=True, **bad)["err"] != 0      # one slab is a slab
+    assert hip.gemm_plan(**dict(kw, K=64), splitk=4, relu=True)["err"] == 0     # one K-tile: clamped to no split
+
+
 def test_psum_slots_bounds_the_plans_partials(planned):
     """hip.psum_slots sizes the caller's buffer; the kernel writes the plan's psum count."""
     import itertools
