@@ -7,7 +7,7 @@
 
 #define LJS_API extern "C" __attribute__((visibility("default")))
 
-// ---- host-side launch record (gemm.hip, attention.hip; read back through ljs_launch_count /
+// ---- host-side launch record (gemm.hip, attention.hip, fp8.hip, ...; read back through ljs_launch_count /
 // ljs_launch_get, ops/hip.py last_launch / launch_log).  Every launch site stores which kernel
 // instance it launched, on what grid, and what the launcher resolved the request to, so a test can
 // tell the kernel it asked for from the kernel that ran.  Plain host stores into a ring of the last
@@ -19,7 +19,7 @@ struct LjsLaunchRec {
   unsigned gx, gy, gz, block;
   int req_tile, res_tile;    // GEMMs: the tile code asked for / the one the launcher resolved; else -1
   int splitk, splitk1;       // GEMMs: the launched split count (grouped pair: of each GEMM); else -1
-  int variant;               // LDS-DMA / lean GEMMs: the epilogue instance (RES); else -1
+  int variant;               // LDS-DMA / lean GEMMs: the epilogue instance (RES); 4-wave MX GEMM: FIX; else -1
   int acc_mode;              // attention forward: AttnArgs::acc_mode; else -1
 };
 constexpr int kLjsLaunchRing = 32;

@@ -19,6 +19,7 @@
 // barrier per K-tile.  The MFMA operands are swapped (C^T blocks) so each lane ends with 4
 // consecutive output columns: packed 16-byte row stores after a lane-pair exchange.
 #include "common.h"
+#include <stdio.h>
 
 namespace {
 
@@ -197,25 +198,21 @@ __global__ __launch_bounds__(256) void quant_mx_cols_tiled_kernel(const void* __
   }
 }
 
-// x[K][N] (bf16, or f32 with xb != null: xb[K][N] receives x rounded to bf16) -> BOTH its
-// row-blocked (qr [K][N]) and transposed column-blocked (q [N][K]) MX quantizations in one pass;
-// K % 128, N % 64
-LJS_API int ljs_quant_mx_both(const void* in, long ld, int K, int N, void* q, void* s, void* qr, void* sr, void* xb,
-                              hipStream_t stream) {
-  if (K % 128 || N % 64 || ld % 8 || ((uintptr_t)in & 15) || ((uintptr_t)q & 15) || ((uintptr_t)qr & 15) ||
-      ((uintptr_t)xb & 15))
-    return (int)hipErrorInvalidValue;
-  if (xb)
-    hipLaunchKernelGGL(quant_mx_cols_tiled_kernel<true>, dim3(N / 64, K / 128), dim3(256), 0, stream, in, ld, K, N,
-                       (unsigned char*)q, (unsigned char*)s, (unsigned char*)qr, (unsigned char*)sr, (bf16_t*)xb);
-  else
-    hipLaunchKernelGGL(quant_mx_cols_tiled_kernel<false>, dim3(N / 64, K / 128), dim3(256), 0, stream, in, ld, K, N,
-                       (unsigned char*)q, (unsigned char*)s, (unsigned char*)qr, (unsigned char*)sr, nullptr);
+// the tiled column quantizer on its grid (K % 128, N % 64; aligned in / q / qr / xb: the callers check)
+int launch_cols_tiled(const char* name, const void* in, long ld, int K, int N, void* q, void* s, void* qr, void* sr,
+                      void* xb, hipStream_t stream) {
+  const dim3 grid(N / 64, K / 128);
+  ljs_launch_rec(name, grid, 256);
+  void* args[] = {&in, &ld, &K, &N, &q, &s, &qr, &sr, &xb};
+  const void* kernel = xb ? (const void*)quant_mx_cols_tiled_kernel<true> : (const void*)quant_mx_cols_tiled_kernel<false>;
+  (void)hipLaunchKernel(kernel, grid, dim3(256), args, 0, stream);
   return (int)hipGetLastError();
 }
 
-// one scalar cotangent broadcast as TWO rows (lengths C1, C2): bf16 row 1 and the MX bytes of
-// both (the dY rows of y.sum() that the FF block's dA GEMM and dW_out GEMM read), one launch
+// a scalar cotangent g broadcast over a row: its bf16 row (length C1) and that row's MX bytes
+// (every 32-block has amax |bf16(g)|), plus the MX bytes of a second row of length C2 (0: none) --
+// the broadcast dY of y.sum() that the FF block's dA GEMM and dW_out GEMM read as ONE row each
+// (ld 0 / a_bcast), one launch
 __global__ void bcast_scalar_mx2_kernel(const void* __restrict__ g, int g_bf16, int C1, bf16_t* __restrict__ row,
                                         unsigned char* __restrict__ q1, unsigned char* __restrict__ s1, int C2,
                                         unsigned char* __restrict__ q2, unsigned char* __restrict__ s2) {
@@ -235,25 +232,40 @@ __global__ void bcast_scalar_mx2_kernel(const void* __restrict__ g, int g_bf16, 
   }
 }
 
-LJS_API int ljs_bcast_scalar_mx2(const void* g, int g_bf16, int C1, void* row, void* q1, void* s1, int C2, void* q2,
-                                 void* s2, hipStream_t stream) {
+int launch_bcast_scalar(const char* name, const void* g, int g_bf16, int C1, void* row, void* q1, void* s1, int C2,
+                        void* q2, void* s2, hipStream_t stream) {
   if (C1 % 32 || C2 % 32) return (int)hipErrorInvalidValue;
-  const int c = C1 > C2 ? C1 : C2;
-  hipLaunchKernelGGL(bcast_scalar_mx2_kernel, dim3((c / 4 + 255) / 256), dim3(256), 0, stream, g, g_bf16, C1,
-                     (bf16_t*)row, (unsigned char*)q1, (unsigned char*)s1, C2, (unsigned char*)q2, (unsigned char*)s2);
+  const dim3 grid(((C1 > C2 ? C1 : C2) / 4 + 255) / 256);
+  ljs_launch_rec(name, grid, 256);
+  hipLaunchKernelGGL(bcast_scalar_mx2_kernel, grid, dim3(256), 0, stream, g, g_bf16, C1, (bf16_t*)row,
+                     (unsigned char*)q1, (unsigned char*)s1, C2, (unsigned char*)q2, (unsigned char*)s2);
   return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------- GEMM
+// F8Args::flags (mirrored as the MX_* constants of ops/fp8.py)
+enum MxFlag {
+  kMxRelu = 1,
+  kMxBias = 2,
+  kMxBiasF32 = 4,      // the bias is f32 (else bf16)
+  kMxOutF32 = 32,      // f32 output (else bf16)
+  kMxResAdd = 64,      // residual add of R
+  kMxResMask = 128,    // ReLU mask: keep where R > 0
+  kMxQC = 256,         // quantized output copy (QC / SC)
+  kMxQT = 512,         // transposed quantized copy (QT / ST)
+  kMxResE4M3 = 1024,   // R is e4m3 bytes (mask mode: keep where the e4m3 value is > 0)
+  kMxColSum = 2048,    // per-row-tile column sums of the bf16 output (csum; 8-wave kernel)
+};
+constexpr int kMxAllFlags = kMxRelu | kMxBias | kMxBiasF32 | kMxOutF32 | kMxResAdd | kMxResMask | kMxQC | kMxQT |
+                            kMxResE4M3 | kMxColSum;
+
 struct F8Args {
   const unsigned char *A, *B, *SA, *SB;  // A[M][K], B[N][K] e4m3; SA[M][K/32], SB[N][K/32] e8m0
   void* C;
   const void* bias;
   long ldc;
   int M, N, K;
-  int flags;  // 1 relu, 2 bias, 4 bias f32, 32 f32 output, 64 residual add, 128 ReLU mask (R > 0),
-              // 256 quantized output copy (QC / SC), 512 transposed quantized copy (QT / ST),
-              // 1024 R is e4m3 bytes (mask mode: keep where the e4m3 value is > 0)
+  int flags;            // MxFlag bits
   const bf16_t* R;      // epilogue operand [M][N] bf16 (or e4m3), row stride ldr elements (0: one row)
   long ldr;
   unsigned char* QC;    // MX-fp8 copy of the (bf16-rounded) output: QC[M][N] e4m3, SC[M][N/32] e8m0
@@ -265,7 +277,7 @@ struct F8Args {
   int ldb, ldsb;        // B / SB row strides in bytes (K, K / 32; both 0: one broadcast row)
   int kps, nsplit;      // split-K: K-tiles per split, splits (split s -> f32 slab C + s * sC)
   long sC;
-  float* csum;          // flags & 2048 (8-wave kernel, bf16 output): per-row-tile column sums of the
+  float* csum;          // kMxColSum (8-wave kernel, bf16 output): per-row-tile column sums of the
                         // bf16 output, csum[tile row][N] (summed over tile rows by the caller)
 };
 
@@ -299,7 +311,10 @@ __device__ __forceinline__ f32x4 f8_mfma(const i32x8& a, const i32x8& b, const f
 // p.flags at run time
 template <int FIX>
 __device__ __forceinline__ int f8_flags(const F8Args& p) {
-  return FIX == 1 ? (1 | 256 | 512) : FIX == 2 ? (128 | 1024 | 256 | 512) : FIX == 3 ? 32 : p.flags;
+  return FIX == 1   ? (kMxRelu | kMxQC | kMxQT)
+         : FIX == 2 ? (kMxResMask | kMxResE4M3 | kMxQC | kMxQT)
+         : FIX == 3 ? kMxOutF32
+                    : p.flags;
 }
 
 template <int BM, int NST, int FIX = 0>
@@ -421,9 +436,10 @@ __global__ __launch_bounds__(BM * 2) void gemm_mx_fp8_kernel(F8Args p) {
   // halves -> 8 consecutive columns per lane -> one 16-byte (bf16) / 2 x 16-byte (f32) store.
   // A 32-column MX block of a row sits in the 4 lanes r16, r16 + 16, + 32, + 48 (g = 0..3).
   const int flags = f8_flags<FIX>(p);
-  const bool relu = flags & 1, has_bias = flags & 2, bias_f32 = flags & 4, out_f32 = flags & 32;
-  const bool res_add = flags & 64, res_mask = flags & 128, qout = flags & 256;
-  const bool qtout = flags & 512, r_fp8 = flags & 1024;
+  const bool relu = flags & kMxRelu, has_bias = flags & kMxBias, bias_f32 = flags & kMxBiasF32;
+  const bool out_f32 = flags & kMxOutF32;
+  const bool res_add = flags & kMxResAdd, res_mask = flags & kMxResMask, qout = flags & kMxQC;
+  const bool qtout = flags & kMxQT, r_fp8 = flags & kMxResE4M3;
   void* const Cp = (FIX == 1 || FIX == 2) ? nullptr : p.C;   // (those fixed epilogues write no bf16 output)
   const bool even = (g & 1) == 0;
   // the epilogue operand's 8 chunks per lane are all requested before the first is used (one
@@ -662,13 +678,6 @@ __global__ __launch_bounds__(BM * 2) void gemm_mx_fp8_kernel(F8Args p) {
 }
 
 #undef F8_ISSUE
-template __global__ void gemm_mx_fp8_kernel<128, 2, 0>(F8Args);
-template __global__ void gemm_mx_fp8_kernel<128, 3, 0>(F8Args);
-template __global__ void gemm_mx_fp8_kernel<256, 2, 0>(F8Args);
-template __global__ void gemm_mx_fp8_kernel<256, 3, 0>(F8Args);
-template __global__ void gemm_mx_fp8_kernel<128, 2, 1>(F8Args);
-template __global__ void gemm_mx_fp8_kernel<128, 2, 2>(F8Args);
-template __global__ void gemm_mx_fp8_kernel<128, 2, 3>(F8Args);
 
 // ---------------------------------------------------------------------------- GEMM, 8 waves
 // Large-tile MX-fp8 GEMM: BM x BN output tile, 8 waves (WM x WN, each (BM/WM) x (BN/WN)), BK =
@@ -806,7 +815,7 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
 #undef MX8_ISSUE
 
   // lane (g, r16) holds C[m0 + wr WTM + 16 i + r16][n0 + wc WTN + 16 j + 4 g + e], e = 0..3
-  const bool relu = p.flags & 1, has_bias = p.flags & 2, bias_f32 = p.flags & 4;
+  const bool relu = p.flags & kMxRelu, has_bias = p.flags & kMxBias, bias_f32 = p.flags & kMxBiasF32;
   const int rowb = wr * WTM + r16, colb = wc * WTN + 4 * g;
   float bv[TN][4];
 #pragma unroll
@@ -838,8 +847,8 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
     }
     return;
   } else {
-    const bool res_add = p.flags & 64, res_mask = p.flags & 128, qout = p.flags & 256;
-    const bool qtout = p.flags & 512, r_fp8 = p.flags & 1024;
+    const bool res_add = p.flags & kMxResAdd, res_mask = p.flags & kMxResMask, qout = p.flags & kMxQC;
+    const bool qtout = p.flags & kMxQT, r_fp8 = p.flags & kMxResE4M3;
     __syncthreads();  // every wave is done reading the ring: it becomes the bf16 image
     const __amdgpu_buffer_rsrc_t rr =
         f8_rsrc(p.R, (r_fp8 ? 1 : 2) * ((long)(p.M - 1) * p.ldr + p.N) * ((res_add || res_mask) ? 1 : 0));
@@ -888,7 +897,7 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
       }
     }
     __syncthreads();
-    if (p.flags & 2048) {
+    if (p.flags & kMxColSum) {
       // column sums of the bf16 output tile (a bias gradient downstream): CSP threads per column
       // over row ranges, partials through LDS, one f32 per column and tile row to csum
       float* part = reinterpret_cast<float*>(smem + BM * RS);
@@ -987,36 +996,169 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
   }
 }
 
-template <int BM, int BN, int WM, int NST = 2>
-hipError_t launch_mx8(const F8Args& a, int tiles, hipStream_t s) {
-  if (a.flags & 32)
-    hipLaunchKernelGGL((gemm_mx8_kernel<BM, BN, WM, true, NST>), dim3(tiles), dim3(512), 0, s, a);
-  else
-    hipLaunchKernelGGL((gemm_mx8_kernel<BM, BN, WM, false, NST>), dim3(tiles), dim3(512), 0, s, a);
+// ---------------------------------------------------------------------------- tile table
+// Every tile code of ljs_gemm_mx_fp8, one row each; the explicit instantiations and the plan's
+// dispatch switch are generated from it (tests/test_fp8_picks.py restates it as data).
+//   FAM  W4: gemm_mx_fp8_kernel, the "4-wave" kernel: BM x 128, BM / 64 x 2 waves, block BM * 2
+//        W8: gemm_mx8_kernel: BM x BN, 8 waves as WM x 8 / WM, block 512; a bf16 and an f32 instance
+//   NST  stages of the LDS-DMA ring
+#define LJS_MX_TILES(X)                   \
+  /* code     FAM  BM   BN  WM NST */     \
+  X(1282,     W4, 128, 128, 2, 2)         \
+  X(1283,     W4, 128, 128, 2, 3)         \
+  X(2562,     W4, 256, 128, 4, 2)         \
+  X(2563,     W4, 256, 128, 4, 3)         \
+  X(256256,   W8, 256, 256, 2, 2)         \
+  X(256128,   W8, 256, 128, 2, 2)         \
+  X(256160,   W8, 256, 160, 4, 2)         \
+  X(128320,   W8, 128, 320, 2, 2)         \
+  X(128256,   W8, 128, 256, 2, 2)         \
+  X(128128,   W8, 128, 128, 2, 2)         \
+  X(128160,   W8, 128, 160, 4, 2)         \
+  X(3128128,  W8, 128, 128, 2, 3)         \
+  X(3128160,  W8, 128, 160, 4, 3)         \
+  X(3128256,  W8, 128, 256, 2, 3)         \
+  X(3256128,  W8, 256, 128, 2, 3)
+constexpr int kMxDefaultTile = 1282;  // tile code 0; the only tile with the FIX instances
+
+#define LJS_MX_INST_W4(BM_, BN_, WM_, NST_) template __global__ void gemm_mx_fp8_kernel<BM_, NST_, 0>(F8Args);
+#define LJS_MX_INST_W8(BM_, BN_, WM_, NST_)                                        \
+  template __global__ void gemm_mx8_kernel<BM_, BN_, WM_, false, NST_>(F8Args);    \
+  template __global__ void gemm_mx8_kernel<BM_, BN_, WM_, true, NST_>(F8Args);
+#define LJS_MX_INST(CODE, FAM, BM_, BN_, WM_, NST_) LJS_MX_INST_##FAM(BM_, BN_, WM_, NST_)
+LJS_MX_TILES(LJS_MX_INST)
+#undef LJS_MX_INST
+#undef LJS_MX_INST_W8
+#undef LJS_MX_INST_W4
+template __global__ void gemm_mx_fp8_kernel<128, 2, 1>(F8Args);
+template __global__ void gemm_mx_fp8_kernel<128, 2, 2>(F8Args);
+template __global__ void gemm_mx_fp8_kernel<128, 2, 3>(F8Args);
+
+// ---------------------------------------------------------------------------- plan
+// What one ljs_gemm_mx_fp8 call launches, worked out from the call's numbers alone: mx_plan
+// dereferences nothing and calls no HIP function, so it answers on a machine without a GPU too
+// (ljs_gemm_mx_plan).
+enum MxFamily { kW4 = 0, kW8 = 1 };
+
+struct MxPlan {
+  hipError_t err;
+  int tile;                // the resolved tile code
+  int family;
+  int BM, BN, WM, NST;
+  int fix;                 // W4: the FIX instance (0: flags read at run time); W8: -1
+  bool out_f32;
+  int nsplit, kps;         // splits, K-tiles per split
+  unsigned grid, block;
+  const char* name;
+  void (*kernel)(F8Args);
+};
+
+template <int FIX>
+void set_fix(MxPlan& p) {
+  p.fix = FIX;
+  p.kernel = gemm_mx_fp8_kernel<128, 2, FIX>;
+  p.name = FIX == 1 ? "gemm_mx_fp8<128,2,fix=1>" : FIX == 2 ? "gemm_mx_fp8<128,2,fix=2>" : "gemm_mx_fp8<128,2,fix=3>";
+}
+
+// a: the call as ljs_gemm_mx_fp8 received it (a.kps and a.nsplit are not read)
+MxPlan mx_plan(const F8Args& a, int tile, int nsplit) {
+  MxPlan p{};
+  p.err = hipErrorInvalidValue;
+  const int f = a.flags, M = a.M, N = a.N, K = a.K;
+  const bool res = f & (kMxResAdd | kMxResMask);
+  p.out_f32 = f & kMxOutF32;
+  // whole K-tiles, 8-column stores, operand byte offsets within 32 bits
+  if (K % F8_BK || N % 8 || a.ldc % 8 || (long)M * K >= (1L << 31) || (long)N * K >= (1L << 31)) return p;
+  if (res && (!a.R || a.ldr % 8 || ((uintptr_t)a.R & 15) || p.out_f32)) return p;
+  if ((f & kMxResE4M3) && !(f & kMxResMask)) return p;
+  if ((f & kMxQC) && (!a.QC || !a.SC || N % 32)) return p;
+  if ((f & kMxQT) && (!a.QT || !a.ST || M % 32 || a.ldqt < M || a.ldqt % 32 || p.out_f32 || ((uintptr_t)a.QT & 15)))
+    return p;
+  p.nsplit = nsplit < 1 ? 1 : nsplit;
+  const int nkt = K / F8_BK;
+  p.kps = (nkt + p.nsplit - 1) / p.nsplit;
+  // split-K: plain f32 slabs (a ReLU would be applied to each partial), the caller's slab count exact
+  if (p.nsplit > 1 && (!p.out_f32 || res || (f & (kMxQC | kMxQT | kMxBias | kMxRelu)) || p.kps == 0 ||
+                       (nkt + p.kps - 1) / p.kps != p.nsplit))
+    return p;
+  // fused column sums: the 8-wave kernels' bf16 epilogue only
+  if ((f & kMxColSum) && (!a.csum || tile < 10000 || p.out_f32)) return p;
+  // what no kernel would honour: bits none of them reads, a bias type without a bias, both uses of
+  // R at once (the epilogues take one), an output or a bias that is not there
+  if ((f & ~kMxAllFlags) || ((f & kMxBiasF32) && !(f & kMxBias)) || ((f & kMxResAdd) && (f & kMxResMask))) return p;
+  if (((f & kMxBias) && !a.bias) || (p.out_f32 && !a.C)) return p;
+
+  p.tile = tile == 0 ? kMxDefaultTile : tile;
+  switch (p.tile) {
+#define LJS_MX_SET_W4(BM_, BN_, WM_, NST_)     \
+  p.kernel = gemm_mx_fp8_kernel<BM_, NST_, 0>; \
+  p.name = "gemm_mx_fp8<" #BM_ "," #NST_ ",fix=0>";
+#define LJS_MX_SET_W8(BM_, BN_, WM_, NST_)                                              \
+  p.kernel = p.out_f32 ? gemm_mx8_kernel<BM_, BN_, WM_, true, NST_>                     \
+                       : gemm_mx8_kernel<BM_, BN_, WM_, false, NST_>;                   \
+  p.name = p.out_f32 ? "gemm_mx8<" #BM_ "," #BN_ "," #WM_ ",f32," #NST_ ">"             \
+                     : "gemm_mx8<" #BM_ "," #BN_ "," #WM_ ",bf16," #NST_ ">";
+#define LJS_CASE(CODE, FAM, BM_, BN_, WM_, NST_)                          \
+  case CODE:                                                              \
+    p.family = k##FAM; p.BM = BM_; p.BN = BN_; p.WM = WM_; p.NST = NST_;  \
+    LJS_MX_SET_##FAM(BM_, BN_, WM_, NST_)                                 \
+    break;
+    LJS_MX_TILES(LJS_CASE)
+#undef LJS_CASE
+#undef LJS_MX_SET_W8
+#undef LJS_MX_SET_W4
+    default: return p;  // no such tile
+  }
+  p.fix = p.family == kW4 ? 0 : -1;
+  // the 8-wave f32 instance returns after its f32 stores: it writes no quantized copy
+  if (p.family == kW8 && p.out_f32 && (f & kMxQC)) return p;
+  if (p.tile == kMxDefaultTile) {
+    // The FF block's GEMMs run epilogues fixed at compile time (100 VGPRs against the general
+    // kernel's 160).  Such an instance reads no flag at run time, so it serves exactly its own
+    // flag set: any other bit would be dropped.  FIX 1 (up projection: ReLU + both MX copies) and
+    // FIX 2 (dA: e4m3 ReLU mask + both MX copies) never touch C or the bias, so both must be
+    // absent, and they are not slab kernels: one split.  FIX 3 (the weight gradients' plain f32
+    // output) adds no bias and serves any split count.
+    const bool copies_only = !a.C && !a.bias && p.nsplit == 1;
+    if (copies_only && f == (kMxRelu | kMxQC | kMxQT)) set_fix<1>(p);
+    else if (copies_only && f == (kMxResMask | kMxResE4M3 | kMxQC | kMxQT)) set_fix<2>(p);
+    else if (f == kMxOutF32 && !a.bias) set_fix<3>(p);
+  }
+  p.grid = (unsigned)(((M + p.BM - 1) / p.BM) * ((N + p.BN - 1) / p.BN) * p.nsplit);
+  p.block = p.family == kW4 ? p.BM * 2 : 512;
+  p.err = hipSuccess;
+  return p;
+}
+
+hipError_t launch_plan(const MxPlan& p, F8Args a, int req_tile, hipStream_t s) {
+  a.kps = p.kps;
+  a.nsplit = p.nsplit;
+  LjsLaunchRec r = ljs_launch_make(p.name, dim3(p.grid), p.block);
+  r.req_tile = req_tile; r.res_tile = p.tile;
+  r.splitk = p.nsplit; r.variant = p.fix;
+  ljs_launch_push(r);
+  void* args[] = {&a};
+  (void)hipLaunchKernel((const void*)p.kernel, dim3(p.grid), dim3(p.block), args, 0, s);
   return hipGetLastError();
 }
 
-template <int BM, int NST>
-hipError_t launch_f8(const F8Args& a, int tiles, hipStream_t s) {
-  // the FF block's up projection / dA epilogues get their compile-time specialisations
-  if (BM == 128 && NST == 2 && a.C == nullptr && a.bias == nullptr && a.nsplit == 1) {
-    if (a.flags == (1 | 256 | 512)) {
-      hipLaunchKernelGGL((gemm_mx_fp8_kernel<128, 2, 1>), dim3(tiles), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-    if (a.flags == (128 | 1024 | 256 | 512)) {
-      hipLaunchKernelGGL((gemm_mx_fp8_kernel<128, 2, 2>), dim3(tiles), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-  }
-  // plain f32 output (the FF weight gradients): its own instance -- the general kernel's 288
-  // registers (VGPR + AGPR) left one wave per SIMD
-  if (BM == 128 && NST == 2 && a.flags == 32 && a.bias == nullptr) {
-    hipLaunchKernelGGL((gemm_mx_fp8_kernel<128, 2, 3>), dim3(tiles), dim3(256), 0, s, a);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL((gemm_mx_fp8_kernel<BM, NST, 0>), dim3(tiles), dim3(BM * 2), 0, s, a);
-  return hipGetLastError();
+// a_bcast / b_bcast: A / B (and their scales) hold ONE row, read for every output row / column
+F8Args make_args(const void* A, const void* SA, const void* B, const void* SB, void* C, const void* bias, int M, int N,
+                 int K, long ldc, int flags, const void* R, long ldr, void* QC, void* SC, int a_bcast, int b_bcast,
+                 void* QT, void* ST, long ldqt, long sC, void* csum) {
+  F8Args a{};  // (kps, nsplit: the plan's)
+  a.A = (const unsigned char*)A; a.B = (const unsigned char*)B;
+  a.SA = (const unsigned char*)SA; a.SB = (const unsigned char*)SB;
+  a.C = C; a.bias = bias; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.flags = flags;
+  a.R = (const bf16_t*)R; a.ldr = ldr; a.QC = (unsigned char*)QC; a.SC = (unsigned char*)SC;
+  a.lda = a_bcast ? 0 : K;
+  a.ldsa = a_bcast ? 0 : K / 32;
+  a.ldb = b_bcast ? 0 : K;
+  a.ldsb = b_bcast ? 0 : K / 32;
+  a.QT = (unsigned char*)QT; a.ST = (unsigned char*)ST; a.ldqt = ldqt;
+  a.sC = sC;
+  a.csum = (float*)csum;
+  return a;
 }
 
 // one wave, one block-scaled MFMA on raw per-lane operands (layout validation in the tests)
@@ -1066,26 +1208,16 @@ LJS_API int ljs_debug_mfma_f8(const void* a, const void* b, const void* sa, cons
   return (int)hipGetLastError();
 }
 
-// a scalar cotangent g broadcast over a row of C: its bf16 row and that row's MX-fp8 rows (every
-// 32-block has amax |bf16(g)|) in one launch -- the broadcast dY of y.sum(), read by the GEMMs
-// as ONE row (ld 0 / a_bcast); C % 32 == 0
-__global__ void bcast_scalar_mx_kernel(const void* __restrict__ g, int g_bf16, int C, bf16_t* __restrict__ row,
-                                       unsigned char* __restrict__ q, unsigned char* __restrict__ s) {
-  const int c4 = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
-  if (c4 >= C) return;
-  const float v = bf2f(f2bf(g_bf16 ? bf2f(*reinterpret_cast<const bf16_t*>(g)) : *reinterpret_cast<const float*>(g)));
-  *reinterpret_cast<u32x2*>(row + c4) = u32x2{pack_bf16x2(v, v), pack_bf16x2(v, v)};
-  const int x = mx_exponent(fabsf(v));
-  const float sv = v * ldexpf(1.f, -x);
-  *reinterpret_cast<unsigned*>(q + c4) = pack4_e4m3(sv, sv, sv, sv);
-  if ((c4 & 31) == 0) s[c4 / 32] = (unsigned char)(x + 127);
+// a scalar cotangent g broadcast over a row of C: its bf16 row and that row's MX-fp8 bytes in one
+// launch (bcast_scalar_mx2_kernel without a second row); C % 32 == 0
+LJS_API int ljs_bcast_scalar_mx(const void* g, int g_bf16, int C, void* row, void* q, void* s, hipStream_t stream) {
+  return launch_bcast_scalar("bcast_scalar_mx", g, g_bf16, C, row, q, s, 0, nullptr, nullptr, stream);
 }
 
-LJS_API int ljs_bcast_scalar_mx(const void* g, int g_bf16, int C, void* row, void* q, void* s, hipStream_t stream) {
-  if (C % 32) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(bcast_scalar_mx_kernel, dim3((C / 4 + 255) / 256), dim3(256), 0, stream, g, g_bf16, C,
-                     (bf16_t*)row, (unsigned char*)q, (unsigned char*)s);
-  return (int)hipGetLastError();
+// ... and the MX bytes of a second row of length C2; C1 % 32 == 0, C2 % 32 == 0
+LJS_API int ljs_bcast_scalar_mx2(const void* g, int g_bf16, int C1, void* row, void* q1, void* s1, int C2, void* q2,
+                                 void* s2, hipStream_t stream) {
+  return launch_bcast_scalar("bcast_scalar_mx2", g, g_bf16, C1, row, q1, s1, C2, q2, s2, stream);
 }
 
 // x[R][K] (row stride ld elements) -> q[R][K], s[R][K/32] (+ xb[R][K] bf16 for an f32 x, when
@@ -1094,89 +1226,72 @@ LJS_API int ljs_quant_mx_rows(const void* in, int is_bf16, long ld, int R, int K
                               hipStream_t stream) {
   if (K % 32 || ld % 8 || (xb && (is_bf16 || ((uintptr_t)xb & 15)))) return (int)hipErrorInvalidValue;
   const long nb = (long)R * (K / 32);
-  hipLaunchKernelGGL(quant_mx_rows_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, in, is_bf16, ld,
-                     R, K, (unsigned char*)q, (unsigned char*)s, (bf16_t*)xb);
+  const dim3 grid((unsigned)((nb + 255) / 256));
+  ljs_launch_rec("quant_mx_rows", grid, 256);
+  hipLaunchKernelGGL(quant_mx_rows_kernel, grid, dim3(256), 0, stream, in, is_bf16, ld, R, K, (unsigned char*)q,
+                     (unsigned char*)s, (bf16_t*)xb);
   return (int)hipGetLastError();
 }
 
-// w[K][N] (row stride ld) -> q[N][K], s[N][K/32]
+// w[K][N] (row stride ld) -> q[N][K], s[N][K/32]: the tiled kernel where the shape and the
+// alignment allow it, else one thread per block
 LJS_API int ljs_quant_mx_cols(const void* in, int is_bf16, long ld, int K, int N, void* q, void* s,
                               hipStream_t stream) {
   if (K % 32) return (int)hipErrorInvalidValue;
-  if (is_bf16 && K % 128 == 0 && N % 64 == 0 && ld % 8 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)q & 15) == 0) {
-    hipLaunchKernelGGL(quant_mx_cols_tiled_kernel<false>, dim3(N / 64, K / 128), dim3(256), 0, stream, in, ld, K, N,
-                       (unsigned char*)q, (unsigned char*)s, nullptr, nullptr, nullptr);
-    return (int)hipGetLastError();
-  }
-  dim3 grid((N + 63) / 64, K / 32);
+  if (is_bf16 && K % 128 == 0 && N % 64 == 0 && ld % 8 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)q & 15) == 0)
+    return launch_cols_tiled("quant_mx_cols<tiled>", in, ld, K, N, q, s, nullptr, nullptr, nullptr, stream);
+  const dim3 grid((N + 63) / 64, K / 32);
+  ljs_launch_rec("quant_mx_cols<generic>", grid, 64);
   hipLaunchKernelGGL(quant_mx_cols_kernel, grid, dim3(64), 0, stream, in, is_bf16, ld, K, N, (unsigned char*)q,
                      (unsigned char*)s);
   return (int)hipGetLastError();
 }
 
-// C[M][N] (bf16, or f32 with flags & 32) = A . B^T of MX-fp8 operands; K % 128 == 0, N % 8 == 0.
-// R (bf16 [M][N], row stride ldr) with flags 64 / 128: residual add / ReLU mask in the epilogue;
-// QC / SC with flags 256: also an MX-fp8 copy of the output (N % 32 == 0); QT / ST with flags 512:
-// its TRANSPOSED MX copy QT[N][M] (row stride ldqt = M, blocks along M; M % 32 == 0, bf16-path
-// outputs only); flags 1024: R is e4m3 [M][N] (ReLU mask of an fp8-only activation).
-// a_bcast / b_bcast: A / B (and scales) hold one row, read for every row.  nsplit > 1: split-K,
-// split s writing the f32 slab C + s * sC (summed by the caller).  tile: 1282 / 1283 / 2562 /
-// 2563 = BM x 128 with 2 or 3 stages (0: automatic).
+// x[K][N] (bf16, or f32 with xb != null: xb[K][N] receives x rounded to bf16) -> BOTH its
+// row-blocked (qr [K][N]) and transposed column-blocked (q [N][K]) MX quantizations in one pass;
+// K % 128, N % 64
+LJS_API int ljs_quant_mx_both(const void* in, long ld, int K, int N, void* q, void* s, void* qr, void* sr, void* xb,
+                              hipStream_t stream) {
+  if (K % 128 || N % 64 || ld % 8 || ((uintptr_t)in & 15) || ((uintptr_t)q & 15) || ((uintptr_t)qr & 15) ||
+      ((uintptr_t)xb & 15))
+    return (int)hipErrorInvalidValue;
+  return launch_cols_tiled(xb ? "quant_mx_both<f32>" : "quant_mx_both<bf16>", in, ld, K, N, q, s, qr, sr, xb, stream);
+}
+
+// C[M][N] (bf16, or f32 with kMxOutF32) = A . B^T of MX-fp8 operands; K % 128 == 0, N % 8 == 0.
+// flags: MxFlag bits.  R (bf16 [M][N], row stride ldr) with kMxResAdd / kMxResMask: residual add /
+// ReLU mask in the epilogue (kMxResE4M3: R is e4m3 [M][N], the mask of an fp8-only activation);
+// QC / SC with kMxQC: also an MX-fp8 copy of the output (N % 32 == 0); QT / ST with kMxQT: its
+// TRANSPOSED MX copy QT[N][M] (row stride ldqt = M, blocks along M; M % 32 == 0, bf16-path
+// outputs only).  a_bcast / b_bcast: A / B (and scales) hold one row, read for every row.
+// nsplit > 1: split-K, split s writing the f32 slab C + s * sC (summed by the caller).  tile: a
+// code of LJS_MX_TILES (0: kMxDefaultTile).  Returns 0 on success; a call the plan rejects returns
+// hipErrorInvalidValue with nothing launched or recorded.
 LJS_API int ljs_gemm_mx_fp8(const void* A, const void* SA, const void* B, const void* SB, void* C, const void* bias,
                             int M, int N, int K, long ldc, int flags, const void* R, long ldr, void* QC, void* SC,
                             int tile, int a_bcast, int b_bcast, void* QT, void* ST, long ldqt, int nsplit, long sC,
                             void* csum, hipStream_t stream) {
-  if (K % F8_BK || N % 8 || ldc % 8 || (long)M * K >= (1L << 31) || (long)N * K >= (1L << 31))
-    return (int)hipErrorInvalidValue;
-  if ((flags & (64 | 128)) && (!R || ldr % 8 || (((uintptr_t)R) & 15) || (flags & 32)))
-    return (int)hipErrorInvalidValue;
-  if ((flags & 1024) && !(flags & 128)) return (int)hipErrorInvalidValue;
-  if ((flags & 256) && (!QC || !SC || N % 32)) return (int)hipErrorInvalidValue;
-  if ((flags & 512) && (!QT || !ST || M % 32 || ldqt < M || ldqt % 32 || (flags & 32) || ((uintptr_t)QT & 15)))
-    return (int)hipErrorInvalidValue;
-  if (nsplit < 1) nsplit = 1;
-  const int nkt = K / F8_BK;
-  const int kps = (nkt + nsplit - 1) / nsplit;
-  if (nsplit > 1 && (!(flags & 32) || (flags & (64 | 128 | 256 | 512 | 2)) || (nkt + kps - 1) / kps != nsplit))
-    return (int)hipErrorInvalidValue;  // split-K: plain f32 slabs, and the caller's slab count exact
-  F8Args a;
-  a.A = (const unsigned char*)A; a.B = (const unsigned char*)B;
-  a.SA = (const unsigned char*)SA; a.SB = (const unsigned char*)SB;
-  a.C = C; a.bias = bias; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.flags = flags;
-  a.R = (const bf16_t*)R; a.ldr = ldr; a.QC = (unsigned char*)QC; a.SC = (unsigned char*)SC;
-  a.lda = a_bcast ? 0 : K;  // a_bcast: A / SA hold ONE row, read for every output row
-  a.ldsa = a_bcast ? 0 : K / 32;
-  a.ldb = b_bcast ? 0 : K;
-  a.ldsb = b_bcast ? 0 : K / 32;
-  a.QT = (unsigned char*)QT; a.ST = (unsigned char*)ST; a.ldqt = ldqt;
-  a.kps = kps; a.nsplit = nsplit; a.sC = sC;
-  a.csum = (float*)csum;
-  // fused column sums: the 8-wave kernels' bf16 epilogue only
-  if ((flags & 2048) && (!csum || tile < 10000 || (flags & 32))) return (int)hipErrorInvalidValue;
-  if (tile == 0) tile = 1282;
-  if (tile >= 10000) {  // 8-wave large tiles: tile = BM * 1000 + BN (+ 1000000 * 3: three stages)
-    const int t6 = tile % 1000000;
-    const int bm = t6 / 1000, bn = t6 % 1000;
-    const int tl = ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * nsplit;
-    switch (tile) {
-      case 256256: return (int)launch_mx8<256, 256, 2>(a, tl, stream);
-      case 256128: return (int)launch_mx8<256, 128, 2>(a, tl, stream);
-      case 256160: return (int)launch_mx8<256, 160, 4>(a, tl, stream);
-      case 128320: return (int)launch_mx8<128, 320, 2>(a, tl, stream);
-      case 128256: return (int)launch_mx8<128, 256, 2>(a, tl, stream);
-      case 128128: return (int)launch_mx8<128, 128, 2>(a, tl, stream);
-      case 128160: return (int)launch_mx8<128, 160, 4>(a, tl, stream);
-      case 3128128: return (int)launch_mx8<128, 128, 2, 3>(a, tl, stream);
-      case 3128160: return (int)launch_mx8<128, 160, 4, 3>(a, tl, stream);
-      case 3128256: return (int)launch_mx8<128, 256, 2, 3>(a, tl, stream);
-      case 3256128: return (int)launch_mx8<256, 128, 2, 3>(a, tl, stream);
-      default: return (int)hipErrorInvalidValue;
-    }
-  }
-  const int bm = tile / 10 >= 256 ? 256 : 128;
-  const int tiles = ((M + bm - 1) / bm) * ((N + 127) / 128) * nsplit;
-  if (tile == 1283) return (int)launch_f8<128, 3>(a, tiles, stream);
-  if (tile == 2562) return (int)launch_f8<256, 2>(a, tiles, stream);
-  if (tile == 2563) return (int)launch_f8<256, 3>(a, tiles, stream);
-  return (int)launch_f8<128, 2>(a, tiles, stream);
+  const F8Args a = make_args(A, SA, B, SB, C, bias, M, N, K, ldc, flags, R, ldr, QC, SC, a_bcast, b_bcast, QT, ST, ldqt,
+                             sC, csum);
+  const MxPlan p = mx_plan(a, tile, nsplit);
+  if (p.err != hipSuccess) return (int)p.err;
+  return (int)launch_plan(p, a, tile, stream);
+}
+
+// The plan of the same call, without a GPU: nothing is dereferenced or launched (the pointers are
+// read as addresses, for the null and alignment checks).  out[0..12]: error, resolved tile, family
+// (0 4-wave, 1 8-wave), BM, BN, WM, NST, fix, out_f32, nsplit, kps, grid, block; name: the kernel
+// instance.  Returns the error.
+LJS_API int ljs_gemm_mx_plan(const void* A, const void* SA, const void* B, const void* SB, void* C, const void* bias,
+                             int M, int N, int K, long ldc, int flags, const void* R, long ldr, void* QC, void* SC,
+                             int tile, int a_bcast, int b_bcast, void* QT, void* ST, long ldqt, int nsplit, long sC,
+                             void* csum, int* out, char* name, int name_cap) {
+  const MxPlan p = mx_plan(make_args(A, SA, B, SB, C, bias, M, N, K, ldc, flags, R, ldr, QC, SC, a_bcast, b_bcast, QT,
+                                     ST, ldqt, sC, csum),
+                           tile, nsplit);
+  const int v[13] = {(int)p.err, p.tile, p.family, p.BM,     p.BN,  p.WM,        p.NST,
+                     p.fix,      p.out_f32, p.nsplit, p.kps, (int)p.grid, (int)p.block};
+  for (int i = 0; i < 13; ++i) out[i] = v[i];
+  if (name && name_cap > 0) snprintf(name, (size_t)name_cap, "%s", p.err == hipSuccess ? p.name : "");
+  return (int)p.err;
 }

@@ -28,10 +28,17 @@ from . import hip
 from .linear import _Linear, _bf16, _inv_perm
 
 __all__ = ["quantize_mx_ref", "dequantize_mx_ref", "mx_linear_ref", "quant_rows", "quant_cols", "gemm_mx",
-           "linear_fp8", "fp8_dense", "E4M3_MAX", "BLOCK"]
+           "gemm_mx_plan", "mx_flags", "linear_fp8", "fp8_dense", "E4M3_MAX", "BLOCK"]
 
 E4M3_MAX = 448.0
 BLOCK = 32
+
+# the epilogue flags of ljs_gemm_mx_fp8 (enum MxFlag, csrc/kernels/fp8.hip)
+MX_RELU, MX_BIAS, MX_BIAS_F32, MX_OUT_F32 = 1, 2, 4, 32
+MX_RES_ADD, MX_RES_MASK = 64, 128            # residual add of ``res`` / ReLU mask (keep where res > 0)
+MX_QC, MX_QT = 256, 512                      # MX copy of the output / its transposed MX copy
+MX_RES_E4M3 = 1024                           # ``res`` is e4m3 bytes (mask mode)
+MX_COLSUM = 2048                             # per-row-tile column sums of the bf16 output (8-wave tiles)
 
 _SIGS = {
     "ljs_quant_mx_rows": [ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -50,6 +57,11 @@ _SIGS = {
                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int,
                         ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p],
 }
+# the same call without the stream, plus (int* out, char* name, int name_cap)
+_PLAN_SIG = _SIGS["ljs_gemm_mx_fp8"][:-1] + [ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, ctypes.c_int]
+_PLAN_FIELDS = ("err", "resolved_tile", "family", "BM", "BN", "WM", "NST", "fix", "out_f32", "nsplit", "kps", "grid",
+                "block")
+_PLAN_FAMILIES = ("4-wave", "8-wave")
 _bound = False
 
 
@@ -161,6 +173,51 @@ def _weight_q(w: torch.Tensor):
     return q, s
 
 
+def mx_flags(out_dtype=None, bias_dtype=None, relu: bool = False, res_dtype=None, res_mode: str = "add",
+             qout: bool = False, qtout: bool = False, colsum: bool = False) -> int:
+    """The flags word of one :func:`gemm_mx` call, from the dtypes of its tensors (None: absent)."""
+    flags = (MX_RELU if relu else 0) | (MX_OUT_F32 if out_dtype == torch.float32 else 0)
+    if bias_dtype is not None:
+        flags |= MX_BIAS | (MX_BIAS_F32 if bias_dtype == torch.float32 else 0)
+    if res_dtype is not None:
+        assert res_dtype in (torch.bfloat16, torch.uint8)
+        assert res_dtype == torch.bfloat16 or res_mode == "mask"
+        flags |= (MX_RES_ADD if res_mode == "add" else MX_RES_MASK) | (MX_RES_E4M3 if res_dtype == torch.uint8 else 0)
+    return flags | (MX_QC if qout else 0) | (MX_QT if qtout else 0) | (MX_COLSUM if colsum else 0)
+
+
+def gemm_mx_plan(M: int, N: int, K: int, flags: int = 0, tile: int = 0, nsplit: int = 1, ldc: Optional[int] = None,
+                 ldr: Optional[int] = None, ldqt: Optional[int] = None, **addr) -> dict:
+    """What ``ljs_gemm_mx_fp8`` would launch for these numbers (``ljs_gemm_mx_plan``: the launcher's
+    own plan step; needs the library, not a GPU).  ``flags``: the ``MX_*`` bits (:func:`mx_flags`);
+    ``tile`` as the launcher receives it (:func:`gemm_mx` passes :func:`_auto_tile`'s answer for 0).
+    Tensors are given by what the plan reads of them, their addresses: by default the output C and
+    every tensor ``flags`` asks for are present and aligned; ``addr`` (keys ``C``, ``bias``, ``R``,
+    ``QC``, ``SC``, ``QT``, ``ST``, ``csum``) overrides one, 0 meaning absent.  Returns the fields of
+    a launch record (``name``, ``grid``, ``blocks``, ``block``, ``resolved_tile``, ``splitk``,
+    ``variant``) plus ``family``, ``BM``, ``BN``, ``WM``, ``NST``, ``fix`` (the 4-wave kernel's
+    compile-time epilogue, None for an 8-wave tile), ``out_f32``, ``nsplit`` and ``kps``; ``err`` is
+    the launcher's error code (0: it would launch)."""
+    res = flags & (MX_RES_ADD | MX_RES_MASK)
+    a = dict(C=4096, bias=4096 if flags & MX_BIAS else 0, R=4096 if res else 0, QC=4096 if flags & MX_QC else 0,
+             SC=4096 if flags & MX_QC else 0, QT=4096 if flags & MX_QT else 0, ST=4096 if flags & MX_QT else 0,
+             csum=4096 if flags & MX_COLSUM else 0)
+    assert set(addr) <= set(a), addr
+    a.update(addr)
+    p = {k: ctypes.c_void_p(v) if v else None for k, v in a.items()}
+    fn = hip.lib().ljs_gemm_mx_plan     # (bound here: gemm_mx also serves a library without the plan export)
+    fn.argtypes, fn.restype = _PLAN_SIG, ctypes.c_int
+    out, name, fake = (ctypes.c_int * len(_PLAN_FIELDS))(), ctypes.create_string_buffer(64), ctypes.c_void_p(4096)
+    fn(fake, fake, fake, fake, p["C"], p["bias"], M, N, K, N if ldc is None else ldc, flags, p["R"],
+       (N if res else 0) if ldr is None else ldr, p["QC"], p["SC"], tile, 0, 0, p["QT"], p["ST"],
+       M if ldqt is None else ldqt, nsplit, M * N if nsplit > 1 else 0, p["csum"], out, name, len(name))
+    plan = dict(zip(_PLAN_FIELDS, out))
+    fix = None if plan["fix"] < 0 else plan["fix"]
+    plan.update(name=name.value.decode(), family=_PLAN_FAMILIES[plan["family"]], grid=(plan["grid"], 1, 1),
+                blocks=plan["grid"], out_f32=bool(plan["out_f32"]), fix=fix, variant=fix, splitk=plan["nsplit"])
+    return plan
+
+
 def gemm_mx(qa, sa, qb, sb, M: int, N: int, K: int, out: Optional[torch.Tensor], bias: Optional[torch.Tensor] = None,
             relu: bool = False, res: Optional[torch.Tensor] = None, res_mode: str = "add",
             qout: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, tile: int = 0,
@@ -172,39 +229,31 @@ def gemm_mx(qa, sa, qb, sb, M: int, N: int, K: int, out: Optional[torch.Tensor],
     add) or used as a ReLU mask (``"mask"``: keep where res > 0); ``qout = (q, s)`` also receives
     the MX-fp8 quantization of the (bf16-rounded) output, blocks of 32 along N - the next GEMM's
     operand without a quantization pass.  ``out`` may be None when only ``qout`` is wanted.
-    ``tile``: 1282 / 1283 / 2562 / 2563 (BM x 128, stages), 0 = automatic.  ``a_bcast`` /
+    ``tile``: a code of ``LJS_MX_TILES`` (csrc/kernels/fp8.hip), 0 = automatic.  ``a_bcast`` /
     ``b_bcast``: ``qa`` / ``qb`` (and scales) hold ONE row, used for all rows (a broadcast
     gradient, never materialised).  ``qtout = (qT, sT)``: the TRANSPOSED MX copy of the output,
     qT [N][M] with blocks of 32 along M (the output as the K-major operand of a GEMM that
     contracts over M, e.g. a weight gradient over tokens).  ``res`` of dtype uint8 in "mask"
     mode: an e4m3 activation (keep where its value > 0).  ``nsplit`` > 1: split-K into f32
     slabs ``out[s]`` (``out`` [nsplit][M][N]; the caller sums them)."""
-    od = out if out is not None else None
-    flags = (1 if relu else 0) | (2 if bias is not None else 0) | \
-        (4 if (bias is not None and bias.dtype == torch.float32) else 0) | \
-        (32 if (od is not None and od.dtype == torch.float32) else 0)
+    flags = mx_flags(None if out is None else out.dtype, None if bias is None else bias.dtype, relu,
+                     None if res is None else res.dtype, res_mode, qout is not None, qtout is not None)
     ldr = 0
     if res is not None:
-        assert res.dtype in (torch.bfloat16, torch.uint8) and res.stride(-1) == 1
-        assert res.dtype == torch.bfloat16 or res_mode == "mask"
-        flags |= (64 if res_mode == "add" else 128) | (1024 if res.dtype == torch.uint8 else 0)
+        assert res.stride(-1) == 1
         ldr = res.stride(0) if res.dim() == 2 else N
     q_o, s_o = qout if qout is not None else (None, None)
-    if qout is not None:
-        flags |= 256
     qt_o, st_o = qtout if qtout is not None else (None, None)
-    if qtout is not None:
-        flags |= 512
-    ldc = (od.stride(-2) if od is not None else N)
-    sC = od.stride(0) if (od is not None and nsplit > 1) else 0
+    ldc = out.stride(-2) if out is not None else N
+    sC = out.stride(0) if (out is not None and nsplit > 1) else 0
     if tile == 0:
         tile = _auto_tile(M, N, K, flags, nsplit)
     if colsum is not None:
         # ``colsum`` f32 [ceil(M / BM)][N]: per-row-tile column sums of the bf16 output (8-wave
         # tiles only; the caller sums the rows)
         assert tile >= 10000 and colsum.dtype == torch.float32 and colsum.shape == (-(-M // (tile % 1000000 // 1000)), N)
-        flags |= 2048
-    rc = _lib().ljs_gemm_mx_fp8(hip._p(qa), hip._p(sa), hip._p(qb), hip._p(sb), hip._p(od), hip._p(bias), M, N, K,
+        flags |= MX_COLSUM
+    rc = _lib().ljs_gemm_mx_fp8(hip._p(qa), hip._p(sa), hip._p(qb), hip._p(sb), hip._p(out), hip._p(bias), M, N, K,
                                 ldc, flags, hip._p(res), ldr, hip._p(q_o), hip._p(s_o), tile, int(a_bcast),
                                 int(b_bcast), hip._p(qt_o), hip._p(st_o), M, nsplit, sC, hip._p(colsum), hip._stream(qa))
     hip._ck(rc, "gemm_mx_fp8")
@@ -222,7 +271,7 @@ _F8_AUTO = True
 def _auto_tile(M: int, N: int, K: int, flags: int, nsplit: int) -> int:
     if not _F8_AUTO:
         return 0
-    quant_out = flags & (256 | 512)
+    quant_out = flags & (MX_QC | MX_QT)
     if not quant_out and nsplit == 1 and N % 160 == 0 and N <= 1280 and M >= 4096 and K >= 1024:
         return _F8_N640_TILE
     return 0
@@ -526,7 +575,7 @@ class _FFBlockFp8(torch.autograd.Function):
             # on the 8-wave tiles the epilogue also writes dx's column sums per row tile: the bias
             # gradient of the dense that produced x (a transformer layer's out projection) is then
             # one small reduction, computed only if that backward asks (hip.colsum_for)
-            tile = _auto_tile(T, M, F, 64 if fold else 0, 1)
+            tile = _auto_tile(T, M, F, MX_RES_ADD if fold else 0, 1)
             cs = None
             if tile >= 10000 and _FUSED_COLSUM:
                 rows = tile % 1000000 // 1000

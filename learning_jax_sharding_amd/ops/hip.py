@@ -164,14 +164,17 @@ def _launch_at(i: int) -> Optional[dict]:
 
 
 def last_launch() -> dict:
-    """The host-side record of the last GEMM / attention kernel the library launched:
+    """The host-side record of the last GEMM / attention / MX-fp8 kernel the library launched:
 
     ``name`` (the kernel instance, e.g. ``gemm_lean<256,192,4,2,2>``, ``gemm_dma<128,128,2,2,4,kc,kc,bf16>``,
-    ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``, ``rope<bf16,bf16>`` / ``rope<bf16,bf16,inv>``),
-    ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 GEMMs
+    ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``, ``rope<bf16,bf16>`` / ``rope<bf16,bf16,inv>``,
+    ``gemm_mx_fp8<128,2,fix=1>``, ``gemm_mx8<256,160,4,bf16,2>``, ``quant_mx_rows``, ``quant_mx_cols<tiled>`` /
+    ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``),
+    ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
     it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
-    and ``variant`` (the LDS-DMA / lean kernels' epilogue instance); for the attention forward
+    and ``variant`` (the LDS-DMA / lean kernels' epilogue instance; the 4-wave MX-fp8 kernel's
+    compile-time epilogue ``FIX``, None on the 8-wave tiles); for the attention forward
     ``acc_mode``.  Fields that do not apply are None.
 
     The record is made where the launch is issued, so under graph capture it is made when the

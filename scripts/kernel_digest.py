@@ -1,7 +1,8 @@
-"""SHA-256 of what the streaming kernels (norm, xent, loss, elementwise) and the bf16 GEMMs compute on
-a fixed list of small seeded cases, one ``case-name sha256`` line per output tensor: two builds of
-the library compute the same bits exactly when their lines are equal.  The ``gemm`` group also
-prints each case's launch record, so equal lines mean the same kernels on the same grids too.
+"""SHA-256 of what the streaming kernels (norm, xent, loss, elementwise), the bf16 GEMMs and the MX-fp8
+GEMMs compute on a fixed list of small seeded cases, one ``case-name sha256`` line per output tensor:
+two builds of the library compute the same bits exactly when their lines are equal.  The ``gemm``
+group also prints each case's launch record, so equal lines mean the same kernels on the same grids
+too; the ``mx`` group prints hashes only, so it also runs on a library that records no fp8 launch.
 
     python scripts/kernel_digest.py [--json out.json] [--grep norm]
     LJS_KERNELS_LIB=path/to/libljs_kernels.so python scripts/kernel_digest.py    # another build
@@ -281,7 +282,62 @@ def gemm_cases(out):
     _gemm(out, "gemm/atomics/1282/320x128x2048s4", 1282, 0, 0, 1, 320, 128, 2048, hashed=False, splitk=4, zero_c=True)
 
 
-GROUPS = {"gemm": gemm_cases, "norm": norm_cases, "xent": xent_cases, "sum": sum_cases, "colsum": colsum_cases, "mse": mse_cases,
+def mx_cases(out):
+    """fp8.hip's MX GEMM launcher on the cases of tests/test_fp8_gemm_oracle_gpu.py (constructed
+    operands of tests/gemm_oracle.py mx_case): every tile code x {f32, bf16 + bias + ReLU}, the split,
+    the broadcast operands, residual and masks, the MX copies, the fused column sums and the two
+    copies-only calls of the FF block (FIX 1 / 2)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gemm_oracle as O
+    import test_fp8_picks as P
+    from learning_jax_sharding_amd.ops import fp8
+
+    def run(name, c, M, N, K, odt, tile, nsplit=1, copies=False, colsum_rows=0, **kw):
+        ops = [c[n].to(DEV) for n in ("qa", "sa", "qb", "sb")]
+        bias = None if c["bias"] is None else c["bias"].to(DEV)
+        res = None if c["res"] is None else c["res"].to(DEV)
+        C = None if odt is None else torch.full((nsplit, M, N), float("nan"), dtype=odt, device=DEV)
+        if copies:
+            q = [torch.full(s, 0xAB, dtype=torch.uint8, device=DEV) for s in ((M, N), (M, N // 32), (N, M), (N, M // 32))]
+            kw.update(qout=(q[0], q[1]), qtout=(q[2], q[3]))
+        if colsum_rows:
+            kw["colsum"] = torch.full((colsum_rows, N), float("nan"), device=DEV)
+        fp8.gemm_mx(*ops, M, N, K, None if C is None else (C if nsplit > 1 else C[0]), bias=bias, res=res,
+                    res_mode=c["res_mode"], tile=tile, nsplit=nsplit, **kw)
+        if C is not None:
+            out.add(name + "/C", C)
+        for k, t in zip(("QC", "SC", "QT", "ST"), q if copies else ()):
+            out.add(f"{name}/{k}", t)
+        if colsum_rows:
+            out.add(name + "/colsum", kw["colsum"])
+
+    for tile, (_, bm, bn, _, _) in P.MX_TILES.items():
+        M, N = bm + 8, bn + 8
+        for K in (128, 384):
+            run(f"mx/tile/{tile}/f32/{M}x{N}x{K}", O.mx_case(M, N, K, seed=tile % 977 + K), M, N, K, F32, tile)
+            c = O.mx_case(M, N, K, bias=True, relu=True, out=BF16, seed=tile % 977 + K)
+            run(f"mx/tile/{tile}/bf16-bias-relu/{M}x{N}x{K}", c, M, N, K, BF16, tile, relu=True)
+    for tile in (1282, 256160):
+        bm, bn = P.MX_TILES[tile][1:3]
+        M, N = bm + 8, bn + 8
+        run(f"mx/split/{tile}", O.mx_case(M, N, 384, nsplit=2, seed=tile % 977), M, N, 384, F32, tile, nsplit=2)
+        for which in ("a_bcast", "b_bcast"):
+            c = O.mx_case(M, N, 384, seed=tile % 977 + 1, **{which: True})
+            run(f"mx/{which}/{tile}", c, M, N, 384, F32, tile, **{which: True})
+        for mode, kind in (("add", "bf16"), ("mask", "bf16"), ("mask", "e4m3")):
+            c = O.mx_case(M, N, 128, bias=True, out=BF16, res=(mode, kind), seed=tile % 977 + 2)
+            run(f"mx/res/{tile}/{mode}-{kind}", c, M, N, 128, BF16, tile)
+        M, N = bm + 32, bn + 32
+        c = O.mx_case(M, N, 128, bias=True, relu=True, out=BF16, seed=tile % 977 + 3)
+        run(f"mx/copies/{tile}", c, M, N, 128, BF16, tile, relu=True, copies=True)
+    M, N = 256 + 8, 160 + 8
+    run("mx/colsum/256160", O.mx_case(M, N, 128, lo=-2, hi=2, out=BF16, seed=7), M, N, 128, BF16, 256160, colsum_rows=2)
+    for fix, K in ((1, 128), (1, 384), (2, 128), (2, 384)):
+        c = O.mx_case(160, 160, K, relu=fix == 1, out=BF16, res=("mask", "e4m3") if fix == 2 else None, seed=fix + K)
+        run(f"mx/fix{fix}/160x160x{K}", c, 160, 160, K, None, 1282, relu=fix == 1, copies=True)
+
+
+GROUPS = {"gemm": gemm_cases, "mx": mx_cases, "norm": norm_cases, "xent": xent_cases, "sum": sum_cases, "colsum": colsum_cases, "mse": mse_cases,
           "misc": misc_cases}
 
 

@@ -29,7 +29,7 @@ def test_kernel_library_abi(built):
     from learning_jax_sharding_amd.ops.hip import _SIGS
     ex = _exports(built[0])
     missing = [n for n in list(_SIGS) + ["ljs_p2p_barrier", "ljs_p2p_reduce", "ljs_p2p_gather", "ljs_p2p_copy",
-                                         "ljs_attn_set_trace", "ljs_gemm_mx_fp8", "ljs_quant_mx_rows"]
+                                         "ljs_attn_set_trace", "ljs_gemm_mx_fp8", "ljs_gemm_mx_plan", "ljs_quant_mx_rows"]
                if n not in ex]
     assert not missing, missing
     # every template kernel has its host launch stub (hipcc drops them without explicit instantiation)
