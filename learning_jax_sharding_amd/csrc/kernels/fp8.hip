@@ -32,6 +32,49 @@ __device__ __forceinline__ float ldf(const void* p, long i, int is_bf16) {
 
 // (mx_exponent / pack4_e4m3: common.h, shared with the optimizer's MX weight shadows)
 
+// Row-blocked MX quantization of 32 consecutive bf16 held as four 16-byte words: the block amax as
+// an integer max of the magnitude bits, then the gfx950 scaled conversions straight from the pairs
+// (cvt4_e4m3_bf16; bit-identical to the multiply + pack4 path).  o: the 32 e4m3 bytes; returns
+// the block's unbiased exponent.
+__device__ __forceinline__ int mx_quant_row32(const u32x4 (&w)[4], u32x4 (&o)[2]) {
+  unsigned mx = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const unsigned a = w[k][e] & 0x7fff7fffu;
+      mx = max(mx, max(a & 0xffffu, a >> 16));
+    }
+  const int x = mx_exponent(__uint_as_float(mx << 16));
+  const float sc = mx_scale_pow2(x);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) o[c >> 2][c & 3] = cvt4_e4m3_bf16(w[c >> 1][2 * (c & 1)], w[c >> 1][2 * (c & 1) + 1], sc);
+  return x;
+}
+
+// Transposed MX copy of a bf16 image, one work item: h = 32 rows of the column pair (c, c + 1) as
+// packed words (column c in the low halves).  The block amax of each column as an integer max of
+// the magnitude bits (both columns at once), then the rows re-paired along the column for the
+// scaled conversions.  x[j], o[j]: unbiased exponent and 32 e4m3 bytes of column c + j.
+__device__ __forceinline__ void mx_quant_colpair32(const unsigned (&h)[32], int (&x)[2], u32x4 (&o)[2][2]) {
+  unsigned mx = 0u;
+#pragma unroll
+  for (int k = 0; k < 32; ++k) {
+    const unsigned a = h[k] & 0x7fff7fffu;
+    mx = max(mx & 0xffffu, a & 0xffffu) | max(mx & 0xffff0000u, a & 0xffff0000u);
+  }
+  x[0] = mx_exponent(__uint_as_float(mx << 16));
+  x[1] = mx_exponent(__uint_as_float(mx & 0xffff0000u));
+  const float s0 = mx_scale_pow2(x[0]), s1 = mx_scale_pow2(x[1]);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    o[0][k >> 2][k & 3] = cvt4_e4m3_bf16((h[4 * k] & 0xffffu) | (h[4 * k + 1] << 16),
+                                         (h[4 * k + 2] & 0xffffu) | (h[4 * k + 3] << 16), s0);
+    o[1][k >> 2][k & 3] = cvt4_e4m3_bf16((h[4 * k] >> 16) | (h[4 * k + 1] & 0xffff0000u),
+                                         (h[4 * k + 2] >> 16) | (h[4 * k + 3] & 0xffff0000u), s1);
+  }
+}
+
 // one thread per 32-element block of a row.  xb (f32 input only, may be null): the same rows
 // rounded to bf16, [R][K] contiguous -- the MX layer's backward operand, written from the values
 // already in registers instead of by a second pass over x (verdict r5 item 5: no standalone
@@ -173,24 +216,11 @@ __global__ __launch_bounds__(256) void quant_mx_cols_tiled_kernel(const void* __
   if (qr) {
     // row blocks: thread (tile row r, 32-column half hb) -- 4 x 16 B LDS chunks
     const int r = tid >> 1, hb = tid & 1;
-    u32x4 raw[4];
-    unsigned mr = 0u;
+    u32x4 raw[4], orr[2];
 #pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4) {
-      const int ch = hb * 4 + c4;
-      raw[c4] = *reinterpret_cast<const u32x4*>(tile + r * 128 + ((ch ^ ((r >> 5) & 3)) << 4));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned a = raw[c4][e] & 0x7fff7fffu;
-        mr = max(mr, max(a & 0xffffu, a >> 16));
-      }
-    }
-    const int xr = mx_exponent(__uint_as_float(mr << 16));
-    const float scr = mx_scale_pow2(xr);
-    u32x4 orr[2];
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-      orr[c >> 2][c & 3] = cvt4_e4m3_bf16(raw[c >> 1][2 * (c & 1)], raw[c >> 1][2 * (c & 1) + 1], scr);
+    for (int c4 = 0; c4 < 4; ++c4)
+      raw[c4] = *reinterpret_cast<const u32x4*>(tile + r * 128 + (((hb * 4 + c4) ^ ((r >> 5) & 3)) << 4));
+    const int xr = mx_quant_row32(raw, orr);
     u32x4* qd = reinterpret_cast<u32x4*>(qr + (long)(k0 + r) * N + n0 + hb * 32);
     qd[0] = orr[0];
     qd[1] = orr[1];
@@ -300,6 +330,45 @@ __device__ __forceinline__ void f8_dma(__amdgpu_buffer_rsrc_t rs, void* lds, int
 }
 __device__ __forceinline__ f32x4 f8_mfma(const i32x8& a, const i32x8& b, const f32x4& c, int sa, int sb) {
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, sa, 0, sb);
+}
+
+// the bias of output column col as f32 (0 without a bias or past N)
+__device__ __forceinline__ float mx_bias(const F8Args& p, int col, bool has_bias, bool bias_f32) {
+  if (!has_bias || col >= p.N) return 0.f;
+  return bias_f32 ? reinterpret_cast<const float*>(p.bias)[col] : bf2f(reinterpret_cast<const bf16_t*>(p.bias)[col]);
+}
+
+// Epilogue operand R applied to N consecutive output values (after bias / ReLU, f32).  r: R's N
+// values as packed words -- bf16 pairs (N / 2 words), or with r_fp8 e4m3 bytes (N / 4 words).
+//   residual add : bf16(y) + R, rounded by the caller's pack: the unfused bf16 add, both roundings kept
+//   ReLU mask    : keep where R > 0; for e4m3 R (a ReLU output kept only as e4m3): sign clear, not zero
+template <int N, typename RV>
+__device__ __forceinline__ void mx_apply_res(float (&v)[N], const RV& r, bool res_add, bool res_mask, bool r_fp8) {
+  if (res_mask && r_fp8) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const unsigned byte = (r[e >> 2] >> (8 * (e & 3))) & 0xffu;
+      v[e] = ((byte & 0x80u) == 0u && byte != 0u) ? v[e] : 0.f;
+    }
+  } else if (res_add || res_mask) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const unsigned w = r[e >> 1];
+      const float rf = (e & 1) ? __uint_as_float(w & 0xffff0000u) : __uint_as_float(w << 16);
+      if (res_add) v[e] = bf2f(f2bf(v[e])) + rf;
+      else v[e] = rf > 0.f ? v[e] : 0.f;
+    }
+  }
+}
+
+// mx_quant_colpair32's result for column gcol, rows grow .. grow + 31, to QT / ST (M % 32 == 0
+// (launcher): blocks are whole; N % 8: pairs are whole)
+__device__ __forceinline__ void mx_store_qt_col(const F8Args& p, int gcol, int grow, int x, const u32x4 (&o)[2]) {
+  if (grow >= p.M || gcol >= p.N) return;
+  u32x4* dst = reinterpret_cast<u32x4*>(p.QT + (long)gcol * p.ldqt + grow);
+  dst[0] = o[0];
+  dst[1] = o[1];
+  p.ST[(long)gcol * (p.ldqt / 32) + grow / 32] = (unsigned char)(x + 127);
 }
 
 // BM x 128 output tile, BM / 64 x 2 waves of 64 x 64 (BM = 128: 4 waves; 256: 8 waves, two per
@@ -480,11 +549,7 @@ __global__ __launch_bounds__(BM * 2) void gemm_mx_fp8_kernel(F8Args p) {
     const int col = n0 + wc * 64 + 16 * (even ? 2 * q : 2 * q + 1) + 4 * (g & ~1);
     float bv[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      bv[e] = 0.f;
-      if (has_bias && col + e < p.N) bv[e] = bias_f32 ? reinterpret_cast<const float*>(p.bias)[col + e]
-                                                      : bf2f(reinterpret_cast<const bf16_t*>(p.bias)[col + e]);
-    }
+    for (int e = 0; e < 8; ++e) bv[e] = mx_bias(p, col + e, has_bias, bias_f32);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const f32x4 a0 = acc[i][2 * q], a1 = acc[i][2 * q + 1];
@@ -501,28 +566,7 @@ __global__ __launch_bounds__(BM * 2) void gemm_mx_fp8_kernel(F8Args p) {
       }
       const int row = m0 + wr * 64 + 16 * i + r16;
       const bool ok = row < p.M && col < p.N;  // N % 8 == 0 (launcher)
-      if (res_mask && r_fp8) {
-        // the mask of a ReLU whose output is kept only as e4m3: keep where that value is > 0
-        // (sign clear, not zero)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const unsigned byte = (rv[q][i][e >> 2] >> (8 * (e & 3))) & 0xffu;
-          v[e] = (byte & 0x80u) == 0u && byte != 0u ? v[e] : 0.f;
-        }
-      } else if (res_add || res_mask) {
-        const u32x4 rw = rv[q][i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float r0 = __uint_as_float(rw[e] << 16), r1 = __uint_as_float(rw[e] & 0xffff0000u);
-          if (res_add) {  // bf16(bf16(y) + R): the unfused bf16 add
-            v[2 * e] = bf2f(f2bf(v[2 * e])) + r0;
-            v[2 * e + 1] = bf2f(f2bf(v[2 * e + 1])) + r1;
-          } else {
-            v[2 * e] = r0 > 0.f ? v[2 * e] : 0.f;
-            v[2 * e + 1] = r1 > 0.f ? v[2 * e + 1] : 0.f;
-          }
-        }
-      }
+      mx_apply_res(v, rv[q][i], res_add, res_mask, r_fp8);
       if (qout && staged) {
         // MX-fp8 copy of the bf16-rounded outputs from their packed bf16 pairs: block amax over
         // the 4 lanes of the block (rounding is monotonic: max of the rounded values = the
@@ -633,46 +677,17 @@ __global__ __launch_bounds__(BM * 2) void gemm_mx_fp8_kernel(F8Args p) {
 #pragma unroll
     for (int r = 0; r < 64 * NB / NT; ++r) {
       const int w = tid + NT * r, c = 2 * (w / NB), tb = w % NB;
-      // 32 rows of the column pair (c, c + 1) as packed bf16 words; the block amax of each column
-      // as an integer max of the magnitude bits (both columns at once), then the rows re-paired
-      // along the column for the scaled conversions
       unsigned h[32];
-      unsigned mx = 0u;
 #pragma unroll
       for (int k = 0; k < 32; ++k) {
         const int lr = tb * 32 + k;
         h[k] = *reinterpret_cast<const unsigned*>(Cs + lr * 256 + (((c >> 3) ^ (lr & 15)) << 4) + ((c & 7) << 1));
-        const unsigned a = h[k] & 0x7fff7fffu;
-        mx = max(mx & 0xffffu, a & 0xffffu) | max(mx & 0xffff0000u, a & 0xffff0000u);
       }
-      const float a0 = __uint_as_float(mx << 16), a1 = __uint_as_float(mx & 0xffff0000u);
-      const int x0 = mx_exponent(a0), x1 = mx_exponent(a1);
-      const float s0 = mx_scale_pow2(x0), s1 = mx_scale_pow2(x1);
-      u32x4 o0[2], o1[2];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const unsigned p00 = (h[4 * k] & 0xffffu) | (h[4 * k + 1] << 16);
-        const unsigned p01 = (h[4 * k + 2] & 0xffffu) | (h[4 * k + 3] << 16);
-        const unsigned p10 = (h[4 * k] >> 16) | (h[4 * k + 1] & 0xffff0000u);
-        const unsigned p11 = (h[4 * k + 2] >> 16) | (h[4 * k + 3] & 0xffff0000u);
-        o0[k >> 2][k & 3] = cvt4_e4m3_bf16(p00, p01, s0);
-        o1[k >> 2][k & 3] = cvt4_e4m3_bf16(p10, p11, s1);
-      }
-      const int gcol = n0 + c, grow = m0 + tb * 32;
-      if (grow < p.M) {  // M % 32 == 0 (launcher): blocks are whole; N % 8: pairs are whole
-        if (gcol < p.N) {
-          u32x4* dst = reinterpret_cast<u32x4*>(p.QT + (long)gcol * p.ldqt + grow);
-          dst[0] = o0[0];
-          dst[1] = o0[1];
-          p.ST[(long)gcol * (p.ldqt / 32) + grow / 32] = (unsigned char)(x0 + 127);
-        }
-        if (gcol + 1 < p.N) {
-          u32x4* dst = reinterpret_cast<u32x4*>(p.QT + (long)(gcol + 1) * p.ldqt + grow);
-          dst[0] = o1[0];
-          dst[1] = o1[1];
-          p.ST[(long)(gcol + 1) * (p.ldqt / 32) + grow / 32] = (unsigned char)(x1 + 127);
-        }
-      }
+      int x[2];
+      u32x4 o[2][2];
+      mx_quant_colpair32(h, x, o);
+      mx_store_qt_col(p, n0 + c, m0 + tb * 32, x[0], o[0]);
+      mx_store_qt_col(p, n0 + c + 1, m0 + tb * 32, x[1], o[1]);
     }
   }
 }
@@ -821,12 +836,7 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
 #pragma unroll
   for (int j = 0; j < TN; ++j)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int col = n0 + colb + 16 * j + e;
-      bv[j][e] = (has_bias && col < p.N) ? (bias_f32 ? reinterpret_cast<const float*>(p.bias)[col]
-                                                     : bf2f(reinterpret_cast<const bf16_t*>(p.bias)[col]))
-                                         : 0.f;
-    }
+    for (int e = 0; e < 4; ++e) bv[j][e] = mx_bias(p, n0 + colb + 16 * j + e, has_bias, bias_f32);
   if constexpr (F32) {
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -877,21 +887,7 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
           v[e] = acc[i][j][e] + bv[j][e];
           if (relu) v[e] = fmaxf(v[e], 0.f);
         }
-        if (res_mask && r_fp8) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const unsigned byte = (rv[j][0] >> (8 * e)) & 0xffu;
-            v[e] = ((byte & 0x80u) == 0u && byte != 0u) ? v[e] : 0.f;
-          }
-        } else if (res_add || res_mask) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const unsigned w = rv[j][e >> 1];
-            const float r = (e & 1) ? __uint_as_float(w & 0xffff0000u) : __uint_as_float(w << 16);
-            if (res_add) v[e] = bf2f(f2bf(v[e])) + r;
-            else v[e] = r > 0.f ? v[e] : 0.f;
-          }
-        }
+        mx_apply_res(v, rv[j], res_add, res_mask, r_fp8);
         *reinterpret_cast<u32x2*>(smem + lr * RS + (colb + 16 * j) * 2) =
             u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
       }
@@ -929,24 +925,10 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
       for (int it = tid; it < BM * (BN / 32); it += 512) {
         const int lr = it % BM, b = it / BM;
         const int grow = m0 + lr, gcol = n0 + 32 * b;
-        // 32 bf16 of the row as 16 packed words: amax as an integer max of the magnitude bits,
-        // then the scaled conversions straight from the pairs
-        u32x4 w[4];
-        unsigned mx = 0u;
+        u32x4 w[4], o[2];  // 32 bf16 of the row as 16 packed words
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          w[k] = *reinterpret_cast<const u32x4*>(smem + lr * RS + b * 64 + k * 16);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const unsigned a = w[k][e] & 0x7fff7fffu;
-            mx = max(mx, max(a & 0xffffu, a >> 16));
-          }
-        }
-        const int x = mx_exponent(__uint_as_float(mx << 16));
-        const float sc = mx_scale_pow2(x);
-        u32x4 o[2];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o[c >> 2][c & 3] = cvt4_e4m3_bf16(w[c >> 1][2 * (c & 1)], w[c >> 1][2 * (c & 1) + 1], sc);
+        for (int k = 0; k < 4; ++k) w[k] = *reinterpret_cast<const u32x4*>(smem + lr * RS + b * 64 + k * 16);
+        const int x = mx_quant_row32(w, o);
         if (grow < p.M && gcol < p.N) {
           u32x4* dst = reinterpret_cast<u32x4*>(p.QC + (long)grow * p.N + gcol);
           dst[0] = o[0];
@@ -959,38 +941,13 @@ __global__ __launch_bounds__(512) void gemm_mx8_kernel(F8Args p) {
       for (int it = tid; it < (BN / 2) * (BM / 32); it += 512) {
         const int cp = it % (BN / 2), tb = it / (BN / 2);
         unsigned h[32];
-        unsigned mx = 0u;
 #pragma unroll
-        for (int k = 0; k < 32; ++k) {
-          h[k] = *reinterpret_cast<const unsigned*>(smem + (tb * 32 + k) * RS + cp * 4);
-          const unsigned a = h[k] & 0x7fff7fffu;
-          mx = max(mx & 0xffffu, a & 0xffffu) | max(mx & 0xffff0000u, a & 0xffff0000u);
-        }
-        const int x0 = mx_exponent(__uint_as_float(mx << 16)), x1 = mx_exponent(__uint_as_float(mx & 0xffff0000u));
-        const float s0 = mx_scale_pow2(x0), s1 = mx_scale_pow2(x1);
-        u32x4 o0[2], o1[2];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          o0[k >> 2][k & 3] = cvt4_e4m3_bf16((h[4 * k] & 0xffffu) | (h[4 * k + 1] << 16),
-                                             (h[4 * k + 2] & 0xffffu) | (h[4 * k + 3] << 16), s0);
-          o1[k >> 2][k & 3] = cvt4_e4m3_bf16((h[4 * k] >> 16) | (h[4 * k + 1] & 0xffff0000u),
-                                             (h[4 * k + 2] >> 16) | (h[4 * k + 3] & 0xffff0000u), s1);
-        }
-        const int gcol = n0 + 2 * cp, grow = m0 + tb * 32;
-        if (grow < p.M) {  // M % 32 == 0 (launcher): blocks are whole; N % 8: pairs are whole
-          if (gcol < p.N) {
-            u32x4* dst = reinterpret_cast<u32x4*>(p.QT + (long)gcol * p.ldqt + grow);
-            dst[0] = o0[0];
-            dst[1] = o0[1];
-            p.ST[(long)gcol * (p.ldqt / 32) + grow / 32] = (unsigned char)(x0 + 127);
-          }
-          if (gcol + 1 < p.N) {
-            u32x4* dst = reinterpret_cast<u32x4*>(p.QT + (long)(gcol + 1) * p.ldqt + grow);
-            dst[0] = o1[0];
-            dst[1] = o1[1];
-            p.ST[(long)(gcol + 1) * (p.ldqt / 32) + grow / 32] = (unsigned char)(x1 + 127);
-          }
-        }
+        for (int k = 0; k < 32; ++k) h[k] = *reinterpret_cast<const unsigned*>(smem + (tb * 32 + k) * RS + cp * 4);
+        int x[2];
+        u32x4 o[2][2];
+        mx_quant_colpair32(h, x, o);
+        mx_store_qt_col(p, n0 + 2 * cp, m0 + tb * 32, x[0], o[0]);
+        mx_store_qt_col(p, n0 + 2 * cp + 1, m0 + tb * 32, x[1], o[1]);
       }
     }
   }

@@ -921,112 +921,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const int bid, 
     const int m0 = w.m0 * BM + wr * (BM / WM), n0 = w.n0 * BN + wc * (BN / WN);
     const int g = lane >> 4;
     if constexpr (!OUT_F32) {
-      // lane holds C[16 ii + (lane & 15)][16 j + 4 g + 0..3]; lanes g, g^1 trade halves so
-      // even g owns cols 16 j0 + 4 g .. +7 and odd g owns 16 j1 + 4 (g - 1) .. +7
-      const bool even = (g & 1) == 0;
-      // epilogue operand: one row block (ii) of R chunks in flight at a time (all of an item's
-      // chunks at once cost the second resident block its registers); rows / columns past
-      // M / N read 0 through the buffer range check, and the compiler's counted vmcnt waits
-      // for them at first use
-      // (two row blocks in registers: block ii + 1's loads are issued before block ii is
-      // processed, so only the first block's latency is exposed per item)
-      u32x4 rv[2][TN / 2][RES == 2 ? 2 : 1];
-      __amdgpu_buffer_rsrc_t rr;
-      if constexpr (HAS_R)
-        rr = make_rsrc(p.res, (RES == 2 ? 4 : 2) * ((long)(p.batch - 1) * p.sR + (long)(p.M - 1) * p.ldr + p.N));
-      auto load_r = [&](int ii) {
-        if constexpr (HAS_R) {
-#pragma unroll
-          for (int q = 0; q < TN / 2; ++q) {
-            const int col = n0 + 16 * (even ? 2 * q : 2 * q + 1) + 4 * (g & ~1);
-            const int row = m0 + ii * 16 + (lane & 15);
-            const bool ok = row < p.M && col < p.N;
-            const int off = ok ? (int)(((long)w.b * p.sR + (long)row * p.ldr + col) * (RES == 2 ? 4 : 2)) : 0x7ffffff0;
-            rv[ii & 1][q][0] = __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0);
-            if constexpr (RES == 2)
-              rv[ii & 1][q][RES == 2 ? 1 : 0] = __builtin_amdgcn_raw_buffer_load_b128(rr, ok ? off + 16 : off, 0, 0);
-          }
-        }
-      };
-      load_r(0);
-      float bvs[TN / 2][8];
-      // bias: this lane's 8 consecutive columns as one or two 16-byte loads (aligned bias rows;
-      // N % 8 == 0 here) instead of 8 scalar loads of each width
-      const bool bias_vec = has_bias && ((((uintptr_t)p.bias) & 15) == 0) && (p.sBias % 8) == 0;
-#pragma unroll
-      for (int q = 0; q < TN / 2; ++q) {
-        const int col = n0 + 16 * (even ? 2 * q : 2 * q + 1) + 4 * (g & ~1);
-        const long bo = (long)w.b * p.sBias + col;
-        if (bias_vec && col + 8 <= p.N) {
-          if (bias_f32) {
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + bo);
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + bo + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              bvs[q][e] = lo[e];
-              bvs[q][4 + e] = hi[e];
-            }
-          } else {
-            const u32x4 u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(p.bias) + bo);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              bvs[q][2 * e] = __uint_as_float(u[e] << 16);
-              bvs[q][2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u);
-            }
-          }
-          continue;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          bvs[q][e] = 0.f;
-          if (has_bias && col + e < p.N) {
-            bvs[q][e] = bias_f32 ? reinterpret_cast<const float*>(p.bias)[bo + e]
-                                 : bf2f(reinterpret_cast<const bf16_t*>(p.bias)[bo + e]);
-          }
-        }
-      }
-#pragma unroll
-      for (int ii = 0; ii < TM; ++ii) {
-        if (ii + 1 < TM) load_r(ii + 1);
-#pragma unroll
-        for (int q = 0; q < TN / 2; ++q) {  // both halves of a row's 128 B back to back
-          const int col = n0 + 16 * (even ? 2 * q : 2 * q + 1) + 4 * (g & ~1);
-          const float* bv = bvs[q];
-          const f32x4 a0 = NOALPHA ? acc[ii][2 * q] : acc[ii][2 * q] * p.alpha;
-          const f32x4 a1 = NOALPHA ? acc[ii][2 * q + 1] : acc[ii][2 * q + 1] * p.alpha;
-          acc[ii][2 * q] = f32x4{0.f, 0.f, 0.f, 0.f};
-          acc[ii][2 * q + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-          float v[8];
-          pair_rows16(a0, a1, even, v);
-          u32x4 pk;
-          if constexpr (!PLAIN) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              v[e] += bv[e];
-              if (relu) v[e] = fmaxf(v[e], 0.f);
-            }
-          }
-          if constexpr (HAS_R) apply_res8(v, p.flags, rv[ii & 1][q][0], rv[ii & 1][q][0], rv[ii & 1][q][RES == 2 ? 1 : 0]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) pk[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-          const int row = m0 + ii * 16 + (lane & 15);
-          const bool ok = row < p.M && col < p.N;  // N % 8 == 0 (launcher): chunks are whole
-          const int off = ok ? (int)(((long)w.b * p.sC + (long)row * p.ldc + col) * 2) : 0x7ffffff0;
-          if (st_sc1) __builtin_amdgcn_raw_buffer_store_b128(pk, rc, off, 0, kSC1);
-          else __builtin_amdgcn_raw_buffer_store_b128(pk, rc, off, 0, 0);
-          if (psum_on && ok) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) tsum += __uint_as_float(pk[e] << 16) + __uint_as_float(pk[e] & 0xffff0000u);
-          }
-        }
-      }
-      if (psum_on) {
-        // fused loss reduction: this wave's share of sum(C) -- of the bf16 values just stored --
-        // to its own slot (one store per wave, counted in the next K-step's vmcnt)
-        tsum = warp_sum64(tsum);
-        if (lane == 0) p.psum[(long)(slot + G * it) * NW + wave] = tsum;
-        tsum = 0.f;
-      }
+#include "gemm_epi_bf16.h"   // S_EPI (+1 fused-sum) stores per lane: what wait_landed counts after_epi
       after_epi = true;
     } else {
       // lane holds C[16 ii + (lane & 15)][16 j + 4 g + 0..3]
@@ -1170,7 +1065,8 @@ gemm_dma_group2_kernel(GemmArgs p0, GemmArgs p1, int g0) {
 //    item's last K-tile, its epilogue and the next item's first barrier are peeled;
 //  * the issue cursor never tests for the end: past the block's last item it issues K-tiles that
 //    read zeros (an empty-range descriptor) into stages nothing reads again, so every step's count is the same.
-// Operands, images, fragment reads, MFMA orientation and the epilogue are gemm_dma_kernel's
+// Operands, images, fragment reads and MFMA orientation are gemm_dma_kernel's; the epilogue is
+// shared with it, one text included by both (gemm_epi_bf16.h)
 // (bit-identical results: tests/test_kernels_gpu.py::test_gemm_lean_bit_exact).
 // The issue cursor's K-tiles past the block's last item go through a buffer descriptor with an
 // empty range: every lane is out of range whatever its offsets, so the pieces read zeros without a
@@ -1322,100 +1218,7 @@ gemm_lean_kernel(GemmArgs p) {
     const WorkItem w = decode_item(p, slot + G * it, ntm, ntn);
     const int m0 = w.m0 * BM + wr * (BM / WM), n0 = w.n0 * BN + wc * (BN / WN);
     const int g = lane >> 4;
-    const bool even = (g & 1) == 0;
-    u32x4 rv[2][TN / 2][RES == 2 ? 2 : 1];
-    __amdgpu_buffer_rsrc_t rr;
-    if constexpr (HAS_R)
-      rr = make_rsrc(p.res, (RES == 2 ? 4 : 2) * ((long)(p.batch - 1) * p.sR + (long)(p.M - 1) * p.ldr + p.N));
-    auto load_r = [&](int ii) {
-      if constexpr (HAS_R) {
-#pragma unroll
-        for (int q = 0; q < TN / 2; ++q) {
-          const int col = n0 + 16 * (even ? 2 * q : 2 * q + 1) + 4 * (g & ~1);
-          const int row = m0 + ii * 16 + (lane & 15);
-          const bool ok = row < p.M && col < p.N;
-          const int off = ok ? (int)(((long)w.b * p.sR + (long)row * p.ldr + col) * (RES == 2 ? 4 : 2)) : 0x7ffffff0;
-          rv[ii & 1][q][0] = __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0);
-          if constexpr (RES == 2)
-            rv[ii & 1][q][RES == 2 ? 1 : 0] = __builtin_amdgcn_raw_buffer_load_b128(rr, ok ? off + 16 : off, 0, 0);
-        }
-      }
-    };
-    load_r(0);
-    float bvs[TN / 2][8];
-    const bool bias_vec = has_bias && ((((uintptr_t)p.bias) & 15) == 0) && (p.sBias % 8) == 0;
-#pragma unroll
-    for (int q = 0; q < TN / 2; ++q) {
-      const int col = n0 + 16 * (even ? 2 * q : 2 * q + 1) + 4 * (g & ~1);
-      const long bo = (long)w.b * p.sBias + col;
-      if (bias_vec && col + 8 <= p.N) {
-        if (bias_f32) {
-          const f32x4 lo = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + bo);
-          const f32x4 hi = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(p.bias) + bo + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            bvs[q][e] = lo[e];
-            bvs[q][4 + e] = hi[e];
-          }
-        } else {
-          const u32x4 u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(p.bias) + bo);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            bvs[q][2 * e] = __uint_as_float(u[e] << 16);
-            bvs[q][2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u);
-          }
-        }
-        continue;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        bvs[q][e] = 0.f;
-        if (has_bias && col + e < p.N) {
-          bvs[q][e] = bias_f32 ? reinterpret_cast<const float*>(p.bias)[bo + e]
-                               : bf2f(reinterpret_cast<const bf16_t*>(p.bias)[bo + e]);
-        }
-      }
-    }
-#pragma unroll
-    for (int ii = 0; ii < TM; ++ii) {
-      if (ii + 1 < TM) load_r(ii + 1);
-#pragma unroll
-      for (int q = 0; q < TN / 2; ++q) {
-        const int col = n0 + 16 * (even ? 2 * q : 2 * q + 1) + 4 * (g & ~1);
-        const float* bv = bvs[q];
-        const f32x4 a0 = NOALPHA ? acc[ii][2 * q] : acc[ii][2 * q] * p.alpha;
-        const f32x4 a1 = NOALPHA ? acc[ii][2 * q + 1] : acc[ii][2 * q + 1] * p.alpha;
-        acc[ii][2 * q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        acc[ii][2 * q + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float v[8];
-        pair_rows16(a0, a1, even, v);
-        u32x4 pk;
-        if constexpr (!PLAIN) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            v[e] += bv[e];
-            if (relu) v[e] = fmaxf(v[e], 0.f);
-          }
-        }
-        if constexpr (HAS_R) apply_res8(v, p.flags, rv[ii & 1][q][0], rv[ii & 1][q][0], rv[ii & 1][q][RES == 2 ? 1 : 0]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pk[e] = pack_bf16x2(v[2 * e], v[2 * e + 1]);
-        const int row = m0 + ii * 16 + (lane & 15);
-        const bool ok = row < p.M && col < p.N;  // N % 8 == 0 (launcher): chunks are whole
-        const int off = ok ? (int)(((long)w.b * p.sC + (long)row * p.ldc + col) * 2) : 0x7ffffff0;
-        if (st_sc1) __builtin_amdgcn_raw_buffer_store_b128(pk, rc, off, 0, kSC1);
-        else __builtin_amdgcn_raw_buffer_store_b128(pk, rc, off, 0, 0);
-        if (psum_on && ok) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) tsum += __uint_as_float(pk[e] << 16) + __uint_as_float(pk[e] & 0xffff0000u);
-        }
-      }
-    }
-    if (psum_on) {
-      tsum = warp_sum64(tsum);
-      if (lane == 0) p.psum[(long)(slot + G * it) * NW + wave] = tsum;
-      tsum = 0.f;
-    }
+#include "gemm_epi_bf16.h"   // S_EPI (+1 fused-sum) stores per lane: what item_start(true) counts
     if (it + 1 < my_items) item_start(true);
   }
   // the DMA pieces still in flight (the cursor's past-the-end tiles) write this block's LDS: let

@@ -261,7 +261,8 @@ def mx_operand(gen, R, K, lo=-8, hi=8):
 
 def mx_case(M, N, K, lo=-8, hi=8, a_bcast=False, b_bcast=False, bias=False, relu=False, out=torch.float32,
             res=None, nsplit=1, seed=0):
-    """One ``gemm_mx`` call on constructed operands and its exact answer.  ``res``: None or
+    """One ``gemm_mx`` call on constructed operands and its exact answer.  ``bias``: False, True (an
+    f32 bias) or its dtype.  ``res``: None or
     (mode, kind) with kind "bf16" or "e4m3" (the uint8 mask).  ``nsplit`` > 1: f32 slabs."""
     gen = torch.Generator().manual_seed(seed)
     qa, sa, A = mx_operand(gen, 1 if a_bcast else M, K, lo, hi)
@@ -274,7 +275,7 @@ def mx_case(M, N, K, lo=-8, hi=8, a_bcast=False, b_bcast=False, bias=False, relu
     mag = torch.stack([A[:, a:b].abs() @ B[:, a:b].abs().t() for a, b in parts])
     bias_t = None
     if bias:
-        bias_t = _ints(gen, (N,), lo, hi).float()
+        bias_t = _ints(gen, (N,), lo, hi).to(bias if isinstance(bias, torch.dtype) else torch.float32)   # (exact in bf16)
         y, mag = y + bias_t.double(), mag + bias_t.abs().double()
     if relu:
         y = y.clamp_min(0.0)
@@ -498,6 +499,28 @@ def build_table():
         call=dict(M=264, N=136, K=320, res=("add", bf16, False), **ga))
     add("gauss-slab", 1282, (dma_name(1282, 0, 0, 1), 3), 1282, kind="gauss", splitk=3,
         call=dict(M=136, N=72, K=448, a_kc=False, b_kc=False, out=f32, splitk=3, slabs=True, gaussian=True))
+    # ---- the shared bf16 epilogue's other combinations, general and lean (last, so the rows above
+    # keep their seeds): a misaligned f32 bias (RES 4's scalar loads), the fused sum behind the f32
+    # bias (RES 4, the out-projection's call) and behind a residual add (RES 1); then the operand
+    # instances RES 1 (bf16 R) and RES 2 (f32 R) with an aligned bias, a misaligned one and the fused
+    # sum.  With RES 0's rows above (bias-bf16-n72, bias-bf16-skew, psum) every instance that has the
+    # code runs it: RES 3 is the plain store loop, which a bias or a fused sum never reaches (the
+    # plan gives such a call RES 0 or 4), and RES 4's bias is f32 by definition.
+    for tag, req, nm in (("g", G, gname), ("l", L, lname)):
+        add(f"res1-bias-{tag}", req, (nm, 1), 1282,
+            call=dict(M=136, N=72, K=64, bias=bf16, res=("add", bf16, False)))
+        add(f"res1-bias-skew-{tag}", req, (nm, 1), 1282,
+            call=dict(M=136, N=72, K=64, bias=f32, bias_skew=1, res=("mask", bf16, False)))
+        add(f"res2-bias-{tag}", req, (nm, 2), 1282,
+            call=dict(M=136, N=72, K=64, bias=f32, res=("add", f32, False)))
+        add(f"res2-bias-skew-{tag}", req, (nm, 2), 1282,
+            call=dict(M=136, N=72, K=64, bias=bf16, bias_skew=5, relu=True, res=("mask", f32, False)))
+        add(f"psum-res2-{tag}", req, (nm, 2), 1282,
+            call=dict(M=136, N=136, K=64, lo=-2, hi=2, bias=f32, res=("add", f32, False)), psum=True)
+        add(f"bias-f32-skew-{tag}", req, (nm, 4), 1282, call=dict(M=136, N=72, K=64, bias=f32, bias_skew=1))
+        add(f"psum-bias-{tag}", req, (nm, 4), 1282, call=dict(M=136, N=136, K=64, lo=-2, hi=2, bias=f32), psum=True)
+        add(f"psum-res-{tag}", req, (nm, 1), 1282,
+            call=dict(M=136, N=136, K=64, lo=-2, hi=2, res=("add", bf16, False)), psum=True)
     return rows
 
 

@@ -60,14 +60,16 @@ def _run(F, c, M, N, K, out_dtype, tile, nsplit=1, **kw):
 
 
 @pytest.mark.parametrize("K", [128, 384])
-@pytest.mark.parametrize("mode", ["f32", "bf16_bias_relu"])
+@pytest.mark.parametrize("mode", ["f32", "bf16_bias_relu", "bf16_bias16_relu"])
 @pytest.mark.parametrize("tile", _W4 + _W8)
 def test_mx_gemm_tile_is_exact(F, tile, mode, K):
-    """Every tile code at one ragged block in each direction, one and three 128-wide K-tiles."""
+    """Every tile code at one ragged block in each direction, one and three 128-wide K-tiles
+    (bias16: the bias is bf16, else f32)."""
     bm, bn = _bm_bn(tile)
     M, N = bm + 8, bn + 8
     f32 = mode == "f32"
-    c = O.mx_case(M, N, K, bias=not f32, relu=not f32, out=torch.float32 if f32 else torch.bfloat16, seed=tile % 977 + K)
+    bias = False if f32 else (torch.bfloat16 if "bias16" in mode else True)
+    c = O.mx_case(M, N, K, bias=bias, relu=not f32, out=torch.float32 if f32 else torch.bfloat16, seed=tile % 977 + K)
     assert O.exactness(c) < 2 ** 20
     g = _run(F, c, M, N, K, c["expected"].dtype, tile, relu=not f32)
     O.assert_bits_equal(g.view, c["expected"], bm, bn)
