@@ -1,7 +1,7 @@
 // Memory-bound kernels: casts (optionally transposing), reductions, softmax, fused Adam,
 // Philox RNG.  All vectorised to 16 bytes per lane (CDNA Guideline 13); grid-stride loops
 // capped at 2048 workgroups so one launch fills the 256 CUs without oversubscription.
-#include "rowwise.h"
+#include "adam_common.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <algorithm>
@@ -316,20 +316,7 @@ __global__ void colsum_bcast_kernel(const void* __restrict__ in, int is_bf16, in
 // reading each slab as one streaming pass.  The output's columns may be split into column
 // blocks of width cb stored as separate [R][cb] matrices (out_bs apart): the fused dW[q|k|v]
 // GEMM produces [640][1536] slabs whose column blocks are dWq, dWk, dWv.
-// 4 consecutive slab elements as f32 from f32 or bf16 slabs (bf16 slabs: the weight-gradient
-// GEMM's split-K partials rounded once each, summed here in f32)
-template <typename ST>
-__device__ __forceinline__ f32x4 ld_slab4(const ST* __restrict__ p, long e) {
-  // global (not flat) loads: they retire in order, so a loop can wait for an older group with a
-  // counted vmcnt while a younger one is in flight (a flat load forces vmcnt(0) + lgkmcnt(0))
-  if constexpr (sizeof(ST) == 4) {
-    return *(const __attribute__((address_space(1))) f32x4*)(reinterpret_cast<const float*>(p) + e);
-  } else {
-    const u32x2 r = *(const __attribute__((address_space(1))) u32x2*)(reinterpret_cast<const bf16_t*>(p) + e);
-    return unpack_bf16x4(r);
-  }
-}
-
+// (ld_slab4, the slabs' 4-element load: adam_common.h)
 template <typename ST>
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const ST* __restrict__ slabs, int S, long slab_stride,
                                                           int R, int C, float* __restrict__ out, int cb,
@@ -508,42 +495,10 @@ __global__ void adam_kernel(const float* __restrict__ p, const G* __restrict__ g
   }
 }
 
-// Multi-tensor Adam over 64x64 tiles of up to 32 parameters per launch (pointers passed by value
-// in the kernel arguments, so the launch is HIP-graph capturable).  Besides p/m/v (in place) it
-// refreshes the parameter's bf16 "shadows" used by the next step's MFMA GEMMs: the plain [R][C]
-// copy and the transposed [C][R] copy (staged through LDS so both writes are coalesced).  This
-// removes every per-step f32->bf16 weight cast kernel from the training step.
-struct AdamTensor {
-  long p, g, m, v, st, sn, R, C, g_bf16, tiles_c, vec;  // vec: 4-wide path allowed (C % 4, alignment)
-  // MX-fp8 shadows of the new weight (0 = none; R, C % 64 == 0, 64-row tiles, vec path):
-  // qn[R][C] + sn8[R][C/32] (blocks along rows, quant_mx_rows' layout: a dX GEMM's B operand)
-  // and qt[C][R] + st8[C][R/32] (blocks along columns, transposed: a forward GEMM's B operand)
-  long qn, sn8, qt, st8;
-  // gradient source: gS = 0 a plain [R][C] tensor (row stride g_ld = C); gS > 0 the gS f32
-  // split-K slabs of a weight-gradient GEMM, g_ss floats apart, row stride g_ld (the gradient is
-  // their sum, added in slab_reduce's order: bit-identical, and no combine launch); gS = -1 a
-  // constant gradient whose f32 bits are g_ld (the bias gradient of a loss-sum cotangent)
-  long gS, g_ld, g_ss;
-  long trows;   // tile height: the launch's kAdamRows, or 16 / 32 (4-wide path, C % 64 == 0)
-};
-
-// the slab sum of slab_reduce_kernel, in its order (bit-identical results)
-template <typename ST>
-__device__ __forceinline__ float slab_sum1(const ST* __restrict__ g, long gS, long ss, long i) {
-  auto ld = [&](long j) {
-    if constexpr (sizeof(ST) == 4) return reinterpret_cast<const float*>(g)[j];
-    else return bf2f(reinterpret_cast<const bf16_t*>(g)[j]);
-  };
-  float acc = ld(i);
-  long s = 1;
-  for (; s + 3 < gS; s += 4) acc += (ld(s * ss + i) + ld((s + 1) * ss + i)) + (ld((s + 2) * ss + i) + ld((s + 3) * ss + i));
-  for (; s < gS; ++s) acc += ld(s * ss + i);
-  return acc;
-}
+// (AdamTensor, the multi-tensor Adam's table entry, and slab_sum1: adam_common.h)
 #ifndef LJS_ADAM_SLAB_DB
 #define LJS_ADAM_SLAB_DB 1
 #endif
-constexpr int kAdamMax = 32;
 // rows per Adam tile (x 64 columns): a template parameter (LJS_ADAM_ROWS = 16 / 32 / 64); smaller
 // tiles give more, shorter workgroups (a ragged last round of 64-row tiles idles most CUs)
 struct AdamBatch {
@@ -569,11 +524,33 @@ struct CastJob {
   long n;
 };
 
-template <int kAdamRows, int kThreads>
+// g * scale as a value the compiler cannot see into: the moment updates below it are then the same
+// expressions over an opaque g as in the static instances, so -ffp-contract picks the same fused
+// multiply-adds for both (with the product visible it fused the first-moment update the other way
+// round, one rounding apart from the static kernel)
+__device__ __forceinline__ float scaled_grad(float g, float scale) {
+  g *= scale;
+  asm volatile("" : "+v"(g));
+  return g;
+}
+
+// kDyn: the dynamic instance (a clipped and / or scheduled step).  Its learning-rate argument is a
+// pointer to the StepHyper record the step_hyper launch wrote: lr comes from there, and every
+// gradient element is multiplied by the record's grad_scale after the slab sum, before the moments.
+// The static instances (kDyn = false) take `float lr` and contain none of this.
+template <int kAdamRows, int kThreads, bool kDyn = false>
 __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamBatch batch, int* __restrict__ step, int step_offset,
-                                                         float lr, float b1, float b2, float eps, float wd,
-                                                         CastJob cast) {
+                                                         std::conditional_t<kDyn, const StepHyper*, float> lr_arg,
+                                                         float b1, float b2, float eps, float wd, CastJob cast) {
   __shared__ float tr[kAdamRows][65];
+  float lr;
+  [[maybe_unused]] float gscale = 1.f;
+  if constexpr (kDyn) {
+    gscale = lr_arg->grad_scale;
+    lr = lr_arg->lr;
+  } else {
+    lr = lr_arg;
+  }
   const int id = blockIdx.x;
   if (cast.n > 0 && id >= batch.tile_start[batch.n]) {
     // cast_f32_bf16's loop over the cast blocks (same rounding)
@@ -724,7 +701,8 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamBatch batch, i
       const int rl = r0 + RPP * q;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float g = gv[q][e];
+        float g = gv[q][e];
+        if constexpr (kDyn) g = scaled_grad(g, gscale);
         const float m = b1 * mv[q][e] + (1.f - b1) * g;
         const float v = b2 * vv[q][e] + (1.f - b2) * g * g;
         const float p = pv[q][e];
@@ -820,6 +798,7 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(AdamBatch batch, i
                 : T.gS < 0 ? __int_as_float((int)T.g_ld)
                 : T.g_bf16 ? bf2f(reinterpret_cast<const bf16_t*>(T.g)[gi])
                            : reinterpret_cast<const float*>(T.g)[gi];
+      if constexpr (kDyn) g = scaled_grad(g, gscale);
       float m = b1 * Mm[i] + (1.f - b1) * g;
       float v = b2 * Vv[i] + (1.f - b2) * g * g;
       float p = P[i];
@@ -1464,11 +1443,12 @@ LJS_API int ljs_step_add(void* step, int n, hipStream_t s) {
 // (see AdamTensor); up to 32 per call
 static int g_adam_rows = 0;
 LJS_API void ljs_adam_set_rows(int rows) { g_adam_rows = rows; }
-LJS_API int ljs_adam_multi(const long* table, int n, void* step, int step_offset, void* ticket, float lr, float b1,
-                           float b2, float eps, float wd, const void* cast_src, void* cast_dst, long cast_n,
-                           hipStream_t s) {
+// hyper != null: the dynamic instance (ljs_adam_multi_dyn), lr and the gradient scale read from
+// that StepHyper record on the device
+static int adam_multi_launch(const long* table, int n, void* step, int step_offset, const StepHyper* hyper, float lr,
+                             float b1, float b2, float eps, float wd, const void* cast_src, void* cast_dst,
+                             long cast_n, hipStream_t s) {
   if (n < 1 || n > kAdamMax) return (int)hipErrorInvalidValue;
-  if (ticket) return (int)hipErrorInvalidValue;   // (the in-kernel count ticket was removed)
   CastJob cast{(const float*)cast_src, (bf16_t*)cast_dst, cast_src && cast_dst ? cast_n : 0};
   if (cast.n > 0 && ((((uintptr_t)cast.src) & 15) || (((uintptr_t)cast.dst) & 15))) return (int)hipErrorInvalidValue;
   AdamBatch b;
@@ -1496,16 +1476,11 @@ LJS_API int ljs_adam_multi(const long* table, int n, void* step, int step_offset
   for (int i = 0; i < n; ++i) {
     const long* r = table + 16 * i;
     AdamTensor& t = b.t[i];
-    t.p = r[0]; t.g = r[1]; t.m = r[2]; t.v = r[3]; t.st = r[4]; t.sn = r[5]; t.R = r[6]; t.C = r[7];
-    t.g_bf16 = r[8];
+    t.p = r[0]; t.m = r[2]; t.v = r[3]; t.st = r[4]; t.sn = r[5];
     t.qn = r[10]; t.sn8 = r[11]; t.qt = r[12]; t.st8 = r[13];
-    t.gS = r[9]; t.g_ld = r[14]; t.g_ss = r[15];
-    if (t.gS == 0) t.g_ld = t.C;
-    if (t.gS > 0 && (t.g_ld < t.C || t.g_ss < 1)) return (int)hipErrorInvalidValue;   // (g_bf16: bf16 slabs)
-    t.tiles_c = (t.C + 63) / 64;
+    if (!adam_grad_from_row(r, t)) return (int)hipErrorInvalidValue;
     auto al = [](long ptr, long a) { return ptr % a == 0; };
-    t.vec = t.C % 4 == 0 && al(t.p, 16) && al(t.m, 16) && al(t.v, 16) && al(t.sn, 8) && al(t.st, 8) &&
-            (t.gS < 0 || (al(t.g, t.g_bf16 ? 8 : 16) && t.g_ld % 4 == 0 && (t.gS == 0 || t.g_ss % 4 == 0)));
+    t.vec = al(t.p, 16) && al(t.m, 16) && al(t.v, 16) && al(t.sn, 8) && al(t.st, 8) && adam_grad_vec_ok(t);
     // MX shadows are written by the 4-wide path of full 64 x 64 tiles only: refuse anything else
     // (a shadow left stale would silently feed old weights to the fp8 GEMMs)
     if ((t.qn || t.qt) && (!t.vec || kAdamRows != 64 || t.R % 64 || t.C % 64 || !al(t.qn, 4) || !al(t.qt, 4) ||
@@ -1525,6 +1500,20 @@ LJS_API int ljs_adam_multi(const long* table, int n, void* step, int step_offset
   // cast blocks: one 8-element chunk per thread per pass, at most 2048 blocks (grid-stride)
   const long cast_blocks = cast.n > 0 ? std::min<long>(2048, (cast.n + 256 * 8 - 1) / (256 * 8)) : 0;
   const unsigned grid = (unsigned)(tiles + cast_blocks);
+  if (hyper) {
+    ljs_launch_rec(kAdamRows == 16 ? "adam_multi_dyn<16>" : kAdamRows == 32 ? "adam_multi_dyn<32>" : "adam_multi_dyn<64>",
+                   dim3(grid), 256);
+    if (kAdamRows == 16)
+      hipLaunchKernelGGL((adam_multi_kernel<16, 256, true>), dim3(grid), dim3(256), 0, s, b, (int*)step, step_offset,
+                         hyper, b1, b2, eps, wd, cast);
+    else if (kAdamRows == 32)
+      hipLaunchKernelGGL((adam_multi_kernel<32, 256, true>), dim3(grid), dim3(256), 0, s, b, (int*)step, step_offset,
+                         hyper, b1, b2, eps, wd, cast);
+    else
+      hipLaunchKernelGGL((adam_multi_kernel<64, 256, true>), dim3(grid), dim3(256), 0, s, b, (int*)step, step_offset,
+                         hyper, b1, b2, eps, wd, cast);
+    return (int)hipGetLastError();
+  }
   if (kAdamRows == 16)
     hipLaunchKernelGGL((adam_multi_kernel<16, 256>), dim3(grid), dim3(256), 0, s, b, (int*)step, step_offset,
                        lr, b1, b2, eps, wd, cast);
@@ -1535,6 +1524,21 @@ LJS_API int ljs_adam_multi(const long* table, int n, void* step, int step_offset
     hipLaunchKernelGGL((adam_multi_kernel<64, 256>), dim3(grid), dim3(256), 0, s, b, (int*)step, step_offset,
                        lr, b1, b2, eps, wd, cast);
   return (int)hipGetLastError();
+}
+LJS_API int ljs_adam_multi(const long* table, int n, void* step, int step_offset, void* ticket, float lr, float b1,
+                           float b2, float eps, float wd, const void* cast_src, void* cast_dst, long cast_n,
+                           hipStream_t s) {
+  if (ticket) return (int)hipErrorInvalidValue;   // (the in-kernel count ticket was removed)
+  return adam_multi_launch(table, n, step, step_offset, nullptr, lr, b1, b2, eps, wd, cast_src, cast_dst, cast_n, s);
+}
+// The dynamic instance: the same table and arguments, with the learning rate and the gradients'
+// clipping scale taken from the 16-byte StepHyper record `hyper` (ljs_step_hyper, clip.hip)
+LJS_API int ljs_adam_multi_dyn(const long* table, int n, void* step, int step_offset, const void* hyper, float b1,
+                               float b2, float eps, float wd, const void* cast_src, void* cast_dst, long cast_n,
+                               hipStream_t s) {
+  if (!hyper || ((uintptr_t)hyper & 15)) return (int)hipErrorInvalidValue;
+  return adam_multi_launch(table, n, step, step_offset, (const StepHyper*)hyper, 0.f, b1, b2, eps, wd, cast_src,
+                           cast_dst, cast_n, s);
 }
 
 // ------------------------------------------------------------------ collective pack / unpack

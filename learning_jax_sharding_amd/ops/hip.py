@@ -28,6 +28,7 @@ _LIB = None
 _LOCK = threading.Lock()
 
 c_void_p, c_int, c_long, c_float, c_uint = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_uint
+c_double = ctypes.c_double
 _LP = ctypes.POINTER(ctypes.c_long)
 
 _SIGS = {
@@ -81,6 +82,14 @@ _SIGS = {
                      c_float, c_float, c_float, c_float, c_float, c_void_p],
     "ljs_adam_multi": [_LP, c_int, c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_float, c_float,
                        c_void_p, c_void_p, c_long, c_void_p],
+    "ljs_adam_multi_dyn": [_LP, c_int, c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_float,
+                           c_void_p, c_void_p, c_long, c_void_p],
+    "ljs_grad_sumsq": [_LP, c_int, c_void_p, c_int, c_void_p],
+    "ljs_grad_sumsq_ws_words": [],
+    "ljs_grad_sumsq_slot_word": [],
+    "ljs_grad_sumsq_slots": [],
+    "ljs_step_hyper": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
+                       c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p],
     "ljs_step_add": [c_void_p, c_int, c_void_p],
     "ljs_adam_set_rows": [c_int],
     "ljs_clock_probe": [c_void_p, c_void_p, c_uint, c_uint, c_void_p],
@@ -142,6 +151,8 @@ def lib():
                 L.ljs_mse_colsum_ws_bytes.restype = c_long
                 L.ljs_norm_bwd_ws_bytes.restype = c_long
                 L.ljs_launch_count.restype = c_long
+                for name in ("ljs_grad_sumsq_ws_words", "ljs_grad_sumsq_slot_word", "ljs_grad_sumsq_slots"):
+                    getattr(L, name).restype = c_long
                 _LIB = L
     return _LIB
 
@@ -169,7 +180,8 @@ def last_launch() -> dict:
     ``name`` (the kernel instance, e.g. ``gemm_lean<256,192,4,2,2>``, ``gemm_dma<128,128,2,2,4,kc,kc,bf16>``,
     ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``, ``rope<bf16,bf16>`` / ``rope<bf16,bf16,inv>``,
     ``gemm_mx_fp8<128,2,fix=1>``, ``gemm_mx8<256,160,4,bf16,2>``, ``quant_mx_rows``, ``quant_mx_cols<tiled>`` /
-    ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``),
+    ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
+    ``grad_sumsq``, ``step_hyper``, ``adam_multi_dyn<32>``),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
     it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
@@ -2489,33 +2501,118 @@ def adam_rows() -> int:
     return _ADAM_ROWS[0]
 
 
-def adam_multi(entries, step: torch.Tensor, lr, b1, b2, eps, wd, increment_step: bool = False) -> None:
+def _grad_source(g, shape):
+    """One row's gradient fields of the fused Adam's table, ``(R, C, (pointer, is_bf16, gS, g_ld,
+    g_ss), g)`` (csrc/kernels/adam_common.h AdamTensor), for a gradient of ``shape`` in any of its
+    source forms; the returned ``g`` has to outlive the launch."""
+    import numpy as np
+    shape = tuple(shape)
+    R, C = (shape[0], shape[1]) if len(shape) == 2 else (1, int(math.prod(shape)))
+    if isinstance(g, SlabGrad):
+        # the weight gradient is still its split-K slabs: the kernel sums them (no combine)
+        assert g.shape == shape and g.slabs.dtype in (torch.float32, torch.bfloat16) \
+            and g.slabs.is_contiguous()
+        es = g.slabs.element_size()
+        gsrc = (g.slabs.data_ptr() + es * g.offset, int(es == 2), g.S, g.ld, g.slab_stride)
+    elif isinstance(g, ConstGrad):
+        assert g.shape == shape
+        bits = int(np.asarray(g.value, dtype=np.float32).view(np.int32))
+        gsrc = (0, 0, -1, bits, 0)
+    else:
+        if g.dtype not in (torch.float32, torch.bfloat16) or not g.is_contiguous():
+            g = g.float().contiguous() if g.dtype not in (torch.float32, torch.bfloat16) else g.contiguous()
+        gsrc = (g.data_ptr(), int(g.dtype == torch.bfloat16), 0, C, 0)
+    return R, C, gsrc, g
+
+
+def take_step_offset(step: torch.Tensor, increment_step: bool):
+    """``(step_offset, pending)`` of the optimizer launches of one step: the kernels use
+    ``t = *step + step_offset``.  Read once per step and given to every launch of it
+    (:func:`step_hyper`, :func:`adam_multi` with ``taken=``): inside a capture this records one
+    more deferred increment (``_defer_step_inc``)."""
+    if increment_step:
+        assert step.dtype == torch.int32 and step.is_contiguous()
+    pend = _defer_step_inc(step) if increment_step else None
+    return int(increment_step) + (pend or 0), pend
+
+
+def _sumsq_ws(dev: torch.device) -> torch.Tensor:
+    return _workspace(dev, "grad_sumsq", 4 * lib().ljs_grad_sumsq_ws_words())
+
+
+def grad_sumsq(sources, device: torch.device) -> torch.Tensor:
+    """Sum of squares of many gradients read where they lie, one launch per 32: ``sources`` =
+    ``[(shape, g)]`` with ``g`` a plain f32 / bf16 tensor, a :class:`SlabGrad` (the slabs are summed
+    in ``slab_reduce``'s order, then squared) or a :class:`ConstGrad`.  Returns the float64
+    ``[launches]`` view of the launches' slots in the device's persistent workspace (valid until the
+    next call on this device); their sum is the result."""
+    import numpy as np
+    ws = _sumsq_ws(device)
+    rows = []
+    for shape, g in sources:
+        R, C, gsrc, g = _grad_source(g, shape)
+        rows.append(([0, gsrc[0], 0, 0, 0, 0, R, C, gsrc[1], gsrc[2], 0, 0, 0, 0, gsrc[3], gsrc[4]], g))
+    n_launch = (len(rows) + 31) // 32
+    if n_launch > lib().ljs_grad_sumsq_slots():
+        raise ValueError(f"grad_sumsq: {len(rows)} tensors need {n_launch} launches; the workspace holds "
+                         f"{lib().ljs_grad_sumsq_slots()} slots")
+    stream = torch.cuda.current_stream(device).cuda_stream
+    for k in range(n_launch):
+        chunk = rows[32 * k:32 * k + 32]
+        tab = np.asarray([r[0] for r in chunk], dtype=np.int64).reshape(-1)
+        arr = (ctypes.c_long * tab.size)(*tab.tolist())
+        _ck(lib().ljs_grad_sumsq(arr, len(chunk), _p(ws), k, stream), "ljs_grad_sumsq")
+    w0 = lib().ljs_grad_sumsq_slot_word()
+    return ws[w0:w0 + 2 * n_launch].view(torch.float64)
+
+
+def step_hyper(step: torch.Tensor, step_offset: int, schedule=None, lr: float = 0.0, max_norm=None,
+               slots: Optional[torch.Tensor] = None, gathered: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One one-wave launch writing the step's f32 record ``[grad_scale, lr, norm, 0]`` for the dynamic
+    Adam instance.  The sum of squares is ``slots`` (float64, added in index order) or, when given,
+    ``gathered`` (the devices' float64 sums, in device-id order); ``max_norm`` None: no clipping.
+    ``schedule``: an ``optim.schedule.Schedule`` evaluated on the device at ``*step + step_offset - 1``
+    (else the constant ``lr``)."""
+    rec = torch.empty(4, dtype=torch.float32, device=step.device)
+    kind, ps = (schedule.kind, schedule.params) if schedule is not None else (0, (float(lr), 0.0, 0.0, 0.0, 0.0))
+    for t in (slots, gathered):
+        assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.device == step.device)
+    rc = lib().ljs_step_hyper(_p(slots), 0 if slots is None else slots.numel(), _p(gathered),
+                              0 if gathered is None else gathered.numel(), None, _p(step), int(step_offset),
+                              int(max_norm is not None), float(max_norm or 0.0), int(kind), *[float(x) for x in ps],
+                              _p(rec), _stream(step))
+    _ck(rc, "ljs_step_hyper")
+    return rec
+
+
+def sumsq_partial(slots: torch.Tensor) -> torch.Tensor:
+    """The float64 ``[1]`` sum of a device's launch slots, in index order (its contribution to the
+    all-gather of a sharded tree's norm)."""
+    out = torch.empty(1, dtype=torch.float64, device=slots.device)
+    rc = lib().ljs_step_hyper(_p(slots), slots.numel(), None, 0, _p(out), None, 0, 0, 0.0, 0, 0.0, 0.0, 0.0, 0.0, 0.0,
+                              None, _stream(slots))
+    _ck(rc, "ljs_step_hyper")
+    return out
+
+
+def adam_multi(entries, step: torch.Tensor, lr, b1, b2, eps, wd, increment_step: bool = False,
+               hyper: Optional[torch.Tensor] = None, taken=None) -> None:
     """In-place fused Adam over many params (one launch per 32): entries = [(p, g, m, v)].
 
     Also rewrites each param's registered bf16 and MX-fp8 shadows (see :mod:`.shadow`).  With
     ``increment_step`` the bias corrections use ``step + 1`` and int32 ``step`` is incremented in
     place by a one-lane launch -- inside a graph capture one launch per segment for all its
-    steps (``_defer_step_inc``)."""
+    steps (``_defer_step_inc``).
+
+    ``hyper``: the record of :func:`step_hyper` -- the dynamic kernel instance takes the learning
+    rate from it (``lr`` is ignored) and multiplies every gradient by its ``grad_scale``;
+    ``taken``: the step's :func:`take_step_offset`, when a launch before this one already read it."""
     from . import shadow
     import numpy as np
     rows = []
     for p, g, m, v in entries:
         assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous() and p.dtype == torch.float32
-        R, C = (p.shape[0], p.shape[1]) if p.dim() == 2 else (1, p.numel())
-        if isinstance(g, SlabGrad):
-            # the weight gradient is still its split-K slabs: the kernel sums them (no combine)
-            assert g.shape == tuple(p.shape) and g.slabs.dtype in (torch.float32, torch.bfloat16) \
-                and g.slabs.is_contiguous()
-            es = g.slabs.element_size()
-            gsrc = (g.slabs.data_ptr() + es * g.offset, int(es == 2), g.S, g.ld, g.slab_stride)
-        elif isinstance(g, ConstGrad):
-            assert g.shape == tuple(p.shape)
-            bits = int(np.asarray(g.value, dtype=np.float32).view(np.int32))
-            gsrc = (0, 0, -1, bits, 0)
-        else:
-            if g.dtype not in (torch.float32, torch.bfloat16) or not g.is_contiguous():
-                g = g.float().contiguous() if g.dtype not in (torch.float32, torch.bfloat16) else g.contiguous()
-            gsrc = (g.data_ptr(), int(g.dtype == torch.bfloat16), 0, C, 0)
+        R, C, gsrc, g = _grad_source(g, p.shape)
         bufs = shadow.kinds_of(p) if p.dim() == 2 else {}
         st, sn = bufs.get("T"), bufs.get("N")
         ptr = lambda k: bufs[k].data_ptr() if k in bufs else 0  # noqa: E731
@@ -2528,8 +2625,7 @@ def adam_multi(entries, step: torch.Tensor, lr, b1, b2, eps, wd, increment_step:
     step_i = step if step.dtype == torch.int32 else step.to(torch.int32)
     # inside a capture the increments are deferred (one launch per capture segment, see
     # _defer_step_inc): this launch reads the not-yet-incremented count, offset by what is pending
-    pend = _defer_step_inc(step_i) if increment_step else None
-    offset = int(increment_step) + (pend or 0)
+    offset, pend = taken if taken is not None else take_step_offset(step_i, increment_step)
     # the next step's input cast, run by the last launch's extra blocks (ops/linear.py early cast)
     cast = None
     if rows and step_i.is_cuda:
@@ -2541,10 +2637,11 @@ def adam_multi(entries, step: torch.Tensor, lr, b1, b2, eps, wd, increment_step:
         arr = (ctypes.c_long * tab.size)(*tab.tolist())
         last = i + 32 >= len(rows)
         cj = cast if last else None
-        rc = lib().ljs_adam_multi(arr, len(chunk), _p(step_i), offset,
-                                  None, lr, b1, b2, eps, wd,
-                                  _p(cj[0]) if cj else None, _p(cj[1]) if cj else None, cj[0].numel() if cj else 0,
-                                  _stream(step_i))
+        cargs = (_p(cj[0]) if cj else None, _p(cj[1]) if cj else None, cj[0].numel() if cj else 0, _stream(step_i))
+        if hyper is not None:
+            rc = lib().ljs_adam_multi_dyn(arr, len(chunk), _p(step_i), offset, _p(hyper), b1, b2, eps, wd, *cargs)
+        else:
+            rc = lib().ljs_adam_multi(arr, len(chunk), _p(step_i), offset, None, lr, b1, b2, eps, wd, *cargs)
         _ck(rc, "ljs_adam_multi")
         if cj is not None:
             _lin.commit_optimizer_precast(cj)

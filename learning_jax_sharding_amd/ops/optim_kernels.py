@@ -27,7 +27,7 @@ def adam_fused(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
                lr: float, b1: float, b2: float, eps: float, wd: float = 0.0, inplace: bool = False
                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """One fused pass: returns (p', m', v'); writes into p/m/v when ``inplace``."""
-    if use_hip(p):
+    if use_hip(p) and not torch.is_tensor(lr):   # (a schedule's value is a tensor: the torch formulas)
         from . import hip
         return hip.adam(p, g, m, v, step, lr, b1, b2, eps, wd, inplace)
     with torch.no_grad():

@@ -14,6 +14,7 @@ the update is in place (no new parameter buffers).
 """
 from __future__ import annotations
 
+import os
 from typing import Any, Callable, NamedTuple, Optional
 
 import torch
@@ -22,6 +23,7 @@ from ..array import ShardedArray
 from ..ops import optim_kernels as OK
 from ..spmd import state as _state
 from ..utils import tree as T
+from .schedule import Schedule
 
 __all__ = ["GradientTransformation", "ScaleByAdamState", "EmptyState", "adam", "adamw", "sgd", "apply_updates",
            "chain", "scale"]
@@ -102,6 +104,17 @@ class _Adam:
         lr = self.learning_rate
         return float(lr) if not callable(lr) else lr
 
+    def _lr_at(self, count: torch.Tensor):
+        """The step's learning rate given the count BEFORE its increment (step 0 uses
+        ``schedule(0)``): the float, or a schedule's value as an f32 tensor on ``count``'s device."""
+        lr = self._lr()
+        if isinstance(lr, Schedule):
+            return lr.torch_value(count)
+        if callable(lr):
+            raise TypeError("learning_rate must be a float or one of optim's schedule objects "
+                            f"(constant_schedule, linear_schedule, ...), got {lr!r}")
+        return lr
+
     def update(self, grads, state, params=None):
         """optax-style: returns (updates, new_state); updates are added with :func:`apply_updates`."""
         st, empty = state
@@ -115,7 +128,7 @@ class _Adam:
             lu, lm, lv = {}, {}, {}
             for d, gt in g.local.items():
                 u, m2, v2 = OK.adam_moments_and_update(gt, m.local[d], v.local[d], new_count.local[d],
-                                                       self._lr(), self.b1, self.b2, self.eps,
+                                                       self._lr_at(count.local[d]), self.b1, self.b2, self.eps,
                                                        None if p is None else p.local[d], self.weight_decay)
                 lu[d], lm[d], lv[d] = u, m2, v2
             mk = lambda loc: ShardedArray(g.shape, g.dtype, g.sharding, loc)  # noqa: E731
@@ -148,6 +161,8 @@ class _Adam:
             mu = T.tree_unflatten(T.tree_structure(st.mu, is_leaf=_is_arr), new_m)
             nu = T.tree_unflatten(T.tree_structure(st.nu, is_leaf=_is_arr), new_v)
             return params2, (ScaleByAdamState(new_count, mu, nu), empty)
+        # (a schedule reads the count before the increment)
+        lrs = {d: self._lr_at(t) for d, t in count.local.items()}
         if inplace:
             for t in count.local.values():
                 t.add_(1)
@@ -163,7 +178,7 @@ class _Adam:
             for d, pt in p.local.items():
                 ip = inplace and _state.is_donated(pt)
                 lp[d], lm[d], lv[d] = OK.adam_fused(pt, g.local[d], m.local[d], v.local[d], new_count.local[d],
-                                                    self._lr(), self.b1, self.b2, self.eps, self.weight_decay,
+                                                    lrs[d], self.b1, self.b2, self.eps, self.weight_decay,
                                                     inplace=ip)
             new_p.append(ShardedArray(p.shape, p.dtype, p.sharding, lp))
             new_m.append(ShardedArray(m.shape, m.dtype, m.sharding, lm))
@@ -221,11 +236,38 @@ def _raw(count: ShardedArray) -> dict:
     return dict(dict.items(count.local))
 
 
-def _adam_multi_apply(self, pl, gl, ml, vl, count, inplace):
+def fused_clip_enabled() -> bool:
+    # LJS_FUSED_CLIP=0: clipped / scheduled Adam steps on GPU shards take the torch formulas (per-leaf
+    # norm, scale and update) instead of the grad_sumsq + step_hyper + dynamic-Adam launches (A/B
+    # timing; escape hatch)
+    return os.environ.get("LJS_FUSED_CLIP", "1") == "1"
+
+
+# device id -> the last step's f32 record [grad_scale, lr, norm, 0] of the fused clipped / scheduled
+# path (hip.step_hyper); inside a captured step the tensors are rewritten by every replay
+_LAST_HYPER: dict = {}
+
+
+def last_step_hyper() -> dict:
+    """``{device id: f32 [4] tensor (grad_scale, lr, norm, 0)}`` of the last fused clipped or
+    scheduled Adam step (diagnostics and tests)."""
+    return dict(_LAST_HYPER)
+
+
+def _adam_multi_apply(self, pl, gl, ml, vl, count, inplace, clips=()):
     """MI355X path: every local shard of every param in ONE multi-tensor kernel per device
-    (it also refreshes the params' bf16 GEMM shadows).  Returns None to use the per-leaf path."""
+    (it also refreshes the params' bf16 GEMM shadows).  Returns None to use the per-leaf path.
+
+    A schedule as the learning rate, or ``clips`` (the ``max_norm`` of every clip chained in front),
+    selects the dynamic kernel instance: per device a ``grad_sumsq`` launch per 32 gradients reads
+    them where they lie, one ``step_hyper`` launch turns the sums into the step's clipping scale and
+    learning rate, and the Adam launch reads both from that record (ops/hip.py)."""
     arrs = [(p, g, m, v) for p, g, m, v in zip(pl, gl, ml, vl) if _is_arr(p)]
     if not arrs or len(arrs) != len(pl):
+        return None
+    sched = self._lr() if isinstance(self._lr(), Schedule) else None
+    dyn = sched is not None or len(clips) > 0
+    if dyn and not fused_clip_enabled():
         return None
     for p, g, m, v in arrs:
         for d, t in p.local.items():
@@ -235,7 +277,7 @@ def _adam_multi_apply(self, pl, gl, ml, vl, count, inplace):
                 return None
     from ..ops import hip
     new_loc = [({}, {}, {}) for _ in arrs]
-    by_dev = {}
+    by_dev, leaf_of = {}, {}
     for i, (p, g, m, v) in enumerate(arrs):
         for d, pt in p.local.items():
             mt, vt = m.local[d], v.local[d]
@@ -245,6 +287,7 @@ def _adam_multi_apply(self, pl, gl, ml, vl, count, inplace):
                 tp, tm, tv = pt.clone(), mt.clone(), vt.clone()
             new_loc[i][0][d], new_loc[i][1][d], new_loc[i][2][d] = tp, tm, tv
             by_dev.setdefault(d, []).append((tp, _grad_local(g, d), tm, tv))
+            leaf_of.setdefault(d, []).append(i)
     cl = _raw(count)
     fold = inplace and all(t.dtype == torch.int32 and t.is_cuda for t in cl.values()) and set(cl) == set(by_dev)
     if fold:
@@ -255,12 +298,47 @@ def _adam_multi_apply(self, pl, gl, ml, vl, count, inplace):
     else:
         new_count = ShardedArray((), torch.int32, count.sharding, {d: t + 1 for d, t in cl.items()})
     nl = _raw(new_count)
-    for d, entries in by_dev.items():
-        hip.adam_multi(entries, nl[d], self._lr(), self.b1, self.b2, self.eps, self.weight_decay,
-                       increment_step=fold)
+    if dyn:
+        _adam_multi_dyn(self, hip, arrs, by_dev, leaf_of, nl, fold, sched, clips)
+    else:
+        for d, entries in by_dev.items():
+            hip.adam_multi(entries, nl[d], self._lr(), self.b1, self.b2, self.eps, self.weight_decay,
+                           increment_step=fold)
     mk = lambda a, loc: ShardedArray(a.shape, a.dtype, a.sharding, loc)  # noqa: E731
     return ([mk(a[0], l[0]) for a, l in zip(arrs, new_loc)], [mk(a[2], l[1]) for a, l in zip(arrs, new_loc)],
             [mk(a[3], l[2]) for a, l in zip(arrs, new_loc)], new_count)
+
+
+def _adam_multi_dyn(self, hip, arrs, by_dev, leaf_of, nl, fold, sched, clips):
+    """The launches of a clipped and / or scheduled step (see ``_adam_multi_apply``).  Successive
+    clips multiply to one clip at the smallest ``max_norm``.  The devices' sums are all-gathered
+    only when they differ (``clip.norm_plan``); the kernels of one device share its workspace, so
+    a device's slots are consumed before the next device's launch."""
+    from . import clip as _clip
+    max_norm = min(clips) if clips else None
+    devs, gather = _clip.norm_plan([a[0] for a in arrs]) if clips else ((), False)
+    gather = gather and len(devs) > 1
+    lr = 0.0 if sched is not None else self._lr()
+    _LAST_HYPER.clear()
+
+    def sumsq(d):
+        srcs = [(e[0].shape, e[1]) for e, i in zip(by_dev[d], leaf_of[d]) if _clip.counted(arrs[i][0], d, gather)]
+        return hip.grad_sumsq(srcs, by_dev[d][0][0].device)
+
+    def finish(d, slots, gathered):
+        tk = hip.take_step_offset(nl[d], fold)   # read once: step_hyper and Adam see the same step
+        rec = hip.step_hyper(nl[d], tk[0], schedule=sched, lr=lr, max_norm=max_norm, slots=slots, gathered=gathered)
+        _LAST_HYPER[d] = rec
+        hip.adam_multi(by_dev[d], nl[d], 0.0, self.b1, self.b2, self.eps, self.weight_decay, increment_step=fold,
+                       hyper=rec, taken=tk)
+
+    if gather:
+        parts = {d: hip.sumsq_partial(sumsq(d)) for d in by_dev}
+        for d, vec in _clip.gather_partials(parts, devs).items():
+            finish(d, None, vec)
+    else:
+        for d in by_dev:
+            finish(d, sumsq(d) if clips else None, None)
 
 
 _Adam._apply_multi = _adam_multi_apply
@@ -289,7 +367,53 @@ def sgd(learning_rate: float) -> GradientTransformation:
     return scale(-learning_rate)
 
 
+class _ClippedAdam(GradientTransformation):
+    """``chain(clip_by_global_norm(c), ..., adam)``: still an ``(init, update)`` pair with optax's
+    state layout ``(EmptyState(), ..., (ScaleByAdamState, EmptyState()))``, plus the fused ``apply``."""
+
+    def __new__(cls, clips, adam_tx):
+        self = super().__new__(cls, *_chain(*clips, adam_tx))
+        self.clips, self.adam = tuple(clips), adam_tx
+        return self
+
+    def __hash__(self):
+        return hash(("clipped_adam", self.clips, self.adam))
+
+    def __eq__(self, other):
+        return isinstance(other, _ClippedAdam) and (self.clips, self.adam) == (other.clips, other.adam)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def apply(self, params, grads, state):
+        """Fused ``update`` + ``apply_updates``; on host devices (or LJS_FUSED_CLIP=0) the same
+        formulas in torch: each clip's ``update``, then Adam's own ``apply``."""
+        ast = state[-1]
+        st = ast[0]
+        inplace = all(_state.is_donated(t) for t in dict.values(st.count.local))
+        pl, ptd = T.tree_flatten(params, is_leaf=_is_arr)
+        fused = self.adam._apply_multi(pl, T.tree_leaves(grads, is_leaf=_is_arr), T.tree_leaves(st.mu, is_leaf=_is_arr),
+                                       T.tree_leaves(st.nu, is_leaf=_is_arr), st.count, inplace,
+                                       clips=tuple(c.max_norm for c in self.clips))
+        if fused is not None:
+            new_p, new_m, new_v, new_count = fused
+            mu = T.tree_unflatten(T.tree_structure(st.mu, is_leaf=_is_arr), new_m)
+            nu = T.tree_unflatten(T.tree_structure(st.nu, is_leaf=_is_arr), new_v)
+            return T.tree_unflatten(ptd, new_p), tuple(state[:-1]) + ((ScaleByAdamState(new_count, mu, nu), ast[1]),)
+        for c, s in zip(self.clips, state):
+            grads, _ = c.update(grads, s, params)
+        new_params, new_ast = self.adam.apply(params, grads, ast)
+        return new_params, tuple(state[:-1]) + (new_ast,)
+
+
 def chain(*txs) -> GradientTransformation:
+    from .clip import ClipByGlobalNorm
+    if len(txs) >= 2 and isinstance(txs[-1], _Adam) and all(isinstance(t, ClipByGlobalNorm) for t in txs[:-1]):
+        return _ClippedAdam(txs[:-1], txs[-1])
+    return _chain(*txs)
+
+
+def _chain(*txs) -> GradientTransformation:
     def init(params):
         return tuple(t.init(params) for t in txs)
 

@@ -10,6 +10,19 @@ from ..utils import tree as T
 __all__ = ["TrainState"]
 
 
+def _counter(opt_state):
+    """The optimizer's device-side step counter, wherever it sits in a (chained) state, or None."""
+    from ..optim.adam import ScaleByAdamState
+    if isinstance(opt_state, ScaleByAdamState):
+        return opt_state.count
+    if isinstance(opt_state, tuple):
+        for s in opt_state:
+            c = _counter(s)
+            if c is not None:
+                return c
+    return None
+
+
 @dataclasses.dataclass(eq=False)
 class TrainState:
     step: Any
@@ -22,7 +35,8 @@ class TrainState:
     def create(cls, *, apply_fn: Callable, params, tx, **kwargs) -> "TrainState":
         opt_state = tx.init(params)
         # the step counter is the optimizer's device-side counter when there is one
-        step = opt_state[0].count if hasattr(opt_state[0], "count") else 0
+        count = _counter(opt_state)
+        step = count if count is not None else 0
         return cls(step=step, apply_fn=apply_fn, params=params, tx=tx, opt_state=opt_state, **kwargs)
 
     def apply_gradients(self, *, grads, **kwargs) -> "TrainState":
@@ -32,7 +46,8 @@ class TrainState:
             from ..optim.adam import apply_updates
             updates, new_opt = self.tx.update(grads, self.opt_state, self.params)
             new_params = apply_updates(self.params, updates)
-        step = new_opt[0].count if hasattr(new_opt[0], "count") else self.step + 1
+        count = _counter(new_opt)
+        step = count if count is not None else self.step + 1
         return dataclasses.replace(self, step=step, params=new_params, opt_state=new_opt, **kwargs)
 
     def replace(self, **kwargs) -> "TrainState":
