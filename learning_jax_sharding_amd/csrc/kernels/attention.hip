@@ -25,6 +25,7 @@
 // so Q/K/V can be column slices of the fused QKV GEMM output.
 #include "common.h"
 
+#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -2037,9 +2038,18 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
 //     896 / 859 for the tile-only steps 12-18; now every step runs about 930-1030 / 775.  All pieces
 //     up front, and 4 or 2 per step, delay the tile stream more than they save
 //     (profiles/attn_bwd_proj_phases.txt, profiles/PERF_NOTES.md).
-//   * what is left (~775 cycles per 32-deep step against a 256-cycle MFMA floor) is neither the ring's
-//     depth nor load latency: with the dY fragments loaded straight to registers four tiles ahead and
-//     only the weight tile in LDS, the steps cost the same on a broadcast row and more on a full dY.
+//   * what is left of the general phase (~775 cycles per 32-deep step against a 256-cycle MFMA floor) is
+//     neither the ring's depth nor load latency: with the dY fragments loaded straight to registers four
+//     tiles ahead and only the weight tile in LDS, the steps cost the same and more on a full dY.
+//   * BCAST instance (dy_ld == 0: one cotangent row for every token, y.sum()'s; the launcher picks it on
+//     the stride, under the same launch record): the 256 rows of dO_h are one 64-vector, so the dY
+//     stream is one copy of the row in LDS (fetched once, behind the images), only the 4 KiB weight
+//     tiles stream -- sixteen [64][32] stages over the same region, three groups of four in flight --
+//     and tile wave j runs ONE MFMA per K-tile, on the 16 weight rows it loads itself (no barrier in
+//     the loop), then stores its 16 columns to all 256 rows; the piece waves issue every piece before it.
+//     GEMM phase 19.6k -> 15.3k cycles at B = 64 (profiles/PERF_NOTES.md).  Same instruction, A rows,
+//     B column values and k order per element: the same bits as the general phase
+//     (tests/test_attn_bwd_proj_bcast_gpu.py).
 //   * dO_h stays in LDS for the whole sweep ([256][64], img16 per 64-row block); block it's image is
 //     dead once its dS^T is formed and then stages that block's dQ.
 // (The pieces below choose among LDS images at run time: dma_lds_x4_at / dma_lds_x1_at, the
@@ -2060,9 +2070,16 @@ constexpr int PJ_Q = PJ_DO + FK * D, PJ_OS = PJ_Q + 2 * BLK * D, PJ_ROWC = PJ_OS
 constexpr int PJ_LDS = PJ_ROWC + 2 * 2 * BLK * 2;   // 153 KiB
 static_assert(3 * PJ_STAGE <= PJ_Q - PJ_DST, "the ring fits the dS^T and dO images");
 static_assert(PJ_LDS * 2 <= 160 * 1024, "LDS");
-
+// BCAST (dy_ld == 0, M <= PJB_ROW): weight-only stages over the same region, PJB_G tiles per counted
+// wait with PJB_AHEAD groups in flight, and one copy of the row behind the images
+constexpr int PJB_STAGE = D * PJ_BK;   // elements (4 KiB)
+constexpr int PJB_G = 4, PJB_AHEAD = 3, PJB_NST = (PJB_AHEAD + 1) * PJB_G;
+constexpr int PJB_ROW = 2048;          // elements of the row copy: one 1 KiB piece per tile wave
+static_assert((PJB_NST & (PJB_NST - 1)) == 0 && PJB_NST * PJB_STAGE <= PJ_Q - PJ_DST, "the stages fit the two images");
+static_assert((PJ_LDS + PJB_ROW) * 2 <= 160 * 1024, "LDS");
+template <bool BCAST>
 __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjArgs pj) {
-  __shared__ __attribute__((aligned(16))) bf16_t smem[PJ_LDS];
+  __shared__ __attribute__((aligned(16))) bf16_t smem[PJ_LDS + (BCAST ? PJB_ROW : 0)];
   bf16_t* const Ks = smem + PJ_KS;
   bf16_t* const Vs = smem + PJ_VS;
   bf16_t* const dSt = smem + PJ_DST;
@@ -2107,9 +2124,11 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
   // ---- dO_h = dY[b] . Wo_h^T
   {
     const int nk = pj.M / PJ_BK;
+    // (dy_ld 0: the one row, M elements)
     const u32x4 ra = rsrc_u4(pj.dy + (long)b * FK * pj.dy_ld, 2 * ((long)(FK - 1) * pj.dy_ld + pj.M));
     const u32x4 rw = rsrc_u4(pj.w + (long)h * D * pj.M, 2L * D * pj.M);
-    // (diagnostic builds) the top of K-tile step k, after its barrier; slot nk: the phase's last barrier
+    // (diagnostic builds) the top of K-tile step k (BCAST: of tile group k), after its barrier; the slot
+    // after the last: the phase's last barrier
     auto sstamp = [&](int k) {
 #if LJS_ATTN_BWD_TRACE
       const unsigned long long ts = __builtin_amdgcn_s_memtime();
@@ -2123,36 +2142,31 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
       return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
                                             img + row * PJ_BK + ((g ^ (((row >> 3) & 1) << 1)) << 3)));
     };
-    f32x4 acc[2][4];
+    f32x4 acc[BCAST ? 1 : 2][BCAST ? 1 : 4];   // (BCAST: one tile of one 16-token block)
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < (BCAST ? 1 : 2); ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < (BCAST ? 1 : 4); ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // tile waves 0..3 issue every tile piece (16 rows x 64 B: dY pieces wave + 4 i, weight piece wave)
     // and do the counted wait; piece waves 4..7 issue every prologue piece and never wait in the loop
     const bool tw = wave < 4;
     const int pw = wave & 3;
-    int va[4], vw;
+    int va[BCAST ? 1 : 4], vw;
+    if constexpr (BCAST) {
+      va[0] = (pw * 512 + lane * 8) * 2;   // this tile wave's 1 KiB of the row copy
+    } else {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 16 * (pw + 4 * i) + (lane >> 2);
-      const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
-      va[i] = (int)(((long)row * pj.dy_ld + 8 * c) * 2);
+      for (int i = 0; i < 4; ++i) {
+        const int row = 16 * (pw + 4 * i) + (lane >> 2);
+        const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
+        va[i] = (int)(((long)row * pj.dy_ld + 8 * c) * 2);
+      }
     }
     {
       const int row = 16 * pw + (lane >> 2);
       const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
       vw = (row * pj.M + 8 * c) * 2;
     }
-    // K-tile kt into the stage at element offset so; past the last tile every piece reads nothing
-    auto issue_t = [&](int kt, int so) {
-      const bool ok = kt < nk;
-      const int ko = kt * PJ_BK * 2;
-      const int st = PJ_DST + so;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dma_lds_x4_at(ra, ok ? va[i] + ko : OOB, sb + 2 * (st + (pw + 4 * i) * 512));
-      dma_lds_x4_at(rw, ok ? vw + ko : OOB, sb + 2 * (st + PJ_A + pw * 512));
-    };
     // prologue piece j of this piece wave (wave-uniform): K / V pieces pw + 4 i alternate (rows 8 p +
     // ..: the img16 swizzle on the source address depends on the lane alone), then the first block's Q
     // and O pieces pw, pw + 4, then (pw 0) the lse row
@@ -2174,56 +2188,136 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
         dma_lds_x1_at(rl, lane * 4, sb + 2 * PJ_ROWC);
       }
     };
-    int s0 = 0, s1 = PJ_STAGE, s2 = 2 * PJ_STAGE;   // stages of tiles kt, kt + 1, kt + 2
     int pi = 0;                                     // a piece wave's next piece
-    if (tw) {
-      issue_t(0, s0);
-      issue_t(1, s1);
-    } else {
-      // two pieces while the first tile is on its way, then one per step: the pacing is the same for
-      // every nk, and what a short loop leaves is issued after it
-      issue_piece(pi++);
-      issue_piece(pi++);
-    }
-    for (int kt = 0; kt < nk; ++kt) {
-      // tile kt landed (a tile wave's pieces); tile kt + 1 stays in flight
-      if (tw) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    if constexpr (BCAST) {
+      // One row for every token: the 256 rows of dO_h are one 64-vector, and every 16-token block of
+      // C^T has 16 equal columns.  Tile wave j forms the block's rows 16 j .. 16 j + 15 (one accumulator
+      // tile: the weight rows it streams itself, so the loop needs no barrier) and stores them to all 256
+      // rows of the image.  (With all eight waves forming the whole block the groups ran 1.4-1.6k cycles:
+      // every wave read every weight tile, 160 KiB of LDS reads per group; profiles/PERF_NOTES.md, "dO once
+      // per block", whose raw lines are under profiles/attn_bwd_proj_bcast/.)  The B operand's k-fragment (k = 32
+      // kt + 8 g .. + 7, the same for every lane & 15) is read from one copy of the row behind the
+      // kernel's images; the weight tiles stream through PJB_NST stages of [64][32] (the general ring's
+      // weight image and swizzle).  Per element: the general loop's instruction, A row, B column and k
+      // order -- the same bits.  The piece waves are not in the loop: they issue every piece and wait for
+      // the phase's end (the first weight tiles then arrive behind that burst, 8.8k cycles into the block:
+      // the open variant in the notes).
+      const bf16_t* const rowi = smem + PJ_LDS;
+      // weight K-tile kt (this tile wave's 16 rows) into stage kt % PJB_NST; past the last tile the piece
+      // reads nothing, so every group counts PJB_G loads
+      auto issue_w = [&](int kt) {
+        dma_lds_x4_at(rw, kt < nk ? vw + kt * PJ_BK * 2 : OOB,
+                      sb + 2 * (PJ_DST + (kt & (PJB_NST - 1)) * PJB_STAGE + pw * 512));
+      };
+      if (tw) {
+        dma_lds_x4_at(ra, va[0], sb + 2 * (PJ_LDS + pw * 512));   // (past M: zeros, never read as a fragment)
+#pragma unroll
+        for (int kt = 0; kt < PJB_AHEAD * PJB_G; ++kt) issue_w(kt);
+        // the row piece is the oldest of these 1 + PJB_AHEAD PJB_G loads
+        static_assert(PJB_AHEAD * PJB_G == 12, "the counted wait below");
+        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      } else {
+        for (; pi < PJ_NPW; ++pi) issue_piece(pi);
+      }
+      __builtin_amdgcn_s_barrier();   // every tile wave's piece of the row copy landed
+      if (tw) {
+        for (int k0 = 0, gi = 0; k0 < nk; k0 += PJB_G, ++gi) {
+          // This wave has issued, in order, its row piece, then PJB_G loads per group: 1 + (PJB_AHEAD + gi)
+          // PJB_G so far.  Group gi is usable once the first 1 + (gi + 1) PJB_G of them retired:
+          // (PJB_AHEAD - 1) PJB_G = 8 may stay in flight (groups gi + 1 and gi + 2).  Only this wave reads
+          // the 16 rows it loads; its reads of group gi - 1 are done (lgkmcnt) before group gi +
+          // PJB_AHEAD goes into those stages (PJB_NST = (PJB_AHEAD + 1) PJB_G).
+          static_assert((PJB_AHEAD - 1) * PJB_G == 8, "the counted wait below");
+          asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          sstamp(gi);
+#pragma unroll
+          for (int i = 0; i < PJB_G; ++i) issue_w(k0 + PJB_AHEAD * PJB_G + i);
+#pragma unroll
+          for (int i = 0; i < PJB_G; ++i) {
+            const int kt = k0 + i;
+            if (kt < nk) {
+              const bf16x8 wf = frag(dSt + (kt & (PJB_NST - 1)) * PJB_STAGE, 16 * pw);
+              const bf16x8 rf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rowi + kt * PJ_BK + 8 * g));
+              acc[0][0] = mfma16x16x32(wf, rf, acc[0][0]);   // C^T block
+            }
+          }
+        }
+      }
+      // everything landed (the past-the-end tiles too: they cover the image below), every wave is done
+      // with the ring
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();   // ... every tile wave's; every wave's reads of tile kt - 1 done
-      sstamp(kt);
-      bf16x8 af[2], wf[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wf[j] = frag(dSt + s0 + PJ_A, 16 * j);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) af[i] = frag(dSt + s0, 32 * wave + 16 * i);
-      if (tw) issue_t(kt + 2, s2);            // into tile kt - 1's stage
-      else if (pi < PJ_NPW) issue_piece(pi++);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16x16x32(wf[j], af[i], acc[i][j]);   // C^T blocks
-      const int sn = s0;
-      s0 = s1;
-      s1 = s2;
-      s2 = sn;
-    }
-    if (!tw)
-      for (; pi < PJ_NPW; ++pi) issue_piece(pi);
-    // everything landed (the past-the-end tiles too: they cover the image below), every wave is done
-    // with the ring
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    sstamp(nk);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = 32 * wave + 16 * i + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      __builtin_amdgcn_s_barrier();
+      sstamp((nk + PJB_G - 1) / PJB_G);
+      if (tw) {
         u32x2 w2;
-        w2[0] = pack_bf16x2(acc[i][j][0], acc[i][j][1]);
-        w2[1] = pack_bf16x2(acc[i][j][2], acc[i][j][3]);
-        *reinterpret_cast<u32x2*>(dOi + img8(row, 4 * j + g)) = w2;
+        w2[0] = pack_bf16x2(acc[0][0][0], acc[0][0][1]);
+        w2[1] = pack_bf16x2(acc[0][0][2], acc[0][0][3]);
+#pragma unroll
+        for (int rb = 0; rb < FK / 16; ++rb)
+          *reinterpret_cast<u32x2*>(dOi + img8(16 * rb + (lane & 15), 4 * pw + g)) = w2;
+      }
+    } else {
+      // K-tile kt into the stage at element offset so; past the last tile every piece reads nothing
+      auto issue_t = [&](int kt, int so) {
+        const bool ok = kt < nk;
+        const int ko = kt * PJ_BK * 2;
+        const int st = PJ_DST + so;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dma_lds_x4_at(ra, ok ? va[i] + ko : OOB, sb + 2 * (st + (pw + 4 * i) * 512));
+        dma_lds_x4_at(rw, ok ? vw + ko : OOB, sb + 2 * (st + PJ_A + pw * 512));
+      };
+      int s0 = 0, s1 = PJ_STAGE, s2 = 2 * PJ_STAGE;   // stages of tiles kt, kt + 1, kt + 2
+      if (tw) {
+        issue_t(0, s0);
+        issue_t(1, s1);
+      } else {
+        // two pieces while the first tile is on its way, then one per step: the pacing is the same for
+        // every nk, and what a short loop leaves is issued after it
+        issue_piece(pi++);
+        issue_piece(pi++);
+      }
+      for (int kt = 0; kt < nk; ++kt) {
+        // tile kt landed (a tile wave's pieces); tile kt + 1 stays in flight
+        if (tw) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();   // ... every tile wave's; every wave's reads of tile kt - 1 done
+        sstamp(kt);
+        bf16x8 af[2], wf[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wf[j] = frag(dSt + s0 + PJ_A, 16 * j);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) af[i] = frag(dSt + s0, 32 * wave + 16 * i);
+        if (tw) issue_t(kt + 2, s2);            // into tile kt - 1's stage
+        else if (pi < PJ_NPW) issue_piece(pi++);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = mfma16x16x32(wf[j], af[i], acc[i][j]);   // C^T blocks
+        const int sn = s0;
+        s0 = s1;
+        s1 = s2;
+        s2 = sn;
+      }
+      if (!tw)
+        for (; pi < PJ_NPW; ++pi) issue_piece(pi);
+      // everything landed (the past-the-end tiles too: they cover the image below), every wave is done
+      // with the ring
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      sstamp(nk);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int row = 32 * wave + 16 * i + (lane & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          u32x2 w2;
+          w2[0] = pack_bf16x2(acc[i][j][0], acc[i][j][1]);
+          w2[1] = pack_bf16x2(acc[i][j][2], acc[i][j][3]);
+          *reinterpret_cast<u32x2*>(dOi + img8(row, 4 * j + g)) = w2;
+        }
       }
     }
     bstamp(6);
@@ -2497,6 +2591,14 @@ static bool bwd_proj_enabled(long BH) {
 // Whether the switches let ljs_attn_bwd_proj run a (B, H) grid (the shape gate is attn_bwd_proj_plan's)
 LJS_API int ljs_attn_bwd_proj_enabled(int B, int H) { return bwd_proj_enabled((long)B * H); }
 
+static bool bwd_proj_bcast_on() {
+  // LJS_ATTN_BWD_PROJ_BCAST=0: attn_bwd_proj runs its general GEMM phase on a broadcast dY (dy_ld == 0)
+  // too, as it does for M > 2048 (A/B of the broadcast-row instance in one build; read at every launch)
+  const char* e = getenv("LJS_ATTN_BWD_PROJ_BCAST");
+  return !(e && e[0] == '0' && !e[1]);
+}
+static int g_bwd_proj_last_path = -1;
+
 // a: as attn_bwd_plan's, without dout / delta.  Exactly the fused backward's common case: Sq == Sk ==
 // 256, not causal, 16-byte aligned operands and outputs with row strides % 8 == 0
 static AttnPlan attn_bwd_proj_plan(const AttnArgs& a, int B, const BwdProjArgs& pj) {
@@ -2689,9 +2791,16 @@ static int attn_bwd_proj_impl(const void* q, const void* k, const void* v, const
   a.vst = p.vst[0];
   a.trace = g_attn_trace;
   ljs_launch_rec(kAttnInst[kBwdProj].name, dim3(p.l[0].gx), p.l[0].block);
-  hipLaunchKernelGGL(attn_bwd_proj_kernel, dim3(p.l[0].gx), dim3(p.l[0].block), 0, stream, a, pj);
+  // one instance under one record name: the broadcast-row one is chosen on the stride (and M: the row
+  // copy holds PJB_ROW elements; a wider broadcast row runs the general phase), never on values
+  const bool bcast = dy_ld == 0 && M <= PJB_ROW && bwd_proj_bcast_on();
+  g_bwd_proj_last_path = bcast;
+  if (bcast) hipLaunchKernelGGL(attn_bwd_proj_kernel<true>, dim3(p.l[0].gx), dim3(p.l[0].block), 0, stream, a, pj);
+  else hipLaunchKernelGGL(attn_bwd_proj_kernel<false>, dim3(p.l[0].gx), dim3(p.l[0].block), 0, stream, a, pj);
   return (int)hipGetLastError();
 }
+// Which GEMM phase the last ljs_attn_bwd_proj launch ran: 0 general, 1 broadcast row; -1 before any
+LJS_API int ljs_attn_bwd_proj_last_path() { return g_bwd_proj_last_path; }
 LJS_API int ljs_attn_bwd_proj(const void* q, const void* k, const void* v, const void* o, const void* dy, long dy_ld,
                               const void* w, int M, const void* lse, void* dq, void* dk, void* dv, int B, int Sq,
                               int Sk, int H, const long* qs, const long* ks, const long* vs, const long* os,

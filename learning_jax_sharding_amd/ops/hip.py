@@ -60,6 +60,7 @@ _SIGS = {
                           c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP,
                           c_float, c_int, c_void_p],
     "ljs_attn_bwd_proj_enabled": [c_int, c_int],
+    "ljs_attn_bwd_proj_last_path": [],
     "ljs_cast_f32_bf16": [c_void_p, c_void_p, c_long, c_void_p],
     "ljs_cast_bf16_f32": [c_void_p, c_void_p, c_long, c_void_p],
     "ljs_swap01_bf16": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
@@ -2253,6 +2254,14 @@ def attn_bwd_proj_block(q, k, v, o, dy: torch.Tensor, dy_ld: int, w: torch.Tenso
                                  int(causal), _stream(q))
     _ck(rc, "ljs_attn_bwd_proj")
     return dq, dk, dv
+
+
+def attn_bwd_proj_last_path() -> int:
+    """Which GEMM phase the last ``attn_bwd_proj`` launch ran: 0 the general one, 1 the broadcast-row
+    one (``dy_ld`` 0, ``M`` <= 2048 -- the row copy's size in LDS; a wider broadcast row runs the general
+    phase -- and ``LJS_ATTN_BWD_PROJ_BCAST`` not 0); -1 before any launch.  The launch record is the same
+    for both."""
+    return lib().ljs_attn_bwd_proj_last_path()
 
 
 def defer_out_proj(dy: torch.Tensor, ld: int, wn: torch.Tensor, dx: torch.Tensor, launch) -> None:

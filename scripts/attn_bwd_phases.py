@@ -9,7 +9,8 @@
 written, with the K / V / Q / O pieces streaming under it) and the rest (delta of the first block).
 Its K-tile steps are stamped too (top of each step, after the barrier): the mean step time over steps
 1-11 and over steps 12-19 (of the 20 at M = 640), and the phase's tail (last step's top -> everything
-landed).
+landed).  ``proj0`` runs the broadcast-row phase unless LJS_ATTN_BWD_PROJ_BCAST=0: in that one waves
+0-3 stamp each group of four K-tiles after its counted wait, and each group's time is printed.
 
 Per block (averaged over blocks and waves, shader-clock cycles): prologue (start -> first query
 block's Q / dO / O and delta ready), each query block of the sweep, and the dK / dV epilogue;
@@ -68,11 +69,21 @@ def main():
         # step k = stamp k -> stamp k + 1; stamp nk is the phase's last barrier (everything landed)
         nk = M // 32
         st = steps.cpu().double()
-        d = (st[..., 1:nk + 1] - st[..., :nk])[ok]           # [records][step]
-        print(f"  {'K-tile steps':14s} first stamp {(st[..., 0] - t[..., 0])[ok].mean().item():6.0f} cycles after the start; "
-              f"step 0 {d[:, 0].mean().item():6.0f}; steps 1-11 {d[:, 1:12].mean().item():6.0f} / step; "
-              f"steps 12-{nk - 2} {d[:, 12:nk - 1].mean().item():6.0f} / step; "
-              f"step {nk - 1} and the tail {d[:, nk - 1].mean().item():6.0f}")
+        if hip.attn_bwd_proj_last_path() == 1:
+            # the broadcast-row phase: waves 0-3 stamp each group of 4 K-tiles after its counted wait
+            ng = -(-nk // 4)
+            st, t4, ok4 = st[:, :, :4], t[:, :, :4], ok[:, :, :4]
+            d = (st[..., 1:ng + 1] - st[..., :ng])[ok4]      # [records][group]
+            print(f"  {'tile groups':14s} (broadcast-row phase, waves 0-3, {ng} groups of 4 K-tiles) first stamp "
+                  f"{(st[..., 0] - t4[..., 0])[ok4].mean().item():6.0f} cycles after the start; "
+                  + "; ".join(f"group {i} {d[:, i].mean().item():6.0f}" for i in range(ng - 1))
+                  + f"; group {ng - 1} and the tail {d[:, ng - 1].mean().item():6.0f}")
+        else:
+            d = (st[..., 1:nk + 1] - st[..., :nk])[ok]       # [records][step]
+            print(f"  {'K-tile steps':14s} first stamp {(st[..., 0] - t[..., 0])[ok].mean().item():6.0f} cycles after the start; "
+                  f"step 0 {d[:, 0].mean().item():6.0f}; steps 1-11 {d[:, 1:12].mean().item():6.0f} / step; "
+                  f"steps 12-{nk - 2} {d[:, 12:nk - 1].mean().item():6.0f} / step; "
+                  f"step {nk - 1} and the tail {d[:, nk - 1].mean().item():6.0f}")
     names = ["prologue"] + [f"query block {i}" for i in range(4)]
     for i, n in enumerate(names):
         d = (t[..., i + 1] - t[..., i])[ok]
