@@ -1,5 +1,5 @@
 // LJS_HIPCC_FLAGS: -mllvm -amdgpu-mfma-vgpr-form -fno-honor-nans
-// Fused multi-head attention for gfx950 (head_dim 64), forward and backward.
+// Fused multi-head and grouped-query attention for gfx950 (head_dim 64), forward and backward.
 //
 // Semantics (case6_attention.py:120-133): scores = f32(q) . f32(k) * scale, f32 softmax over
 // keys, probabilities rounded to bf16, P . V with f32 accumulation, bf16 output.  q and k
@@ -23,6 +23,13 @@
 //
 // Tensors are (batch, seq, heads, 64) with arbitrary batch/seq/head strides (d contiguous),
 // so Q/K/V can be column slices of the fused QKV GEMM output.
+//
+// Grouped-query attention: K and V may have Hkv = H / G heads.  Query head h reads key/value head
+// h / G (the G query heads of a group are adjacent), a wave-uniform scalar formed with the launch
+// constant divisor AttnArgs::fd_g; G = 1 is the identity.  Q, O, dO, lse, delta and all outputs are
+// indexed by the query head, so for G > 1 the backward's dK / dV are per-QUERY-head tensors that
+// gqa_reduce (gqa.hip) folds over each group.  qkv_attn_fwd_kernel and attn_bwd_proj_kernel stay
+// multi-head only.
 #include "common.h"
 
 #include <cstdlib>
@@ -51,7 +58,8 @@ static inline FastDiv make_fastdiv(int d) {
 }
 struct AttnArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* o; const bf16_t* dout;
-  bf16_t* out;                     // fwd: O ; bwd dkv: dK ; bwd dq: dQ
+                                   // (k, v: H / fd_g.d heads; everything else: H heads)
+  bf16_t* out;                     // fwd: O ; bwd dkv: dK ; bwd dq: dQ  (dK / dV: per query head)
   bf16_t* out2;                    // bwd dkv: dV
   bf16_t* out3;                    // bwd fused: dQ (out = dK, out2 = dV)
   float* lse;                      // [B][H][Sq], log2 domain of scaled scores
@@ -71,6 +79,7 @@ struct AttnArgs {
   int vst;           // outputs 16-byte aligned with row strides % 8 == 0: row tiles leave through an
                      // LDS image as full 128-byte rows (stage_rows16 / flush_rows)
   FastDiv fd_nx, fd_h;  // resident forward: its query-block count and H as launch-constant divisors
+  FastDiv fd_g;         // query heads per key/value head: query head h reads K/V head fdiv(h, fd_g)
   unsigned long long* trace;   // LJS_ATTN_BWD_TRACE builds: fused-backward phase stamps
 };
 #ifndef LJS_ATTN_BWD_TRACE
@@ -508,8 +517,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_res_kernel(AttnArgs a) {
   // vs 0.1975-0.2017 ms with integer divisions, x3 interleaved (gpurun_out/r6e)
   const Tile3 tl = tile3f(a.fd_nx, a.fd_h);
   const int qb = tl.x, h = tl.h, b = tl.b;
-  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
-  const bf16_t* vb = a.v + b * a.v_sb + h * a.v_sh;
+  const bf16_t* kb = a.k + b * a.k_sb + fdiv(h, a.fd_g) * a.k_sh;
+  const bf16_t* vb = a.v + b * a.v_sb + fdiv(h, a.fd_g) * a.v_sh;
 
   int kend = a.Sk;
   if (a.causal) kend = min(a.Sk, a.q_offset + (qb + 1) * QB);
@@ -847,8 +856,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     st[sb].m = -INFINITY;
     st[sb].l = 0.f;
   }
-  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
-  const bf16_t* vb = a.v + b * a.v_sb + h * a.v_sh;
+  const bf16_t* kb = a.k + b * a.k_sb + fdiv(h, a.fd_g) * a.k_sh;
+  const bf16_t* vb = a.v + b * a.v_sb + fdiv(h, a.fd_g) * a.v_sh;
 
   int kend = a.Sk;
   if (a.causal) kend = min(a.Sk, a.q_offset + (qb + 1) * QB);
@@ -994,8 +1003,8 @@ __device__ __forceinline__ void dkv_body(const AttnArgs& a, int kblk, int h, int
   const int key0 = kblk * BLK + wave * 16;
   const int key = key0 + (lane & 15);
   const bool kok = key < a.Sk;
-  const bf16_t* kp = a.k + b * a.k_sb + (long)key * a.k_ss + h * a.k_sh;
-  const bf16_t* vp = a.v + b * a.v_sb + (long)key * a.v_ss + h * a.v_sh;
+  const bf16_t* kp = a.k + b * a.k_sb + (long)key * a.k_ss + fdiv(h, a.fd_g) * a.k_sh;
+  const bf16_t* vp = a.v + b * a.v_sb + (long)key * a.v_ss + fdiv(h, a.fd_g) * a.v_sh;
   bf16x8 kf[2] = {load_row_frag(kp, kok, 0, lane), load_row_frag(kp, kok, 1, lane)};
   bf16x8 vf[2] = {load_row_frag(vp, kok, 0, lane), load_row_frag(vp, kok, 1, lane)};
   const bf16_t* qb = a.q + b * a.q_sb + h * a.q_sh;
@@ -1178,8 +1187,8 @@ __device__ __forceinline__ void dkv32_body(const AttnArgs& a, int kblk, int h, i
   for (int j = 0; j < 2; ++j) {
     const int key = key0 + 16 * j + (lane & 15);
     const bool kok = key < a.Sk;
-    const bf16_t* kp = a.k + b * a.k_sb + (long)key * a.k_ss + h * a.k_sh;
-    const bf16_t* vp = a.v + b * a.v_sb + (long)key * a.v_ss + h * a.v_sh;
+    const bf16_t* kp = a.k + b * a.k_sb + (long)key * a.k_ss + fdiv(h, a.fd_g) * a.k_sh;
+    const bf16_t* vp = a.v + b * a.v_sb + (long)key * a.v_ss + fdiv(h, a.fd_g) * a.v_sh;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       kr[j][ks] = load_row_frag(kp, kok, ks, lane);
@@ -1385,8 +1394,8 @@ __device__ __forceinline__ void dq_body(const AttnArgs& a, int qb, int h, int b,
     dl_q = -s;  // delta is kept negated (it seeds the dP accumulators)
     if (write_delta && qok && (lane >> 4) == 0) const_cast<float*>(a.delta)[((long)b * a.H + h) * a.Sq + qrow] = -s;
   }
-  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
-  const bf16_t* vb = a.v + b * a.v_sb + h * a.v_sh;
+  const bf16_t* kb = a.k + b * a.k_sb + fdiv(h, a.fd_g) * a.k_sh;
+  const bf16_t* vb = a.v + b * a.v_sb + fdiv(h, a.fd_g) * a.v_sh;
   int kend = a.Sk;
   if (a.causal) kend = min(a.Sk, a.q_offset + (qb + 1) * BLK);
   const int nkt = (kend + BLK - 1) / BLK;
@@ -1531,8 +1540,8 @@ __device__ __forceinline__ void dq32_body(const AttnArgs& a, int qb, int h, int 
     }
     dl_q[i] = -row4_sum(sacc);  // delta, kept negated (it seeds the dP accumulators)
   }
-  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
-  const bf16_t* vb = a.v + b * a.v_sb + h * a.v_sh;
+  const bf16_t* kb = a.k + b * a.k_sb + fdiv(h, a.fd_g) * a.k_sh;
+  const bf16_t* vb = a.v + b * a.v_sb + fdiv(h, a.fd_g) * a.v_sh;
   int kend = a.Sk;
   if (a.causal) kend = min(a.Sk, a.q_offset + (qb + 1) * 128);
   const int nkt = (kend + BLK - 1) / BLK;
@@ -1848,8 +1857,8 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
   const bool active = key0 < a.Sk;
   const int nk32 = (a.Sk + 31) / 32;
 
-  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
-  const bf16_t* vb = a.v + b * a.v_sb + h * a.v_sh;
+  const bf16_t* kb = a.k + b * a.k_sb + fdiv(h, a.fd_g) * a.k_sh;
+  const bf16_t* vb = a.v + b * a.v_sb + fdiv(h, a.fd_g) * a.v_sh;
   // K and V land by LDS-DMA (swizzle on the source address, rows past Sk read zeros), in flight
   // together with the first query block's Q / dO / O below: one exposed latency, not two (the
   // register-staged copy waited for K / V before the first block's DMA was even issued)
@@ -2098,7 +2107,7 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
   auto bstamp = [&](int k) { fused_stamp(a, b, h, wave, lane, k); };
   bstamp(0);
 
-  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;
+  const bf16_t* kb = a.k + b * a.k_sb + h * a.k_sh;   // (multi-head only: one K/V head per query head)
   const bf16_t* vb = a.v + b * a.v_sb + h * a.v_sh;
   const bf16_t* qb = a.q + b * a.q_sb + h * a.q_sh;
   const bf16_t* ob = a.o + b * a.o_sb + h * a.o_sh;
@@ -2427,8 +2436,8 @@ LJS_API void ljs_attn_set_trace_steps(void* p) { g_attn_trace_steps = (unsigned 
 // The fields every attention launch fills: Q / K / V / O operands (o: the forward's output, the
 // backward's saved one; the forward also names it as a.out), lse, shape and softmax constants.
 static AttnArgs attn_args(const void* q, const void* k, const void* v, const void* o, const void* lse, const long* qs,
-                          const long* ks, const long* vs, const long* os, int Sq, int Sk, int H, float scale,
-                          int causal, int q_offset) {
+                          const long* ks, const long* vs, const long* os, int Sq, int Sk, int H, int Hkv,
+                          float scale, int causal, int q_offset) {
   AttnArgs a = {};
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o;
   a.lse = (float*)lse;
@@ -2437,6 +2446,7 @@ static AttnArgs attn_args(const void* q, const void* k, const void* v, const voi
   a.v_sb = vs[0]; a.v_ss = vs[1]; a.v_sh = vs[2];
   a.o_sb = os[0]; a.o_ss = os[1]; a.o_sh = os[2];
   a.Sq = Sq; a.Sk = Sk; a.H = H;
+  a.fd_g = make_fastdiv(H / Hkv);
   a.scale = scale; a.scale_log2 = scale * LOG2E;
   a.causal = causal; a.q_offset = q_offset;
   return a;
@@ -2449,6 +2459,8 @@ static AttnArgs attn_outs(AttnArgs a, void* o1, const long* s1, void* o2 = nullp
   if (o3) { a.out3 = (bf16_t*)o3; a.out3_sb = s3[0]; a.out3_ss = s3[1]; a.out3_sh = s3[2]; }
   return a;
 }
+// K/V heads that H query heads can share: a positive divisor of H
+static bool kv_heads_ok(int H, int Hkv) { return H > 0 && Hkv > 0 && H % Hkv == 0; }
 static bool none_null(std::initializer_list<const void*> ps) {
   for (const void* p : ps)
     if (!p) return false;
@@ -2665,11 +2677,14 @@ static void attn_launch(const AttnLaunch& l, hipStream_t stream, const AttnArgs&
 // stop after the plan step (ljs_attn_plan).
 // strides are in elements, ordered (batch, seq, head); head_dim must be 64 and contiguous.
 static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
-                         int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
+                         int H, int Hkv, const long* qs, const long* ks, const long* vs, const long* os, float scale,
                          int causal, int q_offset, void* oacc, const long* oas, int acc_mode, bool acc,
                          hipStream_t stream, AttnPlan* plan = nullptr) {
-  if (!none_null({qs, ks, vs, os}) || (acc && !oas)) return (int)hipErrorInvalidValue;
-  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, q_offset);
+  if (!none_null({qs, ks, vs, os}) || (acc && !oas) || !kv_heads_ok(H, Hkv)) {
+    if (plan) *plan = attn_reject();
+    return (int)hipErrorInvalidValue;
+  }
+  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, Hkv, scale, causal, q_offset);
   a.out = (bf16_t*)o;   // (addressed with the o strides)
   a.oacc = (float*)oacc;
   a.acc_mode = acc_mode;
@@ -2691,8 +2706,15 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* o, v
 LJS_API int ljs_attn_fwd(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
                          int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
                          int causal, int q_offset, hipStream_t stream) {
-  return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, qs, ks, vs, os, scale, causal, q_offset, nullptr, nullptr, 0,
-                       false, stream);
+  return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, H, qs, ks, vs, os, scale, causal, q_offset, nullptr, nullptr,
+                       0, false, stream);
+}
+// ... with k / v of Hkv heads, H % Hkv == 0 (grouped-query attention; Hkv == H is ljs_attn_fwd)
+LJS_API int ljs_attn_fwd_gqa(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
+                             int H, int Hkv, const long* qs, const long* ks, const long* vs, const long* os,
+                             float scale, int causal, int q_offset, hipStream_t stream) {
+  return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, Hkv, qs, ks, vs, os, scale, causal, q_offset, nullptr, nullptr,
+                       0, false, stream);
 }
 
 // blockwise forward with the running-output merge (ring attention's hop): acc_mode 1 / 2 / 3 (see
@@ -2700,8 +2722,15 @@ LJS_API int ljs_attn_fwd(const void* q, const void* k, const void* v, void* o, v
 LJS_API int ljs_attn_fwd_acc(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq, int Sk,
                              int H, const long* qs, const long* ks, const long* vs, const long* os, float scale,
                              int causal, int q_offset, void* oacc, const long* oas, int acc_mode, hipStream_t stream) {
-  return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, qs, ks, vs, os, scale, causal, q_offset, oacc, oas, acc_mode,
+  return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, H, qs, ks, vs, os, scale, causal, q_offset, oacc, oas, acc_mode,
                        true, stream);
+}
+LJS_API int ljs_attn_fwd_acc_gqa(const void* q, const void* k, const void* v, void* o, void* lse, int B, int Sq,
+                                 int Sk, int H, int Hkv, const long* qs, const long* ks, const long* vs,
+                                 const long* os, float scale, int causal, int q_offset, void* oacc, const long* oas,
+                                 int acc_mode, hipStream_t stream) {
+  return attn_fwd_impl(q, k, v, o, lse, B, Sq, Sk, H, Hkv, qs, ks, vs, os, scale, causal, q_offset, oacc, oas,
+                       acc_mode, true, stream);
 }
 
 
@@ -2728,14 +2757,18 @@ LJS_API int ljs_qkv_attn_fwd(const void* x, long ldx, const void* w, void* qkv, 
   return qkv_attn_fwd_impl(x, ldx, w, qkv, o, lse, T, K, N, H, scale, trace, ljs_device_cus(), stream);
 }
 
-// dq/dk/dv outputs get their own strides; delta is a [B][H][Sq] f32 workspace
+// dq/dk/dv outputs get their own strides; delta is a [B][H][Sq] f32 workspace.  dk / dv have H heads
+// whatever Hkv is: with Hkv < H they are the per-query-head gradients that ljs_gqa_reduce folds
 static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* o, const void* dout,
                          const void* lse, void* delta, void* dq, void* dk, void* dv, int B, int Sq, int Sk, int H,
-                         const long* qs, const long* ks, const long* vs, const long* os, const long* dos,
+                         int Hkv, const long* qs, const long* ks, const long* vs, const long* os, const long* dos,
                          const long* dqs, const long* dks, const long* dvs, float scale, int causal, int q_offset,
                          hipStream_t stream, AttnPlan* plan = nullptr) {
-  if (!none_null({qs, ks, vs, os, dos, dqs, dks, dvs})) return (int)hipErrorInvalidValue;
-  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, q_offset);
+  if (!none_null({qs, ks, vs, os, dos, dqs, dks, dvs}) || !kv_heads_ok(H, Hkv)) {
+    if (plan) *plan = attn_reject();
+    return (int)hipErrorInvalidValue;
+  }
+  AttnArgs a = attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, Hkv, scale, causal, q_offset);
   a.dout = (const bf16_t*)dout;
   a.delta = (const float*)delta;
   a.do_sb = dos[0]; a.do_ss = dos[1]; a.do_sh = dos[2];
@@ -2766,8 +2799,16 @@ LJS_API int ljs_attn_bwd(const void* q, const void* k, const void* v, const void
                          const long* qs, const long* ks, const long* vs, const long* os, const long* dos,
                          const long* dqs, const long* dks, const long* dvs, float scale, int causal, int q_offset,
                          hipStream_t stream) {
-  return attn_bwd_impl(q, k, v, o, dout, lse, delta, dq, dk, dv, B, Sq, Sk, H, qs, ks, vs, os, dos, dqs, dks, dvs,
+  return attn_bwd_impl(q, k, v, o, dout, lse, delta, dq, dk, dv, B, Sq, Sk, H, H, qs, ks, vs, os, dos, dqs, dks, dvs,
                        scale, causal, q_offset, stream);
+}
+LJS_API int ljs_attn_bwd_gqa(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                             const void* lse, void* delta, void* dq, void* dk, void* dv, int B, int Sq, int Sk, int H,
+                             int Hkv, const long* qs, const long* ks, const long* vs, const long* os, const long* dos,
+                             const long* dqs, const long* dks, const long* dvs, float scale, int causal, int q_offset,
+                             hipStream_t stream) {
+  return attn_bwd_impl(q, k, v, o, dout, lse, delta, dq, dk, dv, B, Sq, Sk, H, Hkv, qs, ks, vs, os, dos, dqs, dks,
+                       dvs, scale, causal, q_offset, stream);
 }
 
 // The fused backward with dO = dY . W^T formed per (batch, head) inside the kernel
@@ -2780,7 +2821,8 @@ static int attn_bwd_proj_impl(const void* q, const void* k, const void* v, const
                               const long* dqs, const long* dks, const long* dvs, float scale, int causal,
                               hipStream_t stream, AttnPlan* plan = nullptr) {
   if (!none_null({qs, ks, vs, os, dqs, dks, dvs})) return (int)hipErrorInvalidValue;
-  AttnArgs a = attn_outs(attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, scale, causal, 0), dk, dks, dv, dvs,
+  if (H <= 0) return (int)hipErrorInvalidValue;
+  AttnArgs a = attn_outs(attn_args(q, k, v, o, lse, qs, ks, vs, os, Sq, Sk, H, H, scale, causal, 0), dk, dks, dv, dvs,
                          dq, dqs);
   BwdProjArgs pj;
   pj.dy = (const bf16_t*)dy; pj.w = (const bf16_t*)w; pj.dy_ld = dy_ld; pj.M = M;
@@ -2823,10 +2865,10 @@ LJS_API int ljs_attn_plan(int kind, int B, int Sq, int Sk, int H, int causal, in
   void* const* p = addr;
   AttnPlan pl = attn_reject();
   if (kind == 0 || kind == 1)
-    attn_fwd_impl(p[0], p[1], p[2], p[3], p[4], B, Sq, Sk, H, st, st + 3, st + 6, st + 9, 1.f, causal, 0, p[7],
+    attn_fwd_impl(p[0], p[1], p[2], p[3], p[4], B, Sq, Sk, H, H, st, st + 3, st + 6, st + 9, 1.f, causal, 0, p[7],
                   kind ? st + 15 : nullptr, acc_mode, kind == 1, nullptr, &pl);
   else if (kind == 2)
-    attn_bwd_impl(p[0], p[1], p[2], p[3], p[5], p[4], p[6], p[8], p[9], p[10], B, Sq, Sk, H, st, st + 3, st + 6, st + 9,
+    attn_bwd_impl(p[0], p[1], p[2], p[3], p[5], p[4], p[6], p[8], p[9], p[10], B, Sq, Sk, H, H, st, st + 3, st + 6, st + 9,
                   st + 12, st + 18, st + 21, st + 24, 1.f, causal, 0, nullptr, &pl);
   else if (kind == 3)
     attn_bwd_proj_impl(p[0], p[1], p[2], p[3], p[11], ld, p[12], M, p[4], p[8], p[9], p[10], B, Sq, Sk, H, st, st + 3,

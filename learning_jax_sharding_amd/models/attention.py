@@ -20,6 +20,11 @@ Beyond the reference: ``causal=True`` masks key positions after the query's (bot
 ``rope_theta`` rotates q and k after the head split by their global positions (``ops.core.rope``:
 half-split pairs, ``y[i] = x[i] cos - x[i + h] sin``, ``y[i + h] = x[i + h] cos + x[i] sin`` with ``h =
 dim_head / 2`` and angle ``p theta^(-2 i / dim_head)``).  Both default to off.
+
+Grouped-query attention: ``kv_heads < heads`` gives ``to_k`` / ``to_v`` of ``kv_heads * dim_head``
+columns; with ``G = heads // kv_heads``, query head ``h`` attends to key/value head ``h // G`` (the G
+query heads of a group are adjacent: HF ``repeat_kv`` / MaxText order).  ``kv_heads=1`` is multi-query
+attention; ``None`` or ``heads`` is multi-head attention with the earlier parameter tree and launches.
 """
 from __future__ import annotations
 
@@ -53,16 +58,22 @@ class MultiHeadAttention(Module):
     verbose: bool = False
     causal: bool = False                  # query position p attends to key positions <= p only
     rope_theta: Optional[float] = None    # rotary position embedding of q and k with this base; None: none
+    kv_heads: Optional[int] = None        # key/value heads shared by groups of heads // kv_heads query heads
 
     def setup(self):
+        if self.kv_heads is not None and (self.kv_heads < 1 or self.heads % self.kv_heads):
+            raise ValueError(f"MultiHeadAttention: kv_heads={self.kv_heads} must be a positive divisor of "
+                             f"heads={self.heads}")
+        self.n_kv = self.heads if self.kv_heads is None else self.kv_heads
         if self.rope_theta is not None and self.dim_head % 2:
             raise ValueError(f"MultiHeadAttention: rope_theta needs an even dim_head, got {self.dim_head}")
         inner_dim = self.dim_head * self.heads
         self.scale = self.dim_head ** -0.5
         qkv_init = with_logical_partitioning(init.lecun_normal(), self.kernel_axes_in)
         self.query = Dense(inner_dim, kernel_init=qkv_init, use_bias=False, dtype=self.dtype, name="to_q")
-        self.key = Dense(inner_dim, kernel_init=qkv_init, use_bias=False, dtype=self.dtype, name="to_k")
-        self.value = Dense(inner_dim, kernel_init=qkv_init, use_bias=False, dtype=self.dtype, name="to_v")
+        kv_dim = self.dim_head * self.n_kv
+        self.key = Dense(kv_dim, kernel_init=qkv_init, use_bias=False, dtype=self.dtype, name="to_k")
+        self.value = Dense(kv_dim, kernel_init=qkv_init, use_bias=False, dtype=self.dtype, name="to_v")
         self.proj_attn = Dense(self.query_dim,
                                kernel_init=with_logical_partitioning(init.lecun_normal(), self.kernel_axes_out),
                                dtype=self.dtype, name="to_out_0")
@@ -119,7 +130,22 @@ class MultiHeadAttention(Module):
         # kernel over the batch axis: gather it on a side stream NOW, while the QKV projection and
         # the attention run, instead of at its use (parallel/fsdp.py Prefetcher, bf16 shadows)
         wo_pf = self._prefetch_out_kernel(hidden_states, dt)
-        if self.fused_qkv and self_attn:
+        gqa = self.n_kv != self.heads
+        if gqa:
+            # a K/V projection whose columns are split more ways than there are key/value heads would
+            # split a head (or need replicated key/value heads, which is not implemented)
+            n = self.key.kernel_param(context.shape[-1]).tile.tile_shape[1]
+            if self.n_kv % n:
+                raise ValueError(f"MultiHeadAttention: kv_heads={self.n_kv} cannot be sharded {n} ways (the shard "
+                                 f"count of the K/V projection's columns); kv_heads must be a multiple of {n}")
+        if self.fused_qkv and self_attn and gqa:
+            # K and V have equal widths and run as one fused two-kernel GEMM; Q, wider, is a GEMM of its
+            # own.  No attention_next hint: the fused projection + forward kernel is multi-head only
+            m = hidden_states.shape[-1]
+            query_proj, = core.dense(hidden_states, [self.query.kernel_param(m)], None, compute_dtype=dt)
+            key_proj, value_proj = core.dense(hidden_states, [self.key.kernel_param(m), self.value.kernel_param(m)],
+                                              None, compute_dtype=dt)
+        elif self.fused_qkv and self_attn:
             m = hidden_states.shape[-1]
             wq = self.query.kernel_param(m)
             wk = self.key.kernel_param(m)
@@ -162,8 +188,8 @@ class MultiHeadAttention(Module):
 
         b = hidden_states.shape[0]
         q = core.reshape(query_proj, (b, -1, self.heads, self.dim_head))
-        k = core.reshape(key_proj, (b, -1, self.heads, self.dim_head))
-        v = core.reshape(value_proj, (b, -1, self.heads, self.dim_head))
+        k = core.reshape(key_proj, (b, -1, self.n_kv, self.dim_head))
+        v = core.reshape(value_proj, (b, -1, self.n_kv, self.dim_head))
         q = with_logical_constraint(q, ("batch", "embed", None, None))
         k = with_logical_constraint(k, ("batch", "embed", None, None))
         v = with_logical_constraint(v, ("batch", "embed", None, None))
@@ -176,6 +202,14 @@ class MultiHeadAttention(Module):
         if self.impl == "fused":
             hidden = core.dot_product_attention(q, k, v, self.scale, causal=self.causal)
         else:
+            if gqa:
+                # every key/value head repeated for the G query heads of its group
+                def per_group(t):
+                    bt, st = t.shape[0], t.shape[1]
+                    t = core.reshape(t, (bt, st, self.n_kv, 1, self.dim_head))
+                    t = core.broadcast_to(t, (bt, st, self.n_kv, self.heads // self.n_kv, self.dim_head))
+                    return core.reshape(t, (bt, st, self.heads, self.dim_head))
+                k, v = per_group(k), per_group(v)
             qf = core.convert(q, torch.float32)
             kf = core.convert(k, torch.float32)
             scores = core.einsum("b t n h, b f n h -> b n f t", kf, qf)
@@ -238,11 +272,15 @@ def _fsdp_axis(w: ShardedArray, x: ShardedArray):
     return None
 
 
-def attention_block_flops(batch: int, seq: int, dim: int, heads: int, dim_head: int, train: bool) -> float:
-    """Matmul FLOPs of the case6 block: fwd 6.442 GFLOP at B=8,S=256,M=640; train 15.30."""
+def attention_block_flops(batch: int, seq: int, dim: int, heads: int, dim_head: int, train: bool,
+                          kv_heads: Optional[int] = None) -> float:
+    """Matmul FLOPs of the case6 block: fwd 6.442 GFLOP at B=8,S=256,M=640; train 15.30.
+    ``kv_heads`` (grouped-query attention) narrows the K and V projections to ``kv_heads * dim_head``
+    columns; the score and P.V products are per query head and unchanged."""
     t = batch * seq
     inner = heads * dim_head
-    qkv = 3 * 2 * t * dim * inner
+    kv_inner = (heads if kv_heads is None else kv_heads) * dim_head
+    qkv = 2 * t * dim * (inner + 2 * kv_inner)
     qk = 2 * batch * heads * seq * seq * dim_head
     pv = qk
     out = 2 * t * inner * dim

@@ -56,6 +56,7 @@ class TransformerLM(Module):
     causal: bool = False                  # causal self-attention in every layer
     rope_theta: Optional[float] = None    # rotary position embedding with this base in every layer
     ff: str = "relu"                      # "relu": FeedForward; "swiglu": GatedFeedForward (no fp8)
+    kv_heads: Optional[int] = None        # grouped-query attention in every layer (MultiHeadAttention.kv_heads)
 
     def default_ff_dim(self) -> int:
         """``ff_dim=None``: 4 dim for the ReLU feed-forward; for the gated one, whose three matrices then
@@ -79,7 +80,8 @@ class TransformerLM(Module):
         ff = self.ff_dim if self.ff_dim is not None else self.default_ff_dim()
         self.blocks = [TransformerLayer(self.dim, heads=self.heads, dim_head=self.dim_head, ff_dim=ff,
                                         dtype=self.dtype, fp8=self.fp8, norm=self.norm, causal=self.causal,
-                                        rope_theta=self.rope_theta, ff=self.ff, name=f"layer_{i}")
+                                        rope_theta=self.rope_theta, ff=self.ff, kv_heads=self.kv_heads,
+                                        name=f"layer_{i}")
                        for i in range(self.layers)]
         cls = LayerNorm if self.norm == "layer" else RMSNorm
         self.final_norm = cls(dtype=self.dtype, name="final_norm")

@@ -41,6 +41,7 @@ class TransformerLayer(Module):
     causal: bool = False                  # causal self-attention (MultiHeadAttention.causal)
     rope_theta: Optional[float] = None    # rotary position embedding of q and k (MultiHeadAttention.rope_theta)
     ff: str = "relu"                      # "relu": FeedForward; "swiglu": GatedFeedForward (no fp8)
+    kv_heads: Optional[int] = None        # grouped-query attention (MultiHeadAttention.kv_heads)
 
     def __post_init__(self):
         super().__post_init__()
@@ -48,7 +49,8 @@ class TransformerLayer(Module):
 
     def setup(self):
         self.attn = MultiHeadAttention(self.query_dim, self.heads, self.dim_head, dtype=self.dtype,
-                                       causal=self.causal, rope_theta=self.rope_theta, name="attn")
+                                       causal=self.causal, rope_theta=self.rope_theta, kv_heads=self.kv_heads,
+                                       name="attn")
         # the field `ff` names the kind; on the bound module the submodule takes its place (callers
         # reach the block as `layer.ff`, and its parameters sit under "ff" either way).  The kind is
         # kept aside so that a copy of a module that is already set up builds its block again
@@ -80,10 +82,11 @@ class TransformerLayer(Module):
         return self.ff(h, residual=h)
 
 
-def transformer_layer_flops(batch, seq, dim, heads, dim_head, ff_dim, train: bool, gated: bool = False) -> float:
+def transformer_layer_flops(batch, seq, dim, heads, dim_head, ff_dim, train: bool, gated: bool = False,
+                            kv_heads: Optional[int] = None) -> float:
     """Matmul FLOPs of one layer step (the project's convention: the memory-bound norms of a
     pre-norm layer and the activation are not counted).  ``gated``: a GatedFeedForward, three GEMMs
-    (gate, up, down) where the ReLU FeedForward has two."""
-    att = attention_block_flops(batch, seq, dim, heads, dim_head, train)
+    (gate, up, down) where the ReLU FeedForward has two.  ``kv_heads``: attention_block_flops'."""
+    att = attention_block_flops(batch, seq, dim, heads, dim_head, train, kv_heads=kv_heads)
     ff = (3 if gated else 2) * 2 * batch * seq * dim * ff_dim
     return att + (3 * ff if train else ff)

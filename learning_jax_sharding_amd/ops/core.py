@@ -829,6 +829,23 @@ def softmax(x: ShardedArray, axis: int = -1) -> ShardedArray:
     return ShardedArray(x.shape, x.dtype, x.sharding, loc)
 
 
+def _attention_kv_heads(q: ShardedArray, k: ShardedArray, v: ShardedArray, n: int) -> int:
+    """The key/value head count of an attention whose query heads are sharded ``n`` ways.  Grouped-query
+    attention (fewer k / v heads than q heads; query head h reads key/value head h // G, G = heads //
+    kv_heads): k / v are sharded on their heads like q, and because the G query heads of a group are
+    adjacent, a device's query heads read exactly its own key/value heads -- which needs kv_heads % n
+    == 0 (replicating key/value heads across shards is not implemented)."""
+    H, Hkv = q.shape[2], k.shape[2]
+    if v.shape[2] != Hkv:
+        raise ValueError(f"attention: k has {Hkv} heads and v has {v.shape[2]}; they must have the same head count")
+    if Hkv < 1 or H % Hkv != 0:
+        raise ValueError(f"attention: heads={H} is not a multiple of kv_heads={Hkv}")
+    if Hkv != H and Hkv % n != 0:
+        raise ValueError(f"attention: kv_heads={Hkv} cannot be sharded {n} ways with the query heads (heads={H}): "
+                         f"kv_heads must be a multiple of the head shard count {n}")
+    return Hkv
+
+
 def dot_product_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, scale: Optional[float] = None,
                           causal: bool = False) -> ShardedArray:
     """Fused ``softmax(f32(q)·f32(k)ᵀ·scale)`` → bf16 → ``·v`` on (batch, seq, heads, head_dim).
@@ -840,7 +857,9 @@ def dot_product_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, sca
 
     Sharding rule: batch/heads tiling of q is kept; q's sequence tiling is kept
     (context parallel); k and v are gathered over the sequence (the reference's
-    implicit all-gather of K/V over ``model``, SURVEY §2.7 case 6).
+    implicit all-gather of K/V over ``model``, SURVEY §2.7 case 6).  k and v may have fewer heads
+    than q (grouped-query attention, :func:`_attention_kv_heads`): they are then sharded on their own
+    heads the way q is, and the gathers move ``kv_heads`` heads.
     """
     if scale is None:
         scale = q.shape[-1] ** -0.5
@@ -848,6 +867,7 @@ def dot_product_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, sca
     if qt.tile_shape[3] > 1:
         q = reshard_tile(q, qt.unshard([3]), note="attn.q")
         qt = q.tile
+    kv_heads = _attention_kv_heads(q, k, v, qt.tile_shape[2])
     kv_tile = qt.unshard([1])
     q_offsets = {}
     ss = qt.shard_shape(q.shape)
@@ -857,7 +877,7 @@ def dot_product_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, sca
         return _attention_local_first(q, k, v, kv_tile, scale, causal, q_offsets)
     k2 = reshard_tile(k, kv_tile, note="attn.k") if k.tile != kv_tile else k
     v2 = reshard_tile(v, kv_tile, note="attn.v") if v.tile != kv_tile else v
-    _plan.record("attention", q_tiles=qt.tile_shape)
+    _plan.record("attention", q_tiles=qt.tile_shape, kv_heads=kv_heads)
     loc = {d: K.attention(q.local[d], k2.local[d], v2.local[d], scale, causal, q_offsets[d]) for d in q.local}
     return ShardedArray(q.shape, v.dtype, q.sharding, loc)
 
@@ -938,7 +958,7 @@ def _attention_local_first(q, k, v, kv_tile, scale, causal, q_offsets):
     else:
         k2 = reshard_tile(k, kv_tile, note="attn.k.local_first")
         v2 = reshard_tile(v, kv_tile, note="attn.v.local_first")
-    _plan.record("attention", q_tiles=q.tile.tile_shape, local_first=True)
+    _plan.record("attention", q_tiles=q.tile.tile_shape, local_first=True, kv_heads=k.shape[2])
     loc = {}
     for d in q.local:
         me = k.tile.coords[d][1]

@@ -59,6 +59,16 @@ _SIGS = {
     "ljs_attn_bwd_proj": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP,
                           c_float, c_int, c_void_p],
+    "ljs_attn_fwd_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP,
+                         _LP, _LP, c_float, c_int, c_int, c_void_p],
+    "ljs_attn_fwd_acc_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _LP,
+                             _LP, _LP, _LP, c_float, c_int, c_int, c_void_p, _LP, c_int, c_void_p],
+    "ljs_attn_bwd_gqa": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP, _LP, c_float,
+                         c_int, c_int, c_void_p],
+    "ljs_gqa_reduce": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP,
+                       c_void_p],
+    "ljs_gqa_set_max_blocks": [c_int],
     "ljs_attn_bwd_proj_enabled": [c_int, c_int],
     "ljs_attn_bwd_proj_last_path": [],
     "ljs_cast_f32_bf16": [c_void_p, c_void_p, c_long, c_void_p],
@@ -2183,7 +2193,7 @@ def register_fused_attention(out: torch.Tensor, o: torch.Tensor, lse: torch.Tens
 
 
 def _take_fused_attention(q, k, v, scale, causal, q_offset):
-    if not _FUSED_ATTN or causal or q_offset:
+    if not _FUSED_ATTN or causal or q_offset or k.shape[2] != q.shape[2]:
         return None
     ent = _FUSED_ATTN.get(_fused_key(q, scale))
     if ent is None:
@@ -2228,6 +2238,8 @@ def attn_bwd_proj_ok(q, k, v, o, dy: torch.Tensor, dy_ld: int, w: torch.Tensor, 
     the plan, and here only what the library cannot see -- dtypes, a contiguous head_dim and weight."""
     B, Sq, H, D = q.shape
     ts = dict(zip(("q", "k", "v", "o", "dq", "dk", "dv"), (q, k, v, o) + tuple(outs or ())))
+    if k.shape[2] != H or v.shape[2] != H:   # (the kernel is multi-head only: one K/V head per query head)
+        return False
     if not (D == 64 and w.shape[0] == H * D and dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
             and w.is_contiguous() and all(t.dtype == torch.bfloat16 and t.stride(3) == 1 for t in ts.values())):
         return False
@@ -2299,9 +2311,59 @@ def _take_out_proj(do: torch.Tensor, q, k, v, o, outs, causal):
     return None
 
 
+# ---------------------------------------------------------------------------- grouped-query attention
+# k / v of (B, Sk, Hkv, 64) with H % Hkv == 0: query head h reads key/value head h // (H // Hkv) inside
+# the kernels (ljs_attn_*_gqa); the backward kernels then write per-query-head dK / dV into a scratch
+# pair that gqa_reduce folds over each group.  Hkv == H runs the multi-head entry points unchanged.
+def _kv_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> int:
+    """The key/value head count of a call (``q`` (B, Sq, H, D), ``k`` / ``v`` (B, Sk, Hkv, D)); raises
+    a ValueError naming both counts where k's and v's differ or do not divide H."""
+    from .kernels import kv_groups
+    return q.shape[2] // kv_groups(q, k, v)
+
+
+def gqa_kernels() -> bool:
+    """``LJS_GQA_KERNELS=0`` (A/B, read at every call): grouped-query attention expands K / V to one head
+    per query head in torch and runs the multi-head path, autograd summing dK / dV over each group --
+    the baseline of scripts/gqa_probe.py."""
+    # LJS_GQA_KERNELS=0: K / V of a grouped-query attention are expanded per query head in torch in front
+    # of the multi-head kernels (autograd sums dK / dV); default: the kernels look the K/V head up
+    return os.environ.get("LJS_GQA_KERNELS", "1") != "0"
+
+
+def set_gqa_max_blocks(n: Optional[int]) -> None:
+    """Cap ``gqa_reduce``'s grid at ``n`` blocks (tests: the grid-stride loop on small shapes); None or
+    0 restores the default."""
+    lib().ljs_gqa_set_max_blocks(int(n or 0))
+
+
+def gqa_reduce_raw(dkx, dvx, dk, dv) -> int:
+    """``ljs_gqa_reduce``'s return code: dk / dv (B, Sk, Hkv, 64) = the sum of dkx / dvx (B, Sk, H, 64)
+    over each group of H // Hkv adjacent heads, f32 adds in ascending order and one rounding to bf16."""
+    B, Sk, H, _ = dkx.shape
+    return lib().ljs_gqa_reduce(_p(dkx), _p(dvx), _p(dk), _p(dv), B, Sk, H, dk.shape[2], _longs(_strides3(dkx)),
+                                _longs(_strides3(dvx)), _longs(_strides3(dk)), _longs(_strides3(dv)), _stream(dkx))
+
+
+def gqa_reduce(dkx: torch.Tensor, dvx: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor):
+    """Fold the per-query-head gradients ``dkx`` / ``dvx`` into ``dk`` / ``dv`` (one launch for both)."""
+    ok = all(t.dtype == torch.bfloat16 and t.shape[-1] == 64 and t.stride(3) == 1 for t in (dkx, dvx, dk, dv))
+    if not (ok and dkx.shape == dvx.shape and dk.shape == dv.shape and dk.shape[:2] == dkx.shape[:2]):
+        raise ValueError(f"gqa_reduce: bf16 (B, Sk, H, 64) -> (B, Sk, Hkv, 64) expected; got {tuple(dkx.shape)}, "
+                         f"{tuple(dvx.shape)} -> {tuple(dk.shape)}, {tuple(dv.shape)}")
+    _ck(gqa_reduce_raw(dkx, dvx, dk, dv), "ljs_gqa_reduce")
+    return dk, dv
+
+
 def _attn_fwd_call(q, k, v, o, lse, scale, causal, q_offset):
     """ljs_attn_fwd into ``o`` (bf16 [B, Sq, H, 64]) and ``lse`` (f32 [B, H, Sq]); returns both."""
     B, Sq, H, _ = q.shape
+    Hkv = _kv_heads(q, k, v)
+    if Hkv != H:
+        _ck(lib().ljs_attn_fwd_gqa(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, k.shape[1], H, Hkv,
+                                   _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)),
+                                   _longs(_strides3(o)), scale, int(causal), q_offset, _stream(q)), "ljs_attn_fwd_gqa")
+        return o, lse
     _ck(lib().ljs_attn_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, k.shape[1], H, _longs(_strides3(q)),
                            _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)), scale, int(causal),
                            q_offset, _stream(q)), "ljs_attn_fwd")
@@ -2319,9 +2381,25 @@ def _bf16_rows(do: torch.Tensor) -> torch.Tensor:
 
 
 def _attn_bwd_call(q, k, v, o, do, lse, dq, dk, dv, scale, causal, q_offset):
-    """ljs_attn_bwd into dq / dk / dv (``do`` as _bf16_rows gives it); allocates the delta workspace."""
+    """ljs_attn_bwd into dq / dk / dv (``do`` as _bf16_rows gives it); allocates the delta workspace.
+    With fewer key/value heads than query heads (dk / dv of Hkv heads) the kernels write per-query-head
+    gradients into a scratch pair, allocated here like any other intermediate (inside a graph capture
+    it belongs to the graph's pool, so a replay reuses the same addresses), and gqa_reduce folds them
+    into dk / dv on the same stream."""
     B, Sq, H, _ = q.shape
     delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    Hkv = _kv_heads(q, k, v)
+    if Hkv != H:
+        Sk = k.shape[1]
+        dkx = torch.empty((B, Sk, H, 64), dtype=torch.bfloat16, device=q.device)
+        dvx = torch.empty((B, Sk, H, 64), dtype=torch.bfloat16, device=q.device)
+        _ck(lib().ljs_attn_bwd_gqa(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dkx), _p(dvx),
+                                   B, Sq, Sk, H, Hkv, _longs(_strides3(q)), _longs(_strides3(k)),
+                                   _longs(_strides3(v)), _longs(_strides3(o)), _longs(_strides3(do)),
+                                   _longs(_strides3(dq)), _longs(_strides3(dkx)), _longs(_strides3(dvx)), scale,
+                                   int(causal), q_offset, _stream(q)), "ljs_attn_bwd_gqa")
+        gqa_reduce(dkx, dvx, dk, dv)
+        return
     _ck(lib().ljs_attn_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), B, Sq,
                            k.shape[1], H, _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)),
                            _longs(_strides3(o)), _longs(_strides3(do)), _longs(_strides3(dq)), _longs(_strides3(dk)),
@@ -2351,15 +2429,25 @@ class _Attention(torch.autograd.Function):
         fused = (Sq == Sk and k.stride() == st and v.stride() == st and st[3] == 1 and st[2] == D
                  and k.data_ptr() - q.data_ptr() == H * D * 2 and v.data_ptr() - q.data_ptr() == 2 * H * D * 2
                  and st[1] == 3 * H * D and st[0] == Sq * st[1])
-        if fused:
+        Hkv = k.shape[2]
+        sk = k.stride()
+        if fused and Hkv == H:
             # q/k/v are column blocks of one fused-QKV buffer: write dq/dk/dv the same way so the
             # dense backward sees one [M, 3*H*D] gradient and runs ONE batched weight-grad GEMM
             dqkv = torch.empty((B, Sq, 3, H, D), dtype=torch.bfloat16, device=q.device)
             dq, dk, dv = dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2]
+        elif (Hkv != H and v.stride() == sk and sk[3] == 1 and sk[2] == D and sk[1] == 2 * Hkv * D
+              and sk[0] == Sk * sk[1] and v.data_ptr() - k.data_ptr() == Hkv * D * 2):
+            # grouped-query attention with k / v the two column blocks of one [T][2 Hkv D] buffer (the fused
+            # K | V projection): dk / dv are the same column blocks of one fresh buffer, the adjacency
+            # linear._wgrads looks for, so the projection's weight gradient is one batched launch
+            dq = _bs_like((B, Sq, H, D), q)
+            dkv = torch.empty((B, Sk, 2, Hkv, D), dtype=torch.bfloat16, device=q.device)
+            dk, dv = dkv[:, :, 0], dkv[:, :, 1]
         else:
             dq = _bs_like((B, Sq, H, D), q)
-            dk = _bs_like((B, Sk, H, D), k)
-            dv = _bs_like((B, Sk, H, D), v)
+            dk = _bs_like((B, Sk, Hkv, D), k)
+            dv = _bs_like((B, Sk, Hkv, D), v)
         proj = _take_out_proj(do, q, k, v, o, (dq, dk, dv), causal) if _PROJ_PENDING else None
         if proj is not None:
             attn_bwd_proj_block(q, k, v, o, proj[0], proj[1], proj[2], lse, scale, causal, outs=(dq, dk, dv))
@@ -2370,7 +2458,9 @@ class _Attention(torch.autograd.Function):
 
 def attn_fwd_lse(q, k, v, scale: float, causal: bool = False, q_offset: int = 0):
     """Raw flash forward of one (q block, kv block) pair: (o bf16 [B,Sq,H,D], lse f32 [B,H,Sq]).
-    lse is log2 of the scaled-score partition function; +inf marks rows with no unmasked key."""
+    lse is log2 of the scaled-score partition function; +inf marks rows with no unmasked key.
+    k / v are (B, Sk, Hkv, D) with H % Hkv == 0 (grouped-query attention), here and in attn_fwd_acc,
+    attn_bwd_block (dk / dv of Hkv heads) and attention."""
     o = torch.empty(q.shape, dtype=torch.bfloat16, device=q.device)
     return _attn_fwd_call(q, k, v, o, _lse_like(q), scale, causal, q_offset)
 
@@ -2386,6 +2476,14 @@ def attn_fwd_acc(q, k, v, scale: float, causal: bool, q_offset: int, oacc: torch
     if mode == 3 and out is None:
         out = _bs_like((B, Sq, H, D), q)
     o = out if out is not None else q   # (unused unless mode 3)
+    Hkv = _kv_heads(q, k, v)
+    if Hkv != H:
+        rc = lib().ljs_attn_fwd_acc_gqa(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, Sk, H, Hkv, _longs(_strides3(q)),
+                                        _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)), scale,
+                                        int(causal), q_offset, _p(oacc), _longs(_strides3(oacc)), int(mode),
+                                        _stream(q))
+        _ck(rc, "ljs_attn_fwd_acc_gqa")
+        return out
     rc = lib().ljs_attn_fwd_acc(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, Sk, H, _longs(_strides3(q)),
                                 _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)), scale, int(causal),
                                 q_offset, _p(oacc), _longs(_strides3(oacc)), int(mode), _stream(q))
@@ -2399,8 +2497,8 @@ def attn_bwd_block(q, k, v, o, do, lse, scale: float, causal: bool = False, q_of
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     dq = torch.empty((B, Sq, H, D), dtype=torch.bfloat16, device=q.device)
-    dk = torch.empty((B, Sk, H, D), dtype=torch.bfloat16, device=q.device)
-    dv = torch.empty((B, Sk, H, D), dtype=torch.bfloat16, device=q.device)
+    dk = torch.empty((B, Sk, k.shape[2], D), dtype=torch.bfloat16, device=q.device)
+    dv = torch.empty((B, Sk, v.shape[2], D), dtype=torch.bfloat16, device=q.device)
     _attn_bwd_call(q, k, v, o, _bf16_rows(do), lse, dq, dk, dv, scale, causal, q_offset)
     return dq, dk, dv
 
@@ -2411,6 +2509,10 @@ def attention(q, k, v, scale: float, causal: bool = False, q_offset: int = 0) ->
     if not ok:
         raise NotImplementedError(f"HIP attention supports head_dim 64 with contiguous head_dim; got {q.shape}")
     qb, kb, vb = (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16) for t in (q, k, v))
+    Hkv = _kv_heads(q, k, v)
+    if Hkv != q.shape[2] and not gqa_kernels():
+        from .kernels import expand_kv
+        kb, vb = expand_kv(kb, q.shape[2] // Hkv), expand_kv(vb, q.shape[2] // Hkv)
     out = _Attention.apply(qb, kb, vb, float(scale), bool(causal), int(q_offset))
     return out if v.dtype == torch.bfloat16 else out.to(v.dtype)
 

@@ -477,8 +477,40 @@ def softmax(t: torch.Tensor, axis: int) -> torch.Tensor:
     return torch.softmax(t.float(), dim=axis).to(t.dtype)
 
 
+def kv_groups(q, k, v) -> int:
+    """G = heads // kv_heads of (b, s, heads, h) ``q`` against (b, s, kv_heads, h) ``k`` / ``v``
+    (grouped-query attention: query head n reads key/value head n // G, so the G query heads of a
+    group are adjacent); 1 is multi-head attention."""
+    H, Hk, Hv = q.shape[2], k.shape[2], v.shape[2]
+    if Hk != Hv:
+        raise ValueError(f"attention: k has {Hk} heads and v has {Hv}; they must have the same head count")
+    if Hk < 1 or H % Hk != 0:
+        raise ValueError(f"attention: {H} query heads are not a multiple of {Hk} key/value heads")
+    return H // Hk
+
+
+def expand_kv(t: torch.Tensor, G: int) -> torch.Tensor:
+    """(b, s, kv_heads, h) with every head repeated G times in place (``repeat_interleave`` on the head
+    dim); ``t`` itself for G == 1."""
+    if G == 1:
+        return t
+    b, s, n, h = t.shape
+    return t.unsqueeze(3).expand(b, s, n, G, h).reshape(b, s, n * G, h)
+
+
+def _group_sum(t: torch.Tensor, G: int) -> torch.Tensor:
+    """f32 (b, s, heads, h) per-query-head gradients summed over each group of G adjacent heads."""
+    if G == 1:
+        return t
+    b, s, n, h = t.shape
+    return t.reshape(b, s, n // G, G, h).sum(3)
+
+
 def attention_reference(q, k, v, scale: float, causal: bool = False, q_offset: int = 0) -> torch.Tensor:
-    """Plain torch oracle of ``case6_attention.py:120-133`` on (b, s, n, h) tensors."""
+    """Plain torch oracle of ``case6_attention.py:120-133`` on (b, s, n, h) tensors; k / v may have
+    fewer heads than q (:func:`kv_groups`)."""
+    G = kv_groups(q, k, v)
+    k, v = expand_kv(k, G), expand_kv(v, G)
     qf, kf = q.float(), k.float()
     s = torch.einsum("btnh,bfnh->bnft", kf, qf) * scale
     if causal:
@@ -501,6 +533,7 @@ def _hip_attn(q, k, v) -> bool:
     with a one-time warning."""
     if not use_hip(q):
         return False
+    kv_groups(q, k, v)   # (raises on unequal K / V head counts or heads that do not divide)
     if all(t.shape[-1] == 64 and t.stride(-1) == 1 for t in (q, k, v)):
         return True
     key = (q.shape[-1], v.shape[-1])
@@ -537,6 +570,8 @@ def attention_fwd_lse(q, k, v, scale: float, causal: bool = False, q_offset: int
     without any unmasked key."""
     if _hip_attn(q, k, v):
         return _hip().attn_fwd_lse(q, k, v, scale, causal, q_offset)
+    G = kv_groups(q, k, v)
+    k, v = expand_kv(k, G), expand_kv(v, G)
     s = _block_scores(q, k, scale, causal, q_offset)
     m = s.amax(-1, keepdim=True)
     empty = torch.isinf(m) & (m < 0)
@@ -597,6 +632,9 @@ def attention_bwd_block(q, k, v, o, do, lse, scale: float, causal: bool = False,
     """One kv block's (dq, dk, dv) given the final output ``o`` and global (log2) ``lse``."""
     if _hip_attn(q, k, v):
         return _hip().attn_bwd_block(q, k, v, o, do, lse, scale, causal, q_offset)
+    G = kv_groups(q, k, v)
+    kd, vd = k.dtype, v.dtype
+    k, v = expand_kv(k, G), expand_kv(v, G)
     s = _block_scores(q, k, scale, causal, q_offset)
     p = torch.exp(s - (lse / _LOG2E)[..., None])
     dof = do.float()
@@ -604,6 +642,6 @@ def attention_bwd_block(q, k, v, o, do, lse, scale: float, causal: bool = False,
     delta = (dof * o.float()).sum(-1).permute(0, 2, 1)[..., None]       # [b,h,q,1]
     ds = p * (dp - delta)
     dq = torch.einsum("bhqk,bkhd->bqhd", ds, k.float()) * scale
-    dk = torch.einsum("bhqk,bqhd->bkhd", ds, q.float()) * scale
-    dv = torch.einsum("bhqk,bqhd->bkhd", p.to(v.dtype).float(), dof)
-    return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
+    dk = _group_sum(torch.einsum("bhqk,bqhd->bkhd", ds, q.float()) * scale, G)
+    dv = _group_sum(torch.einsum("bhqk,bqhd->bkhd", p.to(v.dtype).float(), dof), G)
+    return dq.to(q.dtype), dk.to(kd), dv.to(vd)

@@ -22,7 +22,8 @@ Two schedules are provided on (batch, seq, heads, head_dim) arrays whose seq dim
   output back to sequence sharding.  Per device it moves 3 + 1 tensors of (n-1)/n of its shard
   (the all-gather plan receives (n-1) shards of K and V), and the attention kernels see the
   single-device shape (all keys, whole heads) instead of S/n-query blocks against S keys.
-  Needs the head count divisible by n; the backward is the transposed all-to-alls.
+  Needs the head count (and the key/value head count, where k and v have fewer heads than q)
+  divisible by n; the backward is the transposed all-to-alls.
 
 Memory per device is O(S/n) for K/V instead of O(S), the stepping stone to long-context
 training on 288 GB parts; on xGMI the hop is a point-to-point neighbour transfer, one link.
@@ -74,7 +75,8 @@ def _seq_to_heads(t):
 def ulysses_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, scale: Optional[float] = None,
                       causal: bool = False) -> ShardedArray:
     """All-to-all (sequence <-> heads) attention over q's sequence sharding (see module doc); the
-    all-gather plan when the heads are already split or do not divide over the group."""
+    all-gather plan when the heads are already split or do not divide over the group -- the query
+    heads, or the key/value heads of a grouped-query attention (k / v with fewer heads than q)."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
     qt = q.tile
@@ -82,7 +84,7 @@ def ulysses_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, scale: 
         q = reshard_tile(q, qt.unshard([3]), note="ulysses.q")
         qt = q.tile
     n = qt.tile_shape[1]
-    if n == 1 or qt.tile_shape[2] != 1 or q.shape[2] % n:
+    if n == 1 or qt.tile_shape[2] != 1 or q.shape[2] % n or k.shape[2] % n or v.shape[2] % n:
         return core.dot_product_attention(q, k, v, scale=scale, causal=causal)
     ht = _seq_to_heads(qt)
     if ht is None:
@@ -239,13 +241,15 @@ class _RingAttention(torch.autograd.Function):
 
 def ring_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, scale: Optional[float] = None,
                    causal: bool = False) -> ShardedArray:
-    """Ring (blockwise, log-sum-exp merged) attention over q's sequence sharding."""
+    """Ring (blockwise, log-sum-exp merged) attention over q's sequence sharding.  k / v may have
+    fewer heads than q (grouped-query attention): the hops then carry ``kv_heads`` heads."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
     qt = q.tile
     if qt.tile_shape[3] > 1:
         q = reshard_tile(q, qt.unshard([3]), note="ring.q")
         qt = q.tile
+    core._attention_kv_heads(q, k, v, qt.tile_shape[2])
     k = reshard_tile(k, qt, note="ring.k") if k.tile != qt else k
     v = reshard_tile(v, qt, note="ring.v") if v.tile != qt else v
     n = qt.tile_shape[1]
