@@ -1,0 +1,586 @@
+// Decoding with a key/value cache: the cache append (with the rotary embedding of the new q and k at
+// a position read on the device) and single-query split-K attention over the cache.
+//
+// Layout.  q is (B, T, H, 64), new k / v are (B, T, Hkv, 64), the caches kc / vc are (B, cap, Hkv, 64),
+// all bf16 with the head dim contiguous and their own (batch, position, head) strides in elements
+// (column blocks of a fused projection buffer are read in place); every base and stride is 16-byte
+// aligned and offsets are 64-bit.  lens is int32 [B] ON THE DEVICE: no kernel argument depends on the
+// current lengths, so a launch captured into a graph stays valid while the sequences grow.  Query
+// head h reads key/value head h / G, G = H / Hkv (attention.hip's convention).
+//
+// kv_append.  With p = base[b] + t, base[b] = lens[b] (decode) or 0 when lens is null (prefill):
+//     vc[b][p] = v[b][t]                      (the 16-byte chunks as they are)
+//     kc[b][p] = rot(k[b][t], p)              (or k[b][t] as it is without a table)
+//     q_out[b][t] = rot(q[b][t], p)           (optional)
+// rot is rope.hip's map: the same f32 cos / sin table, the same half-split pairs and the same f32
+// expressions, so the bits are rope_kernel's at position p.  Rows with p outside [0, cap) are not
+// written to the caches (q_out gets zeros there).  One work item is (tensor, batch, t, head, j): the
+// chunks j and j + 4 of one head row (the two halves' matching 8 elements), grid-stride over a grid
+// sized from the CU count.  No LDS, no cross-lane traffic, no atomics.
+//
+// attn_decode.  For sequence b the keys are the rows [0, n_b), n_b = min(lens[b] + extra, cap) (extra
+// = 1 after an append that lens does not count yet):
+//     o[b][0][h]  = bf16( sum_key bf16(p[key]) vc[b][key][h / G] / l ),  p = exp2(s scale log2e - m)
+//     lse2[b][h]  = m + log2(l)          (log2 of the partition function of the scaled scores)
+// and n_b = 0 gives o = 0, lse2 = +inf.  f32 scores, the scale folded into the exp2 argument, a running
+// max, probabilities rounded to bf16 before P.V, f32 accumulation, one rounding of O: the forward of
+// attention.hip.  The key axis is cut into `splits` ranges of `keys_per_split` keys by a pure plan
+// (plan_decode: of B, Hkv, cap and the CU count, never of the lengths); the grid is splits x Hkv x B
+// and a block whose range starts at or beyond n_b writes the empty partial (m = -inf, l = 0, acc = 0).
+//
+// One block of 4 waves takes one (batch, key/value head, split) and ALL G <= 16 query heads of the
+// group, so a K/V byte is fetched once per key/value head.  A key row is 8 chunks of 16 bytes: 8
+// lanes hold one key, a wave 8 keys per step, and every lane keeps its chunk's 8 columns of q and of
+// the accumulator of each head.  K and V go straight from memory to VGPRs (kDecUnroll steps of
+// buffer loads are issued before the first is used; no LDS staging); a score is 4 packed bf16 dot
+// products and a 3-step DPP sum over the key's 8 lanes, after which all 8 lanes hold it.  A wave
+// carries at most 8 heads (registers): for G > 8 waves 0-1 take heads 0..7 and waves 2-3 heads 8..15,
+// each pair sweeping the whole range (the second pair's loads hit the cache).  Every 8-lane slot runs
+// its own online softmax; the 8 slots of a wave are merged by shuffles and the waves through 9 KiB of
+// LDS, both in a fixed order.
+//
+// Rows at and beyond the end of a block's range never reach a register: K and V are read through
+// buffer descriptors that end with the last row of the range, so a load past it returns zeros
+// whatever the memory holds (NaN, Inf), and its score is replaced by -inf.
+//
+// splits == 1: the block writes o and lse2 itself.  Otherwise the partials (m, l, acc[64] per head,
+// f32) go to a workspace and a second small launch (decode_merge, one wave per (b, h)) merges them in
+// a fixed order -- eight interleaved chains, each in ascending split order, then a fixed tree: the
+// same bits on every run.  (The in-launch last-arriver form of rowwise.h would save that
+// launch, about 2 us inside a graph, at the price of write-through stores, a ticket per (b, kv head) and
+// a serial merge tail in whichever block arrives last; with a kernel boundary in between, plain
+// stores are enough.)
+#include "rowwise.h"
+
+namespace {
+
+constexpr int kDecD = 64;                 // head dim
+constexpr int kDecChunks = kDecD / 8;     // 16-byte chunks per head row = lanes per key
+constexpr int kDecThreads = 256;
+constexpr int kDecWaves = kDecThreads / 64;
+constexpr int kDecSlots = 64 / kDecChunks;             // keys a wave holds per step
+constexpr int kDecKeyTile = kDecWaves * kDecSlots;     // keys a block holds per step: 32
+constexpr int kDecUnroll = 4;             // steps whose loads are in flight together (8 measured slower at
+                                          // one head per wave: 119.7 against 112.6 us at B = 64, 4096 keys)
+constexpr int kDecWaveHeads = 8;          // query heads one wave carries
+constexpr int kDecMaxG = 2 * kDecWaveHeads;
+constexpr int kDecPart = 72;              // floats of one partial: acc[64], m, l, padded to 16 bytes
+constexpr int kDecBlocksPerCu = 4;        // the plan's target: blocks per compute unit
+constexpr int kDecMinTiles = 8;           // a split sweeps at least 8 key tiles (256 keys), 4 on an unfilled chip
+constexpr int kDecOneSplitTiles = 16;     // up to 512 rows of capacity: one split (no merge launch)
+constexpr int kAppBlocksPerCu = 8;
+
+int g_dec_splits = 0, g_dec_keys = 0;     // > 0: a plan forced by tests
+
+__device__ __forceinline__ float dec_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+  return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xf, 0xf, false));
+}
+// sum over the 8 lanes of a key; every one of them ends up with the same bits (each step adds the
+// same two numbers in both partners)
+__device__ __forceinline__ float sum8(float v) {
+  v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+  v += dpp_mov<0x141>(v);   // row_half_mirror: lane i <-> 7 - i, the other quad
+  return v;
+}
+
+__device__ __forceinline__ float dot2_bf16(unsigned a, unsigned b, float c) {
+#if __has_builtin(__builtin_amdgcn_fdot2_f32_bf16)
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
+#else
+  return fmaf(bf16_hi(a), bf16_hi(b), fmaf(bf16_lo(a), bf16_lo(b), c));
+#endif
+}
+
+// (m, l, acc) <- merged with (m2, l2, acc2): log-sum-exp in the log2 domain; m = -inf is "no key yet"
+__device__ __forceinline__ void dec_merge(float& m, float& l, float (&acc)[8], float m2, float l2,
+                                          const float (&acc2)[8]) {
+  const float mn = fmaxf(m, m2);
+  const float mu = mn == -INFINITY ? 0.f : mn;
+  const float a1 = dec_exp2(m - mu), a2 = dec_exp2(m2 - mu);
+  l = l * a1 + l2 * a2;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = acc[e] * a1 + acc2[e] * a2;
+  m = mn;
+}
+
+struct DecodeArgs {
+  const bf16_t *q, *kc, *vc;
+  bf16_t* o;
+  float* lse;                 // [B][H]
+  float* ws;                  // [B][H][splits][kDecPart]
+  const int* lens;
+  long qb, qh;                // strides (elements): batch, head (one position)
+  long kb, ks, kh, vb, vs, vh, ob, oh;
+  int B, H, Hkv, G, cap, extra, splits, kps;
+  float scale_log2;
+};
+
+// final output of one (b, h, chunk) from a merged state
+__device__ __forceinline__ void dec_store_out(const DecodeArgs& a, int b, int h, int cc, float m, float l,
+                                              const float (&acc)[8]) {
+  const float inv = l > 0.f ? 1.f / l : 0.f;
+  float y[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] = acc[e] * inv;
+  store_chunk(a.o + (long)b * a.ob + (long)h * a.oh + cc * 8, y);
+  if (cc == 0) a.lse[(long)b * a.H + h] = l > 0.f ? m + __log2f(l) : INFINITY;
+}
+
+template <int HW>
+__global__ __launch_bounds__(kDecThreads)
+void attn_decode_kernel(const DecodeArgs a) {
+  __shared__ alignas(16) float sh[kDecWaves][HW][kDecPart];
+  const int split = blockIdx.x, j = blockIdx.y, b = blockIdx.z;
+  const int lane = threadIdx.x & 63, slot = lane >> 3, c = lane & 7;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int parts = (a.G + HW - 1) / HW;       // 1, or 2 for G > 8
+  const int wpp = kDecWaves / parts;           // waves sweeping the range for one part's heads
+  const int part = wave / wpp, wk = wave % wpp;
+  const int g0 = part * HW;
+
+  int n = a.lens[b] + a.extra;
+  n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+  const int k0 = split * a.kps;
+  const int k1 = k0 + a.kps < n ? k0 + a.kps : n;
+
+  u32x4 qw[HW];
+#pragma unroll
+  for (int i = 0; i < HW; ++i) {
+    qw[i] = u32x4{0u, 0u, 0u, 0u};
+    if (g0 + i < a.G)
+      qw[i] = load16<u32x4, kAligned16>(a.q + (long)b * a.qb + (long)(j * a.G + g0 + i) * a.qh + c * 8);
+  }
+
+  // descriptors that end with row k1 - 1 of this (batch, key/value head): rows beyond read as zeros
+  const bool any_key = k1 > k0;
+  const long kbytes = any_key ? ((long)(k1 - 1) * a.ks + kDecD) * 2 : 0;
+  const long vbytes = any_key ? ((long)(k1 - 1) * a.vs + kDecD) * 2 : 0;
+  const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.kc + (long)b * a.kb + (long)j * a.kh, kbytes);
+  const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.vc + (long)b * a.vb + (long)j * a.vh, vbytes);
+  const int kstep = (int)a.ks * 2, vstep = (int)a.vs * 2;    // bytes per key (host: cap x stride fits an int)
+
+  float m[HW], l[HW];
+  f32x2 acc[HW][4];
+#pragma unroll
+  for (int i = 0; i < HW; ++i) {
+    m[i] = -INFINITY;
+    l[i] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[i][e] = f32x2{0.f, 0.f};
+  }
+
+  const int stride = wpp * kDecSlots;          // keys one step of this part's waves covers
+  for (int base = k0; base < k1; base += stride * kDecUnroll) {
+    int key[kDecUnroll];
+    u32x4 kr[kDecUnroll], vr[kDecUnroll];
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u) {
+      key[u] = base + u * stride + wk * kDecSlots + slot;
+      kr[u] = __builtin_amdgcn_raw_buffer_load_b128(rk, key[u] * kstep + c * 16, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u) vr[u] = __builtin_amdgcn_raw_buffer_load_b128(rv, key[u] * vstep + c * 16, 0, 0);
+
+    f32x2 vf[kDecUnroll][4];
+#pragma unroll
+    for (int u = 0; u < kDecUnroll; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) vf[u][e] = f32x2{bf16_lo(vr[u][e]), bf16_hi(vr[u][e])};
+
+#pragma unroll
+    for (int i = 0; i < HW; ++i) {
+      float s[kDecUnroll];
+#pragma unroll
+      for (int u = 0; u < kDecUnroll; ++u) {
+        float d = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) d = dot2_bf16(kr[u][w], qw[i][w], d);
+        d = sum8(d);
+        s[u] = key[u] < k1 ? d : -INFINITY;
+      }
+      float tmax = s[0];
+#pragma unroll
+      for (int u = 1; u < kDecUnroll; ++u) tmax = fmaxf(tmax, s[u]);
+      // scores are compared raw (scale > 0 keeps the order); the scale is applied in the FMA below
+      const float m_new = fmaxf(m[i], tmax * a.scale_log2);
+      const float m_use = m_new == -INFINITY ? 0.f : m_new;
+      const float alpha = dec_exp2(m[i] - m_use);
+      float p[kDecUnroll], psum = 0.f;
+#pragma unroll
+      for (int u = 0; u < kDecUnroll; ++u) {
+        p[u] = dec_exp2(s[u] * a.scale_log2 - m_use);
+        psum += p[u];
+      }
+      l[i] = l[i] * alpha + psum;
+      // no slot's running max moved (the usual case after the first keys): alpha is exactly 1
+      if (__any(m_new != m[i])) {
+        const f32x2 al2 = {alpha, alpha};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][e] = acc[i][e] * al2;
+      }
+      m[i] = m_new;
+#pragma unroll
+      for (int u = 0; u < kDecUnroll; ++u) {
+        const float pb = bf2f(f2bf(p[u]));     // probabilities rounded to bf16 before P.V
+        const f32x2 pb2 = {pb, pb};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][e] = pb2 * vf[u][e] + acc[i][e];
+      }
+    }
+  }
+
+  // the 8 slots of the wave, merged into slot 0 (lanes 0..7) in a fixed order
+#pragma unroll
+  for (int i = 0; i < HW; ++i) {
+    float av[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      av[2 * e] = acc[i][e][0];
+      av[2 * e + 1] = acc[i][e][1];
+    }
+#pragma unroll
+    for (int x = kDecChunks; x < 64; x <<= 1) {
+      const float m2 = __shfl_xor(m[i], x, 64), l2 = __shfl_xor(l[i], x, 64);
+      float a2[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a2[e] = __shfl_xor(av[e], x, 64);
+      dec_merge(m[i], l[i], av, m2, l2, a2);
+    }
+    if (slot == 0) {
+      store_chunk(&sh[wave][i][c * 8], av);
+      store_chunk(&sh[wave][i][c * 8 + 4], av + 4);
+      if (c == 0) {
+        sh[wave][i][kDecD] = m[i];
+        sh[wave][i][kDecD + 1] = l[i];
+      }
+    }
+  }
+  __syncthreads();
+
+  // the waves of a head's part, in ascending order: thread (g, chunk)
+  const int t = threadIdx.x;
+  if (t < a.G * kDecChunks) {
+    const int g = t >> 3, cc = t & 7, pg = g / HW, gi = g % HW;
+    float mm = -INFINITY, ll = 0.f, av[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int w = pg * wpp; w < (pg + 1) * wpp; ++w) {
+      float a2[8];
+      load_chunk(&sh[w][gi][cc * 8], a2);
+      load_chunk(&sh[w][gi][cc * 8 + 4], a2 + 4);
+      dec_merge(mm, ll, av, sh[w][gi][kDecD], sh[w][gi][kDecD + 1], a2);
+    }
+    const int h = j * a.G + g;
+    if (a.splits == 1) {
+      dec_store_out(a, b, h, cc, mm, ll, av);
+    } else {
+      float* p = a.ws + (((long)b * a.H + h) * a.splits + split) * kDecPart;
+      store_chunk(p + cc * 8, av);
+      store_chunk(p + cc * 8 + 4, av + 4);
+      if (cc == 0) {
+        p[kDecD] = mm;
+        p[kDecD + 1] = ll;
+      }
+    }
+  }
+}
+
+// The partials of one (b, h) per wave: lane = (slot, chunk).  Pass 1 finds the largest m of all splits
+// (exact, whatever the order).  Pass 2: slot j adds the splits j, j + 8, .. in ascending order, each
+// weighted by exp2(m_s - M), with the loads of 4 splits in flight; the 8 slots are then added by a
+// fixed tree of plain adds.  Every order is fixed, so the bits are the same on every run.
+constexpr int kMergeUnroll = 4;
+__global__ __launch_bounds__(64)
+void decode_merge_kernel(const DecodeArgs a) {
+  const int lane = threadIdx.x, slot = lane >> 3, cc = lane & 7;
+  const long bh = blockIdx.x;
+  const float* base = a.ws + bh * a.splits * kDecPart;
+  float mx = -INFINITY;
+  for (int s = lane; s < a.splits; s += 64) mx = fmaxf(mx, base[(long)s * kDecPart + kDecD]);
+  mx = warp_max64(mx);
+  const float mu = mx == -INFINITY ? 0.f : mx;
+  float ll = 0.f, av[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int s0 = slot; s0 < a.splits; s0 += kDecSlots * kMergeUnroll) {
+    float a2[kMergeUnroll][8], m2[kMergeUnroll], l2[kMergeUnroll];
+#pragma unroll
+    for (int u = 0; u < kMergeUnroll; ++u) {
+      const int s = s0 + u * kDecSlots;
+      const float* p = base + (long)s * kDecPart;
+      m2[u] = -INFINITY;
+      l2[u] = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a2[u][e] = 0.f;
+      if (s < a.splits) {                         // (uniform over a slot's 8 lanes)
+        load_chunk(p + cc * 8, a2[u]);
+        load_chunk(p + cc * 8 + 4, a2[u] + 4);
+        m2[u] = p[kDecD];
+        l2[u] = p[kDecD + 1];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kMergeUnroll; ++u) {
+      const float w = dec_exp2(m2[u] - mu);       // 0 for an empty partial and past the last split
+      ll += l2[u] * w;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) av[e] += a2[u][e] * w;
+    }
+  }
+#pragma unroll
+  for (int x = kDecChunks; x < 64; x <<= 1) {
+    ll += __shfl_xor(ll, x, 64);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) av[e] += __shfl_xor(av[e], x, 64);
+  }
+  if (slot == 0) dec_store_out(a, (int)(bh / a.H), (int)(bh % a.H), cc, mx, ll, av);
+}
+
+// ---- the plan: pure, of the capacity and never of the lengths
+inline void plan_decode(int B, int Hkv, int cap, int cus, int* splits, int* kps) {
+  const long tiles = ((long)cap + kDecKeyTile - 1) / kDecKeyTile;
+  const long groups = (long)B * Hkv;
+  long s = 1;
+  if (tiles > kDecOneSplitTiles) {
+    const long want = ((long)kDecBlocksPerCu * cus + groups - 1) / groups;   // several blocks per CU
+    const long fill = ((long)cus + groups - 1) / groups;                      // one block per CU
+    const long most = (tiles + kDecMinTiles - 1) / kDecMinTiles;              // a split is worth a block
+    s = want < most ? want : most;
+    if (s < fill) {                      // too few blocks for the chip: allow splits of half the size
+      const long most2 = (tiles + kDecMinTiles / 2 - 1) / (kDecMinTiles / 2);
+      s = fill < most2 ? fill : most2;
+    }
+  }
+  const long per = (tiles + s - 1) / s;
+  *kps = (int)(per * kDecKeyTile);
+  *splits = (int)((tiles + per - 1) / per);
+}
+
+inline int decode_launch_plan(int B, int Hkv, int cap, int* splits, int* kps) {
+  if (g_dec_splits > 0) {
+    if (g_dec_keys % kDecKeyTile != 0 || (long)g_dec_splits * g_dec_keys < cap) return (int)hipErrorInvalidValue;
+    *splits = g_dec_splits;
+    *kps = g_dec_keys;
+    return 0;
+  }
+  plan_decode(B, Hkv, cap, ljs_device_cus(), splits, kps);
+  return 0;
+}
+
+inline bool dec_aligned(const void* p, const long* st) {
+  return p && st && (((uintptr_t)p) & 15u) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0;
+}
+
+// ---- kv_append
+struct AppTensor {
+  const bf16_t* in;
+  bf16_t* out;
+  long ib, it, ih;            // input strides (elements): batch, position, head
+  long ob, op, oh;            // output strides
+  long first;                 // its first work item
+  int H, rotate, cache;
+};
+
+struct AppendArgs {
+  AppTensor t[3];             // k -> kc, v -> vc, q -> q_out
+  const float *cos_t, *sin_t;
+  const int* lens;
+  long total;
+  int nt, T, cap;
+};
+
+__global__ __launch_bounds__(kRowBlockThreads)
+void kv_append_kernel(const AppendArgs a) {
+  constexpr int h = kDecD / 2;
+  const long step = (long)gridDim.x * kRowBlockThreads;
+  for (long item = (long)blockIdx.x * kRowBlockThreads + threadIdx.x; item < a.total; item += step) {
+    int which = 0;
+    if (a.nt > 1 && item >= a.t[1].first) which = 1;
+    if (a.nt > 2 && item >= a.t[2].first) which = 2;
+    const AppTensor& x = a.t[which];
+    long r = item - x.first;
+    const int jj = (int)(r % 4);
+    r /= 4;
+    const int hd = (int)(r % x.H);
+    r /= x.H;
+    const int tt = (int)(r % a.T);
+    const long b = r / a.T;
+    const long p = (a.lens ? (long)a.lens[b] : 0L) + tt;
+    const bool inside = p >= 0 && p < a.cap;
+    if (x.cache && !inside) continue;             // no store outside the cache
+    bf16_t* dst = x.out + b * x.ob + (x.cache ? p : (long)tt) * x.op + (long)hd * x.oh + jj * 8;
+    if (!inside) {                                // q_out of a sequence that is full: zeros
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      store16<kAligned16>(dst, z);
+      store16<kAligned16>(dst + h, z);
+      continue;
+    }
+    const bf16_t* src = x.in + b * x.ib + (long)tt * x.it + (long)hd * x.ih + jj * 8;
+    if (!x.rotate) {
+      const u32x4 lo = load16<u32x4, kAligned16>(src), hi = load16<u32x4, kAligned16>(src + h);
+      store16<kAligned16>(dst, lo);
+      store16<kAligned16>(dst + h, hi);
+      continue;
+    }
+    const long trow = p * (long)h + jj * 8;
+    float x0[8], x1[8], c[8], sn[8], y0[8], y1[8];
+    load_chunk8(src, x0);
+    load_chunk8(src + h, x1);
+    load_chunk8(a.cos_t + trow, c);
+    load_chunk8(a.sin_t + trow, sn);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {                 // rope_kernel's expressions
+      const float sg = sn[e];
+      y0[e] = x0[e] * c[e] - x1[e] * sg;
+      y1[e] = x1[e] * c[e] + x0[e] * sg;
+    }
+    store_chunk8(dst, y0);
+    store_chunk8(dst + h, y1);
+  }
+}
+
+__global__ void lens_add_kernel(int* lens, int B, int n) {
+  for (int i = threadIdx.x; i < B; i += blockDim.x) lens[i] += n;
+}
+
+}  // namespace
+
+// tests: force `n` splits of `keys` keys (keys a multiple of the key tile, n x keys >= cap, else the
+// launcher returns hipErrorInvalidValue); n <= 0 restores the plan
+LJS_API int ljs_decode_set_splits(int n, int keys) {
+  g_dec_splits = n > 0 ? n : 0;
+  g_dec_keys = n > 0 ? keys : 0;
+  return 0;
+}
+
+LJS_API int ljs_decode_key_tile() { return kDecKeyTile; }
+LJS_API int ljs_decode_part_floats() { return kDecPart; }
+LJS_API int ljs_decode_max_group() { return kDecMaxG; }
+
+// out[0] = splits, out[1] = keys_per_split of (B, Hkv, cap) on a device of `cus` compute units: pure
+LJS_API int ljs_decode_plan(int B, int Hkv, int cap, int cus, int* out) {
+  if (B < 1 || Hkv < 1 || cap < 1 || cus < 1 || !out) return (int)hipErrorInvalidValue;
+  plan_decode(B, Hkv, cap, cus, out, out + 1);
+  return 0;
+}
+
+// the plan the next ljs_attn_decode of this shape launches (the forced one, or the pure plan for this
+// device): what the workspace is sized from
+LJS_API int ljs_decode_launch_plan(int B, int Hkv, int cap, int* out) {
+  if (B < 1 || Hkv < 1 || cap < 1 || !out) return (int)hipErrorInvalidValue;
+  return decode_launch_plan(B, Hkv, cap, out, out + 1);
+}
+
+// k, v (B, T, Hkv, 64) -> kc, vc (B, cap, Hkv, 64) at rows base[b] + t, base = lens (int32 [B], device)
+// or 0 when lens is null; q (B, T, H, 64) -> q_out (B, T, H, 64) when both are given.  cos_t / sin_t (f32
+// [table_rows][32], table_rows >= cap) rotate k and q; both null: k is copied as it is.  s*: the
+// (batch, position, head) strides in elements.  Returns hipErrorInvalidValue, and launches and records
+// nothing, for an empty shape, a misaligned base or stride, one of q / q_out alone, q without a
+// table, or a table shorter than the cache.
+LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, void* kc, void* vc, void* q_out, int B, int T,
+                          int H, int Hkv, int cap, const long* sk, const long* sv, const long* sq, const long* skc,
+                          const long* svc, const long* sqo, const void* lens, const void* cos_t, const void* sin_t,
+                          long table_rows, hipStream_t st) {
+  const bool rot = cos_t != nullptr;
+  if (B < 1 || T < 1 || Hkv < 1 || cap < 1 || (cos_t == nullptr) != (sin_t == nullptr) ||
+      (q == nullptr) != (q_out == nullptr) || (q && (!rot || H < 1)))
+    return (int)hipErrorInvalidValue;
+  if (rot && (table_rows < cap || (((uintptr_t)cos_t) & 15u) || (((uintptr_t)sin_t) & 15u)))
+    return (int)hipErrorInvalidValue;
+  if (lens && (((uintptr_t)lens) & 3u)) return (int)hipErrorInvalidValue;
+  if (!dec_aligned(k, sk) || !dec_aligned(v, sv) || !dec_aligned(kc, skc) || !dec_aligned(vc, svc) ||
+      (q && (!dec_aligned(q, sq) || !dec_aligned(q_out, sqo))))
+    return (int)hipErrorInvalidValue;
+  AppendArgs a{};
+  const long per_kv = (long)B * T * Hkv * 4;
+  a.t[0] = AppTensor{(const bf16_t*)k, (bf16_t*)kc, sk[0], sk[1], sk[2], skc[0], skc[1], skc[2], 0, Hkv, rot, 1};
+  a.t[1] = AppTensor{(const bf16_t*)v, (bf16_t*)vc, sv[0], sv[1], sv[2], svc[0], svc[1], svc[2], per_kv, Hkv, 0, 1};
+  a.nt = 2;
+  a.total = 2 * per_kv;
+  if (q) {
+    a.t[2] = AppTensor{(const bf16_t*)q, (bf16_t*)q_out, sq[0], sq[1], sq[2], sqo[0], sqo[1], sqo[2], a.total, H, 1, 0};
+    a.nt = 3;
+    a.total += (long)B * T * H * 4;
+  }
+  a.cos_t = (const float*)cos_t;
+  a.sin_t = (const float*)sin_t;
+  a.lens = (const int*)lens;
+  a.T = T;
+  a.cap = cap;
+  const long need = (a.total + kRowBlockThreads - 1) / kRowBlockThreads;
+  const long most = (long)ljs_device_cus() * kAppBlocksPerCu;
+  const dim3 grid((unsigned)(need < most ? need : most));
+  hipLaunchKernelGGL(kv_append_kernel, grid, dim3(kRowBlockThreads), 0, st, a);
+  ljs_launch_rec(q ? "kv_append<rot,q>" : (rot ? "kv_append<rot>" : "kv_append<copy>"), grid, kRowBlockThreads);
+  return (int)hipGetLastError();
+}
+
+// q (B, 1, H, 64), kc / vc (B, cap, Hkv, 64) -> o (B, 1, H, 64) bf16, lse (B, H) f32 over the keys [0,
+// min(lens[b] + extra, cap)) (the head of the file).  ws: f32 workspace of ws_floats floats, at least B H
+// splits kDecPart of them when the plan has more than one split.  s*: (batch, position, head) strides in
+// elements.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty shape, H %
+// Hkv != 0, H / Hkv > 16, scale <= 0, extra < 0, a misaligned base or stride, a key stride below 64, a
+// cache whose byte offsets do not fit 31 bits, an invalid forced plan or a workspace that is too small.
+LJS_API int ljs_attn_decode(const void* q, const void* kc, const void* vc, void* o, void* lse, void* ws, long ws_floats,
+                            const void* lens, int B, int H, int Hkv, int cap, const long* sq, const long* skc,
+                            const long* svc, const long* so, float scale, int extra, hipStream_t st) {
+  if (B < 1 || H < 1 || Hkv < 1 || cap < 1 || H % Hkv != 0 || H / Hkv > kDecMaxG || !(scale > 0.f) || extra < 0 ||
+      B > 65535 || Hkv > 65535 || (long)B * H > 0x7fffffffL || !lens || !lse || (((uintptr_t)lens) & 3u) || (((uintptr_t)lse) & 3u))
+    return (int)hipErrorInvalidValue;
+  if (!dec_aligned(q, sq) || !dec_aligned(kc, skc) || !dec_aligned(vc, svc) || !dec_aligned(o, so))
+    return (int)hipErrorInvalidValue;
+  // a load's byte offset (of up to one unrolled block step past the cache) stays a positive int
+  const long reach = (long)cap + kDecKeyTile * kDecUnroll;
+  if (skc[1] < kDecD || svc[1] < kDecD || reach * skc[1] * 2 >= 0x7fffffffL || reach * svc[1] * 2 >= 0x7fffffffL)
+    return (int)hipErrorInvalidValue;
+  DecodeArgs a{};
+  if (decode_launch_plan(B, Hkv, cap, &a.splits, &a.kps) != 0) return (int)hipErrorInvalidValue;
+  if (a.splits > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < (long)B * H * a.splits * kDecPart))
+    return (int)hipErrorInvalidValue;
+  a.q = (const bf16_t*)q;
+  a.kc = (const bf16_t*)kc;
+  a.vc = (const bf16_t*)vc;
+  a.o = (bf16_t*)o;
+  a.lse = (float*)lse;
+  a.ws = (float*)ws;
+  a.lens = (const int*)lens;
+  a.qb = sq[0]; a.qh = sq[2];
+  a.kb = skc[0]; a.ks = skc[1]; a.kh = skc[2];
+  a.vb = svc[0]; a.vs = svc[1]; a.vh = svc[2];
+  a.ob = so[0]; a.oh = so[2];
+  a.B = B; a.H = H; a.Hkv = Hkv; a.G = H / Hkv; a.cap = cap; a.extra = extra;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  const dim3 grid((unsigned)a.splits, (unsigned)Hkv, (unsigned)B);
+  const char* name;
+  if (a.G == 1) {
+    hipLaunchKernelGGL(attn_decode_kernel<1>, grid, dim3(kDecThreads), 0, st, a);
+    name = "attn_decode<G1>";
+  } else if (a.G == 2) {
+    hipLaunchKernelGGL(attn_decode_kernel<2>, grid, dim3(kDecThreads), 0, st, a);
+    name = "attn_decode<G2>";
+  } else if (a.G <= 4) {
+    hipLaunchKernelGGL(attn_decode_kernel<4>, grid, dim3(kDecThreads), 0, st, a);
+    name = "attn_decode<G4>";
+  } else if (a.G <= 8) {
+    hipLaunchKernelGGL(attn_decode_kernel<8>, grid, dim3(kDecThreads), 0, st, a);
+    name = "attn_decode<G8>";
+  } else {
+    hipLaunchKernelGGL(attn_decode_kernel<8>, grid, dim3(kDecThreads), 0, st, a);
+    name = "attn_decode<G16>";
+  }
+  ljs_launch_rec(name, grid, kDecThreads);
+  int rc = (int)hipGetLastError();
+  if (rc != 0 || a.splits == 1) return rc;
+  const dim3 mgrid((unsigned)(B * H));
+  hipLaunchKernelGGL(decode_merge_kernel, mgrid, dim3(64), 0, st, a);
+  ljs_launch_rec("decode_merge", mgrid, 64);
+  return (int)hipGetLastError();
+}
+
+// lens[0 .. B) += n: one small launch after the last layer of a decode step
+LJS_API int ljs_lens_add(void* lens, int B, int n, hipStream_t st) {
+  if (!lens || B < 1 || (((uintptr_t)lens) & 3u)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(lens_add_kernel, dim3(1), dim3(64), 0, st, (int*)lens, B, n);
+  ljs_launch_rec("lens_add", dim3(1), 64);
+  return (int)hipGetLastError();
+}

@@ -25,6 +25,12 @@ Grouped-query attention: ``kv_heads < heads`` gives ``to_k`` / ``to_v`` of ``kv_
 columns; with ``G = heads // kv_heads``, query head ``h`` attends to key/value head ``h // G`` (the G
 query heads of a group are adjacent: HF ``repeat_kv`` / MaxText order).  ``kv_heads=1`` is multi-query
 attention; ``None`` or ``heads`` is multi-head attention with the earlier parameter tree and launches.
+
+Decoding: ``cache=(k, v, lens)`` (a layer of :class:`~.cache.KVCache`) makes the call one step of a cached
+decoder and returns ``(output, cache)``.  A call on more than one position is a prefill: positions 0 ..
+T-1, the usual rope and causal kernels, and K (rotated) and V written to rows 0 .. T-1 of the cache; a
+call on one position appends its K / V at row ``lens[b]`` and attends to the cache (``ops.core.
+cached_attention``).  ``lens`` is advanced by the caller, once for all layers.
 """
 from __future__ import annotations
 
@@ -114,11 +120,53 @@ class MultiHeadAttention(Module):
         if self.verbose:
             print(*a)
 
+    def _cached(self, x: ShardedArray, cache, residual: Optional[ShardedArray]):
+        """The cached call (module docstring): no gradient, dropout the identity, no ``attention_next``
+        hint and no weight prefetch; the projections are the uncached call's."""
+        if not self.causal:
+            raise ValueError("MultiHeadAttention: a cache needs causal=True (a decoder: every position attends to "
+                             "the earlier ones only)")
+        if self.impl != "fused":
+            raise ValueError('MultiHeadAttention: impl="einsum" has no cached path; use impl="fused"')
+        kc, vc, lens = cache
+        dt = _dt.canonicalize(self.dtype)
+        with torch.no_grad():
+            m = x.shape[-1]
+            wq, wk, wv = self.query.kernel_param(m), self.key.kernel_param(m), self.value.kernel_param(m)
+            if not self.fused_qkv:
+                q, k, v = self.query(x), self.key(x), self.value(x)
+            elif self.n_kv != self.heads:
+                q, = core.dense(x, [wq], None, compute_dtype=dt)
+                k, v = core.dense(x, [wk, wv], None, compute_dtype=dt)
+            else:
+                q, k, v = core.dense(x, [wq, wk, wv], None, compute_dtype=dt)
+            b = x.shape[0]
+            q = core.reshape(with_logical_constraint(q, ("batch", "embed", None)), (b, -1, self.heads, self.dim_head))
+            k = core.reshape(with_logical_constraint(k, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
+            v = core.reshape(with_logical_constraint(v, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
+            if x.shape[1] == 1:
+                hidden = core.cached_attention(q, k, v, (kc, vc), lens, self.scale, self.rope_theta)
+            else:
+                if self.rope_theta is not None:
+                    q, k = core.rope(q, k, theta=self.rope_theta)
+                hidden = core.dot_product_attention(q, k, v, self.scale, causal=True)
+                core.cache_prefill(k, v, (kc, vc))
+            hidden = core.reshape(hidden, (b, -1, self.heads * self.dim_head))
+            hidden = with_logical_constraint(hidden, ("batch", "kv", "heads"))
+            hidden = self.proj_attn(hidden, residual=residual)
+            return with_logical_constraint(hidden, ("batch", "embed")), cache
+
     def __call__(self, hidden_states: ShardedArray, context: Optional[ShardedArray] = None,
-                 deterministic: bool = True, residual: Optional[ShardedArray] = None) -> ShardedArray:
+                 deterministic: bool = True, residual: Optional[ShardedArray] = None, cache=None):
         """``residual`` (the block's input, for a skip connection): returns
         ``residual + attention(...)`` in the compute dtype, the add fused into the output
-        projection's GEMM epilogue when dropout is the identity."""
+        projection's GEMM epilogue when dropout is the identity.  ``cache``: one layer ``(k, v, lens)`` of a
+        :class:`~.cache.KVCache`; the call then returns ``(output, cache)`` (module docstring)."""
+        if cache is not None:
+            if context is not None:
+                raise ValueError("MultiHeadAttention: a cache with a context (cross-attention) is not implemented: "
+                                 "the cache holds the keys and values of the sequence being decoded")
+            return self._cached(hidden_states, cache, residual)
         self_attn = context is None
         if self.rope_theta is not None and not self_attn:
             raise ValueError("MultiHeadAttention: rope_theta with a context (cross-attention) is not defined: "

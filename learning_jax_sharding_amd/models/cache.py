@@ -1,0 +1,175 @@
+"""The key/value cache of a decoder and greedy generation on top of it.
+
+A :class:`KVCache` holds, per layer, ``k`` and ``v`` of shape ``(batch, max_len, kv_heads, dim_head)`` in the
+model's compute dtype (zero-filled) and ONE shared ``lens``: int32 ``(batch,)``, the rows of every
+sequence that are valid.  ``lens`` lives on the devices and nowhere else: a decode step reads it
+there (the position of the new token, the key count), so the step's signature and launches are the
+same at every length and it can be captured once and replayed as a HIP graph.  It is a pytree
+(``jit`` and ``tree_util`` flatten it); the buffers are updated in place and a cached call returns the
+same buffers (donation semantics).
+
+Layout: like ``k`` after the head split with the length dim whole.  A cache sharded on its batch dim
+(data parallel) or on its ``kv_heads`` dim (tensor parallel, ``kv_heads % n == 0``) needs no collective;
+a length-sharded cache raises ``NotImplementedError``.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import dtypes as _dt
+from ..array import ShardedArray, device_put
+from ..ops import core
+from ..ops import kernels as K
+from ..runtime.devices import get_device, process_index
+from ..sharding.shardings import Sharding, default_sharding, sharding_from_tile
+from ..utils import tree as _tree
+
+__all__ = ["KVCache", "generate"]
+
+
+class KVCache:
+    """``k[i]``, ``v[i]``: layer i's buffers; ``lens``: the shared int32 ``(batch,)`` lengths."""
+
+    def __init__(self, k: Sequence[ShardedArray], v: Sequence[ShardedArray], lens: ShardedArray):
+        self.k, self.v, self.lens = list(k), list(v), lens
+
+    def layer(self, i: int):
+        """``(k, v, lens)`` of layer ``i``: what ``MultiHeadAttention(..., cache=)`` takes."""
+        return self.k[i], self.v[i], self.lens
+
+    @property
+    def max_len(self) -> int:
+        return self.k[0].shape[1]
+
+    @property
+    def batch(self) -> int:
+        return self.k[0].shape[0]
+
+    def __len__(self):
+        return len(self.k)
+
+    def __repr__(self):
+        return f"KVCache(layers={len(self.k)}, shape={self.k[0].shape if self.k else None})"
+
+    @staticmethod
+    def zeros(layers: int, batch: int, max_len: int, kv_heads: int, dim_head: int, dtype=torch.bfloat16,
+              sharding: Optional[Sharding] = None) -> "KVCache":
+        """A zero-filled cache; ``sharding``: of the 4-D buffers (default: where unplaced arrays live)."""
+        if min(layers, batch, max_len, kv_heads, dim_head) < 1:
+            raise ValueError(f"KVCache: layers={layers}, batch={batch}, max_len={max_len}, kv_heads={kv_heads}, "
+                             f"dim_head={dim_head} must all be positive")
+        sharding = sharding or default_sharding()
+        dtype = _dt.canonicalize(dtype)
+        shape = (batch, max_len, kv_heads, dim_head)
+        ta = sharding.tile_assignment(4)
+        ta.check_shape(shape)
+        if ta.tile_shape[1] > 1:
+            raise NotImplementedError("KVCache: a length-sharded cache is not implemented (ring decode); shard it "
+                                      "on its batch and / or kv_heads dims")
+        pi = process_index()
+        devs = [d for d in ta.device_ids if get_device(d).process_index == pi]
+
+        def zeros(shp, tile, dt, sh):
+            ss = tile.shard_shape(shp)
+            return ShardedArray(shp, dt, sh, {d: torch.zeros(ss, dtype=dt, device=get_device(d).torch_device)
+                                              for d in devs})
+
+        lt = ta.project([0])
+        lens = zeros((batch,), lt, torch.int32, sharding_from_tile(lt, like=[sharding]))
+        return KVCache([zeros(shape, ta, dtype, sharding) for _ in range(layers)],
+                       [zeros(shape, ta, dtype, sharding) for _ in range(layers)], lens)
+
+
+_tree.register_pytree_node(KVCache, lambda c: ((c.k, c.v, c.lens), None), lambda _, ch: KVCache(ch[0], ch[1], ch[2]))
+
+
+def _host_lens(prompt_lens, B: int, T: int) -> List[int]:
+    if prompt_lens is None:
+        return [T] * B
+    if isinstance(prompt_lens, ShardedArray):
+        prompt_lens = prompt_lens.to_torch()
+    vals = [int(x) for x in np.asarray(prompt_lens).reshape(-1)]
+    if len(vals) != B or any(n < 1 or n > T for n in vals):
+        raise ValueError(f"generate: prompt_lens must be {B} ints in [1, {T}], got {vals}")
+    return vals
+
+
+def _greedy(logits: ShardedArray, like: ShardedArray, at: Optional[ShardedArray] = None) -> ShardedArray:
+    """``argmax`` over the vocabulary of ``logits`` (batch, T, vocab) at position ``at[b]`` (an int (batch,) array
+    laid out like the batch dim; default: the last), on the devices: ``(batch, 1)`` in ``like``'s dtype."""
+    tile = logits.tile.unshard([1, 2])
+    if logits.tile != tile:
+        from ..spmd.reshard import reshard_tile
+        logits = reshard_tile(logits, tile, note="generate.logits")
+    loc = {}
+    for d, t in logits.local.items():
+        if at is None:
+            row = t[:, -1]
+        else:
+            idx = at.local[d].long().clamp(0, t.shape[1] - 1)
+            row = t[torch.arange(t.shape[0], device=t.device), idx]
+        loc[d] = row.float().argmax(-1, keepdim=True).to(like.dtype)
+    ot = tile.project([0, 1])
+    return ShardedArray((logits.shape[0], 1), like.dtype, sharding_from_tile(ot, like=[logits.sharding]), loc)
+
+
+def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=None, capture: Optional[bool] = None,
+             max_len: Optional[int] = None, cache_sharding: Optional[Sharding] = None) -> torch.Tensor:
+    """Greedy decoding: ``max_new_tokens`` tokens after each prompt of ``ids`` (batch, T), as an int64 host
+    tensor ``[batch, max_new_tokens]``.
+
+    ``prompt_lens`` (``batch`` ints in ``[1, T]``): the real length of each right-padded prompt (default: T).
+    One prefill call fills the cache and gives the first token (the ``argmax``, on the device, of the
+    logits at each sequence's last real position); ``max_new_tokens - 1`` decode steps follow.  The step
+    is ``jit(step, donate_argnums=(token, cache), capture=capture)``: on the GPU with ``capture=True`` it is
+    captured once and replayed.  The cache holds ``max_len`` rows (default: the model's ``max_len``, else
+    ``max(prompt_lens) + max_new_tokens``) and is laid out by ``cache_sharding`` (default: the batch dim
+    sharded the way ``ids``' is); a request that does not fit raises ``ValueError`` before any launch."""
+    from ..spmd.api import jit
+    from ..sharding.tile import TileAssignment
+    if ids.ndim != 2:
+        raise ValueError(f"generate: ids must be (batch, length), got shape {tuple(ids.shape)}")
+    if max_new_tokens < 1:
+        raise ValueError(f"generate: max_new_tokens must be positive, got {max_new_tokens}")
+    B, T = ids.shape
+    plens = _host_lens(prompt_lens, B, T)
+    need = max(plens) + max_new_tokens
+    cap = max_len if max_len is not None else (model.max_len if model.max_len is not None else need)
+    if need > cap or T > cap:
+        raise ValueError(f"generate: max(prompt_lens) + max_new_tokens = {max(plens)} + {max_new_tokens} > max_len "
+                         f"{cap} (or the padded prompt length {T} is)")
+    if cache_sharding is None:
+        it = ids.tile
+        ct = TileAssignment.from_coords({d: (it.coords[d][0], 0, 0, 0) for d in it.device_ids},
+                                        (it.tile_shape[0], 1, 1, 1))
+        cache_sharding = sharding_from_tile(ct, like=[ids.sharding])
+    cache = model.init_cache(B, cap, sharding=cache_sharding)
+    pl = device_put(np.asarray(plens, dtype=np.int32), cache.lens.sharding)
+
+    def prefill(p, x, c, n):
+        logits, c = model.apply({"params": p}, x, cache=c, prompt_lens=n)
+        last = ShardedArray(n.shape, n.dtype, n.sharding, {d: t - 1 for d, t in n.local.items()})
+        return _greedy(logits, x, last), c
+
+    def step(p, tok, c):
+        logits, c = model.apply({"params": p}, tok, cache=c)
+        new = _greedy(logits, tok)
+        for d, t in tok.local.items():     # in place: the next call passes the very same buffers
+            t.copy_(new.local[d])
+        return tok, c
+
+    step_j = jit(step, donate_argnums=(1, 2), capture=capture)
+    with torch.no_grad():
+        tok, cache = prefill(params, ids, cache, pl)
+        out = [tok.to_torch().clone()] if max_new_tokens == 1 else []
+        if max_new_tokens > 1:
+            # the step's token buffers are rewritten at every step: keep a copy of each, on the devices
+            kept = [{d: t.clone() for d, t in tok.local.items()}]
+            for _ in range(max_new_tokens - 1):
+                tok, cache = step_j(params, tok, cache)
+                kept.append({d: t.clone() for d, t in tok.local.items()})
+            out = [ShardedArray(tok.shape, tok.dtype, tok.sharding, loc).to_torch() for loc in kept]
+    return torch.cat([t.reshape(B, 1) for t in out], dim=1).long()

@@ -9,6 +9,10 @@ the tokens it is asked to predict).  Positions come from ``rope_theta`` (rotary 
 in every layer) or from ``max_len`` (a learned additive table), not both; with neither the model sees
 positions through the causal mask alone.
 
+Decoding: :meth:`TransformerLM.init_cache` makes a :class:`~.cache.KVCache`; a call with ``cache=`` is a prefill
+(more than one position) or one decode step (one position) and returns ``(logits, cache)``;
+:func:`~.cache.generate` is greedy decoding on top of both.
+
 The embedding table's logical axes are ``("vocab", "embed")`` and the head kernel's ``("embed",
 "vocab")``: under ``parallel.tensor.VOCAB_PARALLEL_RULES`` both ends of the model are vocab-parallel
 (the lookup all-reduces activations, the loss merges per-shard statistics; no table or logits row
@@ -88,8 +92,68 @@ class TransformerLM(Module):
         self.head = Dense(self.vocab_size, use_bias=False, dtype=self.dtype, name="head",
                           kernel_init=with_logical_partitioning(init.lecun_normal(), ("embed", "vocab")))
 
-    def __call__(self, ids: ShardedArray) -> ShardedArray:
-        """Token ids ``[batch, length]`` (int32 / int64) -> logits ``[batch, length, vocab_size]``."""
+    def init_cache(self, batch: int, max_len: int, sharding=None):
+        """A zero-filled :class:`~.cache.KVCache` for ``batch`` sequences of up to ``max_len`` positions, in the
+        model's compute dtype; ``sharding``: of its ``(batch, max_len, kv_heads, dim_head)`` buffers.  On GPU
+        devices the rope table grows to ``max_len`` rows here (never inside a graph capture)."""
+        from .cache import KVCache
+        if self.max_len is not None and max_len > self.max_len:
+            raise ValueError(f"TransformerLM.init_cache: max_len {max_len} > the position table's {self.max_len} rows")
+        kvh = self.heads if self.kv_heads is None else self.kv_heads
+        cache = KVCache.zeros(self.layers, batch, max_len, kvh, self.dim_head, self.dtype, sharding)
+        if self.rope_theta is not None:
+            from ..ops import kernels as K
+            for t in cache.lens.local.values():
+                if t.is_cuda:
+                    K.rope_table(t.device, self.dim_head, float(self.rope_theta), max_len)
+        return cache
+
+    def _cached(self, ids: ShardedArray, cache, prompt_lens):
+        """Prefill (more than one position: restarts the cache) or one decode step (module docstring)."""
+        for name, bad in (("causal=False", not self.causal), ("fp8=True", self.fp8)):
+            if bad:
+                raise ValueError(f"TransformerLM: {name} has no cached path (a cache needs a causal decoder "
+                                 "without the fp8 feed-forward)")
+        if len(cache) != self.layers:
+            raise ValueError(f"TransformerLM: the cache has {len(cache)} layers, the model {self.layers}")
+        T = ids.shape[-1]
+        if T > cache.max_len:
+            raise ValueError(f"TransformerLM: {T} positions do not fit the cache's max_len {cache.max_len}")
+        if T == 1 and prompt_lens is not None:
+            raise ValueError("TransformerLM: prompt_lens goes with a prefill (more than one position)")
+        if prompt_lens is not None and not isinstance(prompt_lens, ShardedArray):
+            import numpy as np
+            from ..array import device_put
+            prompt_lens = device_put(np.asarray(prompt_lens, dtype=np.int32).reshape(-1), cache.lens.sharding)
+        with torch.no_grad():
+            x = self.embed(ids)
+            if self.max_len is not None:
+                if T > self.max_len:
+                    raise ValueError(f"TransformerLM: sequence length {T} > max_len {self.max_len}")
+                pos = _position_ids(ids) if T > 1 else core.reshape(cache.lens, (ids.shape[0], 1))
+                x = core.binary("add", x, self.pos_embed(pos))
+            x = with_logical_constraint(x, ("batch", "length", "embed"))
+            for i, blk in enumerate(self.blocks):
+                x, _ = blk(x, cache=cache.layer(i))
+            if T == 1:
+                core.cache_advance(cache.lens, 1)       # after the last layer: one small launch
+            else:
+                core.cache_set_lens(cache.lens, T if prompt_lens is None else prompt_lens)
+            x = self.final_norm(x)
+            return with_logical_constraint(self.head(x), ("batch", "length", "vocab")), cache
+
+    def __call__(self, ids: ShardedArray, cache=None, prompt_lens=None):
+        """Token ids ``[batch, length]`` (int32 / int64) -> logits ``[batch, length, vocab_size]``.
+
+        ``cache`` (a :class:`~.cache.KVCache` from :meth:`init_cache`): returns ``(logits, cache)``, the buffers
+        updated in place, without gradient.  ``length > 1`` is a prefill that restarts the cache: positions 0
+        .. length-1, K / V of every layer to rows 0 .. length-1, ``cache.lens := prompt_lens`` (an int
+        ``(batch,)`` array laid out like ``cache.lens``: right-padded ragged prompts) or ``length``.  ``length == 1``
+        is a decode step: the token of sequence b sits at position ``cache.lens[b]``, and ``lens += 1``."""
+        if cache is not None:
+            return self._cached(ids, cache, prompt_lens)
+        if prompt_lens is not None:
+            raise ValueError("TransformerLM: prompt_lens goes with a cache")
         x = self.embed(ids)
         if self.max_len is not None:
             if ids.shape[-1] > self.max_len:

@@ -37,7 +37,8 @@ __all__ = [
     "binary", "unary", "convert", "reshape", "transpose", "reduce_sum", "reduce_mean", "reduce_max",
     "getitem", "dot_general", "dot", "matmul", "einsum", "softmax", "dot_product_attention", "dense",
     "with_sharding_constraint", "asarray_like", "broadcast_to", "where", "concatenate", "mse_loss",
-    "layer_norm", "softmax_cross_entropy", "embed", "rope", "swiglu",
+    "layer_norm", "softmax_cross_entropy", "embed", "rope", "swiglu", "cached_attention", "cache_prefill",
+    "cache_set_lens", "cache_advance",
 ]
 
 
@@ -1056,3 +1057,89 @@ def dense(x: ShardedArray, kernels: Sequence[ShardedArray], bias: Optional[Shard
                 y = binary("add", y, convert(residual, compute_dtype))
         outs.append(y)
     return outs
+
+
+# ----------------------------------------------------------------------------- KV cache / decode
+# A cache layer is a pair of (batch, max_len, kv_heads, head_dim) arrays laid out like k after the head
+# split with the length dim whole, plus one int32 (batch,) array of lengths that lives on the devices
+# (replicated over head shards): batch sharding and head sharding need no collective.  The buffers
+# are updated IN PLACE (donation semantics); nothing here takes a gradient.
+def _cache_layout(k: ShardedArray, v: ShardedArray, cache_layer, lens: Optional[ShardedArray],
+                  q: Optional[ShardedArray] = None):
+    """(q, k, v) on the cache's tile, after the checks every cached call shares."""
+    kc, vc = cache_layer
+    ct = kc.tile
+    if ct.tile_shape[1] > 1:
+        raise NotImplementedError("KV cache: a length-sharded cache is not implemented (ring decode); shard the "
+                                  "cache on its batch and / or kv_heads dims")
+    if ct.tile_shape[3] > 1:
+        raise ValueError("KV cache: head_dim must be whole on every device")
+    if vc.tile != ct or tuple(vc.shape) != tuple(kc.shape) or vc.dtype != kc.dtype:
+        raise ValueError("KV cache: the k and v buffers of a layer must share shape, dtype and layout")
+    if tuple(k.shape) != tuple(v.shape) or k.shape[0] != kc.shape[0] or tuple(k.shape[2:]) != tuple(kc.shape[2:]):
+        raise ValueError(f"KV cache: new k / v {tuple(k.shape)} / {tuple(v.shape)} do not fit a cache of shape "
+                         f"{tuple(kc.shape)} (batch, max_len, kv_heads, head_dim)")
+    if lens is not None:
+        if lens.dtype != torch.int32 or tuple(lens.shape) != (kc.shape[0],) or lens.tile != ct.project([0]):
+            raise ValueError("KV cache: lens must be an int32 (batch,) array laid out like the cache's batch dim")
+    if q is not None:
+        _attention_kv_heads(q, k, v, ct.tile_shape[2])
+        if q.tile != ct:
+            q = reshard_tile(q, ct, note="cache.q")
+    if k.tile != ct:
+        k = reshard_tile(k, ct, note="cache.k")
+    if v.tile != ct:
+        v = reshard_tile(v, ct, note="cache.v")
+    return q, k, v
+
+
+def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_layer, lens: ShardedArray,
+                     scale: Optional[float] = None, rope_theta: Optional[float] = None) -> ShardedArray:
+    """One decode step of one layer: the single new position's ``k`` / ``v`` (batch, 1, kv_heads, head_dim)
+    are appended to ``cache_layer = (kc, vc)`` at row ``lens[b]`` (k, and q with it, rotated at that
+    position when ``rope_theta`` is given), and ``q`` (batch, 1, heads, head_dim) attends to rows ``[0,
+    lens[b] + 1)``: two launches per device shard (:func:`.kernels.kv_append`, :func:`.kernels.attn_decode`).
+    ``lens`` itself is not changed (the caller advances it once after the last layer)."""
+    if q.shape[1] != 1 or k.shape[1] != 1:
+        raise ValueError(f"cached_attention: one new position per call, got {q.shape[1]} (a longer call is a "
+                         "prefill: attention over the new tokens and cache_prefill)")
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    q, k, v = _cache_layout(k, v, cache_layer, lens, q)
+    kc, vc = cache_layer
+    _plan.record("cached_attention", tiles=kc.tile.tile_shape, kv_heads=k.shape[2])
+    loc = {}
+    for d, qt in q.local.items():
+        ln = lens.local[d]
+        qr = K.kv_append(k.local[d], v.local[d], kc.local[d], vc.local[d], ln,
+                         q=qt if rope_theta is not None else None, theta=rope_theta)
+        loc[d] = K.attn_decode(qt if qr is None else qr, kc.local[d], vc.local[d], ln, float(scale), extra=1)[0]
+    return ShardedArray(q.shape, vc.dtype, q.sharding, loc)
+
+
+def cache_prefill(k: ShardedArray, v: ShardedArray, cache_layer) -> None:
+    """Rows ``0 .. T-1`` of ``cache_layer`` := ``k`` / ``v`` (batch, T, kv_heads, head_dim) as they are (k already
+    rotated): one :func:`.kernels.kv_append` launch per device shard in its host-base mode."""
+    kc, _ = cache_layer
+    if k.shape[1] > kc.shape[1]:
+        raise ValueError(f"KV cache: a prompt of {k.shape[1]} positions does not fit max_len {kc.shape[1]}")
+    _, k, v = _cache_layout(k, v, cache_layer, None)
+    kc, vc = cache_layer
+    _plan.record("cache_prefill", tiles=kc.tile.tile_shape)
+    for d, kt in k.local.items():
+        K.kv_append(kt, v.local[d], kc.local[d], vc.local[d])
+
+
+def cache_set_lens(lens: ShardedArray, value) -> None:
+    """``lens := value`` in place: an int, or an int (batch,) array laid out like ``lens`` (any int dtype)."""
+    for d, t in lens.local.items():
+        if isinstance(value, ShardedArray):
+            t.copy_(value.local[d])
+        else:
+            t.fill_(int(value))
+
+
+def cache_advance(lens: ShardedArray, n: int = 1) -> None:
+    """``lens += n`` in place, one small launch per device (:func:`.kernels.lens_add`)."""
+    for t in lens.local.values():
+        K.lens_add(t, n)

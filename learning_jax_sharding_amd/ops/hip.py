@@ -19,7 +19,7 @@ import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
-           "embed_grad", "rope", "swiglu"]
+           "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "plan_decode", "lens_add"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -69,6 +69,17 @@ _SIGS = {
     "ljs_gqa_reduce": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP,
                        c_void_p],
     "ljs_gqa_set_max_blocks": [c_int],
+    "ljs_kv_append": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                      _LP, _LP, _LP, _LP, _LP, _LP, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
+    "ljs_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int,
+                        c_int, c_int, _LP, _LP, _LP, _LP, c_float, c_int, c_void_p],
+    "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "ljs_decode_launch_plan": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "ljs_decode_set_splits": [c_int, c_int],
+    "ljs_decode_key_tile": [],
+    "ljs_decode_part_floats": [],
+    "ljs_decode_max_group": [],
+    "ljs_lens_add": [c_void_p, c_int, c_int, c_void_p],
     "ljs_attn_bwd_proj_enabled": [c_int, c_int],
     "ljs_attn_bwd_proj_last_path": [],
     "ljs_cast_f32_bf16": [c_void_p, c_void_p, c_long, c_void_p],
@@ -192,7 +203,8 @@ def last_launch() -> dict:
     ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``, ``rope<bf16,bf16>`` / ``rope<bf16,bf16,inv>``,
     ``gemm_mx_fp8<128,2,fix=1>``, ``gemm_mx8<256,160,4,bf16,2>``, ``quant_mx_rows``, ``quant_mx_cols<tiled>`` /
     ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
-    ``grad_sumsq``, ``step_hyper``, ``adam_multi_dyn<32>``),
+    ``grad_sumsq``, ``step_hyper``, ``adam_multi_dyn<32>``, ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
+    ``attn_decode<G4>``, ``decode_merge``, ``lens_add``),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
     it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
@@ -2515,6 +2527,142 @@ def attention(q, k, v, scale: float, causal: bool = False, q_offset: int = 0) ->
         kb, vb = expand_kv(kb, q.shape[2] // Hkv), expand_kv(vb, q.shape[2] // Hkv)
     out = _Attention.apply(qb, kb, vb, float(scale), bool(causal), int(q_offset))
     return out if v.dtype == torch.bfloat16 else out.to(v.dtype)
+
+
+# ============================================================================ KV cache / decode
+# csrc/kernels/decode.hip: the cache append (with the rotary embedding at a position read on the
+# device) and single-query split-K attention over the cache.  Nothing here takes a gradient.
+def set_decode_splits(n: Optional[int], keys: int = 0) -> None:
+    """Tests: force ``attn_decode``'s plan to ``n`` splits of ``keys`` keys (a multiple of
+    :func:`decode_key_tile`, ``n * keys >= cap``); None or 0 restores :func:`plan_decode`."""
+    lib().ljs_decode_set_splits(int(n or 0), int(keys))
+
+
+def decode_key_tile() -> int:
+    """Keys one block of the decode kernel holds per step: ``keys_per_split`` is a multiple of it."""
+    return lib().ljs_decode_key_tile()
+
+
+def decode_max_group() -> int:
+    """The largest ``heads // kv_heads`` the decode kernel takes."""
+    return lib().ljs_decode_max_group()
+
+
+def plan_decode(B: int, Hkv: int, cap: int, cus: Optional[int] = None):
+    """``(splits, keys_per_split)`` of ``attn_decode`` for ``B`` sequences, ``Hkv`` key/value heads and a
+    cache of ``cap`` rows on a device of ``cus`` compute units (default: the current device's).  Pure:
+    it depends on nothing else, the lengths least of all, so a captured launch stays valid."""
+    out = (c_int * 2)()
+    rc = lib().ljs_decode_plan(int(B), int(Hkv), int(cap), int(cus if cus is not None else _cus()), out)
+    if rc != 0:
+        raise ValueError(f"plan_decode: B={B}, Hkv={Hkv}, cap={cap}, cus={cus} must all be positive")
+    return int(out[0]), int(out[1])
+
+
+def _decode_launch_plan(B: int, Hkv: int, cap: int):
+    out = (c_int * 2)()
+    _ck(lib().ljs_decode_launch_plan(int(B), int(Hkv), int(cap), out), "ljs_decode_launch_plan")
+    return int(out[0]), int(out[1])
+
+
+def decode_supported(*ts: torch.Tensor) -> bool:
+    """Whether decode.hip takes these operands as they are: bf16 ``(B, S, H, 64)`` GPU tensors, the head
+    dim contiguous, the base and the three outer strides 16-byte aligned."""
+    return all(t.is_cuda and t.dim() == 4 and t.dtype == torch.bfloat16 and t.shape[-1] == 64 and t.numel()
+               and t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(t.stride(i) % 8 == 0 for i in range(3))
+               for t in ts)
+
+
+def _lens_ok(lens: Optional[torch.Tensor], B: int) -> bool:
+    return lens is None or (lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous())
+
+
+def kv_append_raw(k, v, kc, vc, lens=None, q=None, q_out=None, cos=None, sin=None) -> int:
+    """One ``ljs_kv_append`` launch on the tensors as they are; returns the launcher's code (non-zero:
+    rejected, nothing launched) instead of raising."""
+    B, T, Hkv, _ = k.shape
+    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
+    return lib().ljs_kv_append(_p(k), _p(v), _p(q), _p(kc), _p(vc), _p(q_out), B, T, q.shape[2] if q is not None else 0,
+                               Hkv, kc.shape[1], st(k), st(v), st(q), st(kc), st(vc), st(q_out), _p(lens), _p(cos),
+                               _p(sin), cos.shape[0] if cos is not None else 0, _stream(k))
+
+
+def kv_append(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
+    """``vc[b, p] = v[b, t]`` and ``kc[b, p] = k[b, t]`` for ``p = base[b] + t``, ``base = lens`` (int32 ``[B]`` on
+    the device) or 0 without it; with ``theta`` k is rotated by the rotary embedding at position ``p`` on
+    its way (rope.hip's bits), and a ``q`` is rotated the same way into the returned tensor.  Rows with
+    ``p >= cap`` are not written.  One launch."""
+    B = k.shape[0]
+    ok = decode_supported(k, v, kc, vc) and (q is None or decode_supported(q)) and _lens_ok(lens, B) \
+        and k.shape == v.shape and kc.shape == vc.shape and kc.shape[0] == B and kc.shape[2] == k.shape[2] \
+        and (q is None or (theta is not None and q.shape[:2] == k.shape[:2]))
+    if not ok:
+        raise NotImplementedError(f"kv_append kernel: bf16 (B, T, H, 64) operands with 16-byte aligned bases and "
+                                  f"strides and an int32 [B] lens; got k {k.dtype} {tuple(k.shape)} strides "
+                                  f"{k.stride()}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}")
+    cos = sin = q_out = None
+    if theta is not None:
+        from .kernels import rope_table
+        cos, sin = rope_table(k.device, 64, theta, kc.shape[1])
+    if q is not None:
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    _ck(kv_append_raw(k, v, kc, vc, lens, q, q_out, cos, sin), "ljs_kv_append")
+    return q_out
+
+
+def _decode_ws(dev: torch.device, floats: int) -> torch.Tensor:
+    """The per-device f32 workspace of the split partials.  It grows outside a capture only: a graph
+    holds its address."""
+    key = (dev.index, "decode")
+    t = _WS.get(key)
+    if t is None or t.numel() < floats:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"attn_decode: the split workspace on {dev} has {0 if t is None else t.numel()} floats "
+                               f"and {floats} are needed, and it cannot be created during a graph capture: run the "
+                               "function once outside the capture first")
+        if t is not None:
+            _WS[(dev.index, "decode", t.data_ptr())] = t     # a captured graph may still write into it
+        t = torch.empty(max(floats, 1 << 16), dtype=torch.float32, device=dev)
+        _WS[key] = t
+    return t
+
+
+def attn_decode_raw(q, kc, vc, o, lse, ws, lens, scale: float, extra: int = 1) -> int:
+    """One ``ljs_attn_decode`` call (the decode launch, and the merge launch when the plan has more than
+    one split) on the tensors as they are; returns the launcher's code instead of raising."""
+    B, _, H, _ = q.shape
+    return lib().ljs_attn_decode(_p(q), _p(kc), _p(vc), _p(o), _p(lse), _p(ws), ws.numel() if ws is not None else 0,
+                                 _p(lens), B, H, kc.shape[2], kc.shape[1], _longs(_strides3(q)),
+                                 _longs(_strides3(kc)), _longs(_strides3(vc)), _longs(_strides3(o)), float(scale),
+                                 int(extra), _stream(q))
+
+
+def attn_decode(q, kc, vc, lens, scale: float, extra: int = 1):
+    """Single-query attention of ``q`` (B, 1, H, 64) over rows ``[0, min(lens[b] + extra, cap))`` of the caches
+    ``kc`` / ``vc`` (B, cap, Hkv, 64): ``(o`` bf16 (B, 1, H, 64), ``lse2`` f32 (B, H, 1)``)``; a sequence without
+    keys gets ``o = 0``, ``lse2 = +inf``."""
+    B, T, H, _ = q.shape
+    Hkv = kc.shape[2]
+    ok = decode_supported(q, kc, vc) and T == 1 and kc.shape == vc.shape and kc.shape[0] == B and lens is not None \
+        and _lens_ok(lens, B) and H % Hkv == 0 and H // Hkv <= decode_max_group() and scale > 0
+    if not ok:
+        raise NotImplementedError(f"attn_decode kernel: bf16 q (B, 1, H, 64) and caches (B, cap, Hkv, 64) with 16-byte "
+                                  f"aligned bases and strides, H / Hkv <= {decode_max_group()}, int32 [B] lens; got q "
+                                  f"{q.dtype} {tuple(q.shape)}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}")
+    splits, _ = _decode_launch_plan(B, Hkv, kc.shape[1])
+    ws = _decode_ws(q.device, B * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
+    o = torch.empty((B, 1, H, 64), dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device)
+    _ck(attn_decode_raw(q, kc, vc, o, lse, ws, lens, scale, extra), "ljs_attn_decode")
+    return o, lse
+
+
+def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:
+    """``lens += n`` in place (int32 on the device): one small launch, after the last layer of a step."""
+    if not (lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel()):
+        raise NotImplementedError(f"lens_add: a contiguous int32 GPU tensor, got {lens.dtype} on {lens.device}")
+    _ck(lib().ljs_lens_add(_p(lens), lens.numel(), int(n), _stream(lens)), "ljs_lens_add")
+    return lens
 
 
 # ============================================================================ optimizer

@@ -645,3 +645,123 @@ def attention_bwd_block(q, k, v, o, do, lse, scale: float, causal: bool = False,
     dk = _group_sum(torch.einsum("bhqk,bqhd->bkhd", ds, q.float()) * scale, G)
     dv = _group_sum(torch.einsum("bhqk,bqhd->bkhd", p.to(v.dtype).float(), dof), G)
     return dq.to(q.dtype), dk.to(kd), dv.to(vd)
+
+
+# ----------------------------------------------------------------------------- KV cache / decode
+# The cache append and single-query attention over a cache (csrc/kernels/decode.hip).  ``lens`` is an
+# int32 [B] tensor ON THE DEVICE: nothing below reads it on the host, so a captured step stays valid
+# while the sequences grow.  Neither function takes a gradient (decoding runs under no_grad).
+def fused_decode_enabled() -> bool:
+    # LJS_FUSED_DECODE=0: the cache append and the decode attention on GPU shards as the torch
+    # formulations below instead of the HIP kernels of csrc/kernels/decode.hip (A/B timing; escape hatch)
+    return os.environ.get("LJS_FUSED_DECODE", "1") != "0"
+
+
+def kv_append_reference(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
+    """Plain torch cache append, in place: ``vc[b, p] = v[b, t]``, ``kc[b, p] = k'[b, t]`` for ``p = base[b] + t``
+    with ``base = lens`` (int [B]) or 0 without it, rows with ``p >= cap`` dropped.  With ``theta``, ``k'`` is k
+    rotated at position ``p`` exactly as :func:`rope_reference` does (same table, same f32 arithmetic),
+    and a ``q`` is rotated the same way into the returned tensor (zeros where ``p >= cap``); without,
+    ``k' = k``.  No host read of ``lens``."""
+    B, T, _, D = k.shape
+    cap = kc.shape[1]
+    t_idx = torch.arange(T, device=k.device)
+    base = lens.long() if lens is not None else torch.zeros(B, dtype=torch.long, device=k.device)
+    p = base[:, None] + t_idx[None, :]                        # (B, T)
+    inside = (p >= 0) & (p < cap)
+    rows = p.clamp(0, cap - 1)
+    q_out = None
+    if theta is not None:
+        cos, sin = rope_table(k.device, D, theta, cap)
+        cos, sin = cos[rows].unsqueeze(2), sin[rows].unsqueeze(2)   # (B, T, 1, D / 2)
+        k = _rope_one(k, cos, sin, k.dtype)
+        if q is not None:
+            q_out = _rope_one(q, cos, sin, q.dtype)
+            q_out = torch.where(inside[:, :, None, None], q_out, torch.zeros_like(q_out))
+    elif q is not None:
+        raise ValueError("kv_append: a q is rotated only with a theta")
+    ar = torch.arange(B, device=k.device)
+    keep = inside[:, :, None, None]
+    for t in range(T):                                        # one row per sequence at a time: no duplicates
+        r = rows[:, t]
+        kc[ar, r] = torch.where(keep[:, t], k[:, t].to(kc.dtype), kc[ar, r])
+        vc[ar, r] = torch.where(keep[:, t], v[:, t].to(vc.dtype), vc[ar, r])
+    return q_out
+
+
+def attn_decode_reference(q, kc, vc, lens, scale: float, extra: int = 1):
+    """Plain torch single-query attention over a cache: q (B, 1, H, D) against rows ``[0, n_b)`` of kc / vc
+    (B, cap, Hkv, D), ``n_b = min(lens[b] + extra, cap)``; query head h reads key/value head h // G.  Returns
+    ``(o`` (B, 1, H, D) in vc's dtype, ``lse2`` f32 (B, H, 1)``)`` in the kernels' convention (log2 of the
+    partition function of the scaled scores); ``n_b = 0`` gives ``o = 0``, ``lse2 = +inf``.  Rows at and beyond
+    ``n_b`` are selected away before any arithmetic, so whatever they hold (NaN, Inf) has no influence.
+    The recipe of :func:`attention_fwd_lse`: f32 scores, probabilities rounded to v's dtype before P.V."""
+    G = kv_groups(q, kc, vc)
+    cap = kc.shape[1]
+    n = (lens.long() + int(extra)).clamp(0, cap)              # (B,)
+    live = torch.arange(cap, device=q.device)[None, :] < n[:, None]      # (B, cap)
+    sel = live[:, :, None, None]
+    k = expand_kv(torch.where(sel, kc, torch.zeros_like(kc)), G)
+    v = expand_kv(torch.where(sel, vc, torch.zeros_like(vc)), G)
+    s = torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) * scale
+    s = s.masked_fill(~live[:, None, None, :], float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    empty = torch.isinf(m) & (m < 0)
+    m = torch.where(empty, torch.zeros_like(m), m)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    probs = (p / l.clamp(min=1e-30)).to(v.dtype).float()
+    o = torch.einsum("bhqk,bkhd->bqhd", probs, v.float()).to(v.dtype)
+    lse = (m + torch.log(l)) * _LOG2E
+    lse = torch.where(empty, torch.full_like(lse, float("inf")), lse)
+    return o, lse.squeeze(-1)
+
+
+_WARNED_DECODE = set()
+
+
+def _hip_decode(what: str, ts, lens, G: int = 1) -> bool:
+    """Whether decode.hip takes these shards: bf16 ``(B, S, H, 64)`` GPU tensors with 16-byte aligned bases
+    and strides, an int32 lens and at most 16 query heads per key/value head.  Anything else on a GPU
+    runs the torch formulation there, with a one-time warning per reason; host devices and
+    ``LJS_FUSED_DECODE=0`` run it silently."""
+    if not use_hip(ts[0]) or not fused_decode_enabled():
+        return False
+    hip = _hip()
+    ok = hip.decode_supported(*ts) and (lens is None or lens.dtype == torch.int32) and G <= hip.decode_max_group()
+    if not ok:
+        key = (what, ts[0].dtype, ts[0].shape[-1], G > hip.decode_max_group())
+        if key not in _WARNED_DECODE:
+            _WARNED_DECODE.add(key)
+            import warnings
+            warnings.warn(f"HIP {what} kernel takes bf16 (B, S, H, 64) shards with 16-byte aligned bases and strides, "
+                          f"an int32 lens and heads / kv_heads <= {hip.decode_max_group()}; {ts[0].dtype} "
+                          f"{tuple(ts[0].shape)} strides {ts[0].stride()} with heads / kv_heads = {G} runs the torch "
+                          "formulation on the GPU")
+    return ok
+
+
+def kv_append(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
+    """Append one device's new ``k`` / ``v`` (B, T, Hkv, D) to its caches ``kc`` / ``vc`` (B, cap, Hkv, D) in place
+    (:func:`kv_append_reference`'s semantics); returns the rotated ``q`` (or None).  One HIP launch on a GPU."""
+    ts = [k, v, kc, vc] + ([q] if q is not None else [])
+    if _hip_decode("kv_append", ts, lens):
+        return _hip().kv_append(k, v, kc, vc, lens, q, theta)
+    return kv_append_reference(k, v, kc, vc, lens, q, theta)
+
+
+def attn_decode(q, kc, vc, lens, scale: float, extra: int = 1):
+    """Single-query attention of one device's ``q`` (B, 1, H, D) over its caches: ``(o, lse2)``
+    (:func:`attn_decode_reference`'s semantics).  One HIP launch, and a small merge launch when the
+    key axis is split, on a GPU."""
+    G = kv_groups(q, kc, vc)
+    if _hip_decode("attn_decode", [q, kc, vc], lens, G):
+        return _hip().attn_decode(q, kc, vc, lens, scale, extra)
+    return attn_decode_reference(q, kc, vc, lens, scale, extra)
+
+
+def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:
+    """``lens += n`` in place: one small HIP launch on a GPU, torch's ``add_`` elsewhere."""
+    if use_hip(lens) and fused_decode_enabled() and lens.dtype == torch.int32 and lens.is_contiguous():
+        return _hip().lens_add(lens, n)
+    return lens.add_(n)
