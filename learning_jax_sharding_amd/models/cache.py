@@ -1,4 +1,4 @@
-"""The key/value cache of a decoder and greedy generation on top of it.
+"""The key/value cache of a decoder and generation (greedy or sampled, with stop tokens) on top of it.
 
 A :class:`KVCache` holds, per layer, ``k`` and ``v`` of shape ``(batch, max_len, kv_heads, dim_head)`` in the
 model's compute dtype (zero-filled) and ONE shared ``lens``: int32 ``(batch,)``, the rows of every
@@ -116,10 +116,88 @@ def _greedy(logits: ShardedArray, like: ShardedArray, at: Optional[ShardedArray]
     return ShardedArray((logits.shape[0], 1), like.dtype, sharding_from_tile(ot, like=[logits.sharding]), loc)
 
 
+def _sampling_request(V: int, key, temperature, top_k, top_p, eos_id, pad_id, stop_poll):
+    """The checks of ``generate``'s sampling arguments, on the host before any launch: the eos ids as a tuple."""
+    eos = () if eos_id is None else ((int(eos_id),) if isinstance(eos_id, (int, np.integer)) else
+                                     tuple(int(e) for e in eos_id))
+    if eos_id is not None and not eos:
+        raise ValueError("generate: eos_id must be an int or 1 to 8 ints, got none")
+    if eos and pad_id is None:
+        raise ValueError("generate: eos_id needs a pad_id (what a finished sequence writes)")
+    if int(stop_poll) < 0:
+        raise ValueError(f"generate: stop_poll must be >= 0, got {stop_poll}")
+    K.sample_params(V, key, temperature, top_k, top_p, eos, 0 if pad_id is None else pad_id, pad_id is not None,
+                    "generate")
+    return eos
+
+
+def _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p, eos,
+                      pad_id, stop_poll) -> torch.Tensor:
+    """``generate`` with a key and / or stop tokens: the prefill and the step end in ``sample_logits``.  ``done`` (int32
+    (batch,), next to ``cache.lens``) is made before the capture and donated with the token."""
+    from ..spmd.api import jit
+    B = ids.shape[0]
+    pad = 0 if pad_id is None else int(pad_id)
+    opts = dict(temperature=temperature, top_k=top_k, top_p=top_p, eos=eos, pad=pad)
+    lens = cache.lens
+    done = ShardedArray(lens.shape, lens.dtype, lens.sharding,
+                        {d: torch.zeros_like(t) for d, t in lens.local.items()}) if eos else None
+
+    def prefill(p, x, c, n):
+        logits, c = model.apply({"params": p}, x, cache=c, prompt_lens=n)
+        last = ShardedArray(n.shape, n.dtype, n.sharding, {d: t - 1 for d, t in n.local.items()})
+        # pos = lens after the prefill set it: the position the new token will occupy
+        return core.sample_logits(logits, None, key, at=last, pos=c.lens, done=done, dtype=x.dtype, **opts), c
+
+    def step(p, st, c):
+        logits, c = model.apply({"params": p}, st[0], cache=c)
+        core.sample_logits(logits, st[0], key, pos=c.lens, done=st[1] if eos else None, **opts)   # in place
+        return st, c
+
+    step_j = jit(step, donate_argnums=(1, 2), capture=capture)
+    with torch.no_grad():
+        tok, cache = prefill(params, ids, cache, pl)
+        st = (tok, done) if eos else (tok,)
+        kept = [{d: t.clone() for d, t in tok.local.items()}]
+        for s in range(1, max_new_tokens):
+            # outside the graph: one host read of done every stop_poll steps
+            if eos and stop_poll and s % int(stop_poll) == 0 and all(bool(t.all()) for t in done.local.values()):
+                break
+            st, cache = step_j(params, st, cache)
+            kept.append({d: t.clone() for d, t in st[0].local.items()})
+        out = [ShardedArray(tok.shape, tok.dtype, tok.sharding, loc).to_torch().reshape(B, 1) for loc in kept]
+    out = torch.cat(out, dim=1).long()
+    if out.shape[1] < max_new_tokens:      # every sequence had stopped
+        out = torch.cat([out, torch.full((B, max_new_tokens - out.shape[1]), pad, dtype=torch.long)], dim=1)
+    return out
+
+
+def _stop_lens(out: torch.Tensor, eos) -> torch.Tensor:
+    """Per sequence, the count of tokens up to and including its first eos (all of them without one)."""
+    hit = torch.zeros_like(out, dtype=torch.bool)
+    for e in eos:
+        hit |= out == e
+    n = out.shape[1]
+    first = torch.where(hit, torch.arange(n).expand_as(out), n - 1).amin(-1)
+    return first + 1
+
+
 def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=None, capture: Optional[bool] = None,
-             max_len: Optional[int] = None, cache_sharding: Optional[Sharding] = None) -> torch.Tensor:
-    """Greedy decoding: ``max_new_tokens`` tokens after each prompt of ``ids`` (batch, T), as an int64 host
-    tensor ``[batch, max_new_tokens]``.
+             max_len: Optional[int] = None, cache_sharding: Optional[Sharding] = None, *, key=None,
+             temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id=None,
+             pad_id: Optional[int] = None, stop_poll: int = 16, return_lens: bool = False):
+    """Decoding: ``max_new_tokens`` tokens after each prompt of ``ids`` (batch, T), as an int64 host tensor
+    ``[batch, max_new_tokens]``; greedy without a ``key``.
+
+    ``key`` (a ``random.Key``): every token is drawn from the softmax of ``logits / temperature`` restricted by ``top_k``
+    and ``top_p`` (:func:`~..ops.kernels.sample_reference` states the rule), the stream id of a draw being (the
+    sequence's global batch index, the position the token will occupy): the tokens do not depend on the mesh, on
+    ``capture`` or on the batch a sequence is decoded in.  ``eos_id`` (an int or up to 8): a sequence that has
+    produced one writes ``pad_id`` from then on; every ``stop_poll`` steps (0: never) the host reads whether all
+    sequences have stopped and, if so, ends early, the remaining columns being ``pad_id``.  ``return_lens=True``
+    returns ``(tokens, lens)``, ``lens[b]`` the count of tokens up to and including sequence b's eos.  With a key
+    or an ``eos_id`` the prefill and the step end in :func:`~..ops.core.sample_logits` on the devices; with neither, in
+    the argmax on the devices, as before.  Bad arguments raise ``ValueError`` before any launch.
 
     ``prompt_lens`` (``batch`` ints in ``[1, T]``): the real length of each right-padded prompt (default: T).
     One prefill call fills the cache and gives the first token (the ``argmax``, on the device, of the
@@ -146,8 +224,13 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
         ct = TileAssignment.from_coords({d: (it.coords[d][0], 0, 0, 0) for d in it.device_ids},
                                         (it.tile_shape[0], 1, 1, 1))
         cache_sharding = sharding_from_tile(ct, like=[ids.sharding])
+    eos = _sampling_request(model.vocab_size, key, temperature, top_k, top_p, eos_id, pad_id, stop_poll)
     cache = model.init_cache(B, cap, sharding=cache_sharding)
     pl = device_put(np.asarray(plens, dtype=np.int32), cache.lens.sharding)
+    if key is not None or eos:
+        out = _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p,
+                                eos, pad_id, stop_poll)
+        return (out, _stop_lens(out, eos)) if return_lens else out
 
     def prefill(p, x, c, n):
         logits, c = model.apply({"params": p}, x, cache=c, prompt_lens=n)
@@ -172,4 +255,5 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
                 tok, cache = step_j(params, tok, cache)
                 kept.append({d: t.clone() for d, t in tok.local.items()})
             out = [ShardedArray(tok.shape, tok.dtype, tok.sharding, loc).to_torch() for loc in kept]
-    return torch.cat([t.reshape(B, 1) for t in out], dim=1).long()
+    out = torch.cat([t.reshape(B, 1) for t in out], dim=1).long()
+    return (out, torch.full((B,), max_new_tokens, dtype=torch.long)) if return_lens else out

@@ -38,7 +38,7 @@ __all__ = [
     "getitem", "dot_general", "dot", "matmul", "einsum", "softmax", "dot_product_attention", "dense",
     "with_sharding_constraint", "asarray_like", "broadcast_to", "where", "concatenate", "mse_loss",
     "layer_norm", "softmax_cross_entropy", "embed", "rope", "swiglu", "cached_attention", "cache_prefill",
-    "cache_set_lens", "cache_advance",
+    "cache_set_lens", "cache_advance", "sample_logits",
 ]
 
 
@@ -1143,3 +1143,33 @@ def cache_advance(lens: ShardedArray, n: int = 1) -> None:
     """``lens += n`` in place, one small launch per device (:func:`.kernels.lens_add`)."""
     for t in lens.local.values():
         K.lens_add(t, n)
+
+
+def sample_logits(logits: ShardedArray, token: Optional[ShardedArray] = None, key=None, at: Optional[ShardedArray] = None,
+                  pos: Optional[ShardedArray] = None, temperature: float = 1.0, top_k: Optional[int] = None,
+                  top_p: Optional[float] = None, done: Optional[ShardedArray] = None, eos=(), pad: int = 0,
+                  dtype=torch.int64) -> ShardedArray:
+    """One token per sequence from ``logits`` (batch, T, vocab) at position ``at[b]`` (default: the last), by
+    :func:`.kernels.sample` (its reference states the semantics), one call per device shard.  Dims 1 and 2 of the
+    logits are made whole first and the batch sharding is kept, so a vocab-sharded head gives the same tokens; each
+    shard passes its batch start as the stream's ``batch_offset``, so a draw does not depend on the mesh.  ``at``,
+    ``pos`` and ``done`` are int ``(batch,)`` arrays laid out like the batch dim and stay on the devices.  ``token``
+    (batch, 1) is written in place and returned; without it a new array of ``dtype`` is."""
+    if logits.ndim != 3:
+        raise ValueError(f"sample_logits: logits must be (batch, length, vocab), got shape {tuple(logits.shape)}")
+    K.sample_params(logits.shape[-1], key, temperature, top_k, top_p, eos, pad, done is not None, "sample_logits")
+    tile = logits.tile.unshard([1, 2])
+    if logits.tile != tile:
+        logits = reshard_tile(logits, tile, note="sample.logits")
+    ot = tile.project([0, 1])
+    if token is None:
+        dtype = _dt.canonicalize(dtype)
+        token = ShardedArray((logits.shape[0], 1), dtype, sharding_from_tile(ot, like=[logits.sharding]),
+                             {d: torch.empty((t.shape[0], 1), dtype=dtype, device=t.device)
+                              for d, t in logits.local.items()})
+    _plan.record("sample", tiles=tile.tile_shape, mode=("greedy" if key is None else "gumbel"))
+    for d, t in logits.local.items():
+        pick = lambda a: None if a is None else a.local[d]   # noqa: E731
+        K.sample(t, token.local[d], key, pick(at), pick(pos), tile.region(d, logits.shape)[0][0], temperature, top_k,
+                 top_p, pick(done), eos, pad)
+    return token

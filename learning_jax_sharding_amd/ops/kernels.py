@@ -765,3 +765,143 @@ def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:
     if use_hip(lens) and fused_decode_enabled() and lens.dtype == torch.int32 and lens.is_contiguous():
         return _hip().lens_add(lens, n)
     return lens.add_(n)
+
+
+# ----------------------------------------------------------------------------- sampling
+# One token per row of logits: temperature, top-k, top-p, the Gumbel-max draw and the stop-token rule.
+# ``at``, ``pos`` and ``done`` are tensors ON THE DEVICE: nothing below reads them on the host, so a captured
+# decode step replays and still advances its random stream.
+SAMPLE_STREAM = 0x5A3D      # Philox counter word 3 of a sampling draw
+SAMPLE_MAX_EOS = 8
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1, _MASK32 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
+
+
+def _philox_torch(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 on int64 tensors holding 32-bit words (``random._philox_np``'s stream).  A product of two
+    32-bit words wraps in int64, which keeps all 64 of its bits."""
+    for _ in range(10):
+        p0, p1 = c0 * _PHILOX_M0, c2 * _PHILOX_M1
+        hi0, lo0, hi1, lo1 = (p0 >> 32) & _MASK32, p0 & _MASK32, (p1 >> 32) & _MASK32, p1 & _MASK32
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W0) & _MASK32, (k1 + _PHILOX_W1) & _MASK32
+    return c0, c1, c2, c3
+
+
+def sample_params(V: int, key, temperature, top_k, top_p, eos=(), pad=0, done=True, what: str = "sample"):
+    """The host-side checks of a sampling request (``ValueError`` before any launch) and its normal form:
+    ``(top_k or None, top_p or None, eos tuple)`` with ``top_k >= V`` and ``top_p == 1`` turned into None."""
+    if not float(temperature) > 0.0:
+        raise ValueError(f"{what}: temperature must be > 0, got {temperature}")
+    if top_k is not None and int(top_k) < 1:
+        raise ValueError(f"{what}: top_k must be >= 1, got {top_k}")
+    if top_p is not None and not 0.0 < float(top_p) <= 1.0:
+        raise ValueError(f"{what}: top_p must be in (0, 1], got {top_p}")
+    if key is None and (top_k is not None or top_p is not None):
+        raise ValueError(f"{what}: top_k / top_p filter a random draw and need a key (without one the token is the "
+                         "argmax)")
+    eos = (int(eos),) if isinstance(eos, int) else tuple(int(e) for e in eos)
+    if len(eos) > SAMPLE_MAX_EOS:
+        raise ValueError(f"{what}: at most {SAMPLE_MAX_EOS} eos ids, got {len(eos)}")
+    for name, ids in (("eos", eos), ("pad", (int(pad),) if done else ())):
+        if any(i < 0 or i >= V for i in ids):
+            raise ValueError(f"{what}: {name} ids {ids} must lie in the vocabulary [0, {V})")
+    top_k = None if top_k is None or int(top_k) >= V else int(top_k)
+    top_p = None if top_p is None or float(top_p) >= 1.0 else float(top_p)
+    return top_k, top_p, eos
+
+
+def _sample_rows(logits: torch.Tensor, at: Optional[torch.Tensor]) -> torch.Tensor:
+    """The ``[B, V]`` rows to sample of ``[B, V]`` or ``[B, T, V]`` logits: position ``at[b]`` (clamped), default the last."""
+    if logits.dim() == 2:
+        return logits
+    if at is None:
+        return logits[:, -1]
+    idx = at.long().clamp(0, logits.shape[1] - 1)
+    return logits[torch.arange(logits.shape[0], device=logits.device), idx]
+
+
+def sample_reference(logits, token_out, key=None, at=None, pos=None, batch_offset: int = 0, temperature: float = 1.0,
+                     top_k=None, top_p=None, done=None, eos=(), pad: int = 0, stats: bool = False):
+    """Plain torch sampling of one token per sequence: the contract a fused kernel will be held to.
+
+    ``logits``: ``[B, V]`` or ``[B, T, V]`` (f32 / bf16 / any float); the row of sequence b is position ``at[b]`` (an int
+    ``[B]`` tensor, clamped; default: the last).  ``token_out``: an int tensor of B elements, written in place and
+    returned.  For one row ``x[0..V)``, with ``z_i = f32(x_i) * f32(1 / temperature)``:
+
+    * ``top_k``: ``K = {i : x_i >= v_k}``, ``v_k`` the k-th largest value with multiplicity (ties at the threshold
+      are all kept); ``top_k >= V`` or None: every index.
+    * ``top_p`` (over K): ``w_i = exp(z_i - max_K z)`` in f32, ``S = sum_K w``; keep ``i`` iff ``sum {w_j : j in K,
+      x_j > x_i} < p S`` (sums in f64).  The maximum's tie group is always kept; ``top_p = 1`` or None: no filter.
+    * Both filters amount to a threshold ``tau`` on the raw x (the smallest kept value; ``-inf`` without a filter).
+    * ``key`` (a ``random.Key``): ``token = argmax over {x >= tau} of z_i + g_i``, the lowest index on an exact tie, with
+      ``g_i = -log(-log(u_i))`` in f64, ``u_i = ((word >> 8) + 0.5) 2^-24`` (``random._u01``), ``word`` = output ``i & 3`` of
+      Philox4x32-10 at counter ``(i >> 2, lo, hi, 0x5A3D)``; ``hi = batch_offset + b``, ``lo = pos[b]`` (an int ``[B]``
+      tensor; 0 without it), ``i`` the vocabulary index.  An entry of ``-inf`` is never drawn while a finite one
+      exists.  Without a key: the lowest index of the row maximum, no filters, no random numbers.
+    * ``done`` (int32 ``[B]``, updated in place): a sequence with ``done[b]`` writes ``pad``; otherwise the drawn
+      token is written and ``done[b] = 1`` if it is one of ``eos``.
+
+    ``stats=True`` also returns ``kept`` (int32 ``[B]``: ``|{x >= tau}|``) and ``tau`` (f32 ``[B]``).  No host read of a
+    device tensor."""
+    x = _sample_rows(logits, at)
+    B, V = x.shape
+    dev = x.device
+    top_k, top_p, eos = sample_params(V, key, temperature, top_k, top_p, eos, pad, done is not None)
+    if key is None:
+        # the lowest index of the maximum (argmax's tie rule is not specified)
+        idx = torch.arange(V, device=dev).expand(B, V)
+        tok = torch.where(x == x.amax(-1, keepdim=True), idx, V).amin(-1).clamp(max=V - 1)
+        kept = torch.full((B,), V, dtype=torch.int32, device=dev)
+        tau = torch.full((B,), float("-inf"), dtype=torch.float32, device=dev)
+    else:
+        # f32(1 / T) as a host number: a tensor made from it on the device would be a copy a capture cannot record
+        z = x.float() * float(torch.tensor(1.0 / float(temperature), dtype=torch.float32))
+        tau = torch.full((B, 1), float("-inf"), dtype=x.dtype, device=dev)
+        if top_k is not None:
+            tau = x.topk(top_k, dim=-1).values[:, -1:]
+        if top_p is not None:
+            inK = x >= tau
+            xs, order = torch.where(inK, x, float("-inf")).sort(dim=-1, descending=True, stable=True)
+            zs = z.gather(-1, order)
+            ins = inK.gather(-1, order)
+            w = torch.where(ins, torch.exp(zs - zs[:, :1]), torch.zeros_like(zs)).double()
+            cs = w.cumsum(-1)
+            pos_i = torch.arange(V, device=dev).expand(B, V)
+            new = torch.ones_like(ins)
+            new[:, 1:] = xs[:, 1:] != xs[:, :-1]
+            first = torch.where(new, pos_i, 0).cummax(-1).values          # start of each tie group
+            above = torch.where(first > 0, cs.gather(-1, (first - 1).clamp(min=0)), torch.zeros_like(cs))
+            keep = ins & (above < float(top_p) * cs[:, -1:])
+            keep[:, 0] = True
+            tau = torch.where(keep, xs, float("inf")).amin(-1, keepdim=True).to(x.dtype)
+        keep = x >= tau
+        i = torch.arange(V, dtype=torch.int64, device=dev).expand(B, V)
+        rows = torch.arange(B, dtype=torch.int64, device=dev)
+        hi = ((rows + int(batch_offset)) & _MASK32)[:, None].expand(B, V)
+        lo = (pos.reshape(B).long() & _MASK32 if pos is not None else torch.zeros_like(rows))[:, None].expand(B, V)
+        words = torch.stack(_philox_torch(i >> 2, lo, hi, torch.full_like(i, SAMPLE_STREAM), key.k0, key.k1), -1)
+        word = words.gather(-1, (i & 3)[..., None]).squeeze(-1)
+        u = ((word >> 8).double() + 0.5) * (1.0 / 16777216.0)
+        score = torch.where(keep, z.double() - torch.log(-torch.log(u)), float("-inf"))
+        tok = torch.where(score == score.amax(-1, keepdim=True), i, V).amin(-1).clamp(max=V - 1)
+        kept = keep.sum(-1).to(torch.int32)
+        tau = tau.reshape(B).float()
+    if done is not None:
+        was = done.reshape(B) != 0
+        stop = torch.zeros_like(was)
+        for e in eos:
+            stop |= tok == e
+        done.reshape(B).copy_(torch.where(was | stop, 1, 0).to(done.dtype))
+        tok = torch.where(was, int(pad), tok)
+    token_out.reshape(B).copy_(tok.to(token_out.dtype))
+    return (token_out, kept, tau) if stats else token_out
+
+
+def sample(logits, token_out, key=None, at=None, pos=None, batch_offset: int = 0, temperature: float = 1.0,
+           top_k=None, top_p=None, done=None, eos=(), pad: int = 0, stats: bool = False):
+    """Sample one token per sequence of one device's logits into ``token_out`` in place.  There is no HIP kernel
+    for this yet: host devices and GPUs alike run :func:`sample_reference`, a composite of torch launches without a
+    host read, which a captured decode step records and replays (like ``models.cache._greedy``, the other step of a
+    decode iteration that is not a kernel of this project)."""
+    return sample_reference(logits, token_out, key, at, pos, batch_offset, temperature, top_k, top_p, done, eos, pad,
+                            stats)

@@ -29,7 +29,7 @@ from .runtime.devices import devices as _devices, get_device, process_index
 from .sharding.shardings import Sharding, SingleDeviceSharding
 
 __all__ = ["PRNGKey", "key", "split", "fold_in", "normal", "uniform", "truncated_normal", "bits", "Key",
-           "key_data"]
+           "key_data", "categorical"]
 
 _M0, _M1 = 0xD2511F53, 0xCD9E8D57
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
@@ -200,3 +200,49 @@ def truncated_normal(key: Key, lower: float, upper: float, shape: Sequence[int] 
 
 def bits(key: Key, shape: Sequence[int] = (), *, sharding: Optional[Sharding] = None) -> ShardedArray:
     return _generate(key, shape, torch.int64, sharding, "bits")
+
+
+def categorical(key: Key, logits: ShardedArray, axis: int = -1, shape: Optional[Sequence[int]] = None) -> ShardedArray:
+    """``jax.random.categorical``: indices drawn from ``softmax(logits)`` along ``axis``, int32, of shape ``shape``
+    (default: ``logits``' shape without ``axis``; else a shape the batch shape broadcasts to, for several draws per
+    row).  The draw is the Gumbel-max of :func:`.ops.kernels.sample_reference` with the stream id ``hi`` = the flat
+    (row-major) index of the output element and ``lo = 0``, so the indices do not depend on the mesh.  A dim-0
+    sharding of the logits is kept; any other is gathered."""
+    from .ops import kernels as K
+    from .sharding.shardings import sharding_from_tile
+    from .spmd.reshard import reshard_tile
+    if not isinstance(key, Key):
+        raise TypeError(f"expected a PRNG key from random.PRNGKey/key, got {type(key)}")
+    nd = logits.ndim
+    if nd < 1 or not -nd <= axis < nd:
+        raise ValueError(f"categorical: axis {axis} is out of range for logits of shape {tuple(logits.shape)}")
+    axis %= nd
+    batch = tuple(s for i, s in enumerate(logits.shape) if i != axis)
+    out_shape = batch if shape is None else tuple(int(s) for s in shape)
+    if len(out_shape) < len(batch) or any(b not in (1, o) for b, o in zip(batch[::-1], out_shape[::-1])):
+        raise ValueError(f"categorical: shape {out_shape} is not one the batch shape {batch} broadcasts to")
+    # keep a dim-0 sharding only where the local rows are a contiguous run of the flat output rows
+    keep0 = out_shape == batch and axis != 0 and nd >= 2
+    tile = logits.tile.unshard([i for i in range(nd) if not (keep0 and i == 0)])
+    if logits.tile != tile:
+        logits = reshard_tile(logits, tile, note="categorical.logits")
+    V = logits.shape[axis]
+    inner = int(np.prod(out_shape[1:])) if len(out_shape) > 1 else 1
+    loc = {}
+    for d, t in logits.local.items():
+        if axis != nd - 1:
+            t = t.movedim(axis, -1)
+        lead = t.shape[:-1]
+        if out_shape != batch:
+            t = t.expand(out_shape + (V,))
+            lead = out_shape
+        rows = t.reshape(-1, V)
+        tok = torch.empty(rows.shape[0], dtype=torch.int32, device=rows.device)
+        off = tile.region(d, logits.shape)[0][0] * inner if keep0 else 0
+        K.sample(rows, tok, key, batch_offset=off)
+        loc[d] = tok.reshape(lead)
+    ot = tile.project([i for i in range(nd) if i != axis]) if out_shape == batch else None
+    if ot is None:
+        from .sharding.tile import TileAssignment
+        ot = TileAssignment.replicated(tile.device_ids, len(out_shape))
+    return ShardedArray(out_shape, torch.int32, sharding_from_tile(ot, like=[logits.sharding]), loc)
