@@ -19,7 +19,8 @@ import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
-           "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "plan_decode", "lens_add"]
+           "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "plan_decode", "lens_add", "skinny",
+           "skinny_plan", "skinny_supported", "set_skinny_waves"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -76,6 +77,10 @@ _SIGS = {
     "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_launch_plan": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_set_splits": [c_int, c_int],
+    "ljs_skinny_set_waves": [c_int],
+    "ljs_skinny_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "ljs_skinny_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long,
+                        c_long, c_int, c_int, c_int, c_int, c_void_p],
     "ljs_decode_key_tile": [],
     "ljs_decode_part_floats": [],
     "ljs_decode_max_group": [],
@@ -204,7 +209,8 @@ def last_launch() -> dict:
     ``gemm_mx_fp8<128,2,fix=1>``, ``gemm_mx8<256,160,4,bf16,2>``, ``quant_mx_rows``, ``quant_mx_cols<tiled>`` /
     ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
     ``grad_sumsq``, ``step_hyper``, ``adam_multi_dyn<32>``, ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
-    ``attn_decode<G4>``, ``decode_merge``, ``lens_add``),
+    ``attn_decode<G4>``, ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
+    the epilogue parts present)),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
     it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
@@ -1756,6 +1762,8 @@ def linear(x: torch.Tensor, ws: List[torch.Tensor], b: Optional[torch.Tensor], c
     """Fused dense layer (see :mod:`.linear`).  Every GPU shape runs on a HIP GEMM:
 
     * bf16 compute, K and N multiples of 8, f32 row-major kernels: the fused MFMA path;
+    * the same under ``no_grad`` with at most 16 rows (any row count) and ``K % 32 == 0``: one
+      weight-streaming ``skinny<`` launch (:func:`skinny`; ``LJS_SKINNY_GEMM=0``: as without it);
     * bf16 compute otherwise: the same path on zero-padded operands (rows M, K and N up to the
       next multiple of 8; zero rows/columns change no sum), result sliced back;
     * f32 compute: the MFMA ``v_mfma_f32_16x16x4f32`` GEMM (:class:`_MatmulF32`, strided
@@ -1766,8 +1774,12 @@ def linear(x: torch.Tensor, ws: List[torch.Tensor], b: Optional[torch.Tensor], c
 
     Anything else raises unless ``LJS_ALLOW_TORCH_FALLBACK=1`` (debugging only)."""
     from . import linear as _lin
-    if compute_dtype == torch.bfloat16 and _lin.supported(x, ws, b):
-        return _lin.linear(x, list(ws), b, relu, out_dtype, residual=residual)
+    # (at most 16 rows without a backward: the skinny GEMM takes any row count, so M = 1 .. 7 and other
+    # non-multiples of 8 do not leave through the padded path)
+    if compute_dtype == torch.bfloat16:
+        sk = _lin.skinny_route(x, ws, b)       # (False at once with grad enabled; evaluated once per call)
+        if sk or _lin.supported(x, ws, b):
+            return _lin.linear(x, list(ws), b, relu, out_dtype, residual=residual, skinny=sk)
     from . import shadow
     if any(shadow.is_proxy(w) for w in ws):
         # a gathered-weight proxy holds no f32 values; a shape the fused path does not take (M, K
@@ -2663,6 +2675,86 @@ def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:
         raise NotImplementedError(f"lens_add: a contiguous int32 GPU tensor, got {lens.dtype} on {lens.device}")
     _ck(lib().ljs_lens_add(_p(lens), lens.numel(), int(n), _stream(lens)), "ljs_lens_add")
     return lens
+
+
+# ============================================================================ skinny GEMM (M <= 16)
+# csrc/kernels/skinny.hip: the decode projections' weight-streaming GEMM, forward only.
+SKINNY_MAX_M = 16
+SKINNY_WAVES = (1, 2, 4, 8, 16)     # the block sizes the kernel takes, in waves
+
+
+def set_skinny_waves(n: Optional[int]) -> None:
+    """Tests: force ``skinny``'s blocks to ``n`` waves (one of :data:`SKINNY_WAVES`); None or <= 0 restores
+    :func:`skinny_plan`."""
+    if lib().ljs_skinny_set_waves(int(n or 0)) != 0:
+        raise ValueError(f"set_skinny_waves: {n} is not one of {SKINNY_WAVES}")
+
+
+def skinny_plan(M: int, N: int, K: int, cus: int = 256):
+    """``(waves_per_block, blocks)`` of :func:`skinny` for ``x [M][K] @ Wt [N][K]^T`` on a device of ``cus``
+    compute units (``ljs_skinny_plan``: needs the library, not a GPU).  Pure: of the shape and the CU count
+    alone, and ``M`` only has to lie in 1 .. 16.  ValueError outside ``1 <= M <= 16, K % 32 == 0, N % 8 == 0``."""
+    out = (c_int * 2)()
+    if lib().ljs_skinny_plan(int(M), int(N), int(K), int(cus), out) != 0:
+        raise ValueError(f"skinny_plan: M={M}, N={N}, K={K}, cus={cus}: 1 <= M <= {SKINNY_MAX_M}, K % 32 == 0, "
+                         "N % 8 == 0 and cus >= 1 are required")
+    return int(out[0]), int(out[1])
+
+
+def skinny_supported(M: int, N: int, K: int, lda: int, ldb: int, ldc: int, out_dtype: torch.dtype, x_addr: int = 0,
+                     wt_addr: int = 0, out_addr: int = 0, bias_dtype: Optional[torch.dtype] = None, bias_addr: int = 0,
+                     res_dtype: Optional[torch.dtype] = None, res_ld: int = 0, res_addr: int = 0,
+                     x_dtype: torch.dtype = torch.bfloat16, wt_dtype: torch.dtype = torch.bfloat16) -> bool:
+    """``ljs_skinny_bf16``'s gate as a pure predicate of shapes, dtypes, leading dimensions (elements) and
+    byte addresses: ``1 <= M <= 16``, ``K % 32 == 0``, ``N % 8 == 0``; bf16 x and Wt with 16-byte aligned
+    rows; a bf16 or f32 output (and a bf16 or f32 residual, bf16 output only) aligned to a lane's four
+    values, 8 bytes of bf16 or 16 of f32; an f32 or bf16 bias."""
+    if not (1 <= M <= SKINNY_MAX_M and N >= 8 and N % 8 == 0 and K >= 32 and K % 32 == 0):
+        return False
+    if x_dtype != torch.bfloat16 or wt_dtype != torch.bfloat16 or out_dtype not in (torch.bfloat16, torch.float32):
+        return False
+    if lda < K or ldb < K or ldc < N or lda % 8 or ldb % 8 or ldc % 4 or x_addr % 16 or wt_addr % 16:
+        return False
+    if out_addr % (16 if out_dtype == torch.float32 else 8):
+        return False
+    if bias_dtype is not None and (bias_dtype not in (torch.bfloat16, torch.float32)
+                                   or bias_addr % (4 if bias_dtype == torch.float32 else 2)):
+        return False
+    if res_dtype is not None and (res_dtype not in (torch.bfloat16, torch.float32) or out_dtype != torch.bfloat16
+                                  or res_ld < N or res_ld % 4
+                                  or res_addr % (16 if res_dtype == torch.float32 else 8)):
+        return False
+    return True
+
+
+def skinny_raw(x, wt, out, M: int, N: int, K: int, lda: int, ldc: int, bias=None, relu: bool = False, res=None,
+               res_ld: int = 0, ldb: Optional[int] = None) -> int:
+    """One ``ljs_skinny_bf16`` call on the operands as they are (``wt`` may be None: a null operand); returns
+    the launcher's code (non-zero: rejected, nothing launched or recorded) instead of raising."""
+    f32 = torch.float32
+    return lib().ljs_skinny_bf16(_p(x), _p(wt), _p(out), _p(bias), _p(res), int(M), int(N), int(K), int(lda),
+                                 int(K if ldb is None else ldb), int(ldc), int(res_ld), int(out.dtype == f32),
+                                 int(bias is not None and bias.dtype == f32), int(res is not None and res.dtype == f32),
+                                 int(bool(relu)), _stream(out))
+
+
+def skinny(x: torch.Tensor, wt: torch.Tensor, out: torch.Tensor, M: int, N: int, K: int, lda: int, ldc: int,
+           bias: Optional[torch.Tensor] = None, relu: bool = False, res: Optional[torch.Tensor] = None,
+           res_ld: int = 0, ldb: Optional[int] = None) -> None:
+    """``out[m][n] = epi(sum_k x[m][k] wt[n][k])`` for ``1 <= M <= 16`` (csrc/kernels/skinny.hip): bf16 ``x`` (row
+    stride ``lda``) and ``wt`` (the ``[N][K]`` transposed weight shadow, row stride ``ldb``, default ``K``), ``out`` bf16
+    or f32 with row stride ``ldc >= N``.  Epilogue: ``+ bias`` (f32 or bf16) in f32, ReLU, the rounding, then
+    ``bf16(bf16(y) + bf16(res))`` for a residual (f32 or bf16, row stride ``res_ld``; bf16 output only).  One launch,
+    deterministic, no workspace.  Raises for anything :func:`skinny_supported` refuses."""
+    ok = all(t is None or t.is_cuda for t in (x, wt, out, bias, res)) and skinny_supported(
+        M, N, K, lda, K if ldb is None else ldb, ldc, out.dtype, x.data_ptr(), wt.data_ptr(), out.data_ptr(),
+        None if bias is None else bias.dtype, 0 if bias is None else bias.data_ptr(),
+        None if res is None else res.dtype, res_ld, 0 if res is None else res.data_ptr(), x.dtype, wt.dtype)
+    if not ok:
+        raise NotImplementedError(f"skinny kernel: bf16 GPU x [M <= 16][K % 32 == 0] and wt [N % 8 == 0][K] with 16-byte "
+                                  f"aligned rows, a bf16 / f32 output; got M={M} N={N} K={K} lda={lda} ldb={ldb} "
+                                  f"ldc={ldc} x {x.dtype} wt {wt.dtype} out {out.dtype}")
+    _ck(skinny_raw(x, wt, out, M, N, K, lda, ldc, bias, relu, res, res_ld, ldb), "ljs_skinny_bf16")
 
 
 # ============================================================================ optimizer

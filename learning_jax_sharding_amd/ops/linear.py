@@ -5,6 +5,11 @@ f32 weight through its persistent bf16 transposed shadow (:mod:`.shadow`; refres
 fused Adam kernel, so no per-step cast).  Output columns of the kernels are interleaved in
 one ``[M, n*N]`` buffer, so downstream slices (the attention's q/k/v) are views.
 
+Without a backward (``torch.no_grad``) and with at most 16 rows -- a decode step's ``B x 1`` tokens -- the
+forward is one launch of the weight-streaming skinny GEMM instead (``csrc/kernels/skinny.hip``,
+:func:`skinny_route`, ``LJS_SKINNY_GEMM=0``: the tile GEMM as with a backward): the same rounding of x, the
+same shadows and the same column views.
+
 Backward:
 * ``dX = sum_i dY_i W_i^T``    - (KC, KC) GEMM against the plain bf16 shadow of W_i
   (f32 accumulation across kernels);
@@ -1012,16 +1017,86 @@ _WMAJOR_BATCH = os.environ.get("LJS_WMAJOR_DW_BATCH", "1") == "1"
 
 
 def supported(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
+    M = x.numel() // max(1, x.shape[-1])   # the weight-gradient GEMM contracts over the M rows
+    return M % 8 == 0 and weights_supported(x, ws, b)
+
+
+def weights_supported(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
+    """What :func:`supported` asks of the weights and the feature dims (its ``M % 8 == 0`` clause, the
+    weight-gradient GEMM's, left out)."""
     K = x.shape[-1]
     N = ws[0].shape[1]
-    M = x.numel() // max(1, K)   # the weight-gradient GEMM contracts over the M rows
-    return (K % 8 == 0 and N % 8 == 0 and M % 8 == 0 and all(w.shape == ws[0].shape and w.dim() == 2 for w in ws)
-            and all(w.dtype == torch.float32 and w.stride(1) == 1 for w in ws)
-            and (b is None or len(ws) == 1))
+    return (K % 8 == 0 and N % 8 == 0 and all(w.shape == ws[0].shape and w.dim() == 2 for w in ws)
+            and all(w.dtype == torch.float32 and w.stride(1) == 1 for w in ws) and (b is None or len(ws) == 1))
+
+
+def skinny_enabled() -> bool:
+    # LJS_SKINNY_GEMM=0: no-grad dense layers of at most 16 rows run the tile GEMMs of the training
+    # path (hip.gemm) instead of the weight-streaming kernel of csrc/kernels/skinny.hip
+    return os.environ.get("LJS_SKINNY_GEMM", "1") != "0"
+
+
+def skinny_route(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
+    """Whether :func:`linear` runs this call on the skinny GEMM (hip.skinny): no gradient is being
+    recorded, at most 16 rows of a GPU activation in plain row order, weights the fused path takes,
+    ``K % 32 == 0``, and ``LJS_SKINNY_GEMM`` is not 0."""
+    K = x.shape[-1]
+    M = x.numel() // max(1, K)
+    if (torch.is_grad_enabled() or not 1 <= M <= hip.SKINNY_MAX_M or not x.is_cuda or K % 32 != 0
+            or x.dtype not in (torch.float32, torch.bfloat16) or not weights_supported(x, ws, b)
+            or not skinny_enabled()):
+        return False
+    # plain row order: the rows in storage order are the rows in logical order (hip.storage_order puts
+    # size-1 dims first, so the (B, 1, K) activation of a decode step reads (1, 0, 2): still plain)
+    order, swap = _row_order(x)
+    big = [d for d in order if x.shape[d] > 1]
+    return not swap and big == sorted(big)
+
+
+def _linear_skinny(x, ws, b, relu, out_dtype, res) -> List[torch.Tensor]:
+    """The forward of :class:`_Linear` for at most 16 rows without a backward: the same bf16 rounding
+    of x, the same weight shadows, the same column views of one ``[M][nw * N]`` buffer, one
+    ``skinny<`` launch.  No attention fusion, no fused output sum, no ReLU registration."""
+    K = x.shape[-1]
+    M = x.numel() // K
+    nw, N = len(ws), ws[0].shape[1]
+    x2 = x.reshape(-1, K)
+    xb = _bf16(x2 if x2.is_contiguous() else x2.contiguous())
+    take_pending_waits(x.device)
+    wt = shadow.get(ws[0], "T") if nw == 1 else shadow.get_stacked(ws)   # [nw * N][K]
+    od = out_dtype if out_dtype in (torch.bfloat16, torch.float32) else torch.float32
+    out = torch.empty((M, nw * N), dtype=od, device=x.device)
+    bias = None
+    if b is not None:
+        bias = (b if b.dtype in (torch.float32, torch.bfloat16) else b.float()).contiguous()
+    r2, r_ld = None, 0
+    if res is not None and od == torch.bfloat16:
+        r2 = res.reshape(M, N)
+        if r2.dtype not in (torch.bfloat16, torch.float32):
+            r2 = r2.float()
+        if not (r2.stride(1) == 1 and r2.stride(0) % 8 == 0 and r2.data_ptr() % 16 == 0):
+            r2 = r2.contiguous()
+        r_ld = r2.stride(0)
+    if xb.data_ptr() % 16:      # (a bf16 view that starts inside a 16-byte chunk)
+        xb = xb.clone()
+    hip.skinny(xb, wt, out, M, nw * N, K, K, nw * N, bias=bias, relu=relu, res=r2, res_ld=r_ld)
+    ys = [out[:, i * N:(i + 1) * N].view(tuple(x.shape[:-1]) + (N,)) for i in range(nw)]
+    if res is not None and r2 is None:
+        ys = [ys[0] + res.to(ys[0].dtype)]
+    if od != out_dtype:
+        ys = [y.to(out_dtype) for y in ys]
+    return ys
 
 
 def linear(x: torch.Tensor, ws: List[torch.Tensor], b: Optional[torch.Tensor], relu: bool,
-           out_dtype: torch.dtype, residual: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+           out_dtype: torch.dtype, residual: Optional[torch.Tensor] = None,
+           skinny: Optional[bool] = None) -> List[torch.Tensor]:
+    """``skinny``: :func:`skinny_route` of this call when the caller has evaluated it already."""
+    if skinny_route(x, ws, b) if skinny is None else skinny:
+        if residual is not None and (relu or len(ws) != 1):
+            ys = _linear_skinny(x, ws, b, relu, out_dtype, None)
+            return [ys[0] + residual.to(ys[0].dtype)] + ys[1:]
+        return _linear_skinny(x, ws, b, relu, out_dtype, residual)
     if residual is not None and (relu or len(ws) != 1):
         # the epilogue adds the residual after the activation; a ReLU dense keeps its own output
         # for the backward mask, so that combination adds separately
