@@ -50,6 +50,15 @@
 // launch, about 2 us inside a graph, at the price of write-through stores, a ticket per (b, kv head) and
 // a serial merge tail in whichever block arrives last; with a kernel boundary in between, plain
 // stores are enough.)
+//
+// MX-fp8 caches (the mx8 instances; ljs_kv_append_q8, ljs_attn_decode_q8).  kc / vc hold OCP e4m3 bytes (B,
+// cap, Hkv, 64) and two more buffers one e8m0 byte per 32 elements (B, cap, Hkv, 2), in the encoding
+// ljs_quant_mx_rows writes (exponent + 127); strides of all four count bytes.  The append stores
+// quantize_mx_ref of the bf16 row the bf16 cache would hold (rope's bits first, then the quantiser;
+// kv_append_q8_kernel), the attention is the bf16 attention over the dequantised rows, which are exact
+// bf16 values (attn_decode_kernel<HW, true>: the same grid, plan, partials and merge; only the loads and
+// two scaled conversions per 4 elements differ).  Rows beyond a block's range read zero bytes and a
+// zero scale byte through the descriptors: zeros.
 #include "rowwise.h"
 
 namespace {
@@ -117,6 +126,10 @@ struct DecodeArgs {
   long kb, ks, kh, vb, vs, vh, ob, oh;
   int B, H, Hkv, G, cap, extra, splits, kps;
   float scale_log2;
+  // MX-fp8 caches only (kc / vc are then e4m3 bytes and their strides count bytes): the e8m0 scales
+  // (B, cap, Hkv, 2) and their (batch, position, head) strides in bytes
+  const unsigned char *ksc, *vsc;
+  long ksb, kss, ksh, vsb, vss, vsh;
 };
 
 // final output of one (b, h, chunk) from a merged state
@@ -130,7 +143,15 @@ __device__ __forceinline__ void dec_store_out(const DecodeArgs& a, int b, int h,
   if (cc == 0) a.lse[(long)b * a.H + h] = l > 0.f ? m + __log2f(l) : INFINITY;
 }
 
-template <int HW>
+// 2^(e - 127) of an e8m0 byte as the f32 the scaled conversions take (they read its exponent field); the
+// zero byte of a row past the descriptor gives 0 or 2^-127 times zero bytes: zero either way
+__device__ __forceinline__ float e8m0_f32(unsigned e) { return __uint_as_float(e << 23); }
+
+// MX8: kc / vc hold e4m3 bytes with one e8m0 scale per 32 elements.  A key row is 64 bytes, the lane's
+// chunk 8 of them (inside one scale block: block c / 4); the gfx950 scaled conversions turn them into
+// the packed bf16 of K (exact: 4 significant bits times a power of two) and the f32 of V, after which
+// the sweep is the bf16 one.
+template <int HW, bool MX8 = false>
 __global__ __launch_bounds__(kDecThreads)
 void attn_decode_kernel(const DecodeArgs a) {
   __shared__ alignas(16) float sh[kDecWaves][HW][kDecPart];
@@ -157,11 +178,23 @@ void attn_decode_kernel(const DecodeArgs a) {
 
   // descriptors that end with row k1 - 1 of this (batch, key/value head): rows beyond read as zeros
   const bool any_key = k1 > k0;
-  const long kbytes = any_key ? ((long)(k1 - 1) * a.ks + kDecD) * 2 : 0;
-  const long vbytes = any_key ? ((long)(k1 - 1) * a.vs + kDecD) * 2 : 0;
-  const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.kc + (long)b * a.kb + (long)j * a.kh, kbytes);
-  const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.vc + (long)b * a.vb + (long)j * a.vh, vbytes);
-  const int kstep = (int)a.ks * 2, vstep = (int)a.vs * 2;    // bytes per key (host: cap x stride fits an int)
+  constexpr int ES = MX8 ? 1 : 2;              // bytes per cache element
+  const long kbytes = any_key ? ((long)(k1 - 1) * a.ks + kDecD) * ES : 0;
+  const long vbytes = any_key ? ((long)(k1 - 1) * a.vs + kDecD) * ES : 0;
+  const __amdgpu_buffer_rsrc_t rk =
+      make_rsrc(reinterpret_cast<const unsigned char*>(a.kc) + ((long)b * a.kb + (long)j * a.kh) * ES, kbytes);
+  const __amdgpu_buffer_rsrc_t rv =
+      make_rsrc(reinterpret_cast<const unsigned char*>(a.vc) + ((long)b * a.vb + (long)j * a.vh) * ES, vbytes);
+  const int kstep = (int)a.ks * ES, vstep = (int)a.vs * ES;  // bytes per key (host: cap x stride fits an int)
+  // the scales of the same rows, through descriptors that end with the same last row
+  __amdgpu_buffer_rsrc_t rks = rk, rvs = rv;
+  int ksstep = 0, vsstep = 0;
+  if constexpr (MX8) {
+    rks = make_rsrc(a.ksc + (long)b * a.ksb + (long)j * a.ksh, any_key ? (long)(k1 - 1) * a.kss + 2 : 0);
+    rvs = make_rsrc(a.vsc + (long)b * a.vsb + (long)j * a.vsh, any_key ? (long)(k1 - 1) * a.vss + 2 : 0);
+    ksstep = (int)a.kss;
+    vsstep = (int)a.vss;
+  }
 
   float m[HW], l[HW];
   f32x2 acc[HW][4];
@@ -176,20 +209,47 @@ void attn_decode_kernel(const DecodeArgs a) {
   const int stride = wpp * kDecSlots;          // keys one step of this part's waves covers
   for (int base = k0; base < k1; base += stride * kDecUnroll) {
     int key[kDecUnroll];
-    u32x4 kr[kDecUnroll], vr[kDecUnroll];
-#pragma unroll
-    for (int u = 0; u < kDecUnroll; ++u) {
-      key[u] = base + u * stride + wk * kDecSlots + slot;
-      kr[u] = __builtin_amdgcn_raw_buffer_load_b128(rk, key[u] * kstep + c * 16, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < kDecUnroll; ++u) vr[u] = __builtin_amdgcn_raw_buffer_load_b128(rv, key[u] * vstep + c * 16, 0, 0);
-
+    u32x4 kr[kDecUnroll];
     f32x2 vf[kDecUnroll][4];
+    if constexpr (MX8) {
+      u32x2 kq[kDecUnroll], vq[kDecUnroll];
+      unsigned ke[kDecUnroll], ve[kDecUnroll];
 #pragma unroll
-    for (int u = 0; u < kDecUnroll; ++u)
+      for (int u = 0; u < kDecUnroll; ++u) {
+        key[u] = base + u * stride + wk * kDecSlots + slot;
+        kq[u] = __builtin_amdgcn_raw_buffer_load_b64(rk, key[u] * kstep + c * 8, 0, 0);
+        ke[u] = __builtin_amdgcn_raw_buffer_load_b8(rks, key[u] * ksstep + (c >> 2), 0, 0);
+      }
 #pragma unroll
-      for (int e = 0; e < 4; ++e) vf[u][e] = f32x2{bf16_lo(vr[u][e]), bf16_hi(vr[u][e])};
+      for (int u = 0; u < kDecUnroll; ++u) {
+        vq[u] = __builtin_amdgcn_raw_buffer_load_b64(rv, key[u] * vstep + c * 8, 0, 0);
+        ve[u] = __builtin_amdgcn_raw_buffer_load_b8(rvs, key[u] * vsstep + (c >> 2), 0, 0);
+      }
+#pragma unroll
+      for (int u = 0; u < kDecUnroll; ++u) {
+        const float ksf = e8m0_f32(ke[u]), vsf = e8m0_f32(ve[u]);
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {          // (the half-word select is an immediate)
+          kr[u][2 * w] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(kq[u][w], ksf, false));
+          kr[u][2 * w + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(kq[u][w], ksf, true));
+          vf[u][2 * w] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(vq[u][w], vsf, false);
+          vf[u][2 * w + 1] = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(vq[u][w], vsf, true);
+        }
+      }
+    } else {
+      u32x4 vr[kDecUnroll];
+#pragma unroll
+      for (int u = 0; u < kDecUnroll; ++u) {
+        key[u] = base + u * stride + wk * kDecSlots + slot;
+        kr[u] = __builtin_amdgcn_raw_buffer_load_b128(rk, key[u] * kstep + c * 16, 0, 0);
+      }
+#pragma unroll
+      for (int u = 0; u < kDecUnroll; ++u) vr[u] = __builtin_amdgcn_raw_buffer_load_b128(rv, key[u] * vstep + c * 16, 0, 0);
+#pragma unroll
+      for (int u = 0; u < kDecUnroll; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) vf[u][e] = f32x2{bf16_lo(vr[u][e]), bf16_hi(vr[u][e])};
+    }
 
 #pragma unroll
     for (int i = 0; i < HW; ++i) {
@@ -439,6 +499,101 @@ void kv_append_kernel(const AppendArgs a) {
   }
 }
 
+// ---- kv_append into an MX-fp8 cache
+// The bf16 kernel's work items and position rule; a cached row is stored as quantize_mx_ref of the bf16
+// row the bf16 cache would hold: 64 e4m3 bytes and two e8m0 scale bytes (elements 0..31, 32..63).  The
+// four items of a row are the four lanes of a quad (item % 4 is the lane's, as the tensors' first
+// items, the total and the grid stride are all multiples of 4), and the quad takes every branch
+// together, so a block maximum is an integer max of bf16 magnitude bits over the lane's 8 elements and
+// then over the quad by two DPP quad_perm steps.  No LDS, no atomics, no workspace.
+struct AppendQ8Args {
+  AppendArgs a;               // t[0].out / t[1].out: the e4m3 bytes, their o* strides in bytes
+  unsigned char* sc[2];       // the scales of k and v, (B, cap, Hkv, 2)
+  long sb[2], sp[2], sh[2];   // their (batch, position, head) strides in bytes
+};
+
+__device__ __forceinline__ unsigned quad_max(unsigned v) {
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
+  return max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
+}
+
+// the largest bf16 magnitude (bits) of four packed pairs
+__device__ __forceinline__ unsigned amax_bits8(const u32x4& w) {
+  unsigned mx = 0u;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned m = w[e] & 0x7fff7fffu;
+    mx = max(mx, max(m & 0xffffu, m >> 16));
+  }
+  return mx;
+}
+
+__global__ __launch_bounds__(kRowBlockThreads)
+void kv_append_q8_kernel(const AppendQ8Args qa) {
+  constexpr int h = kDecD / 2;
+  const AppendArgs& a = qa.a;
+  const long step = (long)gridDim.x * kRowBlockThreads;
+  for (long item = (long)blockIdx.x * kRowBlockThreads + threadIdx.x; item < a.total; item += step) {
+    int which = 0;
+    if (item >= a.t[1].first) which = 1;
+    if (a.nt > 2 && item >= a.t[2].first) which = 2;
+    const AppTensor& x = a.t[which];
+    long r = item - x.first;
+    const int jj = (int)(r % 4);
+    r /= 4;
+    const int hd = (int)(r % x.H);
+    r /= x.H;
+    const int tt = (int)(r % a.T);
+    const long b = r / a.T;
+    const long p = (a.lens ? (long)a.lens[b] : 0L) + tt;
+    const bool inside = p >= 0 && p < a.cap;
+    if (x.cache && !inside) continue;             // no store outside the cache: neither bytes nor scales
+    if (!x.cache && !inside) {                    // q_out of a sequence that is full: zeros
+      bf16_t* dst = x.out + b * x.ob + (long)tt * x.op + (long)hd * x.oh + jj * 8;
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      store16<kAligned16>(dst, z);
+      store16<kAligned16>(dst + h, z);
+      continue;
+    }
+    const bf16_t* src = x.in + b * x.ib + (long)tt * x.it + (long)hd * x.ih + jj * 8;
+    u32x4 lo, hi;                                 // the row's chunks jj and jj + 4 as the bf16 cache holds them
+    if (!x.rotate) {
+      lo = load16<u32x4, kAligned16>(src);
+      hi = load16<u32x4, kAligned16>(src + h);
+    } else {
+      const long trow = p * (long)h + jj * 8;
+      float x0[8], x1[8], c[8], sn[8], y0[8], y1[8];
+      load_chunk8(src, x0);
+      load_chunk8(src + h, x1);
+      load_chunk8(a.cos_t + trow, c);
+      load_chunk8(a.sin_t + trow, sn);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {               // rope_kernel's expressions
+        const float sg = sn[e];
+        y0[e] = x0[e] * c[e] - x1[e] * sg;
+        y1[e] = x1[e] * c[e] + x0[e] * sg;
+      }
+      lo = pack_bf16x8(y0);                       // rope's bits first, then the quantiser
+      hi = pack_bf16x8(y1);
+    }
+    if (!x.cache) {
+      bf16_t* dst = x.out + b * x.ob + (long)tt * x.op + (long)hd * x.oh + jj * 8;
+      store16<kAligned16>(dst, lo);
+      store16<kAligned16>(dst + h, hi);
+      continue;
+    }
+    const int e0 = mx_exponent(__uint_as_float(quad_max(amax_bits8(lo)) << 16));
+    const int e1 = mx_exponent(__uint_as_float(quad_max(amax_bits8(hi)) << 16));
+    const float s0 = mx_scale_pow2(e0), s1 = mx_scale_pow2(e1);
+    unsigned char* dst = reinterpret_cast<unsigned char*>(x.out) + b * x.ob + p * x.op + (long)hd * x.oh + jj * 8;
+    *reinterpret_cast<u32x2*>(dst) = u32x2{cvt4_e4m3_bf16(lo[0], lo[1], s0), cvt4_e4m3_bf16(lo[2], lo[3], s0)};
+    *reinterpret_cast<u32x2*>(dst + h) = u32x2{cvt4_e4m3_bf16(hi[0], hi[1], s1), cvt4_e4m3_bf16(hi[2], hi[3], s1)};
+    if (jj == 0)
+      *reinterpret_cast<unsigned short*>(qa.sc[which] + b * qa.sb[which] + p * qa.sp[which] + (long)hd * qa.sh[which]) =
+          (unsigned short)((e0 + 127) | ((e1 + 127) << 8));
+  }
+}
+
 __global__ void lens_add_kernel(int* lens, int B, int n) {
   for (int i = threadIdx.x; i < B; i += blockDim.x) lens[i] += n;
 }
@@ -471,16 +626,23 @@ LJS_API int ljs_decode_launch_plan(int B, int Hkv, int cap, int* out) {
   return decode_launch_plan(B, Hkv, cap, out, out + 1);
 }
 
-// k, v (B, T, Hkv, 64) -> kc, vc (B, cap, Hkv, 64) at rows base[b] + t, base = lens (int32 [B], device)
-// or 0 when lens is null; q (B, T, H, 64) -> q_out (B, T, H, 64) when both are given.  cos_t / sin_t (f32
-// [table_rows][32], table_rows >= cap) rotate k and q; both null: k is copied as it is.  s*: the
-// (batch, position, head) strides in elements.  Returns hipErrorInvalidValue, and launches and records
-// nothing, for an empty shape, a misaligned base or stride, one of q / q_out alone, q without a
-// table, or a table shorter than the cache.
-LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, void* kc, void* vc, void* q_out, int B, int T,
-                          int H, int Hkv, int cap, const long* sk, const long* sv, const long* sq, const long* skc,
-                          const long* svc, const long* sqo, const void* lens, const void* cos_t, const void* sin_t,
-                          long table_rows, hipStream_t st) {
+namespace {
+
+// an MX-fp8 cache operand: e4m3 bytes (B, cap, Hkv, 64), 16-byte aligned base and byte strides; its e8m0
+// scales (B, cap, Hkv, 2): a 2-byte aligned base and even byte strides (one lane stores both bytes)
+inline bool q8_aligned(const void* p, const long* st) {
+  return p && st && (((uintptr_t)p) & 15u) == 0 && st[0] % 16 == 0 && st[1] % 16 == 0 && st[2] % 16 == 0;
+}
+inline bool q8_scale_aligned(const void* p, const long* st) {
+  return p && st && (((uintptr_t)p) & 1u) == 0 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0;
+}
+
+// the checks and the work items the two append launchers share (the cache operands' own alignment is
+// the caller's): 0 and *a filled, or hipErrorInvalidValue
+inline int append_plan(const void* k, const void* v, const void* q, void* kc, void* vc, void* q_out, int B, int T,
+                       int H, int Hkv, int cap, const long* sk, const long* sv, const long* sq, const long* skc,
+                       const long* svc, const long* sqo, const void* lens, const void* cos_t, const void* sin_t,
+                       long table_rows, AppendArgs* out) {
   const bool rot = cos_t != nullptr;
   if (B < 1 || T < 1 || Hkv < 1 || cap < 1 || (cos_t == nullptr) != (sin_t == nullptr) ||
       (q == nullptr) != (q_out == nullptr) || (q && (!rot || H < 1)))
@@ -488,8 +650,7 @@ LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, void* kc,
   if (rot && (table_rows < cap || (((uintptr_t)cos_t) & 15u) || (((uintptr_t)sin_t) & 15u)))
     return (int)hipErrorInvalidValue;
   if (lens && (((uintptr_t)lens) & 3u)) return (int)hipErrorInvalidValue;
-  if (!dec_aligned(k, sk) || !dec_aligned(v, sv) || !dec_aligned(kc, skc) || !dec_aligned(vc, svc) ||
-      (q && (!dec_aligned(q, sq) || !dec_aligned(q_out, sqo))))
+  if (!dec_aligned(k, sk) || !dec_aligned(v, sv) || (q && (!dec_aligned(q, sq) || !dec_aligned(q_out, sqo))))
     return (int)hipErrorInvalidValue;
   AppendArgs a{};
   const long per_kv = (long)B * T * Hkv * 4;
@@ -507,31 +668,87 @@ LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, void* kc,
   a.lens = (const int*)lens;
   a.T = T;
   a.cap = cap;
+  *out = a;
+  return 0;
+}
+
+inline dim3 append_grid(const AppendArgs& a) {
   const long need = (a.total + kRowBlockThreads - 1) / kRowBlockThreads;
   const long most = (long)ljs_device_cus() * kAppBlocksPerCu;
-  const dim3 grid((unsigned)(need < most ? need : most));
+  return dim3((unsigned)(need < most ? need : most));
+}
+
+}  // namespace
+
+// k, v (B, T, Hkv, 64) -> kc, vc (B, cap, Hkv, 64) at rows base[b] + t, base = lens (int32 [B], device)
+// or 0 when lens is null; q (B, T, H, 64) -> q_out (B, T, H, 64) when both are given.  cos_t / sin_t (f32
+// [table_rows][32], table_rows >= cap) rotate k and q; both null: k is copied as it is.  s*: the
+// (batch, position, head) strides in elements.  Returns hipErrorInvalidValue, and launches and records
+// nothing, for an empty shape, a misaligned base or stride, one of q / q_out alone, q without a
+// table, or a table shorter than the cache.
+LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, void* kc, void* vc, void* q_out, int B, int T,
+                          int H, int Hkv, int cap, const long* sk, const long* sv, const long* sq, const long* skc,
+                          const long* svc, const long* sqo, const void* lens, const void* cos_t, const void* sin_t,
+                          long table_rows, hipStream_t st) {
+  if (!dec_aligned(kc, skc) || !dec_aligned(vc, svc)) return (int)hipErrorInvalidValue;
+  AppendArgs a{};
+  if (append_plan(k, v, q, kc, vc, q_out, B, T, H, Hkv, cap, sk, sv, sq, skc, svc, sqo, lens, cos_t, sin_t, table_rows,
+                  &a) != 0)
+    return (int)hipErrorInvalidValue;
+  const dim3 grid = append_grid(a);
   hipLaunchKernelGGL(kv_append_kernel, grid, dim3(kRowBlockThreads), 0, st, a);
-  ljs_launch_rec(q ? "kv_append<rot,q>" : (rot ? "kv_append<rot>" : "kv_append<copy>"), grid, kRowBlockThreads);
+  ljs_launch_rec(q ? "kv_append<rot,q>" : (cos_t ? "kv_append<rot>" : "kv_append<copy>"), grid, kRowBlockThreads);
   return (int)hipGetLastError();
 }
 
-// q (B, 1, H, 64), kc / vc (B, cap, Hkv, 64) -> o (B, 1, H, 64) bf16, lse (B, H) f32 over the keys [0,
-// min(lens[b] + extra, cap)) (the head of the file).  ws: f32 workspace of ws_floats floats, at least B H
-// splits kDecPart of them when the plan has more than one split.  s*: (batch, position, head) strides in
-// elements.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty shape, H %
-// Hkv != 0, H / Hkv > 16, scale <= 0, extra < 0, a misaligned base or stride, a key stride below 64, a
-// cache whose byte offsets do not fit 31 bits, an invalid forced plan or a workspace that is too small.
-LJS_API int ljs_attn_decode(const void* q, const void* kc, const void* vc, void* o, void* lse, void* ws, long ws_floats,
-                            const void* lens, int B, int H, int Hkv, int cap, const long* sq, const long* skc,
-                            const long* svc, const long* so, float scale, int extra, hipStream_t st) {
+// ljs_kv_append into an MX-fp8 cache: kc / vc are e4m3 bytes (B, cap, Hkv, 64) and kcs / vcs their e8m0
+// scales (B, cap, Hkv, 2) -- of every row written, quantize_mx_ref of the bf16 row ljs_kv_append would
+// have stored; q_out stays bf16.  skc / svc / skcs / svcs: (batch, position, head) strides in bytes.
+// Refuses what ljs_kv_append refuses, and a null or odd scale base, an odd scale stride, or a cache
+// base or stride that is not a multiple of 16 bytes.
+LJS_API int ljs_kv_append_q8(const void* k, const void* v, const void* q, void* kc, void* vc, void* kcs, void* vcs,
+                             void* q_out, int B, int T, int H, int Hkv, int cap, const long* sk, const long* sv,
+                             const long* sq, const long* skc, const long* svc, const long* skcs, const long* svcs,
+                             const long* sqo, const void* lens, const void* cos_t, const void* sin_t, long table_rows,
+                             hipStream_t st) {
+  if (!q8_aligned(kc, skc) || !q8_aligned(vc, svc) || !q8_scale_aligned(kcs, skcs) || !q8_scale_aligned(vcs, svcs))
+    return (int)hipErrorInvalidValue;
+  AppendQ8Args qa{};
+  if (append_plan(k, v, q, kc, vc, q_out, B, T, H, Hkv, cap, sk, sv, sq, skc, svc, sqo, lens, cos_t, sin_t, table_rows,
+                  &qa.a) != 0)
+    return (int)hipErrorInvalidValue;
+  qa.sc[0] = (unsigned char*)kcs;
+  qa.sc[1] = (unsigned char*)vcs;
+  qa.sb[0] = skcs[0]; qa.sp[0] = skcs[1]; qa.sh[0] = skcs[2];
+  qa.sb[1] = svcs[0]; qa.sp[1] = svcs[1]; qa.sh[1] = svcs[2];
+  const dim3 grid = append_grid(qa.a);
+  hipLaunchKernelGGL(kv_append_q8_kernel, grid, dim3(kRowBlockThreads), 0, st, qa);
+  ljs_launch_rec(q ? "kv_append<rot,q,mx8>" : (cos_t ? "kv_append<rot,mx8>" : "kv_append<copy,mx8>"), grid,
+                 kRowBlockThreads);
+  return (int)hipGetLastError();
+}
+
+namespace {
+
+// the launch both decode entries share; ES: bytes per cache element; kcs / vcs: the scales (MX8 only)
+template <bool MX8>
+int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o, void* lse,
+                  void* ws, long ws_floats, const void* lens, int B, int H, int Hkv, int cap, const long* sq,
+                  const long* skc, const long* svc, const long* skcs, const long* svcs, const long* so, float scale,
+                  int extra, hipStream_t st) {
+  constexpr long ES = MX8 ? 1 : 2;
   if (B < 1 || H < 1 || Hkv < 1 || cap < 1 || H % Hkv != 0 || H / Hkv > kDecMaxG || !(scale > 0.f) || extra < 0 ||
       B > 65535 || Hkv > 65535 || (long)B * H > 0x7fffffffL || !lens || !lse || (((uintptr_t)lens) & 3u) || (((uintptr_t)lse) & 3u))
     return (int)hipErrorInvalidValue;
-  if (!dec_aligned(q, sq) || !dec_aligned(kc, skc) || !dec_aligned(vc, svc) || !dec_aligned(o, so))
+  if (!dec_aligned(q, sq) || !dec_aligned(o, so)) return (int)hipErrorInvalidValue;
+  if (MX8 ? (!q8_aligned(kc, skc) || !q8_aligned(vc, svc) || !q8_scale_aligned(kcs, skcs) || !q8_scale_aligned(vcs, svcs))
+          : (!dec_aligned(kc, skc) || !dec_aligned(vc, svc)))
     return (int)hipErrorInvalidValue;
   // a load's byte offset (of up to one unrolled block step past the cache) stays a positive int
   const long reach = (long)cap + kDecKeyTile * kDecUnroll;
-  if (skc[1] < kDecD || svc[1] < kDecD || reach * skc[1] * 2 >= 0x7fffffffL || reach * svc[1] * 2 >= 0x7fffffffL)
+  if (skc[1] < kDecD || svc[1] < kDecD || reach * skc[1] * ES >= 0x7fffffffL || reach * svc[1] * ES >= 0x7fffffffL)
+    return (int)hipErrorInvalidValue;
+  if (MX8 && (skcs[1] < 2 || svcs[1] < 2 || reach * skcs[1] >= 0x7fffffffL || reach * svcs[1] >= 0x7fffffffL))
     return (int)hipErrorInvalidValue;
   DecodeArgs a{};
   if (decode_launch_plan(B, Hkv, cap, &a.splits, &a.kps) != 0) return (int)hipErrorInvalidValue;
@@ -550,23 +767,29 @@ LJS_API int ljs_attn_decode(const void* q, const void* kc, const void* vc, void*
   a.ob = so[0]; a.oh = so[2];
   a.B = B; a.H = H; a.Hkv = Hkv; a.G = H / Hkv; a.cap = cap; a.extra = extra;
   a.scale_log2 = scale * 1.4426950408889634f;
+  if (MX8) {
+    a.ksc = (const unsigned char*)kcs;
+    a.vsc = (const unsigned char*)vcs;
+    a.ksb = skcs[0]; a.kss = skcs[1]; a.ksh = skcs[2];
+    a.vsb = svcs[0]; a.vss = svcs[1]; a.vsh = svcs[2];
+  }
   const dim3 grid((unsigned)a.splits, (unsigned)Hkv, (unsigned)B);
   const char* name;
   if (a.G == 1) {
-    hipLaunchKernelGGL(attn_decode_kernel<1>, grid, dim3(kDecThreads), 0, st, a);
-    name = "attn_decode<G1>";
+    hipLaunchKernelGGL((attn_decode_kernel<1, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? "attn_decode<G1,mx8>" : "attn_decode<G1>";
   } else if (a.G == 2) {
-    hipLaunchKernelGGL(attn_decode_kernel<2>, grid, dim3(kDecThreads), 0, st, a);
-    name = "attn_decode<G2>";
+    hipLaunchKernelGGL((attn_decode_kernel<2, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? "attn_decode<G2,mx8>" : "attn_decode<G2>";
   } else if (a.G <= 4) {
-    hipLaunchKernelGGL(attn_decode_kernel<4>, grid, dim3(kDecThreads), 0, st, a);
-    name = "attn_decode<G4>";
+    hipLaunchKernelGGL((attn_decode_kernel<4, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? "attn_decode<G4,mx8>" : "attn_decode<G4>";
   } else if (a.G <= 8) {
-    hipLaunchKernelGGL(attn_decode_kernel<8>, grid, dim3(kDecThreads), 0, st, a);
-    name = "attn_decode<G8>";
+    hipLaunchKernelGGL((attn_decode_kernel<8, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? "attn_decode<G8,mx8>" : "attn_decode<G8>";
   } else {
-    hipLaunchKernelGGL(attn_decode_kernel<8>, grid, dim3(kDecThreads), 0, st, a);
-    name = "attn_decode<G16>";
+    hipLaunchKernelGGL((attn_decode_kernel<8, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? "attn_decode<G16,mx8>" : "attn_decode<G16>";
   }
   ljs_launch_rec(name, grid, kDecThreads);
   int rc = (int)hipGetLastError();
@@ -575,6 +798,34 @@ LJS_API int ljs_attn_decode(const void* q, const void* kc, const void* vc, void*
   hipLaunchKernelGGL(decode_merge_kernel, mgrid, dim3(64), 0, st, a);
   ljs_launch_rec("decode_merge", mgrid, 64);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+// q (B, 1, H, 64), kc / vc (B, cap, Hkv, 64) -> o (B, 1, H, 64) bf16, lse (B, H) f32 over the keys [0,
+// min(lens[b] + extra, cap)) (the head of the file).  ws: f32 workspace of ws_floats floats, at least B H
+// splits kDecPart of them when the plan has more than one split.  s*: (batch, position, head) strides in
+// elements.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty shape, H %
+// Hkv != 0, H / Hkv > 16, scale <= 0, extra < 0, a misaligned base or stride, a key stride below 64, a
+// cache whose byte offsets do not fit 31 bits, an invalid forced plan or a workspace that is too small.
+LJS_API int ljs_attn_decode(const void* q, const void* kc, const void* vc, void* o, void* lse, void* ws, long ws_floats,
+                            const void* lens, int B, int H, int Hkv, int cap, const long* sq, const long* skc,
+                            const long* svc, const long* so, float scale, int extra, hipStream_t st) {
+  return decode_launch<false>(q, kc, vc, nullptr, nullptr, o, lse, ws, ws_floats, lens, B, H, Hkv, cap, sq, skc, svc,
+                              nullptr, nullptr, so, scale, extra, st);
+}
+
+// ljs_attn_decode over an MX-fp8 cache: kc / vc e4m3 bytes (B, cap, Hkv, 64), kcs / vcs their e8m0 scales
+// (B, cap, Hkv, 2), all four with (batch, position, head) strides in bytes; q, o, lse, ws, the plan and
+// the merge launch as there.  The same refusals, with the 31-bit offset check on 1-byte elements and
+// on the scales, plus: a null or odd scale base, an odd scale stride, a scale row stride below 2, a
+// cache base or stride that is not a multiple of 16 bytes.
+LJS_API int ljs_attn_decode_q8(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o,
+                               void* lse, void* ws, long ws_floats, const void* lens, int B, int H, int Hkv, int cap,
+                               const long* sq, const long* skc, const long* svc, const long* skcs, const long* svcs,
+                               const long* so, float scale, int extra, hipStream_t st) {
+  return decode_launch<true>(q, kc, vc, kcs, vcs, o, lse, ws, ws_floats, lens, B, H, Hkv, cap, sq, skc, svc, skcs, svcs,
+                             so, scale, extra, st);
 }
 
 // lens[0 .. B) += n: one small launch after the last layer of a decode step

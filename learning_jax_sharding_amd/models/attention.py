@@ -30,7 +30,9 @@ Decoding: ``cache=(k, v, lens)`` (a layer of :class:`~.cache.KVCache`) makes the
 decoder and returns ``(output, cache)``.  A call on more than one position is a prefill: positions 0 ..
 T-1, the usual rope and causal kernels, and K (rotated) and V written to rows 0 .. T-1 of the cache; a
 call on one position appends its K / V at row ``lens[b]`` and attends to the cache (``ops.core.
-cached_attention``).  ``lens`` is advanced by the caller, once for all layers.
+cached_attention``).  ``lens`` is advanced by the caller, once for all layers.  A layer of an MX-fp8 cache is
+``(k, v, lens, k_scale, v_scale)``: the prefill attends to its own unquantised K / V and stores them quantised, a
+decode step stores its row quantised and attends to the fp8 rows.
 """
 from __future__ import annotations
 
@@ -128,7 +130,8 @@ class MultiHeadAttention(Module):
                              "the earlier ones only)")
         if self.impl != "fused":
             raise ValueError('MultiHeadAttention: impl="einsum" has no cached path; use impl="fused"')
-        kc, vc, lens = cache
+        lens = cache[2]
+        layer = (cache[0], cache[1]) + tuple(cache[3:])      # (k, v), or (k, v, k_scale, v_scale): an MX-fp8 layer
         dt = _dt.canonicalize(self.dtype)
         with torch.no_grad():
             m = x.shape[-1]
@@ -145,12 +148,12 @@ class MultiHeadAttention(Module):
             k = core.reshape(with_logical_constraint(k, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
             v = core.reshape(with_logical_constraint(v, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
             if x.shape[1] == 1:
-                hidden = core.cached_attention(q, k, v, (kc, vc), lens, self.scale, self.rope_theta)
+                hidden = core.cached_attention(q, k, v, layer, lens, self.scale, self.rope_theta)
             else:
                 if self.rope_theta is not None:
                     q, k = core.rope(q, k, theta=self.rope_theta)
                 hidden = core.dot_product_attention(q, k, v, self.scale, causal=True)
-                core.cache_prefill(k, v, (kc, vc))
+                core.cache_prefill(k, v, layer)
             hidden = core.reshape(hidden, (b, -1, self.heads * self.dim_head))
             hidden = with_logical_constraint(hidden, ("batch", "kv", "heads"))
             hidden = self.proj_attn(hidden, residual=residual)

@@ -11,6 +11,14 @@ same buffers (donation semantics).
 Layout: like ``k`` after the head split with the length dim whole.  A cache sharded on its batch dim
 (data parallel) or on its ``kv_heads`` dim (tensor parallel, ``kv_heads % n == 0``) needs no collective;
 a length-sharded cache raises ``NotImplementedError``.
+
+``quant="mxfp8"`` (opt-in) makes the cache MX-fp8: ``k`` / ``v`` hold OCP e4m3 bytes (uint8, the same shape) and
+``k_scale`` / ``v_scale`` one e8m0 byte per 32 elements of a head row (uint8 ``(batch, max_len, kv_heads, dim_head /
+32)``), laid out and sharded like the buffers: 66 bytes per cached head row of 64 instead of 128.  An appended row
+is ``ops.fp8.quantize_mx_ref`` of the row the unquantised cache would hold, and a decode step attends to the
+dequantised rows (``ops.kernels.kv_append_q8_reference`` / ``attn_decode_q8_reference`` state both).  A prefill attends
+to the prompt's own unquantised K / V and then stores them quantised, so the first generated token has seen
+bf16 keys and the later ones see fp8 keys.
 """
 from __future__ import annotations
 
@@ -29,16 +37,35 @@ from ..utils import tree as _tree
 
 __all__ = ["KVCache", "generate"]
 
+QUANT_MXFP8 = "mxfp8"
+
 
 class KVCache:
-    """``k[i]``, ``v[i]``: layer i's buffers; ``lens``: the shared int32 ``(batch,)`` lengths."""
+    """``k[i]``, ``v[i]``: layer i's buffers; ``lens``: the shared int32 ``(batch,)`` lengths; ``k_scale[i]``, ``v_scale[i]``:
+    layer i's e8m0 scales in an MX-fp8 cache (empty lists without ``quant``)."""
 
-    def __init__(self, k: Sequence[ShardedArray], v: Sequence[ShardedArray], lens: ShardedArray):
+    def __init__(self, k: Sequence[ShardedArray], v: Sequence[ShardedArray], lens: ShardedArray,
+                 k_scale: Sequence[ShardedArray] = (), v_scale: Sequence[ShardedArray] = ()):
         self.k, self.v, self.lens = list(k), list(v), lens
+        self.k_scale, self.v_scale = list(k_scale), list(v_scale)
+        if len(self.k_scale) != len(self.v_scale) or len(self.k_scale) not in (0, len(self.k)):
+            raise ValueError(f"KVCache: {len(self.k_scale)} / {len(self.v_scale)} scale buffers for {len(self.k)} layers")
+
+    @property
+    def quant(self) -> Optional[str]:
+        return QUANT_MXFP8 if self.k_scale else None
 
     def layer(self, i: int):
-        """``(k, v, lens)`` of layer ``i``: what ``MultiHeadAttention(..., cache=)`` takes."""
+        """``(k, v, lens)`` of layer ``i``, or ``(k, v, lens, k_scale, v_scale)`` of a quantised cache: what
+        ``MultiHeadAttention(..., cache=)`` takes."""
+        if self.k_scale:
+            return self.k[i], self.v[i], self.lens, self.k_scale[i], self.v_scale[i]
         return self.k[i], self.v[i], self.lens
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the k / v buffers and their scales (all devices, without ``lens``)."""
+        return sum(int(np.prod(a.shape)) * a.dtype.itemsize for a in self.k + self.v + self.k_scale + self.v_scale)
 
     @property
     def max_len(self) -> int:
@@ -52,15 +79,23 @@ class KVCache:
         return len(self.k)
 
     def __repr__(self):
-        return f"KVCache(layers={len(self.k)}, shape={self.k[0].shape if self.k else None})"
+        q = f", quant={self.quant!r}" if self.k_scale else ""
+        return f"KVCache(layers={len(self.k)}, shape={self.k[0].shape if self.k else None}{q})"
 
     @staticmethod
     def zeros(layers: int, batch: int, max_len: int, kv_heads: int, dim_head: int, dtype=torch.bfloat16,
-              sharding: Optional[Sharding] = None) -> "KVCache":
-        """A zero-filled cache; ``sharding``: of the 4-D buffers (default: where unplaced arrays live)."""
+              sharding: Optional[Sharding] = None, quant: Optional[str] = None) -> "KVCache":
+        """A zero-filled cache; ``sharding``: of the 4-D buffers (default: where unplaced arrays live); ``quant``:
+        None, or ``"mxfp8"`` for uint8 e4m3 buffers with e8m0 scales (module docstring; ``dim_head % 32 == 0``,
+        ``dtype`` is then the model's, not the buffers')."""
         if min(layers, batch, max_len, kv_heads, dim_head) < 1:
             raise ValueError(f"KVCache: layers={layers}, batch={batch}, max_len={max_len}, kv_heads={kv_heads}, "
                              f"dim_head={dim_head} must all be positive")
+        if quant not in (None, QUANT_MXFP8):
+            raise ValueError(f"KVCache: quant must be None or {QUANT_MXFP8!r}, got {quant!r}")
+        if quant and dim_head % 32 != 0:
+            raise ValueError(f"KVCache: quant={quant!r} needs dim_head % 32 == 0 (one scale per 32 elements), got "
+                             f"{dim_head}")
         sharding = sharding or default_sharding()
         dtype = _dt.canonicalize(dtype)
         shape = (batch, max_len, kv_heads, dim_head)
@@ -79,11 +114,19 @@ class KVCache:
 
         lt = ta.project([0])
         lens = zeros((batch,), lt, torch.int32, sharding_from_tile(lt, like=[sharding]))
+        if quant:
+            ss = (batch, max_len, kv_heads, dim_head // 32)
+            ta.check_shape(ss)
+            u8 = lambda shp: [zeros(shp, ta, torch.uint8, sharding) for _ in range(layers)]   # noqa: E731
+            return KVCache(u8(shape), u8(shape), lens, u8(ss), u8(ss))
         return KVCache([zeros(shape, ta, dtype, sharding) for _ in range(layers)],
                        [zeros(shape, ta, dtype, sharding) for _ in range(layers)], lens)
 
 
-_tree.register_pytree_node(KVCache, lambda c: ((c.k, c.v, c.lens), None), lambda _, ch: KVCache(ch[0], ch[1], ch[2]))
+# the leaves of an unquantised cache are (k, v, lens) as ever; a quantised one adds its scales
+_tree.register_pytree_node(
+    KVCache, lambda c: ((c.k, c.v, c.lens, c.k_scale, c.v_scale) if c.k_scale else (c.k, c.v, c.lens), None),
+    lambda _, ch: KVCache(*ch))
 
 
 def _host_lens(prompt_lens, B: int, T: int) -> List[int]:
@@ -185,7 +228,8 @@ def _stop_lens(out: torch.Tensor, eos) -> torch.Tensor:
 def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=None, capture: Optional[bool] = None,
              max_len: Optional[int] = None, cache_sharding: Optional[Sharding] = None, *, key=None,
              temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id=None,
-             pad_id: Optional[int] = None, stop_poll: int = 16, return_lens: bool = False):
+             pad_id: Optional[int] = None, stop_poll: int = 16, return_lens: bool = False,
+             cache_quant: Optional[str] = None):
     """Decoding: ``max_new_tokens`` tokens after each prompt of ``ids`` (batch, T), as an int64 host tensor
     ``[batch, max_new_tokens]``; greedy without a ``key``.
 
@@ -205,13 +249,19 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
     is ``jit(step, donate_argnums=(token, cache), capture=capture)``: on the GPU with ``capture=True`` it is
     captured once and replayed.  The cache holds ``max_len`` rows (default: the model's ``max_len``, else
     ``max(prompt_lens) + max_new_tokens``) and is laid out by ``cache_sharding`` (default: the batch dim
-    sharded the way ``ids``' is); a request that does not fit raises ``ValueError`` before any launch."""
+    sharded the way ``ids``' is); a request that does not fit raises ``ValueError`` before any launch.
+
+    ``cache_quant="mxfp8"``: the cache is MX-fp8 (:class:`KVCache`): about half the bytes per cached row, the launch
+    count of a step unchanged.  The prefill attends to the prompt's unquantised K / V, so the first token is the
+    unquantised run's; the later ones attend to fp8 keys and values and may differ from it."""
     from ..spmd.api import jit
     from ..sharding.tile import TileAssignment
     if ids.ndim != 2:
         raise ValueError(f"generate: ids must be (batch, length), got shape {tuple(ids.shape)}")
     if max_new_tokens < 1:
         raise ValueError(f"generate: max_new_tokens must be positive, got {max_new_tokens}")
+    if cache_quant not in (None, QUANT_MXFP8):
+        raise ValueError(f"generate: cache_quant must be None or {QUANT_MXFP8!r}, got {cache_quant!r}")
     B, T = ids.shape
     plens = _host_lens(prompt_lens, B, T)
     need = max(plens) + max_new_tokens
@@ -225,7 +275,7 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
                                         (it.tile_shape[0], 1, 1, 1))
         cache_sharding = sharding_from_tile(ct, like=[ids.sharding])
     eos = _sampling_request(model.vocab_size, key, temperature, top_k, top_p, eos_id, pad_id, stop_poll)
-    cache = model.init_cache(B, cap, sharding=cache_sharding)
+    cache = model.init_cache(B, cap, sharding=cache_sharding, **({"quant": cache_quant} if cache_quant else {}))
     pl = device_put(np.asarray(plens, dtype=np.int32), cache.lens.sharding)
     if key is not None or eos:
         out = _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p,

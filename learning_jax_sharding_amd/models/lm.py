@@ -92,15 +92,17 @@ class TransformerLM(Module):
         self.head = Dense(self.vocab_size, use_bias=False, dtype=self.dtype, name="head",
                           kernel_init=with_logical_partitioning(init.lecun_normal(), ("embed", "vocab")))
 
-    def init_cache(self, batch: int, max_len: int, sharding=None):
+    def init_cache(self, batch: int, max_len: int, sharding=None, quant=None):
         """A zero-filled :class:`~.cache.KVCache` for ``batch`` sequences of up to ``max_len`` positions, in the
         model's compute dtype; ``sharding``: of its ``(batch, max_len, kv_heads, dim_head)`` buffers.  On GPU
-        devices the rope table grows to ``max_len`` rows here (never inside a graph capture)."""
+        devices the rope table grows to ``max_len`` rows here (never inside a graph capture).  ``quant="mxfp8"``:
+        an MX-fp8 cache (e4m3 bytes with e8m0 scales per 32 elements, ``dim_head % 32 == 0``): a prefill attends to
+        the prompt's unquantised K / V and stores them quantised; decode steps attend to the fp8 rows."""
         from .cache import KVCache
         if self.max_len is not None and max_len > self.max_len:
             raise ValueError(f"TransformerLM.init_cache: max_len {max_len} > the position table's {self.max_len} rows")
         kvh = self.heads if self.kv_heads is None else self.kv_heads
-        cache = KVCache.zeros(self.layers, batch, max_len, kvh, self.dim_head, self.dtype, sharding)
+        cache = KVCache.zeros(self.layers, batch, max_len, kvh, self.dim_head, self.dtype, sharding, quant=quant)
         if self.rope_theta is not None:
             from ..ops import kernels as K
             for t in cache.lens.local.values():

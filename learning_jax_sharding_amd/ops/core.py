@@ -1064,10 +1064,18 @@ def dense(x: ShardedArray, kernels: Sequence[ShardedArray], bias: Optional[Shard
 # split with the length dim whole, plus one int32 (batch,) array of lengths that lives on the devices
 # (replicated over head shards): batch sharding and head sharding need no collective.  The buffers
 # are updated IN PLACE (donation semantics); nothing here takes a gradient.
+#
+# An MX-fp8 layer is ``(kc, vc, kcs, vcs)``: uint8 e4m3 bytes of the same shape and uint8 e8m0 scales (batch,
+# max_len, kv_heads, head_dim / 32) laid out and sharded like the cache (:func:`.kernels.kv_append_q8_reference`
+# states the format), so batch and kv_heads sharding still need no collective.
+def _quantised(cache_layer) -> bool:
+    return len(cache_layer) == 4
+
+
 def _cache_layout(k: ShardedArray, v: ShardedArray, cache_layer, lens: Optional[ShardedArray],
                   q: Optional[ShardedArray] = None):
     """(q, k, v) on the cache's tile, after the checks every cached call shares."""
-    kc, vc = cache_layer
+    kc, vc = cache_layer[:2]
     ct = kc.tile
     if ct.tile_shape[1] > 1:
         raise NotImplementedError("KV cache: a length-sharded cache is not implemented (ring decode); shard the "
@@ -1079,6 +1087,12 @@ def _cache_layout(k: ShardedArray, v: ShardedArray, cache_layer, lens: Optional[
     if tuple(k.shape) != tuple(v.shape) or k.shape[0] != kc.shape[0] or tuple(k.shape[2:]) != tuple(kc.shape[2:]):
         raise ValueError(f"KV cache: new k / v {tuple(k.shape)} / {tuple(v.shape)} do not fit a cache of shape "
                          f"{tuple(kc.shape)} (batch, max_len, kv_heads, head_dim)")
+    if _quantised(cache_layer):
+        want = tuple(kc.shape[:3]) + (kc.shape[3] // 32,)
+        if kc.dtype != torch.uint8 or kc.shape[3] % 32 != 0 or any(
+                s.dtype != torch.uint8 or tuple(s.shape) != want or s.tile != ct for s in cache_layer[2:]):
+            raise ValueError(f"KV cache: an MX-fp8 layer is uint8 k / v {tuple(kc.shape)} and uint8 scales {want} laid "
+                             "out like them")
     if lens is not None:
         if lens.dtype != torch.int32 or tuple(lens.shape) != (kc.shape[0],) or lens.tile != ct.project([0]):
             raise ValueError("KV cache: lens must be an int32 (batch,) array laid out like the cache's batch dim")
@@ -1099,35 +1113,45 @@ def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_la
     are appended to ``cache_layer = (kc, vc)`` at row ``lens[b]`` (k, and q with it, rotated at that
     position when ``rope_theta`` is given), and ``q`` (batch, 1, heads, head_dim) attends to rows ``[0,
     lens[b] + 1)``: two launches per device shard (:func:`.kernels.kv_append`, :func:`.kernels.attn_decode`).
-    ``lens`` itself is not changed (the caller advances it once after the last layer)."""
+    ``lens`` itself is not changed (the caller advances it once after the last layer).  An MX-fp8 layer ``(kc, vc,
+    kcs, vcs)`` stores the new row quantised and attends to the dequantised rows, the new one included
+    (:func:`.kernels.kv_append_q8`, :func:`.kernels.attn_decode_q8`): the same two launches."""
     if q.shape[1] != 1 or k.shape[1] != 1:
         raise ValueError(f"cached_attention: one new position per call, got {q.shape[1]} (a longer call is a "
                          "prefill: attention over the new tokens and cache_prefill)")
     if scale is None:
         scale = q.shape[-1] ** -0.5
     q, k, v = _cache_layout(k, v, cache_layer, lens, q)
-    kc, vc = cache_layer
+    kc, vc = cache_layer[:2]
     _plan.record("cached_attention", tiles=kc.tile.tile_shape, kv_heads=k.shape[2])
     loc = {}
     for d, qt in q.local.items():
         ln = lens.local[d]
+        if _quantised(cache_layer):
+            bufs = [c.local[d] for c in cache_layer]
+            qr = K.kv_append_q8(k.local[d], v.local[d], *bufs, ln, q=qt if rope_theta is not None else None,
+                                theta=rope_theta)
+            loc[d] = K.attn_decode_q8(qt if qr is None else qr, *bufs, ln, float(scale), extra=1)[0]
+            continue
         qr = K.kv_append(k.local[d], v.local[d], kc.local[d], vc.local[d], ln,
                          q=qt if rope_theta is not None else None, theta=rope_theta)
         loc[d] = K.attn_decode(qt if qr is None else qr, kc.local[d], vc.local[d], ln, float(scale), extra=1)[0]
-    return ShardedArray(q.shape, vc.dtype, q.sharding, loc)
+    return ShardedArray(q.shape, q.dtype if _quantised(cache_layer) else vc.dtype, q.sharding, loc)
 
 
 def cache_prefill(k: ShardedArray, v: ShardedArray, cache_layer) -> None:
     """Rows ``0 .. T-1`` of ``cache_layer`` := ``k`` / ``v`` (batch, T, kv_heads, head_dim) as they are (k already
-    rotated): one :func:`.kernels.kv_append` launch per device shard in its host-base mode."""
-    kc, _ = cache_layer
+    rotated): one :func:`.kernels.kv_append` launch per device shard in its host-base mode.  An MX-fp8 layer
+    stores the rows quantised (:func:`.kernels.kv_append_q8`): the prefill itself attended to the unquantised k /
+    v, so the first generated token has seen bf16 keys and the later ones see fp8 keys."""
+    kc = cache_layer[0]
     if k.shape[1] > kc.shape[1]:
         raise ValueError(f"KV cache: a prompt of {k.shape[1]} positions does not fit max_len {kc.shape[1]}")
     _, k, v = _cache_layout(k, v, cache_layer, None)
-    kc, vc = cache_layer
     _plan.record("cache_prefill", tiles=kc.tile.tile_shape)
+    append = K.kv_append_q8 if _quantised(cache_layer) else K.kv_append
     for d, kt in k.local.items():
-        K.kv_append(kt, v.local[d], kc.local[d], vc.local[d])
+        append(kt, v.local[d], *[c.local[d] for c in cache_layer])
 
 
 def cache_set_lens(lens: ShardedArray, value) -> None:

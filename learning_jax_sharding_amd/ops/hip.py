@@ -19,7 +19,8 @@ import torch
 
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
-           "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "plan_decode", "lens_add", "skinny",
+           "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "kv_append_q8", "attn_decode_q8", "plan_decode",
+           "lens_add", "skinny",
            "skinny_plan", "skinny_supported", "set_skinny_waves"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,6 +75,11 @@ _SIGS = {
                       _LP, _LP, _LP, _LP, _LP, _LP, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "ljs_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int,
                         c_int, c_int, _LP, _LP, _LP, _LP, c_float, c_int, c_void_p],
+    "ljs_kv_append_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                         c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP, _LP, c_void_p, c_void_p, c_void_p, c_long,
+                         c_void_p],
+    "ljs_attn_decode_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                           c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_int, c_void_p],
     "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_launch_plan": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_set_splits": [c_int, c_int],
@@ -209,7 +215,7 @@ def last_launch() -> dict:
     ``gemm_mx_fp8<128,2,fix=1>``, ``gemm_mx8<256,160,4,bf16,2>``, ``quant_mx_rows``, ``quant_mx_cols<tiled>`` /
     ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
     ``grad_sumsq``, ``step_hyper``, ``adam_multi_dyn<32>``, ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
-    ``attn_decode<G4>``, ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
+    ``attn_decode<G4>``, ``kv_append<rot,q,mx8>``, ``attn_decode<G4,mx8>`` (an MX-fp8 cache), ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
     the epilogue parts present)),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
@@ -2666,6 +2672,96 @@ def attn_decode(q, kc, vc, lens, scale: float, extra: int = 1):
     o = torch.empty((B, 1, H, 64), dtype=torch.bfloat16, device=q.device)
     lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device)
     _ck(attn_decode_raw(q, kc, vc, o, lse, ws, lens, scale, extra), "ljs_attn_decode")
+    return o, lse
+
+
+# ---- the MX-fp8 cache: e4m3 bytes (B, cap, Hkv, 64) and e8m0 scale bytes (B, cap, Hkv, 2), both uint8
+def decode_q8_supported(*ts: torch.Tensor) -> bool:
+    """Whether decode.hip takes these MX-fp8 cache buffers as they are: uint8 ``(B, S, H, 64)`` GPU tensors (e4m3
+    bytes), the head dim contiguous, the base and the three outer strides multiples of 16 bytes."""
+    return all(t.is_cuda and t.dim() == 4 and t.dtype == torch.uint8 and t.shape[-1] == 64 and t.numel()
+               and t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(t.stride(i) % 16 == 0 for i in range(3))
+               for t in ts)
+
+
+def decode_scale_supported(*ts: torch.Tensor) -> bool:
+    """Whether decode.hip takes these e8m0 scale buffers as they are: uint8 ``(B, S, H, 2)`` GPU tensors, the
+    last dim contiguous, the base and the three outer strides even (one 2-byte store writes a row's two)."""
+    return all(t.is_cuda and t.dim() == 4 and t.dtype == torch.uint8 and t.shape[-1] == 2 and t.numel()
+               and t.stride(-1) == 1 and t.data_ptr() % 2 == 0 and all(t.stride(i) % 2 == 0 for i in range(3))
+               for t in ts)
+
+
+def _q8_cache_ok(kc, vc, kcs, vcs) -> bool:
+    return decode_q8_supported(kc, vc) and decode_scale_supported(kcs, vcs) and kc.shape == vc.shape \
+        and kcs.shape == vcs.shape == kc.shape[:3] + (2,)
+
+
+def kv_append_q8_raw(k, v, kc, vc, kcs, vcs, lens=None, q=None, q_out=None, cos=None, sin=None) -> int:
+    """One ``ljs_kv_append_q8`` launch on the tensors as they are; returns the launcher's code (non-zero:
+    rejected, nothing launched) instead of raising."""
+    B, T, Hkv, _ = k.shape
+    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
+    return lib().ljs_kv_append_q8(_p(k), _p(v), _p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(q_out), B, T,
+                                  q.shape[2] if q is not None else 0, Hkv, kc.shape[1], st(k), st(v), st(q), st(kc),
+                                  st(vc), st(kcs), st(vcs), st(q_out), _p(lens), _p(cos), _p(sin),
+                                  cos.shape[0] if cos is not None else 0, _stream(k))
+
+
+def kv_append_q8(k, v, kc, vc, kcs, vcs, lens=None, q=None, theta: Optional[float] = None):
+    """:func:`kv_append` into an MX-fp8 cache: the row :func:`kv_append` would store at ``p`` (k rotated with
+    ``theta``: rope.hip's bits; v as it is) goes through ``fp8.quantize_mx_ref``'s rule into 64 e4m3 bytes of ``kc``
+    / ``vc`` and two e8m0 bytes of ``kcs`` / ``vcs`` (uint8 ``(B, cap, Hkv, 64)`` and ``(B, cap, Hkv, 2)``); rows with
+    ``p >= cap`` write neither.  Returns the rotated ``q`` in bf16, as :func:`kv_append` does.  One launch."""
+    B = k.shape[0]
+    ok = decode_supported(k, v) and (q is None or decode_supported(q)) and _lens_ok(lens, B) \
+        and _q8_cache_ok(kc, vc, kcs, vcs) and k.shape == v.shape and kc.shape[0] == B \
+        and kc.shape[2] == k.shape[2] and (q is None or (theta is not None and q.shape[:2] == k.shape[:2]))
+    if not ok:
+        raise NotImplementedError(f"kv_append_q8 kernel: bf16 (B, T, H, 64) k / v / q, uint8 (B, cap, Hkv, 64) caches "
+                                  f"with 16-byte aligned bases and strides, uint8 (B, cap, Hkv, 2) scales with even "
+                                  f"strides and an int32 [B] lens; got k {k.dtype} {tuple(k.shape)} strides {k.stride()}, "
+                                  f"cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}, scales {kcs.dtype} "
+                                  f"{tuple(kcs.shape)} strides {kcs.stride()}")
+    cos = sin = q_out = None
+    if theta is not None:
+        from .kernels import rope_table
+        cos, sin = rope_table(k.device, 64, theta, kc.shape[1])
+    if q is not None:
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    _ck(kv_append_q8_raw(k, v, kc, vc, kcs, vcs, lens, q, q_out, cos, sin), "ljs_kv_append_q8")
+    return q_out
+
+
+def attn_decode_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale: float, extra: int = 1) -> int:
+    """One ``ljs_attn_decode_q8`` call (the decode launch, and the merge launch when the plan has more than
+    one split) on the tensors as they are; returns the launcher's code instead of raising."""
+    B, _, H, _ = q.shape
+    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
+    return lib().ljs_attn_decode_q8(_p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(o), _p(lse), _p(ws),
+                                    ws.numel() if ws is not None else 0, _p(lens), B, H, kc.shape[2], kc.shape[1],
+                                    st(q), st(kc), st(vc), st(kcs), st(vcs), st(o), float(scale), int(extra), _stream(q))
+
+
+def attn_decode_q8(q, kc, vc, kcs, vcs, lens, scale: float, extra: int = 1):
+    """:func:`attn_decode` over an MX-fp8 cache (e4m3 bytes ``kc`` / ``vc``, e8m0 scale bytes ``kcs`` / ``vcs``): the
+    attention of bf16 ``q`` over the dequantised rows ``[0, min(lens[b] + extra, cap))``, which are exact bf16
+    values; the same plan, workspace and merge launch.  ``(o`` bf16, ``lse2`` f32``)``."""
+    B, T, H, _ = q.shape
+    Hkv = kc.shape[2]
+    ok = decode_supported(q) and _q8_cache_ok(kc, vc, kcs, vcs) and T == 1 and kc.shape[0] == B and lens is not None \
+        and _lens_ok(lens, B) and H % Hkv == 0 and H // Hkv <= decode_max_group() and scale > 0
+    if not ok:
+        raise NotImplementedError(f"attn_decode_q8 kernel: bf16 q (B, 1, H, 64), uint8 caches (B, cap, Hkv, 64) with "
+                                  f"16-byte aligned bases and strides and uint8 scales (B, cap, Hkv, 2) with even strides, "
+                                  f"H / Hkv <= {decode_max_group()}, int32 [B] lens; got q {q.dtype} {tuple(q.shape)}, "
+                                  f"cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}, scales {kcs.dtype} "
+                                  f"{tuple(kcs.shape)} strides {kcs.stride()}")
+    splits, _ = _decode_launch_plan(B, Hkv, kc.shape[1])
+    ws = _decode_ws(q.device, B * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
+    o = torch.empty((B, 1, H, 64), dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device)
+    _ck(attn_decode_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale, extra), "ljs_attn_decode_q8")
     return o, lse
 
 

@@ -657,14 +657,11 @@ def fused_decode_enabled() -> bool:
     return os.environ.get("LJS_FUSED_DECODE", "1") != "0"
 
 
-def kv_append_reference(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
-    """Plain torch cache append, in place: ``vc[b, p] = v[b, t]``, ``kc[b, p] = k'[b, t]`` for ``p = base[b] + t``
-    with ``base = lens`` (int [B]) or 0 without it, rows with ``p >= cap`` dropped.  With ``theta``, ``k'`` is k
-    rotated at position ``p`` exactly as :func:`rope_reference` does (same table, same f32 arithmetic),
-    and a ``q`` is rotated the same way into the returned tensor (zeros where ``p >= cap``); without,
-    ``k' = k``.  No host read of ``lens``."""
+def _append_rows(k, cap: int, lens, q, theta):
+    """What both cache appends share: ``(k', q_out, rows, inside)`` -- k rotated at ``p = base[b] + t`` (as it is
+    without ``theta``), the rotated q (zeros where ``p`` is outside, None without a q), the clamped rows ``p`` and
+    whether ``p`` lies in ``[0, cap)``, both (B, T)."""
     B, T, _, D = k.shape
-    cap = kc.shape[1]
     t_idx = torch.arange(T, device=k.device)
     base = lens.long() if lens is not None else torch.zeros(B, dtype=torch.long, device=k.device)
     p = base[:, None] + t_idx[None, :]                        # (B, T)
@@ -680,12 +677,27 @@ def kv_append_reference(k, v, kc, vc, lens=None, q=None, theta: Optional[float] 
             q_out = torch.where(inside[:, :, None, None], q_out, torch.zeros_like(q_out))
     elif q is not None:
         raise ValueError("kv_append: a q is rotated only with a theta")
-    ar = torch.arange(B, device=k.device)
+    return k, q_out, rows, inside
+
+
+def _scatter_rows(pairs, rows, inside):
+    """``dst[b, rows[b, t]] = src[b, t]`` where ``inside[b, t]``, for every ``(src, dst)`` of ``pairs``."""
+    ar = torch.arange(rows.shape[0], device=rows.device)
     keep = inside[:, :, None, None]
-    for t in range(T):                                        # one row per sequence at a time: no duplicates
+    for t in range(rows.shape[1]):                            # one row per sequence at a time: no duplicates
         r = rows[:, t]
-        kc[ar, r] = torch.where(keep[:, t], k[:, t].to(kc.dtype), kc[ar, r])
-        vc[ar, r] = torch.where(keep[:, t], v[:, t].to(vc.dtype), vc[ar, r])
+        for src, dst in pairs:
+            dst[ar, r] = torch.where(keep[:, t], src[:, t].to(dst.dtype), dst[ar, r])
+
+
+def kv_append_reference(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
+    """Plain torch cache append, in place: ``vc[b, p] = v[b, t]``, ``kc[b, p] = k'[b, t]`` for ``p = base[b] + t``
+    with ``base = lens`` (int [B]) or 0 without it, rows with ``p >= cap`` dropped.  With ``theta``, ``k'`` is k
+    rotated at position ``p`` exactly as :func:`rope_reference` does (same table, same f32 arithmetic),
+    and a ``q`` is rotated the same way into the returned tensor (zeros where ``p >= cap``); without,
+    ``k' = k``.  No host read of ``lens``."""
+    k, q_out, rows, inside = _append_rows(k, kc.shape[1], lens, q, theta)
+    _scatter_rows([(k, kc), (v, vc)], rows, inside)
     return q_out
 
 
@@ -758,6 +770,88 @@ def attn_decode(q, kc, vc, lens, scale: float, extra: int = 1):
     if _hip_decode("attn_decode", [q, kc, vc], lens, G):
         return _hip().attn_decode(q, kc, vc, lens, scale, extra)
     return attn_decode_reference(q, kc, vc, lens, scale, extra)
+
+
+# ---- the MX-fp8 cache.  A quantised layer holds e4m3 bytes ``kc`` / ``vc`` (uint8 (B, cap, Hkv, D)) and e8m0
+# scale bytes ``kcs`` / ``vcs`` (uint8 (B, cap, Hkv, D / 32), exponent + 127: what ``ljs_quant_mx_rows`` writes), one
+# scale per 32 elements of a head row.  The two functions below state the semantics once.
+def _mx_bytes(x: torch.Tensor):
+    """``fp8.quantize_mx_ref`` of rows ``x[..., D]`` as stored: (e4m3 bytes, e8m0 bytes), both uint8."""
+    from .fp8 import quantize_mx_ref
+    qv, ex = quantize_mx_ref(x)
+    return qv.view(torch.uint8), (ex + 127).to(torch.uint8)
+
+
+def mx_cache_dequant(c: torch.Tensor, cs: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """``fp8.dequantize_mx_ref`` of a stored cache buffer, in ``dtype`` (exact in bf16 for blocks of normal
+    magnitude: 4 significant bits times a power of two)."""
+    from .fp8 import dequantize_mx_ref
+    return dequantize_mx_ref(c.view(torch.float8_e4m3fn), cs.to(torch.int32) - 127).to(dtype)
+
+
+def kv_append_q8_reference(k, v, kc, vc, kcs, vcs, lens=None, q=None, theta: Optional[float] = None):
+    """Plain torch append into an MX-fp8 cache, in place: for every appended row, the bytes and scale bytes
+    stored at ``p`` are ``fp8.quantize_mx_ref`` of the row :func:`kv_append_reference` would have stored there (k
+    rotated at ``p`` and rounded to its dtype first, v as it is); rows with ``p`` outside ``[0, cap)`` write
+    neither bytes nor scales.  Returns the rotated ``q`` exactly as :func:`kv_append_reference` does."""
+    k, q_out, rows, inside = _append_rows(k, kc.shape[1], lens, q, theta)
+    kq, ke = _mx_bytes(k)
+    vq, ve = _mx_bytes(v)
+    _scatter_rows([(kq, kc), (ke, kcs), (vq, vc), (ve, vcs)], rows, inside)
+    return q_out
+
+
+def attn_decode_q8_reference(q, kc, vc, kcs, vcs, lens, scale: float, extra: int = 1):
+    """Plain torch single-query attention over an MX-fp8 cache: :func:`attn_decode_reference` on the dequantised
+    cache in q's dtype.  Dead rows (at and beyond ``n_b``) are selected away BEFORE the dequantisation, so
+    whatever their bytes and scale bytes hold (0x7F / 0xFF: the e4m3 and e8m0 NaNs) has no influence."""
+    cap = kc.shape[1]
+    n = (lens.long() + int(extra)).clamp(0, cap)
+    sel = (torch.arange(cap, device=q.device)[None, :] < n[:, None])[:, :, None, None]
+    z = lambda t: torch.where(sel, t, torch.zeros_like(t))   # noqa: E731
+    return attn_decode_reference(q, mx_cache_dequant(z(kc), z(kcs), q.dtype), mx_cache_dequant(z(vc), z(vcs), q.dtype),
+                                 lens, scale, extra)
+
+
+def _hip_decode_q8(what: str, ts, cache, lens, G: int = 1) -> bool:
+    """:func:`_hip_decode` for an MX-fp8 cache ``(kc, vc, kcs, vcs)``: bf16 ``(B, S, H, 64)`` ``ts`` next to uint8
+    buffers decode.hip takes.  The same rule: anything else on a GPU runs the torch formulation there with a
+    one-time warning per reason; host devices and ``LJS_FUSED_DECODE=0`` run it silently."""
+    if not use_hip(ts[0]) or not fused_decode_enabled():
+        return False
+    hip = _hip()
+    kc, vc, kcs, vcs = cache
+    ok = hip.decode_supported(*ts) and hip.decode_q8_supported(kc, vc) and hip.decode_scale_supported(kcs, vcs) \
+        and (lens is None or lens.dtype == torch.int32) and G <= hip.decode_max_group()
+    if not ok:
+        key = (what, ts[0].dtype, ts[0].shape[-1], G > hip.decode_max_group())
+        if key not in _WARNED_DECODE:
+            _WARNED_DECODE.add(key)
+            import warnings
+            warnings.warn(f"HIP {what} kernel takes bf16 (B, S, H, 64) shards and uint8 (B, cap, Hkv, 64) / (B, cap, Hkv, 2) "
+                          f"cache buffers with 16-byte aligned bases and strides (even ones for the scales), an int32 lens "
+                          f"and heads / kv_heads <= {hip.decode_max_group()}; {ts[0].dtype} {tuple(ts[0].shape)} strides "
+                          f"{ts[0].stride()}, cache strides {kc.stride()} / {kcs.stride()} with heads / kv_heads = {G} "
+                          "runs the torch formulation on the GPU")
+    return ok
+
+
+def kv_append_q8(k, v, kc, vc, kcs, vcs, lens=None, q=None, theta: Optional[float] = None):
+    """Append one device's new ``k`` / ``v`` to its MX-fp8 caches in place (:func:`kv_append_q8_reference`'s
+    semantics); returns the rotated ``q`` (or None).  One HIP launch on a GPU."""
+    ts = [k, v] + ([q] if q is not None else [])
+    if _hip_decode_q8("kv_append_q8", ts, (kc, vc, kcs, vcs), lens):
+        return _hip().kv_append_q8(k, v, kc, vc, kcs, vcs, lens, q, theta)
+    return kv_append_q8_reference(k, v, kc, vc, kcs, vcs, lens, q, theta)
+
+
+def attn_decode_q8(q, kc, vc, kcs, vcs, lens, scale: float, extra: int = 1):
+    """Single-query attention of one device's ``q`` over its MX-fp8 caches: ``(o, lse2)``
+    (:func:`attn_decode_q8_reference`'s semantics).  The launches of :func:`attn_decode`, in their ``mx8`` instances."""
+    G = kv_groups(q, kc, vc)
+    if _hip_decode_q8("attn_decode_q8", [q], (kc, vc, kcs, vcs), lens, G):
+        return _hip().attn_decode_q8(q, kc, vc, kcs, vcs, lens, scale, extra)
+    return attn_decode_q8_reference(q, kc, vc, kcs, vcs, lens, scale, extra)
 
 
 def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:
