@@ -1368,6 +1368,7 @@ LJS_API int ljs_adam_f32(const void* p, const void* g, int g_bf16, const void* m
                          void* vo, const void* step, long n, float lr, float b1, float b2, float eps, float wd,
                          hipStream_t s) {
   int grid = grid_for(n, 256 * 4);
+  ljs_launch_rec("adam_f32", dim3(grid), 256);
   if (g_bf16)
     hipLaunchKernelGGL(adam_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const float*)p, (const bf16_t*)g,
                        (const float*)m, (const float*)v, (float*)po, (float*)mo, (float*)vo, (const int*)step, n, lr,
@@ -1514,6 +1515,8 @@ static int adam_multi_launch(const long* table, int n, void* step, int step_offs
                          hyper, b1, b2, eps, wd, cast);
     return (int)hipGetLastError();
   }
+  ljs_launch_rec(kAdamRows == 16 ? "adam_multi<16>" : kAdamRows == 32 ? "adam_multi<32>" : "adam_multi<64>", dim3(grid),
+                 256);
   if (kAdamRows == 16)
     hipLaunchKernelGGL((adam_multi_kernel<16, 256>), dim3(grid), dim3(256), 0, s, b, (int*)step, step_offset,
                        lr, b1, b2, eps, wd, cast);

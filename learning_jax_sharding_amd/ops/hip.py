@@ -214,7 +214,7 @@ def last_launch() -> dict:
     ``gemm_bf16<64,64,kc,mn,f32>``, ``attn_fwd_res<8>``, ``attn_bwd_fused<dma=1,sw=1>``, ``qkv_attn_fwd``, ``rope<bf16,bf16>`` / ``rope<bf16,bf16,inv>``,
     ``gemm_mx_fp8<128,2,fix=1>``, ``gemm_mx8<256,160,4,bf16,2>``, ``quant_mx_rows``, ``quant_mx_cols<tiled>`` /
     ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
-    ``grad_sumsq``, ``step_hyper``, ``adam_multi_dyn<32>``, ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
+    ``grad_sumsq``, ``step_hyper``, ``adam_f32``, ``adam_multi<32>`` / ``adam_multi_dyn<32>`` (the launch's tile height), ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
     ``attn_decode<G4>``, ``kv_append<rot,q,mx8>``, ``attn_decode<G4,mx8>`` (an MX-fp8 cache), ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
     the epilogue parts present)),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs

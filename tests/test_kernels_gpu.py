@@ -357,6 +357,17 @@ def test_elementwise(hip):
     torch.testing.assert_close(hip.cast_transpose_bf16(w), w.t().bfloat16(), rtol=0, atol=0)
 
 
+def _assert_moments(opt, refs, ms, vs):
+    """m and v against torch.optim.Adam's exp_avg / exp_avg_sq.  The reference forms 1 - beta in
+    float64 from the Python float; the kernel's arguments are f32, so its 1 - b is 1 - f32(beta):
+    a relative difference of up to 2^-24 beta / (1 - beta) in the gradient's weight, 5.4e-7 for
+    beta1 = 0.9 (inside the parameters' rtol = 1e-5) and 6e-5 for beta2 = 0.999 (rtol = 1e-4)."""
+    for r, m, v in zip(refs, ms, vs):
+        st = opt.state[r]
+        torch.testing.assert_close(m, st["exp_avg"], rtol=1e-5, atol=1e-6)
+        torch.testing.assert_close(v, st["exp_avg_sq"], rtol=1e-4, atol=1e-6)
+
+
 def test_adam_kernel(hip):
     p = torch.randn(4099, device=dev)
     g = torch.randn(4099, device=dev)
@@ -371,6 +382,7 @@ def test_adam_kernel(hip):
         tp.grad = g.clone()
         opt.step()
     torch.testing.assert_close(p, tp.detach(), rtol=1e-5, atol=1e-6)
+    _assert_moments(opt, [tp], [m], [v])
 
 
 def test_rng_matches_host(hip):
@@ -428,6 +440,7 @@ def test_adam_multi_and_shadows(hip):
         opt.step()
     for w, r in zip(ws, refs):
         torch.testing.assert_close(w, r.detach(), rtol=1e-5, atol=1e-6)
+    _assert_moments(opt, refs, ms, vs)
     # shadows were refreshed by the kernel (no re-cast needed) and equal the new weights
     e0 = shadow.entry(ws[0], create=False)
     assert e0.versions["T"] == ws[0]._version
@@ -549,6 +562,7 @@ def test_adam_multi_vector_and_edges(hip, R, C, g_bf16):
         ref.grad = g.float().clone()
         opt.step()
     torch.testing.assert_close(w, ref.detach(), rtol=1e-5, atol=1e-6)
+    _assert_moments(opt, [ref], [m], [v])
     e = shadow.entry(w, create=False)
     torch.testing.assert_close(e.bufs["T"], w.t().bfloat16())
     torch.testing.assert_close(e.bufs["N"], w.bfloat16())
@@ -768,6 +782,7 @@ def test_adam_multi_folded_step_increment(hip):
         opt.step()
     for w, r in zip(ws, refs):
         torch.testing.assert_close(w, r.detach(), rtol=1e-5, atol=1e-6)
+    _assert_moments(opt, refs, ms, vs)
 
 
 # ----------------------------------------------------------------------------- MX-fp8

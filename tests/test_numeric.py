@@ -162,6 +162,9 @@ def test_adam_matches_torch(host_devices):
         tp.grad = torch.tensor(g)
         topt.step()
     np.testing.assert_allclose(np.asarray(st.params["w"]), tp.detach().numpy(), rtol=1e-5, atol=1e-6)
+    adam_state = st.opt_state[0]
+    np.testing.assert_allclose(np.asarray(adam_state.mu["w"]), topt.state[tp]["exp_avg"].numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(np.asarray(adam_state.nu["w"]), topt.state[tp]["exp_avg_sq"].numpy(), rtol=1e-5, atol=1e-6)
     assert int(np.asarray(st.step)) == 3
 
 
