@@ -51,6 +51,14 @@
 // a serial merge tail in whichever block arrives last; with a kernel boundary in between, plain
 // stores are enough.)
 //
+// attn_extend (ljs_attn_extend, ljs_attn_extend_q8).  q is (B, T, H, 64), 1 <= T <= 64 positions per sequence that
+// a kv_append has just written at rows lens[b] .. lens[b] + T - 1 and lens does not count yet: row (b, t, h)
+// attends to the rows [0, clamp(lens[b] + t + 1, 0, cap)) and gets the bits attn_decode writes for (b, h) with
+// extra = t + 1 under the same plan (the same kernel, its EXT instances: a wave's heads become rows (t, g)
+// with a key limit each; the comment at the kernel).  A block carries all G heads of 8 / G positions (one
+// for G > 4), the row tiles sit beside the splits in grid.x, the partials and decode_merge are reused with
+// B T H outputs, and T == 1 launches attn_decode's own instances.
+//
 // MX-fp8 caches (the mx8 instances; ljs_kv_append_q8, ljs_attn_decode_q8).  kc / vc hold OCP e4m3 bytes (B,
 // cap, Hkv, 64) and two more buffers one e8m0 byte per 32 elements (B, cap, Hkv, 2), in the encoding
 // ljs_quant_mx_rows writes (exponent + 127); strides of all four count bytes.  The append stores
@@ -73,6 +81,7 @@ constexpr int kDecUnroll = 4;             // steps whose loads are in flight tog
                                           // one head per wave: 119.7 against 112.6 us at B = 64, 4096 keys)
 constexpr int kDecWaveHeads = 8;          // query heads one wave carries
 constexpr int kDecMaxG = 2 * kDecWaveHeads;
+constexpr int kExtMaxT = 64;              // query positions per sequence one attn_extend call takes
 constexpr int kDecPart = 72;              // floats of one partial: acc[64], m, l, padded to 16 bytes
 constexpr int kDecBlocksPerCu = 4;        // the plan's target: blocks per compute unit
 constexpr int kDecMinTiles = 8;           // a split sweeps at least 8 key tiles (256 keys), 4 on an unfilled chip
@@ -126,21 +135,24 @@ struct DecodeArgs {
   long kb, ks, kh, vb, vs, vh, ob, oh;
   int B, H, Hkv, G, cap, extra, splits, kps;
   float scale_log2;
+  // attn_extend only (T = 1, P = 1 otherwise): the position strides of q and o, the query positions per
+  // sequence and the positions one block carries
+  long qt, ot;
+  int T, P;
   // MX-fp8 caches only (kc / vc are then e4m3 bytes and their strides count bytes): the e8m0 scales
   // (B, cap, Hkv, 2) and their (batch, position, head) strides in bytes
   const unsigned char *ksc, *vsc;
   long ksb, kss, ksh, vsb, vss, vsh;
 };
 
-// final output of one (b, h, chunk) from a merged state
-__device__ __forceinline__ void dec_store_out(const DecodeArgs& a, int b, int h, int cc, float m, float l,
-                                              const float (&acc)[8]) {
+// final output of one (b, t, h, chunk) from a merged state: o is the row's first element, lse its entry
+__device__ __forceinline__ void dec_store_out(bf16_t* o, float* lse, int cc, float m, float l, const float (&acc)[8]) {
   const float inv = l > 0.f ? 1.f / l : 0.f;
   float y[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) y[e] = acc[e] * inv;
-  store_chunk(a.o + (long)b * a.ob + (long)h * a.oh + cc * 8, y);
-  if (cc == 0) a.lse[(long)b * a.H + h] = l > 0.f ? m + __log2f(l) : INFINITY;
+  store_chunk(o + cc * 8, y);
+  if (cc == 0) *lse = l > 0.f ? m + __log2f(l) : INFINITY;
 }
 
 // 2^(e - 127) of an e8m0 byte as the f32 the scaled conversions take (they read its exponent field); the
@@ -151,29 +163,53 @@ __device__ __forceinline__ float e8m0_f32(unsigned e) { return __uint_as_float(e
 // chunk 8 of them (inside one scale block: block c / 4); the gfx950 scaled conversions turn them into
 // the packed bf16 of K (exact: 4 significant bits times a power of two) and the f32 of V, after which
 // the sweep is the bf16 one.
-template <int HW, bool MX8 = false>
+//
+// EXT (attn_extend): a wave's HW "heads" are rows (t, g) of a.P query positions t0 .. t0 + P - 1 and the G
+// heads of the group, row index t' G + g, each with its own key limit n_t = clamp(lens[b] + t + extra);
+// blockIdx.x carries (row tile, split).  The keys, slots, waves and both merges are attn_decode's for
+// this G; the descriptors and the sweep end with the tile's largest limit, and a row's scores at and
+// beyond its own limit are -inf: p = 0 there, so m, l and acc keep their bits (alpha = exp2(0) = 1, +0
+// products of the finite rows the step itself appended), and row (t, g) ends with attn_decode's bits
+// for extra + t.
+template <int HW, bool MX8 = false, bool EXT = false>
 __global__ __launch_bounds__(kDecThreads)
 void attn_decode_kernel(const DecodeArgs a) {
   __shared__ alignas(16) float sh[kDecWaves][HW][kDecPart];
-  const int split = blockIdx.x, j = blockIdx.y, b = blockIdx.z;
+  const int split = EXT ? blockIdx.x % a.splits : blockIdx.x, j = blockIdx.y, b = blockIdx.z;
+  const int t0 = EXT ? (blockIdx.x / a.splits) * a.P : 0;       // the block's first query position
+  const int rows = EXT ? a.P * a.G : a.G;                       // rows (t, g) of the block
   const int lane = threadIdx.x & 63, slot = lane >> 3, c = lane & 7;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int parts = (a.G + HW - 1) / HW;       // 1, or 2 for G > 8
+  const int parts = (rows + HW - 1) / HW;      // 1, or 2 for G > 8
   const int wpp = kDecWaves / parts;           // waves sweeping the range for one part's heads
   const int part = wave / wpp, wk = wave % wpp;
   const int g0 = part * HW;
 
-  int n = a.lens[b] + a.extra;
-  n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
   const int k0 = split * a.kps;
+  // (EXT: of the block's last position, the largest limit)
+  int n = a.lens[b] + a.extra + (EXT ? (t0 + a.P < a.T ? t0 + a.P : a.T) - 1 : 0);
+  n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
   const int k1 = k0 + a.kps < n ? k0 + a.kps : n;
 
   u32x4 qw[HW];
+  int k1r[HW];                                 // EXT: the end of the range for row i (wave-uniform)
 #pragma unroll
   for (int i = 0; i < HW; ++i) {
     qw[i] = u32x4{0u, 0u, 0u, 0u};
-    if (g0 + i < a.G)
-      qw[i] = load16<u32x4, kAligned16>(a.q + (long)b * a.qb + (long)(j * a.G + g0 + i) * a.qh + c * 8);
+    k1r[i] = k1;
+    if constexpr (EXT) {
+      const int tt = t0 + (g0 + i) / a.G, g = (g0 + i) % a.G;
+      k1r[i] = k0;                             // a row the block does not have: no key
+      if (g0 + i < rows && tt < a.T) {
+        qw[i] = load16<u32x4, kAligned16>(a.q + (long)b * a.qb + (long)tt * a.qt + (long)(j * a.G + g) * a.qh + c * 8);
+        int nt = a.lens[b] + a.extra + tt;
+        nt = nt < 0 ? 0 : (nt > a.cap ? a.cap : nt);
+        k1r[i] = k0 + a.kps < nt ? k0 + a.kps : nt;
+      }
+    } else {
+      if (g0 + i < a.G)
+        qw[i] = load16<u32x4, kAligned16>(a.q + (long)b * a.qb + (long)(j * a.G + g0 + i) * a.qh + c * 8);
+    }
   }
 
   // descriptors that end with row k1 - 1 of this (batch, key/value head): rows beyond read as zeros
@@ -260,7 +296,7 @@ void attn_decode_kernel(const DecodeArgs a) {
 #pragma unroll
         for (int w = 0; w < 4; ++w) d = dot2_bf16(kr[u][w], qw[i][w], d);
         d = sum8(d);
-        s[u] = key[u] < k1 ? d : -INFINITY;
+        s[u] = key[u] < (EXT ? k1r[i] : k1) ? d : -INFINITY;
       }
       float tmax = s[0];
 #pragma unroll
@@ -323,8 +359,8 @@ void attn_decode_kernel(const DecodeArgs a) {
 
   // the waves of a head's part, in ascending order: thread (g, chunk)
   const int t = threadIdx.x;
-  if (t < a.G * kDecChunks) {
-    const int g = t >> 3, cc = t & 7, pg = g / HW, gi = g % HW;
+  if (t < rows * kDecChunks) {
+    const int r = t >> 3, cc = t & 7, pg = r / HW, gi = r % HW;
     float mm = -INFINITY, ll = 0.f, av[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int w = pg * wpp; w < (pg + 1) * wpp; ++w) {
       float a2[8];
@@ -332,11 +368,14 @@ void attn_decode_kernel(const DecodeArgs a) {
       load_chunk(&sh[w][gi][cc * 8 + 4], a2 + 4);
       dec_merge(mm, ll, av, sh[w][gi][kDecD], sh[w][gi][kDecD + 1], a2);
     }
-    const int h = j * a.G + g;
+    const int tt = EXT ? t0 + r / a.G : 0, h = j * a.G + (EXT ? r % a.G : r);
+    if (EXT && tt >= a.T) return;              // a position past the last tile's end
+    const long bt = EXT ? (long)b * a.T + tt : b;
     if (a.splits == 1) {
-      dec_store_out(a, b, h, cc, mm, ll, av);
+      dec_store_out(a.o + (long)b * a.ob + (EXT ? (long)tt * a.ot : 0L) + (long)h * a.oh, a.lse + bt * a.H + h, cc, mm,
+                    ll, av);
     } else {
-      float* p = a.ws + (((long)b * a.H + h) * a.splits + split) * kDecPart;
+      float* p = a.ws + ((bt * a.H + h) * a.splits + split) * kDecPart;
       store_chunk(p + cc * 8, av);
       store_chunk(p + cc * 8 + 4, av + 4);
       if (cc == 0) {
@@ -347,7 +386,7 @@ void attn_decode_kernel(const DecodeArgs a) {
   }
 }
 
-// The partials of one (b, h) per wave: lane = (slot, chunk).  Pass 1 finds the largest m of all splits
+// The partials of one (b, t, h) per wave (T = 1 for attn_decode): lane = (slot, chunk).  Pass 1 finds the largest m of all splits
 // (exact, whatever the order).  Pass 2: slot j adds the splits j, j + 8, .. in ascending order, each
 // weighted by exp2(m_s - M), with the loads of 4 splits in flight; the 8 slots are then added by a
 // fixed tree of plain adds.  Every order is fixed, so the bits are the same on every run.
@@ -393,7 +432,10 @@ void decode_merge_kernel(const DecodeArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) av[e] += __shfl_xor(av[e], x, 64);
   }
-  if (slot == 0) dec_store_out(a, (int)(bh / a.H), (int)(bh % a.H), cc, mx, ll, av);
+  if (slot == 0) {
+    const long bt = bh / a.H, h = bh % a.H;
+    dec_store_out(a.o + (bt / a.T) * a.ob + (bt % a.T) * a.ot + h * a.oh, a.lse + bh, cc, mx, ll, av);
+  }
 }
 
 // ---- the plan: pure, of the capacity and never of the lengths
@@ -730,15 +772,37 @@ LJS_API int ljs_kv_append_q8(const void* k, const void* v, const void* q, void* 
 
 namespace {
 
-// the launch both decode entries share; ES: bytes per cache element; kcs / vcs: the scales (MX8 only)
+// attn_extend's instance for T > 1 positions of groups of G heads: the positions P one block carries (8 / G
+// of them for G <= 8, G rounded up to attn_decode's instance; no more than T rounded up to a power of two,
+// which gives the same row tiles with fewer idle rows), the rows HW of a wave and the logged name
+struct ExtInstance {
+  int P, HW;
+  const char* name;
+};
+inline ExtInstance extend_instance(int G, int T, bool mx8) {
+  static const char* const names[2][8] = {
+      {"attn_extend<G1,P2>", "attn_extend<G1,P4>", "attn_extend<G1,P8>", "attn_extend<G2,P2>", "attn_extend<G2,P4>",
+       "attn_extend<G4,P2>", "attn_extend<G8,P1>", "attn_extend<G16,P1>"},
+      {"attn_extend<G1,P2,mx8>", "attn_extend<G1,P4,mx8>", "attn_extend<G1,P8,mx8>", "attn_extend<G2,P2,mx8>",
+       "attn_extend<G2,P4,mx8>", "attn_extend<G4,P2,mx8>", "attn_extend<G8,P1,mx8>", "attn_extend<G16,P1,mx8>"}};
+  const int t2 = T <= 2 ? 2 : (T <= 4 ? 4 : 8);
+  if (G == 1) return {t2, t2, names[mx8][t2 == 2 ? 0 : (t2 == 4 ? 1 : 2)]};
+  if (G == 2) return t2 == 2 ? ExtInstance{2, 4, names[mx8][3]} : ExtInstance{4, 8, names[mx8][4]};
+  if (G <= 4) return {2, 8, names[mx8][5]};
+  return {1, 8, names[mx8][G <= 8 ? 6 : 7]};
+}
+
+// the launch the decode and extend entries share: T = 1 is attn_decode, T > 1 attn_extend over the keys
+// [0, lens[b] + extra + t); ES: bytes per cache element; kcs / vcs: the scales (MX8 only)
 template <bool MX8>
 int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o, void* lse,
-                  void* ws, long ws_floats, const void* lens, int B, int H, int Hkv, int cap, const long* sq,
+                  void* ws, long ws_floats, const void* lens, int B, int T, int H, int Hkv, int cap, const long* sq,
                   const long* skc, const long* svc, const long* skcs, const long* svcs, const long* so, float scale,
                   int extra, hipStream_t st) {
   constexpr long ES = MX8 ? 1 : 2;
+  if (T < 1 || T > kExtMaxT) return (int)hipErrorInvalidValue;
   if (B < 1 || H < 1 || Hkv < 1 || cap < 1 || H % Hkv != 0 || H / Hkv > kDecMaxG || !(scale > 0.f) || extra < 0 ||
-      B > 65535 || Hkv > 65535 || (long)B * H > 0x7fffffffL || !lens || !lse || (((uintptr_t)lens) & 3u) || (((uintptr_t)lse) & 3u))
+      B > 65535 || Hkv > 65535 || (long)B * T * H > 0x7fffffffL || !lens || !lse || (((uintptr_t)lens) & 3u) || (((uintptr_t)lse) & 3u))
     return (int)hipErrorInvalidValue;
   if (!dec_aligned(q, sq) || !dec_aligned(o, so)) return (int)hipErrorInvalidValue;
   if (MX8 ? (!q8_aligned(kc, skc) || !q8_aligned(vc, svc) || !q8_scale_aligned(kcs, skcs) || !q8_scale_aligned(vcs, svcs))
@@ -752,7 +816,7 @@ int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs
     return (int)hipErrorInvalidValue;
   DecodeArgs a{};
   if (decode_launch_plan(B, Hkv, cap, &a.splits, &a.kps) != 0) return (int)hipErrorInvalidValue;
-  if (a.splits > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < (long)B * H * a.splits * kDecPart))
+  if (a.splits > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < (long)B * T * H * a.splits * kDecPart))
     return (int)hipErrorInvalidValue;
   a.q = (const bf16_t*)q;
   a.kc = (const bf16_t*)kc;
@@ -761,10 +825,11 @@ int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs
   a.lse = (float*)lse;
   a.ws = (float*)ws;
   a.lens = (const int*)lens;
-  a.qb = sq[0]; a.qh = sq[2];
+  a.qb = sq[0]; a.qt = sq[1]; a.qh = sq[2];
   a.kb = skc[0]; a.ks = skc[1]; a.kh = skc[2];
   a.vb = svc[0]; a.vs = svc[1]; a.vh = svc[2];
-  a.ob = so[0]; a.oh = so[2];
+  a.ob = so[0]; a.ot = so[1]; a.oh = so[2];
+  a.T = T; a.P = 1;
   a.B = B; a.H = H; a.Hkv = Hkv; a.G = H / Hkv; a.cap = cap; a.extra = extra;
   a.scale_log2 = scale * 1.4426950408889634f;
   if (MX8) {
@@ -773,9 +838,20 @@ int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs
     a.ksb = skcs[0]; a.kss = skcs[1]; a.ksh = skcs[2];
     a.vsb = svcs[0]; a.vss = svcs[1]; a.vsh = svcs[2];
   }
-  const dim3 grid((unsigned)a.splits, (unsigned)Hkv, (unsigned)B);
+  dim3 grid((unsigned)a.splits, (unsigned)Hkv, (unsigned)B);
   const char* name;
-  if (a.G == 1) {
+  if (T > 1) {
+    const ExtInstance x = extend_instance(a.G, T, MX8);
+    a.P = x.P;
+    grid.x = (unsigned)(a.splits * ((T + x.P - 1) / x.P));      // (row tile, split)
+    name = x.name;
+    if (x.HW == 2)
+      hipLaunchKernelGGL((attn_decode_kernel<2, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
+    else if (x.HW == 4)
+      hipLaunchKernelGGL((attn_decode_kernel<4, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
+    else
+      hipLaunchKernelGGL((attn_decode_kernel<8, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
+  } else if (a.G == 1) {
     hipLaunchKernelGGL((attn_decode_kernel<1, MX8>), grid, dim3(kDecThreads), 0, st, a);
     name = MX8 ? "attn_decode<G1,mx8>" : "attn_decode<G1>";
   } else if (a.G == 2) {
@@ -794,7 +870,7 @@ int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs
   ljs_launch_rec(name, grid, kDecThreads);
   int rc = (int)hipGetLastError();
   if (rc != 0 || a.splits == 1) return rc;
-  const dim3 mgrid((unsigned)(B * H));
+  const dim3 mgrid((unsigned)(B * T * H));
   hipLaunchKernelGGL(decode_merge_kernel, mgrid, dim3(64), 0, st, a);
   ljs_launch_rec("decode_merge", mgrid, 64);
   return (int)hipGetLastError();
@@ -811,7 +887,7 @@ int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs
 LJS_API int ljs_attn_decode(const void* q, const void* kc, const void* vc, void* o, void* lse, void* ws, long ws_floats,
                             const void* lens, int B, int H, int Hkv, int cap, const long* sq, const long* skc,
                             const long* svc, const long* so, float scale, int extra, hipStream_t st) {
-  return decode_launch<false>(q, kc, vc, nullptr, nullptr, o, lse, ws, ws_floats, lens, B, H, Hkv, cap, sq, skc, svc,
+  return decode_launch<false>(q, kc, vc, nullptr, nullptr, o, lse, ws, ws_floats, lens, B, 1, H, Hkv, cap, sq, skc, svc,
                               nullptr, nullptr, so, scale, extra, st);
 }
 
@@ -824,8 +900,31 @@ LJS_API int ljs_attn_decode_q8(const void* q, const void* kc, const void* vc, co
                                void* lse, void* ws, long ws_floats, const void* lens, int B, int H, int Hkv, int cap,
                                const long* sq, const long* skc, const long* svc, const long* skcs, const long* svcs,
                                const long* so, float scale, int extra, hipStream_t st) {
-  return decode_launch<true>(q, kc, vc, kcs, vcs, o, lse, ws, ws_floats, lens, B, H, Hkv, cap, sq, skc, svc, skcs, svcs,
-                             so, scale, extra, st);
+  return decode_launch<true>(q, kc, vc, kcs, vcs, o, lse, ws, ws_floats, lens, B, 1, H, Hkv, cap, sq, skc, svc, skcs,
+                             svcs, so, scale, extra, st);
+}
+
+LJS_API int ljs_extend_max_positions() { return kExtMaxT; }
+
+// q (B, T, H, 64) -> o (B, T, H, 64) bf16, lse (B, T, H) f32: row (b, t, h) over the keys [0, clamp(lens[b] + t + 1,
+// 0, cap)), after an append of the T positions that lens does not count yet -- the bits ljs_attn_decode
+// writes for (b, h) with extra = t + 1 under the same plan.  T == 1 IS that call (its launches, its
+// records).  ws: at least B T H splits kDecPart floats when the plan has more than one split.  Refuses
+// what ljs_attn_decode refuses, and T outside [1, 64].
+LJS_API int ljs_attn_extend(const void* q, const void* kc, const void* vc, void* o, void* lse, void* ws, long ws_floats,
+                            const void* lens, int B, int T, int H, int Hkv, int cap, const long* sq, const long* skc,
+                            const long* svc, const long* so, float scale, hipStream_t st) {
+  return decode_launch<false>(q, kc, vc, nullptr, nullptr, o, lse, ws, ws_floats, lens, B, T, H, Hkv, cap, sq, skc, svc,
+                              nullptr, nullptr, so, scale, 1, st);
+}
+
+// ljs_attn_extend over an MX-fp8 cache (ljs_attn_decode_q8's operands and refusals)
+LJS_API int ljs_attn_extend_q8(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o,
+                               void* lse, void* ws, long ws_floats, const void* lens, int B, int T, int H, int Hkv,
+                               int cap, const long* sq, const long* skc, const long* svc, const long* skcs,
+                               const long* svcs, const long* so, float scale, hipStream_t st) {
+  return decode_launch<true>(q, kc, vc, kcs, vcs, o, lse, ws, ws_floats, lens, B, T, H, Hkv, cap, sq, skc, svc, skcs,
+                             svcs, so, scale, 1, st);
 }
 
 // lens[0 .. B) += n: one small launch after the last layer of a decode step

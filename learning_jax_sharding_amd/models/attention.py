@@ -30,7 +30,10 @@ Decoding: ``cache=(k, v, lens)`` (a layer of :class:`~.cache.KVCache`) makes the
 decoder and returns ``(output, cache)``.  A call on more than one position is a prefill: positions 0 ..
 T-1, the usual rope and causal kernels, and K (rotated) and V written to rows 0 .. T-1 of the cache; a
 call on one position appends its K / V at row ``lens[b]`` and attends to the cache (``ops.core.
-cached_attention``).  ``lens`` is advanced by the caller, once for all layers.  A layer of an MX-fp8 cache is
+cached_attention``).  With ``extend=True`` a call on ``T >= 1`` positions
+(at most 64) appends them at rows ``lens[b] .. lens[b] + T - 1`` and position ``t`` attends to rows ``[0, lens[b] + t + 1)``:
+the result of ``T`` single steps in one append and one attention launch.  ``lens`` is advanced by the caller, once for
+all layers.  A layer of an MX-fp8 cache is
 ``(k, v, lens, k_scale, v_scale)``: the prefill attends to its own unquantised K / V and stores them quantised, a
 decode step stores its row quantised and attends to the fp8 rows.
 """
@@ -122,7 +125,7 @@ class MultiHeadAttention(Module):
         if self.verbose:
             print(*a)
 
-    def _cached(self, x: ShardedArray, cache, residual: Optional[ShardedArray]):
+    def _cached(self, x: ShardedArray, cache, residual: Optional[ShardedArray], extend: bool = False):
         """The cached call (module docstring): no gradient, dropout the identity, no ``attention_next``
         hint and no weight prefetch; the projections are the uncached call's."""
         if not self.causal:
@@ -147,7 +150,9 @@ class MultiHeadAttention(Module):
             q = core.reshape(with_logical_constraint(q, ("batch", "embed", None)), (b, -1, self.heads, self.dim_head))
             k = core.reshape(with_logical_constraint(k, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
             v = core.reshape(with_logical_constraint(v, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
-            if x.shape[1] == 1:
+            if extend:
+                hidden = core.cached_attention(q, k, v, layer, lens, self.scale, self.rope_theta, extend=True)
+            elif x.shape[1] == 1:
                 hidden = core.cached_attention(q, k, v, layer, lens, self.scale, self.rope_theta)
             else:
                 if self.rope_theta is not None:
@@ -160,16 +165,21 @@ class MultiHeadAttention(Module):
             return with_logical_constraint(hidden, ("batch", "embed")), cache
 
     def __call__(self, hidden_states: ShardedArray, context: Optional[ShardedArray] = None,
-                 deterministic: bool = True, residual: Optional[ShardedArray] = None, cache=None):
+                 deterministic: bool = True, residual: Optional[ShardedArray] = None, cache=None,
+                 extend: bool = False):
         """``residual`` (the block's input, for a skip connection): returns
         ``residual + attention(...)`` in the compute dtype, the add fused into the output
         projection's GEMM epilogue when dropout is the identity.  ``cache``: one layer ``(k, v, lens)`` of a
-        :class:`~.cache.KVCache`; the call then returns ``(output, cache)`` (module docstring)."""
+        :class:`~.cache.KVCache`; the call then returns ``(output, cache)`` (module docstring).  ``extend=True`` (with a
+        cache): the ``T >= 1`` positions of the call continue the cached sequence at rows ``lens[b] .. lens[b] + T - 1``
+        instead of restarting it (``ops.core.cached_attention``)."""
+        if extend and cache is None:
+            raise ValueError("MultiHeadAttention: extend=True needs a cache (it continues a cached sequence)")
         if cache is not None:
             if context is not None:
                 raise ValueError("MultiHeadAttention: a cache with a context (cross-attention) is not implemented: "
                                  "the cache holds the keys and values of the sequence being decoded")
-            return self._cached(hidden_states, cache, residual)
+            return self._cached(hidden_states, cache, residual, extend)
         self_attn = context is None
         if self.rope_theta is not None and not self_attn:
             raise ValueError("MultiHeadAttention: rope_theta with a context (cross-attention) is not defined: "

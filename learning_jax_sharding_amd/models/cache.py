@@ -1,4 +1,5 @@
-"""The key/value cache of a decoder and generation (greedy or sampled, with stop tokens) on top of it.
+"""The key/value cache of a decoder and generation (greedy, sampled with stop tokens, or greedy with a draft model:
+speculative decoding) on top of it.
 
 A :class:`KVCache` holds, per layer, ``k`` and ``v`` of shape ``(batch, max_len, kv_heads, dim_head)`` in the
 model's compute dtype (zero-filled) and ONE shared ``lens``: int32 ``(batch,)``, the rows of every
@@ -159,6 +160,128 @@ def _greedy(logits: ShardedArray, like: ShardedArray, at: Optional[ShardedArray]
     return ShardedArray((logits.shape[0], 1), like.dtype, sharding_from_tile(ot, like=[logits.sharding]), loc)
 
 
+def _greedy_all(logits: ShardedArray, like: ShardedArray) -> ShardedArray:
+    """``argmax`` over the vocabulary at every position of ``logits`` (batch, T, vocab), on the devices: ``(batch, T)`` in
+    ``like``'s dtype."""
+    tile = logits.tile.unshard([1, 2])
+    if logits.tile != tile:
+        from ..spmd.reshard import reshard_tile
+        logits = reshard_tile(logits, tile, note="generate.logits")
+    loc = {d: t.float().argmax(-1).to(like.dtype) for d, t in logits.local.items()}
+    return ShardedArray(tuple(logits.shape[:2]), like.dtype, sharding_from_tile(tile.project([0, 1]), like=[logits.sharding]),
+                        loc)
+
+
+def _draft_request(model, draft, draft_tokens, key, eos_id):
+    """The checks of ``generate``'s ``draft`` arguments, on the host before any launch: ``(draft_model, draft_params, k)``."""
+    from ..ops.kernels import EXTEND_MAX_POSITIONS
+    if key is not None or eos_id is not None:
+        raise ValueError("generate: draft= is greedy speculative decoding; it takes neither a key (sampling) nor an eos_id")
+    if not isinstance(draft, (tuple, list)) or len(draft) != 2:
+        raise ValueError("generate: draft must be (draft_model, draft_params)")
+    k = int(draft_tokens)
+    if k < 1 or k + 1 > EXTEND_MAX_POSITIONS:
+        raise ValueError(f"generate: draft_tokens must be in [1, {EXTEND_MAX_POSITIONS - 1}] (the target checks draft_tokens + "
+                         f"1 positions in one call), got {draft_tokens}")
+    if draft[0].vocab_size != model.vocab_size:
+        raise ValueError(f"generate: the draft's vocabulary ({draft[0].vocab_size}) differs from the model's "
+                         f"({model.vocab_size})")
+    return draft[0], draft[1], k
+
+
+def _generate_speculative(model, params, draft, dparams, k: int, ids, plens, max_new_tokens: int, cache, dcache, pl,
+                          capture, stop_poll: int):
+    """Greedy speculative decoding (``generate``'s ``draft=``): ``(tokens [batch, max_new_tokens], mean tokens per round)``.
+
+    One round, captured once, no host read inside.  State per sequence: ``pair``, the last two tokens of the sequence
+    (the second is not in either cache yet); the target's ``lens`` counts everything before it, the draft's one less.
+    The draft takes ``pair`` as one ``extend`` call (it rewrites the row of the first token with the same values, which
+    makes the scheme the same whatever the last round accepted) and then ``k - 1`` single steps: ``d_1 .. d_k``.  The target
+    takes ``[pair[1], d_1 .. d_k]`` as one ``extend`` call: ``g_0 .. g_k``, what it would have decoded after each.  ``a`` leading
+    agreements ``d_(i+1) == g_i`` are accepted and the round emits ``g_0 .. g_a`` (``d_1 .. d_a`` and the target's own next
+    token), cut so that no sequence gets more than ``max_new_tokens``; both ``lens`` are set back by ``k - a`` on the
+    devices (the rows beyond are dead).  A sequence that has all its tokens emits none and stays where it is."""
+    from ..spmd.api import jit
+    B = ids.shape[0]
+    lens = cache.lens
+
+    def prefill(p, dp, x, c, dc, n):
+        logits, c = model.apply({"params": p}, x, cache=c, prompt_lens=n)
+        _, dc = draft.apply({"params": dp}, x, cache=dc, prompt_lens=n)
+        core.cache_advance(dc.lens, -1)
+        last = ShardedArray(n.shape, n.dtype, n.sharding, {d: t - 1 for d, t in n.local.items()})
+        return _greedy(logits, x, last), c, dc
+
+    def rnd(p, dp, st, c, dc):
+        pair, toks, cnt, n_out = st
+        lg, dc = draft.apply({"params": dp}, pair, cache=dc, extend=True)
+        d = [_greedy(lg, pair)]
+        for _ in range(k - 1):
+            lg, dc = draft.apply({"params": dp}, d[-1], cache=dc)
+            d.append(_greedy(lg, pair))
+        x = ShardedArray((B, k + 1), pair.dtype, pair.sharding,
+                         {dev: torch.cat([t[:, 1:2]] + [di.local[dev] for di in d], dim=1)
+                          for dev, t in pair.local.items()})
+        lg, c = model.apply({"params": p}, x, cache=c, extend=True)
+        g = _greedy_all(lg, pair)
+        back = {}
+        for dev, gl in g.local.items():
+            xl, pr, no = x.local[dev], pair.local[dev], n_out.local[dev]
+            a = (xl[:, 1:] == gl[:, :k]).to(torch.int32).cumprod(1).sum(1).to(torch.int32)
+            a = torch.minimum(a, max_new_tokens - 1 - no)          # -1: the sequence has all its tokens
+            at = a.clamp(min=0).long()[:, None]
+            new = torch.cat([xl.gather(1, at), gl.gather(1, at)], dim=1)
+            pr.copy_(torch.where(a[:, None] >= 0, new, pr))
+            toks.local[dev].copy_(gl)
+            cnt.local[dev].copy_(a + 1)
+            no.add_(a + 1)
+            back[dev] = a - k
+        for ln in (c.lens, dc.lens):       # both were advanced by k + 1
+            core.cache_advance(ln, ShardedArray(ln.shape, ln.dtype, ln.sharding, {dev: back[dev] for dev in ln.local}))
+        return st, c, dc
+
+    rnd_j = jit(rnd, donate_argnums=(2, 3, 4), capture=capture)
+    with torch.no_grad():
+        tok, cache, dcache = prefill(params, dparams, ids, cache, dcache, pl)
+        first = tok.to_torch().reshape(B, 1).long()
+        if max_new_tokens == 1:
+            return first, 0.0
+        host_ids = ids.to_torch()
+        prev = torch.stack([host_ids[b, n - 1] for b, n in enumerate(plens)]).reshape(B, 1)
+        pair = device_put(torch.cat([prev.long(), first], dim=1).to(tok.dtype).numpy(), tok.sharding)
+        zeros = lambda shape, dt, sh, like: ShardedArray(   # noqa: E731
+            shape, dt, sh, {d: torch.zeros((t.shape[0],) + tuple(shape[1:]), dtype=dt, device=t.device)
+                            for d, t in like.local.items()})
+        toks = zeros((B, k + 1), tok.dtype, tok.sharding, tok)
+        cnt = zeros((B,), torch.int32, lens.sharding, lens)
+        n_out = zeros((B,), torch.int32, lens.sharding, lens)
+        for t in n_out.local.values():
+            t.fill_(1)                     # the prefill's token
+        st = (pair, toks, cnt, n_out)
+        kept = []
+        for r in range(1, max_new_tokens):             # a round gives every unfinished sequence at least one token
+            st, cache, dcache = rnd_j(params, dparams, st, cache, dcache)
+            kept.append(({d: t.clone() for d, t in st[1].local.items()}, {d: t.clone() for d, t in st[2].local.items()}))
+            # outside the graph: one host read of the counts every stop_poll rounds
+            if stop_poll and r % int(stop_poll) == 0 and all(
+                    bool((t >= max_new_tokens).all()) for t in st[3].local.values()):
+                break
+        rows = [[first[b]] for b in range(B)]
+        emitted = rounds = 0
+        for tl, cl in kept:
+            th = ShardedArray(toks.shape, toks.dtype, toks.sharding, tl).to_torch().long()
+            ch = ShardedArray(cnt.shape, cnt.dtype, cnt.sharding, cl).to_torch()
+            for b in range(B):
+                n = int(ch[b])
+                rows[b].append(th[b, :n])
+                emitted += n
+                rounds += n > 0
+    out = torch.stack([torch.cat(r)[:max_new_tokens] for r in rows])
+    if out.shape[1] != max_new_tokens:
+        raise RuntimeError(f"generate: {out.shape[1]} of {max_new_tokens} tokens after {len(kept)} rounds")
+    return out, emitted / max(rounds, 1)
+
+
 def _sampling_request(V: int, key, temperature, top_k, top_p, eos_id, pad_id, stop_poll):
     """The checks of ``generate``'s sampling arguments, on the host before any launch: the eos ids as a tuple."""
     eos = () if eos_id is None else ((int(eos_id),) if isinstance(eos_id, (int, np.integer)) else
@@ -229,7 +352,7 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
              max_len: Optional[int] = None, cache_sharding: Optional[Sharding] = None, *, key=None,
              temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id=None,
              pad_id: Optional[int] = None, stop_poll: int = 16, return_lens: bool = False,
-             cache_quant: Optional[str] = None):
+             cache_quant: Optional[str] = None, draft=None, draft_tokens: int = 4):
     """Decoding: ``max_new_tokens`` tokens after each prompt of ``ids`` (batch, T), as an int64 host tensor
     ``[batch, max_new_tokens]``; greedy without a ``key``.
 
@@ -253,7 +376,17 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
 
     ``cache_quant="mxfp8"``: the cache is MX-fp8 (:class:`KVCache`): about half the bytes per cached row, the launch
     count of a step unchanged.  The prefill attends to the prompt's unquantised K / V, so the first token is the
-    unquantised run's; the later ones attend to fp8 keys and values and may differ from it."""
+    unquantised run's; the later ones attend to fp8 keys and values and may differ from it.
+
+    ``draft=(draft_model, draft_params)``: greedy speculative decoding.  Per round the draft (a cheaper model of the same
+    vocabulary, with a cache and a prefill of its own) proposes ``draft_tokens`` tokens and the target checks them in ONE
+    cached call on ``draft_tokens + 1`` positions (``extend=True``), keeping the longest prefix it would have decoded itself
+    plus its own next token: the tokens are plain greedy ``generate``'s (a multi-position step has a single step's bits
+    wherever its projections do, ``batch * (draft_tokens + 1) <= 16`` on the GPU), in fewer target calls.  The round is
+    captured once; the host reads the per-sequence counts every ``stop_poll`` rounds and stops when every sequence has
+    its tokens.  Greedy only: with a ``key`` or an ``eos_id``, a draft of another vocabulary, ``draft_tokens`` outside ``[1,
+    63]`` or ``max(prompt_lens) + max_new_tokens + draft_tokens > max_len`` it raises ``ValueError`` before any launch.
+    ``return_lens=True`` then returns ``(tokens, lens, mean tokens per round and unfinished sequence)``."""
     from ..spmd.api import jit
     from ..sharding.tile import TileAssignment
     if ids.ndim != 2:
@@ -264,11 +397,14 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
         raise ValueError(f"generate: cache_quant must be None or {QUANT_MXFP8!r}, got {cache_quant!r}")
     B, T = ids.shape
     plens = _host_lens(prompt_lens, B, T)
-    need = max(plens) + max_new_tokens
+    spec = _draft_request(model, draft, draft_tokens, key, eos_id) if draft is not None else None
+    ahead = spec[2] if spec else 0       # rows a round writes beyond the tokens it may keep
+    need = max(plens) + max_new_tokens + ahead
     cap = max_len if max_len is not None else (model.max_len if model.max_len is not None else need)
     if need > cap or T > cap:
-        raise ValueError(f"generate: max(prompt_lens) + max_new_tokens = {max(plens)} + {max_new_tokens} > max_len "
-                         f"{cap} (or the padded prompt length {T} is)")
+        raise ValueError(f"generate: max(prompt_lens) + max_new_tokens{' + draft_tokens' if spec else ''} = {max(plens)} + "
+                         f"{max_new_tokens}{f' + {ahead}' if spec else ''} > max_len {cap} (or the padded prompt length {T} "
+                         "is)")
     if cache_sharding is None:
         it = ids.tile
         ct = TileAssignment.from_coords({d: (it.coords[d][0], 0, 0, 0) for d in it.device_ids},
@@ -277,6 +413,11 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
     eos = _sampling_request(model.vocab_size, key, temperature, top_k, top_p, eos_id, pad_id, stop_poll)
     cache = model.init_cache(B, cap, sharding=cache_sharding, **({"quant": cache_quant} if cache_quant else {}))
     pl = device_put(np.asarray(plens, dtype=np.int32), cache.lens.sharding)
+    if spec:
+        dcache = spec[0].init_cache(B, cap, sharding=cache_sharding, **({"quant": cache_quant} if cache_quant else {}))
+        out, mean = _generate_speculative(model, params, spec[0], spec[1], spec[2], ids, plens, max_new_tokens, cache,
+                                          dcache, pl, capture, stop_poll)
+        return (out, torch.full((B,), max_new_tokens, dtype=torch.long), mean) if return_lens else out
     if key is not None or eos:
         out = _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p,
                                 eos, pad_id, stop_poll)

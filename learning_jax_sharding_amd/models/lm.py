@@ -10,7 +10,8 @@ in every layer) or from ``max_len`` (a learned additive table), not both; with n
 positions through the causal mask alone.
 
 Decoding: :meth:`TransformerLM.init_cache` makes a :class:`~.cache.KVCache`; a call with ``cache=`` is a prefill
-(more than one position) or one decode step (one position) and returns ``(logits, cache)``;
+(more than one position) or one decode step (one position) and returns ``(logits, cache)``; with ``extend=True`` a
+call on up to 64 positions continues the cache as that many decode steps would;
 :func:`~.cache.generate` is greedy decoding on top of both.
 
 The embedding table's logical axes are ``("vocab", "embed")`` and the head kernel's ``("embed",
@@ -110,8 +111,9 @@ class TransformerLM(Module):
                     K.rope_table(t.device, self.dim_head, float(self.rope_theta), max_len)
         return cache
 
-    def _cached(self, ids: ShardedArray, cache, prompt_lens):
-        """Prefill (more than one position: restarts the cache) or one decode step (module docstring)."""
+    def _cached(self, ids: ShardedArray, cache, prompt_lens, extend: bool = False):
+        """Prefill (more than one position: restarts the cache), one decode step, or with ``extend`` a step of
+        several positions that continues the cache (module docstring)."""
         for name, bad in (("causal=False", not self.causal), ("fp8=True", self.fp8)):
             if bad:
                 raise ValueError(f"TransformerLM: {name} has no cached path (a cache needs a causal decoder "
@@ -119,6 +121,14 @@ class TransformerLM(Module):
         if len(cache) != self.layers:
             raise ValueError(f"TransformerLM: the cache has {len(cache)} layers, the model {self.layers}")
         T = ids.shape[-1]
+        if extend:
+            from ..ops.kernels import EXTEND_MAX_POSITIONS
+            if prompt_lens is not None:
+                raise ValueError("TransformerLM: extend=True continues the cache at cache.lens; prompt_lens goes with a "
+                                 "prefill")
+            if T > EXTEND_MAX_POSITIONS:
+                raise ValueError(f"TransformerLM: extend=True takes at most {EXTEND_MAX_POSITIONS} positions per call, "
+                                 f"got {T}")
         if T > cache.max_len:
             raise ValueError(f"TransformerLM: {T} positions do not fit the cache's max_len {cache.max_len}")
         if T == 1 and prompt_lens is not None:
@@ -132,28 +142,40 @@ class TransformerLM(Module):
             if self.max_len is not None:
                 if T > self.max_len:
                     raise ValueError(f"TransformerLM: sequence length {T} > max_len {self.max_len}")
-                pos = _position_ids(ids) if T > 1 else core.reshape(cache.lens, (ids.shape[0], 1))
+                if extend and T > 1:
+                    # position lens[b] + t, on the devices
+                    base = core.broadcast_to(core.reshape(cache.lens, (ids.shape[0], 1)), tuple(ids.shape))
+                    pos = core.binary("add", base, core.convert(_position_ids(ids), cache.lens.dtype))
+                else:
+                    pos = _position_ids(ids) if T > 1 else core.reshape(cache.lens, (ids.shape[0], 1))
                 x = core.binary("add", x, self.pos_embed(pos))
             x = with_logical_constraint(x, ("batch", "length", "embed"))
             for i, blk in enumerate(self.blocks):
-                x, _ = blk(x, cache=cache.layer(i))
-            if T == 1:
-                core.cache_advance(cache.lens, 1)       # after the last layer: one small launch
+                x, _ = blk(x, cache=cache.layer(i), extend=extend)
+            if T == 1 or extend:
+                core.cache_advance(cache.lens, T)       # after the last layer: one small launch
             else:
                 core.cache_set_lens(cache.lens, T if prompt_lens is None else prompt_lens)
             x = self.final_norm(x)
             return with_logical_constraint(self.head(x), ("batch", "length", "vocab")), cache
 
-    def __call__(self, ids: ShardedArray, cache=None, prompt_lens=None):
+    def __call__(self, ids: ShardedArray, cache=None, prompt_lens=None, extend: bool = False):
         """Token ids ``[batch, length]`` (int32 / int64) -> logits ``[batch, length, vocab_size]``.
 
         ``cache`` (a :class:`~.cache.KVCache` from :meth:`init_cache`): returns ``(logits, cache)``, the buffers
         updated in place, without gradient.  ``length > 1`` is a prefill that restarts the cache: positions 0
         .. length-1, K / V of every layer to rows 0 .. length-1, ``cache.lens := prompt_lens`` (an int
         ``(batch,)`` array laid out like ``cache.lens``: right-padded ragged prompts) or ``length``.  ``length == 1``
-        is a decode step: the token of sequence b sits at position ``cache.lens[b]``, and ``lens += 1``."""
+        is a decode step: the token of sequence b sits at position ``cache.lens[b]``, and ``lens += 1``.
+
+        ``extend=True`` (with a cache, without ``prompt_lens``, ``length <= 64``): the tokens of sequence b sit at positions
+        ``cache.lens[b] .. cache.lens[b] + length - 1`` and continue the cache instead of restarting it; the logits are those
+        of ``length`` decode steps, in one step's launches, and ``lens += length``.  A caller that keeps fewer of the
+        positions sets ``cache.lens`` back (``ops.core.cache_advance`` with a negative array): rows beyond ``lens`` are dead."""
+        if extend and cache is None:
+            raise ValueError("TransformerLM: extend=True needs a cache (it continues a cached sequence)")
         if cache is not None:
-            return self._cached(ids, cache, prompt_lens)
+            return self._cached(ids, cache, prompt_lens, extend)
         if prompt_lens is not None:
             raise ValueError("TransformerLM: prompt_lens goes with a cache")
         x = self.embed(ids)

@@ -69,16 +69,19 @@ class TransformerLayer(Module):
             self.norm1 = cls(dtype=self.dtype, name="norm1")
             self.norm2 = cls(dtype=self.dtype, name="norm2")
 
-    def __call__(self, x, cache=None):
+    def __call__(self, x, cache=None, extend: bool = False):
         """``cache``: one layer ``(k, v, lens)`` of a :class:`~.cache.KVCache`: a cached decoder step or prefill
-        (``MultiHeadAttention``), without gradient; returns ``(y, cache)``."""
+        (``MultiHeadAttention``), without gradient; returns ``(y, cache)``.  ``extend=True``: the call's positions
+        continue the cached sequence (``MultiHeadAttention``)."""
+        if extend and cache is None:
+            raise ValueError("TransformerLayer: extend=True needs a cache (it continues a cached sequence)")
         if cache is not None:
             if self.fp8:
                 raise ValueError("TransformerLayer: fp8=True has no cached path (the fp8 feed-forward under a cache "
                                  "is not implemented); use fp8=False")
             with torch.no_grad():
                 xin = self.norm1(x) if self.norm is not None else x
-                h, cache = self.attn(xin, residual=x, cache=cache)
+                h, cache = self.attn(xin, residual=x, cache=cache, extend=extend)
                 return self.ff(self.norm2(h) if self.norm is not None else h, residual=h), cache
         if self.norm is not None:
             # pre-norm: the skips carry the un-normalised stream.  The attention's stays in its

@@ -1108,17 +1108,29 @@ def _cache_layout(k: ShardedArray, v: ShardedArray, cache_layer, lens: Optional[
 
 
 def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_layer, lens: ShardedArray,
-                     scale: Optional[float] = None, rope_theta: Optional[float] = None) -> ShardedArray:
+                     scale: Optional[float] = None, rope_theta: Optional[float] = None,
+                     extend: bool = False) -> ShardedArray:
     """One decode step of one layer: the single new position's ``k`` / ``v`` (batch, 1, kv_heads, head_dim)
     are appended to ``cache_layer = (kc, vc)`` at row ``lens[b]`` (k, and q with it, rotated at that
     position when ``rope_theta`` is given), and ``q`` (batch, 1, heads, head_dim) attends to rows ``[0,
     lens[b] + 1)``: two launches per device shard (:func:`.kernels.kv_append`, :func:`.kernels.attn_decode`).
     ``lens`` itself is not changed (the caller advances it once after the last layer).  An MX-fp8 layer ``(kc, vc,
     kcs, vcs)`` stores the new row quantised and attends to the dequantised rows, the new one included
-    (:func:`.kernels.kv_append_q8`, :func:`.kernels.attn_decode_q8`): the same two launches."""
-    if q.shape[1] != 1 or k.shape[1] != 1:
+    (:func:`.kernels.kv_append_q8`, :func:`.kernels.attn_decode_q8`): the same two launches.
+
+    ``extend=True``: ``T >= 1`` new positions per sequence (at most :data:`.kernels.EXTEND_MAX_POSITIONS`) are
+    appended at rows ``lens[b] .. lens[b] + T - 1`` (q and k rotated at ``lens[b] + t``; rows at and beyond the capacity are
+    not written) and position ``t`` attends to rows ``[0, lens[b] + t + 1)``: still one append and one attention launch
+    (:func:`.kernels.attn_extend`), and the result of ``T`` single steps."""
+    T = q.shape[1]
+    if k.shape[1] != T:
+        raise ValueError(f"cached_attention: q has {T} new positions and k {k.shape[1]}")
+    if not extend and T != 1:
         raise ValueError(f"cached_attention: one new position per call, got {q.shape[1]} (a longer call is a "
-                         "prefill: attention over the new tokens and cache_prefill)")
+                         "prefill: attention over the new tokens and cache_prefill; or extend=True)")
+    if extend and not 1 <= T <= K.EXTEND_MAX_POSITIONS:
+        raise ValueError(f"cached_attention: extend=True takes 1 to {K.EXTEND_MAX_POSITIONS} new positions per call, "
+                         f"got {T}")
     if scale is None:
         scale = q.shape[-1] ** -0.5
     q, k, v = _cache_layout(k, v, cache_layer, lens, q)
@@ -1131,11 +1143,15 @@ def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_la
             bufs = [c.local[d] for c in cache_layer]
             qr = K.kv_append_q8(k.local[d], v.local[d], *bufs, ln, q=qt if rope_theta is not None else None,
                                 theta=rope_theta)
-            loc[d] = K.attn_decode_q8(qt if qr is None else qr, *bufs, ln, float(scale), extra=1)[0]
+            qn = qt if qr is None else qr
+            loc[d] = (K.attn_extend_q8(qn, *bufs, ln, float(scale)) if extend else
+                      K.attn_decode_q8(qn, *bufs, ln, float(scale), extra=1))[0]
             continue
         qr = K.kv_append(k.local[d], v.local[d], kc.local[d], vc.local[d], ln,
                          q=qt if rope_theta is not None else None, theta=rope_theta)
-        loc[d] = K.attn_decode(qt if qr is None else qr, kc.local[d], vc.local[d], ln, float(scale), extra=1)[0]
+        qn = qt if qr is None else qr
+        loc[d] = (K.attn_extend(qn, kc.local[d], vc.local[d], ln, float(scale)) if extend else
+                  K.attn_decode(qn, kc.local[d], vc.local[d], ln, float(scale), extra=1))[0]
     return ShardedArray(q.shape, q.dtype if _quantised(cache_layer) else vc.dtype, q.sharding, loc)
 
 
@@ -1163,10 +1179,14 @@ def cache_set_lens(lens: ShardedArray, value) -> None:
             t.fill_(int(value))
 
 
-def cache_advance(lens: ShardedArray, n: int = 1) -> None:
-    """``lens += n`` in place, one small launch per device (:func:`.kernels.lens_add`)."""
-    for t in lens.local.values():
-        K.lens_add(t, n)
+def cache_advance(lens: ShardedArray, n=1) -> None:
+    """``lens += n`` in place, one small launch per device (:func:`.kernels.lens_add`); ``n``: an int, or an int32
+    ``(batch,)`` array laid out like ``lens`` that stays on the devices (:func:`.kernels.lens_add_delta`)."""
+    for d, t in lens.local.items():
+        if isinstance(n, ShardedArray):
+            K.lens_add_delta(t, n.local[d])
+        else:
+            K.lens_add(t, n)
 
 
 def sample_logits(logits: ShardedArray, token: Optional[ShardedArray] = None, key=None, at: Optional[ShardedArray] = None,

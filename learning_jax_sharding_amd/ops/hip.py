@@ -20,7 +20,7 @@ import torch
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
            "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "kv_append_q8", "attn_decode_q8", "plan_decode",
-           "lens_add", "skinny",
+           "lens_add", "attn_extend", "attn_extend_q8", "skinny",
            "skinny_plan", "skinny_supported", "set_skinny_waves"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,6 +80,11 @@ _SIGS = {
                          c_void_p],
     "ljs_attn_decode_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
                            c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_int, c_void_p],
+    "ljs_attn_extend": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int,
+                        c_int, c_int, c_int, _LP, _LP, _LP, _LP, c_float, c_void_p],
+    "ljs_attn_extend_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                           c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_void_p],
+    "ljs_extend_max_positions": [],
     "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_launch_plan": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_set_splits": [c_int, c_int],
@@ -215,7 +220,7 @@ def last_launch() -> dict:
     ``gemm_mx_fp8<128,2,fix=1>``, ``gemm_mx8<256,160,4,bf16,2>``, ``quant_mx_rows``, ``quant_mx_cols<tiled>`` /
     ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
     ``grad_sumsq``, ``step_hyper``, ``adam_f32``, ``adam_multi<32>`` / ``adam_multi_dyn<32>`` (the launch's tile height), ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
-    ``attn_decode<G4>``, ``kv_append<rot,q,mx8>``, ``attn_decode<G4,mx8>`` (an MX-fp8 cache), ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
+    ``attn_decode<G4>``, ``kv_append<rot,q,mx8>``, ``attn_decode<G4,mx8>`` (an MX-fp8 cache), ``attn_extend<G4,P2>`` / ``attn_extend<G4,P2,mx8>`` (heads per group, positions per block), ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
     the epilogue parts present)),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
@@ -2763,6 +2768,79 @@ def attn_decode_q8(q, kc, vc, kcs, vcs, lens, scale: float, extra: int = 1):
     lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device)
     _ck(attn_decode_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale, extra), "ljs_attn_decode_q8")
     return o, lse
+
+
+# ---- several query positions per sequence over the cache (attn_extend: decode.hip's EXT instances)
+def extend_max_positions() -> int:
+    """The most query positions per sequence one ``attn_extend`` call takes."""
+    return lib().ljs_extend_max_positions()
+
+
+def attn_extend_raw(q, kc, vc, o, lse, ws, lens, scale: float) -> int:
+    """One ``ljs_attn_extend`` call (the launch, and the merge launch when the plan has more than one split) on
+    the tensors as they are (``lse``: f32 ``(B, T, H)``); returns the launcher's code instead of raising."""
+    B, T, H, _ = q.shape
+    return lib().ljs_attn_extend(_p(q), _p(kc), _p(vc), _p(o), _p(lse), _p(ws), ws.numel() if ws is not None else 0,
+                                 _p(lens), B, T, H, kc.shape[2], kc.shape[1], _longs(_strides3(q)),
+                                 _longs(_strides3(kc)), _longs(_strides3(vc)), _longs(_strides3(o)), float(scale),
+                                 _stream(q))
+
+
+def attn_extend_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale: float) -> int:
+    """One ``ljs_attn_extend_q8`` call on the tensors as they are; returns the launcher's code instead of raising."""
+    B, T, H, _ = q.shape
+    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
+    return lib().ljs_attn_extend_q8(_p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(o), _p(lse), _p(ws),
+                                    ws.numel() if ws is not None else 0, _p(lens), B, T, H, kc.shape[2], kc.shape[1],
+                                    st(q), st(kc), st(vc), st(kcs), st(vcs), st(o), float(scale), _stream(q))
+
+
+def _extend_out(q, Hkv: int, cap: int):
+    """(o, lse (B, T, H), ws) of an extend call on ``q``: the workspace holds ``B T H`` partials per split."""
+    B, T, H, _ = q.shape
+    splits, _ = _decode_launch_plan(B, Hkv, cap)
+    ws = _decode_ws(q.device, B * T * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
+    o = torch.empty((B, T, H, 64), dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty((B, T, H), dtype=torch.float32, device=q.device)
+    return o, lse, ws
+
+
+def attn_extend(q, kc, vc, lens, scale: float):
+    """Attention of ``q`` (B, T, H, 64), ``1 <= T <= 64`` positions that a :func:`kv_append` has just written at rows
+    ``lens[b] .. lens[b] + T - 1``, over the caches: row ``(b, t, h)`` attends to rows ``[0, min(lens[b] + t + 1, cap))``
+    and has the bits :func:`attn_decode` gives ``(b, h)`` with ``extra = t + 1``.  ``(o`` bf16 (B, T, H, 64), ``lse2`` f32
+    (B, H, T)``)``; ``T == 1`` is :func:`attn_decode`'s launches."""
+    B, T, H, _ = q.shape
+    Hkv = kc.shape[2]
+    ok = decode_supported(q, kc, vc) and 1 <= T <= extend_max_positions() and kc.shape == vc.shape \
+        and kc.shape[0] == B and lens is not None and _lens_ok(lens, B) and H % Hkv == 0 \
+        and H // Hkv <= decode_max_group() and scale > 0
+    if not ok:
+        raise NotImplementedError(f"attn_extend kernel: bf16 q (B, T <= {extend_max_positions()}, H, 64) and caches (B, cap, "
+                                  f"Hkv, 64) with 16-byte aligned bases and strides, H / Hkv <= {decode_max_group()}, int32 "
+                                  f"[B] lens; got q {q.dtype} {tuple(q.shape)}, cache {kc.dtype} {tuple(kc.shape)} strides "
+                                  f"{kc.stride()}")
+    o, lse, ws = _extend_out(q, Hkv, kc.shape[1])
+    _ck(attn_extend_raw(q, kc, vc, o, lse, ws, lens, scale), "ljs_attn_extend")
+    return o, lse.permute(0, 2, 1)
+
+
+def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
+    """:func:`attn_extend` over an MX-fp8 cache: the bits of :func:`attn_decode_q8` with ``extra = t + 1``."""
+    B, T, H, _ = q.shape
+    Hkv = kc.shape[2]
+    ok = decode_supported(q) and _q8_cache_ok(kc, vc, kcs, vcs) and 1 <= T <= extend_max_positions() \
+        and kc.shape[0] == B and lens is not None and _lens_ok(lens, B) and H % Hkv == 0 \
+        and H // Hkv <= decode_max_group() and scale > 0
+    if not ok:
+        raise NotImplementedError(f"attn_extend_q8 kernel: bf16 q (B, T <= {extend_max_positions()}, H, 64), uint8 caches (B, "
+                                  f"cap, Hkv, 64) with 16-byte aligned bases and strides and uint8 scales (B, cap, Hkv, 2) "
+                                  f"with even strides, H / Hkv <= {decode_max_group()}, int32 [B] lens; got q {q.dtype} "
+                                  f"{tuple(q.shape)}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}, scales "
+                                  f"{kcs.dtype} {tuple(kcs.shape)} strides {kcs.stride()}")
+    o, lse, ws = _extend_out(q, Hkv, kc.shape[1])
+    _ck(attn_extend_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale), "ljs_attn_extend_q8")
+    return o, lse.permute(0, 2, 1)
 
 
 def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:

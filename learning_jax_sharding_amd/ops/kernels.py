@@ -861,6 +861,55 @@ def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:
     return lens.add_(n)
 
 
+def lens_add_delta(lens: torch.Tensor, delta: torch.Tensor) -> torch.Tensor:
+    """``lens[b] += delta[b]`` in place, ``delta`` an int32 ``(batch,)`` tensor on ``lens``' device (it may be negative:
+    rows beyond the new length are dead and overwritten later).  No host read, so it can be captured."""
+    if delta.dtype != torch.int32 or delta.shape != lens.shape or delta.device != lens.device:
+        raise ValueError(f"lens_add_delta: delta must be an int32 {tuple(lens.shape)} tensor on {lens.device}, got "
+                         f"{delta.dtype} {tuple(delta.shape)} on {delta.device}")
+    return lens.add_(delta)
+
+
+# ---- several new positions per sequence (csrc/kernels/decode.hip, attn_extend).  After an append of T positions at
+# rows lens[b] .. lens[b] + T - 1 that lens does not count yet, position t attends to rows [0, lens[b] + t + 1): by
+# definition the T stacked single-query results, which is what makes greedy speculative decoding exact.
+EXTEND_MAX_POSITIONS = 64
+
+
+def _stack_decode(fn, q, lens):
+    outs = [fn(q[:, t:t + 1], t + 1) for t in range(q.shape[1])]
+    return torch.cat([o for o, _ in outs], dim=1), torch.cat([l for _, l in outs], dim=-1)
+
+
+def attn_extend_reference(q, kc, vc, lens, scale: float):
+    """Plain torch attention of q (B, T, H, D) over a cache: position t is :func:`attn_decode_reference` of ``q[:, t]``
+    with ``extra = t + 1``.  ``(o`` (B, T, H, D), ``lse2`` f32 (B, H, T)``)``."""
+    return _stack_decode(lambda qt, e: attn_decode_reference(qt, kc, vc, lens, scale, extra=e), q, lens)
+
+
+def attn_extend_q8_reference(q, kc, vc, kcs, vcs, lens, scale: float):
+    """:func:`attn_extend_reference` over an MX-fp8 cache: the stacked :func:`attn_decode_q8_reference` results."""
+    return _stack_decode(lambda qt, e: attn_decode_q8_reference(qt, kc, vc, kcs, vcs, lens, scale, extra=e), q, lens)
+
+
+def attn_extend(q, kc, vc, lens, scale: float):
+    """Attention of one device's ``q`` (B, T, H, D) over its caches, a key limit per position: ``(o, lse2)``
+    (:func:`attn_extend_reference`'s semantics).  One HIP launch (and the merge launch of a split key axis) on a
+    GPU; ``T == 1`` is :func:`attn_decode`'s."""
+    G = kv_groups(q, kc, vc)
+    if _hip_decode("attn_extend", [q, kc, vc], lens, G):
+        return _hip().attn_extend(q, kc, vc, lens, scale)
+    return attn_extend_reference(q, kc, vc, lens, scale)
+
+
+def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
+    """:func:`attn_extend` over one device's MX-fp8 caches (:func:`attn_extend_q8_reference`'s semantics)."""
+    G = kv_groups(q, kc, vc)
+    if _hip_decode_q8("attn_extend_q8", [q], (kc, vc, kcs, vcs), lens, G):
+        return _hip().attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale)
+    return attn_extend_q8_reference(q, kc, vc, kcs, vcs, lens, scale)
+
+
 # ----------------------------------------------------------------------------- sampling
 # One token per row of logits: temperature, top-k, top-p, the Gumbel-max draw and the stop-token rule.
 # ``at``, ``pos`` and ``done`` are tensors ON THE DEVICE: nothing below reads them on the host, so a captured
