@@ -235,11 +235,17 @@ __device__ __forceinline__ int mx_exponent(float amax) {
 // change a finite result)
 // 4 e4m3 bytes of two packed bf16 pairs divided by 2^x, in two gfx950 scaled conversions
 // (v_cvt_scalef32_pk_fp8_bf16 with scale 2^x: bit-identical to rounding v * 2^-x with
-// pack4_e4m3, measured on 2^20 pairs by scripts/cvt_scalef_probe.py).  x = -127 (an all-zero
-// block) converts with scale 1 (the values are 0 either way; 2^-127 would be an f32 denormal).
+// pack4_e4m3 -- tests/test_mx_quant_oracle_gpu.py holds every caller of either path to the integer
+// oracle of tests/mx_oracle.py on every finite bf16 pattern, bf16 denormals included).
+// x = -127 is not only the all-zero block: a block with 0 < amax <= 1.75 * 2^-119 has it too and is
+// divided by 2^-127 like any other.  The instruction honours that scale when it is given as the
+// f32 denormal 0x00400000, so the operand is built from its bits and not by an ldexpf, whose
+// result would depend on the denormal mode.
 typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
 typedef short s16x2v_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float mx_scale_pow2(int x) { return x == -127 ? 1.f : ldexpf(1.f, x); }
+__device__ __forceinline__ float mx_scale_pow2(int x) {
+  return __uint_as_float(max(((unsigned)x << 23) + 0x3f800000u, 0x00400000u));  // (x = -127: 0 -> the denormal)
+}
 __device__ __forceinline__ unsigned cvt4_e4m3_bf16(unsigned lo2, unsigned hi2, float sc) {
   s16x2v_t o = {0, 0};
   o = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o, __builtin_bit_cast(bf16x2v_t, lo2), sc, false);

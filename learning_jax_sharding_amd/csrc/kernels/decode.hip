@@ -65,8 +65,9 @@
 // quantize_mx_ref of the bf16 row the bf16 cache would hold (rope's bits first, then the quantiser;
 // kv_append_q8_kernel), the attention is the bf16 attention over the dequantised rows, which are exact
 // bf16 values (attn_decode_kernel<HW, true>: the same grid, plan, partials and merge; only the loads and
-// two scaled conversions per 4 elements differ).  Rows beyond a block's range read zero bytes and a
-// zero scale byte through the descriptors: zeros.
+// two scaled conversions per 4 elements differ).  A zero scale byte is 2^-127, as for dequantize_mx_ref and the
+// block-scaled MFMA: a live row whose block exponent clamped carries it with non-zero bytes.  Rows beyond a
+// block's range read zero bytes (and a zero scale byte) through the descriptors: 0 x 2^-127 = 0.
 #include "rowwise.h"
 
 namespace {
@@ -155,8 +156,8 @@ __device__ __forceinline__ void dec_store_out(bf16_t* o, float* lse, int cc, flo
   if (cc == 0) *lse = l > 0.f ? m + __log2f(l) : INFINITY;
 }
 
-// 2^(e - 127) of an e8m0 byte as the f32 the scaled conversions take (they read its exponent field); the
-// zero byte of a row past the descriptor gives 0 or 2^-127 times zero bytes: zero either way
+// 2^(e - 127) of an e8m0 byte as the f32 the scaled conversions take (they read its exponent field, so the
+// zero byte is 2^-127: tests/test_mx_quant_oracle_gpu.py reads clamped blocks back through attn_decode)
 __device__ __forceinline__ float e8m0_f32(unsigned e) { return __uint_as_float(e << 23); }
 
 // MX8: kc / vc hold e4m3 bytes with one e8m0 scale per 32 elements.  A key row is 64 bytes, the lane's

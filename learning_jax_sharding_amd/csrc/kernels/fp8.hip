@@ -8,6 +8,10 @@
 //
 // Scale rule: OCP MX v1.0's shared exponent floor(log2(amax)) - 8 (8 = emax of e4m3), raised by
 // one when the block max would exceed 448; elements RNE-rounded to e4m3 after division by 2^exp.
+// The exponent clamps at -127 and such a block (0 < amax <= 1.75 * 2^-119) is still divided by
+// 2^-127; nothing saturates and the sign of a zero is kept.  Non-finite inputs are outside the
+// contract: the quantisers need not agree on them (fmaxf skips a NaN, the integer amax picks it).
+// Every quantiser here is held to tests/mx_oracle.py bit for bit (tests/test_mx_quant_oracle_gpu.py).
 //
 // MFMA operand layout (measured with scripts/mfma_f8_layout.py): lane l (g = l >> 4) holds row
 // l & 15, bytes 0-15 = k 16g..16g+15 and bytes 16-31 = k 64+16g..64+16g+15; the scale of

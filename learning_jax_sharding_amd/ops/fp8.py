@@ -89,7 +89,11 @@ def _block_exponent(amax: torch.Tensor) -> torch.Tensor:
 
 
 def quantize_mx_ref(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """x[..., K] -> (e4m3 values as float8_e4m3fn [..., K], int exponents [..., K/32])."""
+    """x[..., K] -> (e4m3 values as float8_e4m3fn [..., K], int exponents [..., K/32]).
+
+    The exponent clamps at -127 and a non-zero block that clamps is still scaled by 2^127 (scale byte 0 is
+    2^-127, never "zeros"); zeros keep their sign.  Non-finite inputs are outside the contract.  Held to the
+    integer oracle of tests/mx_oracle.py on every finite bf16 pattern (tests/test_mx_oracle.py)."""
     K = x.shape[-1]
     assert K % BLOCK == 0, K
     xb = x.float().reshape(*x.shape[:-1], K // BLOCK, BLOCK)
