@@ -30,7 +30,7 @@
 // and does not store the clamped columns.  No load touches memory outside rows [0, N) x columns [0, K)
 // of Wt or rows [0, M) of x.
 //
-// Epilogue, in this order: + bias in f32 (bias f32 or bf16), ReLU, the rounding to bf16 (or the f32
+// Epilogue (skinny_common.h: one function, shared with skinny_mx.hip), in this order: + bias in f32 (bias f32 or bf16), ReLU, the rounding to bf16 (or the f32
 // store), then the residual as the tile kernels add it (gemm.hip apply_res8): bf16(bf16(y) +
 // bf16(res)), res f32 or bf16 with its own leading dimension, bf16 output only.  Alpha is 1; there is
 // no accumulate, no split-K slab, no mask mode and no fused output sum.
@@ -49,18 +49,11 @@
 // The rule rests on this latency / bytes-in-flight argument; the measured figures are in
 // profiles/PERF_NOTES.md ("Skinny GEMM").  It is monotone: W does not grow with N, does not shrink
 // with K or with the CU count.
-#include "common.h"
-#include <string>
+#include "skinny_common.h"
 
 namespace {
 
-constexpr int kSkMaxM = 16;
-constexpr int kSkCols = 16;              // output columns per block
-constexpr int kSkMaxWaves = 16;
 constexpr int kSkUnroll = 8;             // K-steps whose loads a wave has in flight together
-constexpr int kSkWavesPerCu = 8;         // the plan's target
-
-constexpr int kSkBias = 1, kSkBiasF32 = 2, kSkRelu = 4, kSkRes = 8, kSkResF32 = 16, kSkOutF32 = 32;
 
 int g_sk_waves = 0;                      // > 0: a wave count forced by tests
 
@@ -121,59 +114,10 @@ void skinny_kernel(const SkinnyArgs a) {
     xp += kSkUnroll * 32;
   }
 
-  if (W > 1) {
-    part[wave * 64 + lane] = acc;
-    __syncthreads();
-    if (wave != 0) return;
-    acc = part[lane];
-    for (int w = 1; w < W; ++w) acc += part[w * 64 + lane];  // in wave order
-  }
-
-  const int n = n0 + 4 * g, m = r16;
-  if (m >= a.M || n >= a.N) return;                    // (N % 4 == 0: a lane's 4 columns are whole)
-  float v[4] = {acc[0], acc[1], acc[2], acc[3]};
-  if (a.flags & kSkBias) {
-    float b[4];
-    if (a.flags & kSkBiasF32) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) b[e] = reinterpret_cast<const float*>(a.bias)[n + e];
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) b[e] = bf2f(reinterpret_cast<const bf16_t*>(a.bias)[n + e]);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] += b[e];
-  }
-  if (a.flags & kSkRelu) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-  }
-  if (a.flags & kSkOutF32) {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.y) + (long)m * a.ldc + n) = f32x4{v[0], v[1], v[2], v[3]};
-    return;
-  }
-  if (a.flags & kSkRes) {
-    float r[4];
-    if (a.flags & kSkResF32) {
-      const f32x4 rf = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(a.res) + (long)m * a.ldr + n);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) r[e] = rf[e];
-    } else {
-      const u32x2 rb = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(a.res) + (long)m * a.ldr + n);
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        r[2 * e] = __uint_as_float(rb[e] << 16);
-        r[2 * e + 1] = __uint_as_float(rb[e] & 0xffff0000u);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = bf2f(f2bf(v[e])) + bf2f(f2bf(r[e]));
-  }
-  *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(a.y) + (long)m * a.ldc + n) =
-      u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+  if (!skinny_reduce(part, acc, wave, lane, W)) return;    // in wave order
+  const SkinnyEpi e{a.y, a.bias, a.res, a.ldc, a.ldr, a.M, a.N, a.flags};
+  skinny_epilogue(e, acc, r16, n0 + 4 * g);
 }
-
-inline bool sk_waves_ok(int w) { return w == 1 || w == 2 || w == 4 || w == 8 || w == 16; }
 
 inline bool sk_shape_ok(int M, int N, int K) {
   return M >= 1 && M <= kSkMaxM && N >= 8 && N % 8 == 0 && K >= 32 && K % 32 == 0;
@@ -191,24 +135,15 @@ inline void skinny_plan(int N, int K, int cus, int* waves, int* blocks) {
   *blocks = (int)nb;
 }
 
-// "skinny<W,out[,bias][,relu][,res]>": one string per (wave count, flag set), made once
+// "skinny<W,out[,bias][,relu][,res]>"
 const char* skinny_name(int waves, int flags) {
-  static const std::string* table = [] {
-    auto* t = new std::string[5 * 16];
-    const int ws[5] = {1, 2, 4, 8, 16};
-    for (int i = 0; i < 5; ++i)
-      for (int f = 0; f < 16; ++f)
-        t[i * 16 + f] = "skinny<" + std::to_string(ws[i]) + (f & 1 ? ",f32" : ",bf16") + (f & 2 ? ",bias" : "") +
-                        (f & 4 ? ",relu" : "") + (f & 8 ? ",res" : "") + ">";
-    return t;
-  }();
-  const int i = waves == 1 ? 0 : waves == 2 ? 1 : waves == 4 ? 2 : waves == 8 ? 3 : 4;
-  const int f = (flags & kSkOutF32 ? 1 : 0) | (flags & kSkBias ? 2 : 0) | (flags & kSkRelu ? 4 : 0) |
-                (flags & kSkRes ? 8 : 0);
-  return table[i * 16 + f].c_str();
+  static const std::string* table = sk_make_names("skinny");
+  return sk_name(table, waves, flags);
 }
 
 }  // namespace
+
+int ljs_skinny_forced_waves() { return g_sk_waves; }
 
 // out[0] = waves per block, out[1] = blocks of (M, N, K) on a device of `cus` compute units: pure.
 // hipErrorInvalidValue for a shape outside 1 <= M <= 16, K % 32 == 0, N % 8 == 0.
@@ -219,7 +154,7 @@ LJS_API int ljs_skinny_plan(int M, int N, int K, int cus, int* out) {
 }
 
 // tests: force `n` waves per block (1, 2, 4, 8 or 16; anything else is refused and changes nothing);
-// n <= 0 restores the plan
+// n <= 0 restores the plan.  It holds for skinny_mx.hip's kernel too.
 LJS_API int ljs_skinny_set_waves(int n) {
   if (n > 0 && !sk_waves_ok(n)) return (int)hipErrorInvalidValue;
   g_sk_waves = n > 0 ? n : 0;
@@ -235,13 +170,10 @@ LJS_API int ljs_skinny_set_waves(int n) {
 LJS_API int ljs_skinny_bf16(const void* x, const void* wt, void* y, const void* bias, const void* res, int M, int N,
                             int K, long lda, long ldb, long ldc, long res_ld, int out_f32, int bias_f32, int res_f32,
                             int relu, hipStream_t st) {
-  if (!sk_shape_ok(M, N, K) || !x || !wt || !y) return (int)hipErrorInvalidValue;
-  if (lda < K || ldb < K || ldc < N || lda % 8 || ldb % 8 || ldc % 4 || (((uintptr_t)x) & 15u) ||
-      (((uintptr_t)wt) & 15u) || (((uintptr_t)y) & (out_f32 ? 15u : 7u)))
+  if (!sk_shape_ok(M, N, K) || !x || !wt) return (int)hipErrorInvalidValue;
+  if (lda < K || ldb < K || lda % 8 || ldb % 8 || (((uintptr_t)x) & 15u) || (((uintptr_t)wt) & 15u))
     return (int)hipErrorInvalidValue;
-  if (bias && (((uintptr_t)bias) & (bias_f32 ? 3u : 1u))) return (int)hipErrorInvalidValue;
-  if (res && (out_f32 || res_ld < N || res_ld % 4 || (((uintptr_t)res) & (res_f32 ? 15u : 7u))))
-    return (int)hipErrorInvalidValue;
+  if (!sk_epi_ok(y, bias, res, N, ldc, res_ld, out_f32, bias_f32, res_f32)) return (int)hipErrorInvalidValue;
   SkinnyArgs a{};
   a.x = (const bf16_t*)x;
   a.wt = (const bf16_t*)wt;
@@ -250,8 +182,7 @@ LJS_API int ljs_skinny_bf16(const void* x, const void* wt, void* y, const void* 
   a.res = res;
   a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = res_ld;
   a.M = M; a.N = N; a.K = K;
-  a.flags = (bias ? kSkBias : 0) | (bias && bias_f32 ? kSkBiasF32 : 0) | (relu ? kSkRelu : 0) | (res ? kSkRes : 0) |
-            (res && res_f32 ? kSkResF32 : 0) | (out_f32 ? kSkOutF32 : 0);
+  a.flags = sk_epi_flags(bias, res, out_f32, bias_f32, res_f32, relu);
   int waves, blocks;
   skinny_plan(N, K, ljs_device_cus(), &waves, &blocks);
   if (g_sk_waves > 0) waves = g_sk_waves;

@@ -32,6 +32,7 @@ from .. import dtypes as _dt
 from ..array import ShardedArray, device_put
 from ..ops import core
 from ..ops import kernels as K
+from ..ops import linear as _lin
 from ..runtime.devices import get_device, process_index
 from ..sharding.shardings import Sharding, default_sharding, sharding_from_tile
 from ..utils import tree as _tree
@@ -298,7 +299,7 @@ def _sampling_request(V: int, key, temperature, top_k, top_p, eos_id, pad_id, st
 
 
 def _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p, eos,
-                      pad_id, stop_poll) -> torch.Tensor:
+                      pad_id, stop_poll, weight_quant=None) -> torch.Tensor:
     """``generate`` with a key and / or stop tokens: the prefill and the step end in ``sample_logits``.  ``done`` (int32
     (batch,), next to ``cache.lens``) is made before the capture and donated with the token."""
     from ..spmd.api import jit
@@ -329,7 +330,8 @@ def _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, ke
             # outside the graph: one host read of done every stop_poll steps
             if eos and stop_poll and s % int(stop_poll) == 0 and all(bool(t.all()) for t in done.local.values()):
                 break
-            st, cache = step_j(params, st, cache)
+            with _lin.weight_quant(weight_quant):
+                st, cache = step_j(params, st, cache)
             kept.append({d: t.clone() for d, t in st[0].local.items()})
         out = [ShardedArray(tok.shape, tok.dtype, tok.sharding, loc).to_torch().reshape(B, 1) for loc in kept]
     out = torch.cat(out, dim=1).long()
@@ -352,7 +354,7 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
              max_len: Optional[int] = None, cache_sharding: Optional[Sharding] = None, *, key=None,
              temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id=None,
              pad_id: Optional[int] = None, stop_poll: int = 16, return_lens: bool = False,
-             cache_quant: Optional[str] = None, draft=None, draft_tokens: int = 4):
+             cache_quant: Optional[str] = None, draft=None, draft_tokens: int = 4, weight_quant: Optional[str] = None):
     """Decoding: ``max_new_tokens`` tokens after each prompt of ``ids`` (batch, T), as an int64 host tensor
     ``[batch, max_new_tokens]``; greedy without a ``key``.
 
@@ -378,6 +380,14 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
     count of a step unchanged.  The prefill attends to the prompt's unquantised K / V, so the first token is the
     unquantised run's; the later ones attend to fp8 keys and values and may differ from it.
 
+    ``weight_quant="mxfp8"``: every decode step, the LM head included, runs under ``ops.linear.weight_quant``: its dense
+    layers read MX-fp8 weights (``skinny_mx<`` launches in place of ``skinny<``, the launch count of a step unchanged)
+    wherever ``K % 128 == 0`` and the weight is ``shadow.mx_eligible``.  The prefill has more than 16 rows, runs on the tile
+    GEMMs and reads bf16 weights, so the first token has seen bf16 weights and the later ones fp8 weights.  It composes
+    with ``cache_quant``, ``key``, the filters and stop tokens; any other value, and ``weight_quant`` together with ``draft``
+    (the verification call has more than 16 rows and would read other weights than the single steps), raise
+    ``ValueError`` before any launch.
+
     ``draft=(draft_model, draft_params)``: greedy speculative decoding.  Per round the draft (a cheaper model of the same
     vocabulary, with a cache and a prefill of its own) proposes ``draft_tokens`` tokens and the target checks them in ONE
     cached call on ``draft_tokens + 1`` positions (``extend=True``), keeping the longest prefix it would have decoded itself
@@ -395,6 +405,11 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
         raise ValueError(f"generate: max_new_tokens must be positive, got {max_new_tokens}")
     if cache_quant not in (None, QUANT_MXFP8):
         raise ValueError(f"generate: cache_quant must be None or {QUANT_MXFP8!r}, got {cache_quant!r}")
+    if weight_quant not in (None, _lin.WEIGHT_QUANT_MXFP8):
+        raise ValueError(f"generate: weight_quant must be None or {_lin.WEIGHT_QUANT_MXFP8!r}, got {weight_quant!r}")
+    if weight_quant is not None and draft is not None:
+        raise ValueError("generate: weight_quant does not go with draft= (the verification call has more than 16 rows and "
+                         "would read bf16 weights where the single steps read fp8 ones)")
     B, T = ids.shape
     plens = _host_lens(prompt_lens, B, T)
     spec = _draft_request(model, draft, draft_tokens, key, eos_id) if draft is not None else None
@@ -420,7 +435,7 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
         return (out, torch.full((B,), max_new_tokens, dtype=torch.long), mean) if return_lens else out
     if key is not None or eos:
         out = _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p,
-                                eos, pad_id, stop_poll)
+                                eos, pad_id, stop_poll, weight_quant)
         return (out, _stop_lens(out, eos)) if return_lens else out
 
     def prefill(p, x, c, n):
@@ -443,7 +458,8 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
             # the step's token buffers are rewritten at every step: keep a copy of each, on the devices
             kept = [{d: t.clone() for d, t in tok.local.items()}]
             for _ in range(max_new_tokens - 1):
-                tok, cache = step_j(params, tok, cache)
+                with _lin.weight_quant(weight_quant):
+                    tok, cache = step_j(params, tok, cache)
                 kept.append({d: t.clone() for d, t in tok.local.items()})
             out = [ShardedArray(tok.shape, tok.dtype, tok.sharding, loc).to_torch() for loc in kept]
     out = torch.cat([t.reshape(B, 1) for t in out], dim=1).long()

@@ -21,7 +21,8 @@ __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", 
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
            "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "kv_append_q8", "attn_decode_q8", "plan_decode",
            "lens_add", "attn_extend", "attn_extend_q8", "skinny",
-           "skinny_plan", "skinny_supported", "set_skinny_waves"]
+           "skinny_plan", "skinny_supported", "set_skinny_waves", "skinny_mx", "skinny_mx_raw", "skinny_mx_plan",
+           "skinny_mx_supported"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -92,6 +93,9 @@ _SIGS = {
     "ljs_skinny_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_skinny_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long, c_long,
                         c_long, c_int, c_int, c_int, c_int, c_void_p],
+    "ljs_skinny_mx_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "ljs_skinny_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long,
+                      c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_void_p],
     "ljs_decode_key_tile": [],
     "ljs_decode_part_floats": [],
     "ljs_decode_max_group": [],
@@ -221,7 +225,7 @@ def last_launch() -> dict:
     ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
     ``grad_sumsq``, ``step_hyper``, ``adam_f32``, ``adam_multi<32>`` / ``adam_multi_dyn<32>`` (the launch's tile height), ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
     ``attn_decode<G4>``, ``kv_append<rot,q,mx8>``, ``attn_decode<G4,mx8>`` (an MX-fp8 cache), ``attn_extend<G4,P2>`` / ``attn_extend<G4,P2,mx8>`` (heads per group, positions per block), ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
-    the epilogue parts present)),
+    the epilogue parts present; ``skinny_mx<...>`` likewise on MX-fp8 weights)),
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
     it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
@@ -2929,6 +2933,67 @@ def skinny(x: torch.Tensor, wt: torch.Tensor, out: torch.Tensor, M: int, N: int,
                                   f"aligned rows, a bf16 / f32 output; got M={M} N={N} K={K} lda={lda} ldb={ldb} "
                                   f"ldc={ldc} x {x.dtype} wt {wt.dtype} out {out.dtype}")
     _ck(skinny_raw(x, wt, out, M, N, K, lda, ldc, bias, relu, res, res_ld, ldb), "ljs_skinny_bf16")
+
+
+# ---- the same GEMM on MX-fp8 weights (csrc/kernels/skinny_mx.hip): e4m3 codes q [N][K] and e8m0 scale bytes
+# s [N][K / 32], the "QT" shadow of ops/shadow.get_mx; x stays bf16 (W8A16).  set_skinny_waves holds here too.
+def skinny_mx_plan(M: int, N: int, K: int, cus: int = 256):
+    """``(waves_per_block, blocks)`` of :func:`skinny_mx` on a device of ``cus`` compute units (``ljs_skinny_mx_plan``:
+    needs the library, not a GPU): :func:`skinny_plan` with 128-code lines in place of step pairs.  Pure, and ``M``
+    only has to lie in 1 .. 16.  ValueError outside ``1 <= M <= 16, K % 128 == 0, N % 8 == 0``."""
+    out = (c_int * 2)()
+    if lib().ljs_skinny_mx_plan(int(M), int(N), int(K), int(cus), out) != 0:
+        raise ValueError(f"skinny_mx_plan: M={M}, N={N}, K={K}, cus={cus}: 1 <= M <= {SKINNY_MAX_M}, K % 128 == 0, "
+                         "N % 8 == 0 and cus >= 1 are required")
+    return int(out[0]), int(out[1])
+
+
+def skinny_mx_supported(M: int, N: int, K: int, lda: int, ldq: int, lds: int, ldc: int, out_dtype: torch.dtype,
+                        x_addr: int = 0, q_addr: int = 0, s_addr: int = 0, out_addr: int = 0,
+                        bias_dtype: Optional[torch.dtype] = None, bias_addr: int = 0,
+                        res_dtype: Optional[torch.dtype] = None, res_ld: int = 0, res_addr: int = 0,
+                        x_dtype: torch.dtype = torch.bfloat16, q_dtype: torch.dtype = torch.uint8,
+                        s_dtype: torch.dtype = torch.uint8) -> bool:
+    """``ljs_skinny_mx``'s gate as a pure predicate: ``1 <= M <= 16``, ``K % 128 == 0``, ``N % 8 == 0``; bf16 x and uint8
+    codes with 16-byte aligned rows, uint8 scales with 4-byte aligned rows of at least ``K / 32``; the output, bias
+    and residual as :func:`skinny_supported` takes them."""
+    if not (K >= 128 and K % 128 == 0 and q_dtype == torch.uint8 and s_dtype == torch.uint8):
+        return False
+    if ldq < K or ldq % 16 or q_addr % 16 or lds < K // 32 or lds % 4 or s_addr % 4:
+        return False
+    return skinny_supported(M, N, K, lda, K, ldc, out_dtype, x_addr, 0, out_addr, bias_dtype, bias_addr, res_dtype,
+                            res_ld, res_addr, x_dtype)
+
+
+def skinny_mx_raw(x, q, s, out, M: int, N: int, K: int, lda: int, ldc: int, bias=None, relu: bool = False, res=None,
+                  res_ld: int = 0, ldq: Optional[int] = None, lds: Optional[int] = None) -> int:
+    """One ``ljs_skinny_mx`` call on the operands as they are (any of them may be None: a null operand); returns the
+    launcher's code (non-zero: rejected, nothing launched or recorded) instead of raising."""
+    f32 = torch.float32
+    return lib().ljs_skinny_mx(_p(x), _p(q), _p(s), _p(out), _p(bias), _p(res), int(M), int(N), int(K), int(lda),
+                               int(K if ldq is None else ldq), int(K // 32 if lds is None else lds), int(ldc),
+                               int(res_ld), int(out.dtype == f32), int(bias is not None and bias.dtype == f32),
+                               int(res is not None and res.dtype == f32), int(bool(relu)), _stream(out))
+
+
+def skinny_mx(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, out: torch.Tensor, M: int, N: int, K: int, lda: int,
+              ldc: int, bias: Optional[torch.Tensor] = None, relu: bool = False, res: Optional[torch.Tensor] = None,
+              res_ld: int = 0, ldq: Optional[int] = None, lds: Optional[int] = None) -> None:
+    """``out[m][n] = epi(sum_k x[m][k] W_hat[n][k])``, ``W_hat[n][k] = e4m3(q[n][k]) * 2^(s[n][k // 32] - 127)``, for ``1 <=
+    M <= 16`` (:func:`~.kernels.skinny_mx_reference` states it in torch): bf16 ``x``, uint8 codes ``q`` (row stride ``ldq``,
+    default ``K``) and scale bytes ``s`` (row stride ``lds``, default ``K / 32``), :func:`skinny`'s output and epilogue.  One
+    launch, deterministic, no workspace.  Raises for anything :func:`skinny_mx_supported` refuses."""
+    ldq, lds = K if ldq is None else ldq, K // 32 if lds is None else lds
+    ok = all(t is None or t.is_cuda for t in (x, q, s, out, bias, res)) and skinny_mx_supported(
+        M, N, K, lda, ldq, lds, ldc, out.dtype, x.data_ptr(), q.data_ptr(), s.data_ptr(), out.data_ptr(),
+        None if bias is None else bias.dtype, 0 if bias is None else bias.data_ptr(),
+        None if res is None else res.dtype, res_ld, 0 if res is None else res.data_ptr(), x.dtype, q.dtype, s.dtype)
+    if not ok:
+        raise NotImplementedError(f"skinny_mx kernel: bf16 GPU x [M <= 16][K % 128 == 0], uint8 codes [N % 8 == 0][K] with "
+                                  f"16-byte aligned rows and uint8 scales [N][K / 32] with 4-byte aligned rows, a bf16 / "
+                                  f"f32 output; got M={M} N={N} K={K} lda={lda} ldq={ldq} lds={lds} ldc={ldc} x {x.dtype} "
+                                  f"q {q.dtype} s {s.dtype} out {out.dtype}")
+    _ck(skinny_mx_raw(x, q, s, out, M, N, K, lda, ldc, bias, relu, res, res_ld, ldq, lds), "ljs_skinny_mx")
 
 
 # ============================================================================ optimizer

@@ -18,7 +18,9 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-__all__ = ["cast", "reduce_sum", "dot_general", "linear", "softmax", "attention", "use_hip"]
+from ..spmd import state as _state
+
+__all__ = ["cast", "reduce_sum", "dot_general", "linear", "softmax", "attention", "use_hip", "skinny_mx_reference"]
 
 _LOW = (torch.bfloat16, torch.float16)
 
@@ -431,6 +433,28 @@ def dot_general(a: torch.Tensor, b: torch.Tensor, lc, rc, lb, rb, out_dtype: tor
     return C.reshape(out_shape)
 
 
+def skinny_mx_reference(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                        relu: bool = False, res: Optional[torch.Tensor] = None,
+                        out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Plain torch statement of ``hip.skinny_mx`` (weight-only MX-fp8, W8A16): ``y = epi(bf16(x) @ W_hat^T)`` with f32
+    accumulation, ``W_hat[n][k] = e4m3(q[n][k]) * 2^(s[n][k // 32] - 127)`` from the uint8 codes ``q [N][K]`` and scale bytes
+    ``s [N][K / 32]`` (an exact bf16 value for every scale the quantiser produces from finite weights); x ``[M][K]`` is
+    rounded to bf16 and never quantised.  ``epi``, in this order: ``+ bias`` in f32, ReLU, one rounding to ``out_dtype``,
+    then the residual as ``bf16(bf16(y) + bf16(res))`` (bf16 output only)."""
+    from .fp8 import dequantize_mx_ref
+    w_hat = dequantize_mx_ref(q.view(torch.float8_e4m3fn), s.to(torch.int32) - 127)       # [N][K] f32
+    y = x.to(torch.bfloat16).float() @ w_hat.t()
+    if bias is not None:
+        y = y + bias.float()
+    if relu:
+        y = torch.relu(y)
+    if res is None:
+        return y.to(out_dtype)
+    if out_dtype != torch.bfloat16:
+        raise ValueError("skinny_mx_reference: a residual takes a bf16 output")
+    return (y.to(torch.bfloat16).float() + res.to(torch.bfloat16).float()).to(torch.bfloat16)
+
+
 def linear(x: torch.Tensor, ws: Sequence[torch.Tensor], b: Optional[torch.Tensor], compute_dtype: torch.dtype,
            relu: bool = False, out_dtype: Optional[torch.dtype] = None, fp8: bool = False,
            residual: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
@@ -447,6 +471,11 @@ def linear(x: torch.Tensor, ws: Sequence[torch.Tensor], b: Optional[torch.Tensor
         return outs
     if use_hip(x):
         return _hip().linear(x, list(ws), b, compute_dtype, relu, out_dtype, residual=residual)
+    if compute_dtype == torch.bfloat16 and _state.weight_quant() is not None:
+        # ops.linear.weight_quant on a host device: the calls a GPU would run on skinny_mx, on its reference
+        from . import linear as _lin
+        if _lin.skinny_mx_host_route(x, ws, b):
+            return _lin.linear(x, list(ws), b, relu, out_dtype, residual=residual, skinny=True)
     if residual is not None:
         outs = linear(x, ws, b, compute_dtype, relu, out_dtype)
         return [outs[0] + residual.to(outs[0].dtype)] + outs[1:]

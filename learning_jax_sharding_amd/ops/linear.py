@@ -41,8 +41,9 @@ import torch
 
 from . import hip
 from . import shadow
+from ..spmd import state as _state
 
-__all__ = ["linear"]
+__all__ = ["linear", "weight_quant"]
 
 import weakref
 
@@ -1053,17 +1054,89 @@ def skinny_route(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
     return not swap and big == sorted(big)
 
 
+WEIGHT_QUANT_MXFP8 = "mxfp8"
+
+
+@contextlib.contextmanager
+def weight_quant(mode: Optional[str]):
+    """Inside: dense layers that run on the skinny GEMM (:func:`skinny_route`) read their weights as MX-fp8 -- the
+    "QT" shadows of :mod:`.shadow`, e4m3 codes with one e8m0 scale per 32 elements along K -- when ``K % 128 == 0``
+    and the weights are ``shadow.mx_eligible`` (or MX proxies): one ``skinny_mx<`` launch (``hip.skinny_mx``) in place
+    of the ``skinny<`` one, x still bf16 (W8A16, ``kernels.skinny_mx_reference``).  Everything else is unchanged,
+    launch for launch: more than 16 rows, grad enabled, other K, ineligible weights.  Host devices run the
+    reference on ``fp8.quantize_mx_ref`` of the bf16 transposed weight for the same calls, and so does a GPU under
+    ``LJS_SKINNY_MX=0``, on the shadows.  ``jit`` keys its traced and captured steps by the mode.  ``None``: off."""
+    if mode not in (None, WEIGHT_QUANT_MXFP8):
+        raise ValueError(f"weight_quant: the mode must be None or {WEIGHT_QUANT_MXFP8!r}, got {mode!r}")
+    with _state.weight_quant_mode(mode):
+        yield
+
+
+def _mx_weight_ok(w: torch.Tensor) -> bool:
+    if not w.is_cuda:     # a host device: shadow.mx_eligible's shape rule
+        return w.dim() == 2 and w.dtype == torch.float32 and w.is_contiguous() and w.shape[0] % 64 == 0 \
+            and w.shape[1] % 64 == 0
+    e = shadow.entry(w, create=False)
+    if e is not None and e.proxy:
+        return e.mx is not None and "QT" in e.mx
+    return shadow.mx_eligible(w)
+
+
+def skinny_mx_weights(x: torch.Tensor, ws: Sequence[torch.Tensor]) -> bool:
+    """Whether a call :func:`skinny_route` accepts reads MX-fp8 weights: the :func:`weight_quant` mode is on, ``K % 128
+    == 0`` and every weight has "QT" shadows (MX proxies: one weight per call, they hold buffers of their own)."""
+    return (_state.weight_quant() == WEIGHT_QUANT_MXFP8 and x.shape[-1] % 128 == 0 and all(_mx_weight_ok(w) for w in ws)
+            and (len(ws) == 1 or not any(shadow.is_proxy(w) for w in ws)))
+
+
+def skinny_mx_host_route(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
+    """:func:`skinny_route` and :func:`skinny_mx_weights` for a host activation: what a GPU would run on ``skinny_mx<``."""
+    K = x.shape[-1]
+    M = x.numel() // max(1, K)
+    return (not torch.is_grad_enabled() and 1 <= M <= hip.SKINNY_MAX_M and not x.is_cuda
+            and x.dtype in (torch.float32, torch.bfloat16) and weights_supported(x, ws, b) and skinny_enabled()
+            and x.is_contiguous() and skinny_mx_weights(x, ws))
+
+
+def skinny_mx_kernel_enabled() -> bool:
+    # LJS_SKINNY_MX=0: under weight_quant a GPU runs kernels.skinny_mx_reference on the same shadows instead of
+    # the skinny_mx kernel (an A/B baseline and an escape hatch)
+    return os.environ.get("LJS_SKINNY_MX", "1") != "0"
+
+
+def _skinny_mx_launch(xb, ws, out, M, N, K, bias, relu, r2, r_ld) -> None:
+    """``out = epi(xb @ W_hat^T)`` on the MX-fp8 weights of ``ws``: the kernel, or its reference."""
+    from . import fp8, kernels
+    nw = len(ws)
+    if xb.is_cuda:
+        q, s = shadow.get_mx(ws[0], "QT") if nw == 1 else shadow.get_mx_stacked(ws)
+        if skinny_mx_kernel_enabled():
+            hip.skinny_mx(xb, q, s, out, M, nw * N, K, K, nw * N, bias=bias, relu=relu, res=r2, res_ld=r_ld)
+            return
+    else:
+        wt = torch.cat([w.to(torch.bfloat16).t() for w in ws]).contiguous()       # the "T" shadows' values
+        qv, ex = fp8.quantize_mx_ref(wt)
+        q, s = qv.view(torch.uint8), (ex + 127).to(torch.uint8)
+    out.copy_(kernels.skinny_mx_reference(xb, q, s, bias, relu, r2, out.dtype))
+
+
 def _linear_skinny(x, ws, b, relu, out_dtype, res) -> List[torch.Tensor]:
     """The forward of :class:`_Linear` for at most 16 rows without a backward: the same bf16 rounding
     of x, the same weight shadows, the same column views of one ``[M][nw * N]`` buffer, one
-    ``skinny<`` launch.  No attention fusion, no fused output sum, no ReLU registration."""
+    ``skinny<`` launch.  No attention fusion, no fused output sum, no ReLU registration.  Under
+    :func:`weight_quant` (:func:`skinny_mx_weights`) the launch is ``skinny_mx<`` on the MX-fp8 shadows."""
     K = x.shape[-1]
     M = x.numel() // K
     nw, N = len(ws), ws[0].shape[1]
     x2 = x.reshape(-1, K)
-    xb = _bf16(x2 if x2.is_contiguous() else x2.contiguous())
+    mx = skinny_mx_weights(x, ws)
+    if x.is_cuda:
+        xb = _bf16(x2 if x2.is_contiguous() else x2.contiguous())
+    else:
+        xb = x2.to(torch.bfloat16)
     take_pending_waits(x.device)
-    wt = shadow.get(ws[0], "T") if nw == 1 else shadow.get_stacked(ws)   # [nw * N][K]
+    if not mx:
+        wt = shadow.get(ws[0], "T") if nw == 1 else shadow.get_stacked(ws)   # [nw * N][K]
     od = out_dtype if out_dtype in (torch.bfloat16, torch.float32) else torch.float32
     out = torch.empty((M, nw * N), dtype=od, device=x.device)
     bias = None
@@ -1079,8 +1152,11 @@ def _linear_skinny(x, ws, b, relu, out_dtype, res) -> List[torch.Tensor]:
         r_ld = r2.stride(0)
     if xb.data_ptr() % 16:      # (a bf16 view that starts inside a 16-byte chunk)
         xb = xb.clone()
-    hip.skinny(xb, wt, out, M, nw * N, K, K, nw * N, bias=bias, relu=relu, res=r2, res_ld=r_ld)
-    ys = [out[:, i * N:(i + 1) * N].view(tuple(x.shape[:-1]) + (N,)) for i in range(nw)]
+    if mx:
+        _skinny_mx_launch(xb, ws, out, M, N, K, bias, relu, r2, r_ld)
+    else:
+        hip.skinny(xb, wt, out, M, nw * N, K, K, nw * N, bias=bias, relu=relu, res=r2, res_ld=r_ld)
+    ys =[out[:, i * N:(i + 1) * N].view(tuple(x.shape[:-1]) + (N,)) for i in range(nw)]
     if res is not None and r2 is None:
         ys = [ys[0] + res.to(ys[0].dtype)]
     if od != out_dtype:

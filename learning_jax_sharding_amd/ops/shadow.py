@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-__all__ = ["get", "get_stacked", "get_mx", "mx_eligible", "entry", "adopt", "mark_fresh", "kinds_of", "register_proxy",
+__all__ = ["get", "get_stacked", "get_mx", "get_mx_stacked", "mx_eligible", "entry", "adopt", "mark_fresh", "kinds_of", "register_proxy",
            "register_mx_proxy", "is_proxy"]
 
 
@@ -205,6 +205,39 @@ def get_mx(w: torch.Tensor, kind: str):
             fp8.quant_rows(w, out=(q, s))
         e.versions[kind] = e.versions[kind + "s"] = w._version
     return q, s
+
+
+def get_mx_stacked(ws: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(q [n N][K], s [n N][K / 32])``: the "QT" MX-fp8 shadows of same-shape weights as ONE code buffer and ONE scale
+    buffer (a fused projection's operand for ``hip.skinny_mx``), as :func:`get_stacked` keeps the bf16 ones.
+
+    The first call moves the weights' "QT" shadows into consecutive slices of two allocations; the fused Adam then
+    writes them there, and a weight whose version changed otherwise is re-quantised into its slice.  Gathered-weight
+    proxies hold buffers of their own and are not taken."""
+    es = [entry(w) for w in ws]
+    if any(e.proxy for e in es):
+        raise RuntimeError("stacked MX-fp8 shadows of gathered-weight proxies are not available")
+    K, N = ws[0].shape
+    n, kb = len(ws), K // 32
+    qs, ss = [e.bufs.get("QT") for e in es], [e.bufs.get("QTs") for e in es]
+    ok = all(q is not None and s is not None for q, s in zip(qs, ss)) and all(
+        q.data_ptr() == qs[0].data_ptr() + i * N * K and s.data_ptr() == ss[0].data_ptr() + i * N * kb
+        for i, (q, s) in enumerate(zip(qs, ss)))
+    if not ok:
+        gq = torch.empty((n, N, K), dtype=torch.uint8, device=ws[0].device)
+        gs = torch.empty((n, N, kb), dtype=torch.uint8, device=ws[0].device)
+        for i, (w, e) in enumerate(zip(ws, es)):
+            fresh = qs[i] is not None and ss[i] is not None and e.versions.get("QT") == w._version
+            if fresh:
+                gq[i].copy_(qs[i])
+                gs[i].copy_(ss[i])
+            e.bufs["QT"], e.bufs["QTs"] = gq[i], gs[i]
+            if not fresh:
+                e.versions["QT"] = e.versions["QTs"] = -1
+    for w in ws:
+        get_mx(w, "QT")                       # (re-quantises a stale slice in place)
+    q0, s0 = es[0].bufs["QT"], es[0].bufs["QTs"]
+    return q0.as_strided((n * N, K), (K, 1)), s0.as_strided((n * N, kb), (kb, 1))
 
 
 def get_stacked(ws: Sequence[torch.Tensor]) -> torch.Tensor:

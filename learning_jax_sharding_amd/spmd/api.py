@@ -131,7 +131,10 @@ class Jitted:
                 skey.append((i, a))
             except TypeError:
                 skey.append((i, id(a)))
-        return (td, tuple(sig), tuple(skey))
+        # (the weight-quantisation mode decides which kernels the function launches: a step traced or captured
+        # without it is not replayed with it)
+        wq = _state.weight_quant()
+        return (td, tuple(sig), tuple(skey)) + ((wq,) if wq is not None else ())
 
     def _run(self, args, kwargs):
         dyn, static = self._split(args)
@@ -174,7 +177,7 @@ class Jitted:
     # ------------------------------------------------------------------ call
     def __call__(self, *args, **kwargs):
         fast = self._fast
-        if fast is not None and not kwargs and len(args) == len(fast[0]) and all(
+        if fast is not None and not kwargs and len(args) == len(fast[0]) and fast[3] == _state.weight_quant() and all(
                 a is b for a, b in zip(args, fast[0])):
             # the very same argument objects as the last replay (e.g. a train loop feeding the
             # state the graph returned): same leaves, same copies - skip signature and checks.
@@ -273,7 +276,7 @@ class Jitted:
         for t, s in copies:
             t.copy_(s)
         cap.graph.replay()
-        self._fast = (tuple(args), cap, copies)
+        self._fast = (tuple(args), cap, copies, _state.weight_quant())
         return cap.out_tree
 
     def lower(self, *args, **kwargs) -> Lowered:

@@ -61,6 +61,22 @@ def is_donated(t) -> bool:
     return bool(s) and id(t) in s
 
 
+def weight_quant():
+    """The weight-quantisation mode of the dense layers run now (``ops.linear.weight_quant``): None or "mxfp8".  It
+    changes which kernels a function launches, so ``jit`` keys its traced and captured steps by it."""
+    return getattr(_TLS, "weight_quant", None)
+
+
+@contextmanager
+def weight_quant_mode(mode):
+    prev = getattr(_TLS, "weight_quant", None)
+    _TLS.weight_quant = mode
+    try:
+        yield
+    finally:
+        _TLS.weight_quant = prev
+
+
 def in_user_code() -> bool:
     """True while a jitted function's own body runs (not the jit's argument / output handling)."""
     return getattr(_TLS, "user", 0) > 0
