@@ -50,6 +50,13 @@ _SIGS = {
                      c_long, c_long, c_long, c_int, c_void_p],
     "ljs_attn_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP,
                      c_float, c_int, c_int, c_void_p],
+    "ljs_attn128_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP,
+                        _LP, _LP, c_float, c_int, c_int, c_void_p],
+    "ljs_attn128_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                        c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_int, c_int,
+                        c_void_p],
+    "ljs_attn128_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p), _LP,
+                         ctypes.POINTER(c_int), ctypes.c_char_p, c_int],
     "ljs_attn_set_trace": [c_void_p],
     "ljs_attn_set_trace_steps": [c_void_p],
     "ljs_qkv_attn_fwd": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
@@ -2188,6 +2195,30 @@ def attn_plan(kind: str, B: int, Sq: int, Sk: int, H: int, *, causal: bool = Fal
             "nqb": out[14]}
 
 
+_ATTN128_ADDRS = ("q", "k", "v", "o", "lse", "dout", "dq", "dk", "dv")
+_ATTN128_STRIDES = ("q", "k", "v", "o", "dout", "dq", "dk", "dv")
+
+
+def attn128_plan(kind: str, B: int, Sq: int, Sk: int, H: int, Hkv: int, *, causal: bool = False, q_offset: int = 0,
+                 strides=None, addrs=None) -> dict:
+    """What ``ljs_attn128_fwd`` (``kind`` "fwd") / ``ljs_attn128_bwd`` ("bwd") would launch for head_dim
+    128 operands of this shape (``ljs_attn128_plan``: the launcher's own plan step; needs the library,
+    not a GPU).  ``strides`` / ``addrs``: (batch, seq, head) strides and addresses by operand name (q,
+    k, v, o, lse, dout, dq, dk, dv), the rest dense and 16-byte aligned.  No rule reads ``q_offset``.
+    Returns ``err`` and ``launches`` (the :func:`last_launch` keys name, grid, blocks, block)."""
+    strides, addrs = strides or {}, addrs or {}
+    heads = {"k": Hkv, "v": Hkv, "dk": Hkv, "dv": Hkv}
+    rows = {"k": Sk, "v": Sk, "dk": Sk, "dv": Sk}
+    st = [s for n in _ATTN128_STRIDES
+          for s in strides.get(n) or (rows.get(n, Sq) * heads.get(n, H) * 128, heads.get(n, H) * 128, 128)]
+    ad = (c_void_p * len(_ATTN128_ADDRS))(*[addrs.get(n, 4096) for n in _ATTN128_ADDRS])
+    out, name = (c_int * 4)(), ctypes.create_string_buffer(64)
+    lib().ljs_attn128_plan(("fwd", "bwd").index(kind), B, Sq, Sk, H, Hkv, int(causal), ad, _longs(st), out, name,
+                           len(name))
+    launches = [{"name": name.value.decode(), "grid": (out[2], 1, 1), "blocks": out[2], "block": out[3]}] * out[1]
+    return {"err": out[0], "launches": launches}
+
+
 # ---------------------------------------------------------------------------- fused projection
 # The Q/K/V projection GEMM of a self-attention block with a 256-token sequence can run the
 # attention forward of each (batch, head) in the same kernel (ljs_qkv_attn_fwd): ops/linear.py
@@ -2394,10 +2425,22 @@ def gqa_reduce(dkx: torch.Tensor, dvx: torch.Tensor, dk: torch.Tensor, dv: torch
     return dk, dv
 
 
+def on_grid16(t: torch.Tensor) -> bool:
+    """A (b, s, heads, head_dim) bf16 operand as the head_dim 128 kernels take it: a contiguous head_dim,
+    the base 16-byte aligned and the outer strides multiples of 8 elements."""
+    return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1])
+
+
 def _attn_fwd_call(q, k, v, o, lse, scale, causal, q_offset):
-    """ljs_attn_fwd into ``o`` (bf16 [B, Sq, H, 64]) and ``lse`` (f32 [B, H, Sq]); returns both."""
-    B, Sq, H, _ = q.shape
+    """ljs_attn_fwd (head_dim 128: ljs_attn128_fwd) into ``o`` (bf16 [B, Sq, H, D]) and ``lse`` (f32 [B, H, Sq]);
+    returns both."""
+    B, Sq, H, D = q.shape
     Hkv = _kv_heads(q, k, v)
+    if D == 128:
+        _ck(lib().ljs_attn128_fwd(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, k.shape[1], H, Hkv, _longs(_strides3(q)),
+                                  _longs(_strides3(k)), _longs(_strides3(v)), _longs(_strides3(o)), scale, int(causal),
+                                  q_offset, _stream(q)), "ljs_attn128_fwd")
+        return o, lse
     if Hkv != H:
         _ck(lib().ljs_attn_fwd_gqa(_p(q), _p(k), _p(v), _p(o), _p(lse), B, Sq, k.shape[1], H, Hkv,
                                    _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)),
@@ -2424,10 +2467,20 @@ def _attn_bwd_call(q, k, v, o, do, lse, dq, dk, dv, scale, causal, q_offset):
     With fewer key/value heads than query heads (dk / dv of Hkv heads) the kernels write per-query-head
     gradients into a scratch pair, allocated here like any other intermediate (inside a graph capture
     it belongs to the graph's pool, so a replay reuses the same addresses), and gqa_reduce folds them
-    into dk / dv on the same stream."""
-    B, Sq, H, _ = q.shape
-    delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    into dk / dv on the same stream.  Head_dim 128 (ljs_attn128_bwd) takes neither delta nor scratch."""
+    B, Sq, H, D = q.shape
     Hkv = _kv_heads(q, k, v)
+    if D == 128:
+        # (one launch: its blocks form delta themselves and fold dK / dV over each group)
+        if not on_grid16(do):
+            do = do.contiguous()
+        _ck(lib().ljs_attn128_bwd(_p(q), _p(k), _p(v), _p(o), _p(do), _p(lse), _p(dq), _p(dk), _p(dv), B, Sq,
+                                  k.shape[1], H, Hkv, _longs(_strides3(q)), _longs(_strides3(k)), _longs(_strides3(v)),
+                                  _longs(_strides3(o)), _longs(_strides3(do)), _longs(_strides3(dq)),
+                                  _longs(_strides3(dk)), _longs(_strides3(dv)), scale, int(causal), q_offset,
+                                  _stream(q)), "ljs_attn128_bwd")
+        return
+    delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     if Hkv != H:
         Sk = k.shape[1]
         dkx = torch.empty((B, Sk, H, 64), dtype=torch.bfloat16, device=q.device)
@@ -2543,10 +2596,10 @@ def attn_bwd_block(q, k, v, o, do, lse, scale: float, causal: bool = False, q_of
 
 
 def attention(q, k, v, scale: float, causal: bool = False, q_offset: int = 0) -> torch.Tensor:
-    ok = (q.shape[-1] == 64 and k.shape[-1] == 64 and v.shape[-1] == 64 and q.stride(-1) == 1
-          and k.stride(-1) == 1 and v.stride(-1) == 1)
+    ok = (q.shape[-1] in (64, 128) and k.shape[-1] == q.shape[-1] and v.shape[-1] == q.shape[-1]
+          and q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1)
     if not ok:
-        raise NotImplementedError(f"HIP attention supports head_dim 64 with contiguous head_dim; got {q.shape}")
+        raise NotImplementedError(f"HIP attention supports head_dim 64 or 128 with contiguous head_dim; got {q.shape}")
     qb, kb, vb = (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16) for t in (q, k, v))
     Hkv = _kv_heads(q, k, v)
     if Hkv != q.shape[2] and not gqa_kernels():

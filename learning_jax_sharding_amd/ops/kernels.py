@@ -555,22 +555,41 @@ def attention_reference(q, k, v, scale: float, causal: bool = False, q_offset: i
 _WARNED_DH = set()
 
 
-def _hip_attn(q, k, v) -> bool:
+def attn_d128_enabled() -> bool:
+    # LJS_ATTN_D128=1: head_dim 128 attention runs the HIP kernels of csrc/kernels/attention128.hip
+    # (read at every call); default: the torch formulation with its one-time warning, as for every
+    # head_dim other than 64
+    return os.environ.get("LJS_ATTN_D128", "0") == "1"
+
+
+def _hip_attn(q, k, v, merge: bool = False) -> bool:
     """Whether the HIP attention kernels take these (b, s, heads, head_dim) operands: GPU tensors
-    with head_dim 64 (the reference's, ``case6_attention.py``) contiguous in the last dim.  Other
-    head dims run the torch formulation below on the GPU (same math, autograd through torch),
-    with a one-time warning."""
+    with head_dim 64 (the reference's, ``case6_attention.py``) contiguous in the last dim, or -- with
+    ``LJS_ATTN_D128=1`` -- head_dim 128 on the 16-byte grid (``hip.on_grid16``), except for the
+    blockwise ``merge`` entry, whose kernel epilogue exists at 64 only.  Other head dims run the
+    torch formulation below on the GPU (same math, autograd through torch), with a one-time
+    warning."""
     if not use_hip(q):
         return False
     kv_groups(q, k, v)   # (raises on unequal K / V head counts or heads that do not divide)
     if all(t.shape[-1] == 64 and t.stride(-1) == 1 for t in (q, k, v)):
         return True
-    key = (q.shape[-1], v.shape[-1])
+    d128 = all(t.shape[-1] == 128 for t in (q, k, v)) and attn_d128_enabled()
+    if d128 and merge:
+        return False   # (attention_fwd_merge: the 128 block kernel through attention_fwd_lse, merged in torch)
+    if d128 and all(_hip().on_grid16(t) for t in (q, k, v)):
+        return True
+    key = (q.shape[-1], v.shape[-1], d128)
     if key not in _WARNED_DH:
         _WARNED_DH.add(key)
         import warnings
-        warnings.warn(f"HIP attention kernels take head_dim 64; head_dim {q.shape[-1]} (v {v.shape[-1]}) runs "
-                      "the torch attention formulation on the GPU")
+        if d128:
+            warnings.warn("HIP attention kernels take head_dim 128 operands with a contiguous head_dim, 16-byte "
+                          "aligned bases and outer strides that are multiples of 8; these run the torch attention "
+                          "formulation on the GPU")
+        else:
+            warnings.warn(f"HIP attention kernels take head_dim 64; head_dim {q.shape[-1]} (v {v.shape[-1]}) runs "
+                          "the torch attention formulation on the GPU")
     return False
 
 
@@ -618,7 +637,7 @@ def attention_fwd_merge(q, k, v, scale: float, causal: bool, q_offset: int, stat
     """One key block of a blockwise forward merged into ``state`` = [o_acc f32, lse] (None before the
     first block).  On GPU the merge happens in the kernel's epilogue; ``last`` makes it write and
     return the final output in v's dtype (else returns None)."""
-    if _hip_attn(q, k, v):
+    if _hip_attn(q, k, v, merge=True):
         B, Sq, H, D = q.shape
         if state[0] is None:
             state[0] = torch.empty((B, Sq, H, D), dtype=torch.float32, device=q.device)
