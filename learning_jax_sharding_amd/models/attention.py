@@ -125,7 +125,7 @@ class MultiHeadAttention(Module):
         if self.verbose:
             print(*a)
 
-    def _cached(self, x: ShardedArray, cache, residual: Optional[ShardedArray], extend: bool = False):
+    def _cached(self, x: ShardedArray, cache, residual: Optional[ShardedArray], extend=False):
         """The cached call (module docstring): no gradient, dropout the identity, no ``attention_next``
         hint and no weight prefetch; the projections are the uncached call's."""
         if not self.causal:
@@ -151,7 +151,7 @@ class MultiHeadAttention(Module):
             k = core.reshape(with_logical_constraint(k, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
             v = core.reshape(with_logical_constraint(v, ("batch", "embed", None)), (b, -1, self.n_kv, self.dim_head))
             if extend:
-                hidden = core.cached_attention(q, k, v, layer, lens, self.scale, self.rope_theta, extend=True)
+                hidden = core.cached_attention(q, k, v, layer, lens, self.scale, self.rope_theta, extend=extend)
             elif x.shape[1] == 1:
                 hidden = core.cached_attention(q, k, v, layer, lens, self.scale, self.rope_theta)
             else:
@@ -166,13 +166,14 @@ class MultiHeadAttention(Module):
 
     def __call__(self, hidden_states: ShardedArray, context: Optional[ShardedArray] = None,
                  deterministic: bool = True, residual: Optional[ShardedArray] = None, cache=None,
-                 extend: bool = False):
+                 extend=False):
         """``residual`` (the block's input, for a skip connection): returns
         ``residual + attention(...)`` in the compute dtype, the add fused into the output
         projection's GEMM epilogue when dropout is the identity.  ``cache``: one layer ``(k, v, lens)`` of a
         :class:`~.cache.KVCache`; the call then returns ``(output, cache)`` (module docstring).  ``extend=True`` (with a
         cache): the ``T >= 1`` positions of the call continue the cached sequence at rows ``lens[b] .. lens[b] + T - 1``
-        instead of restarting it (``ops.core.cached_attention``)."""
+        instead of restarting it (``ops.core.cached_attention``); ``extend="chunk"`` does the same for any ``T`` up to the
+        cache's capacity through the MFMA chunked-prefill kernel."""
         if extend and cache is None:
             raise ValueError("MultiHeadAttention: extend=True needs a cache (it continues a cached sequence)")
         if cache is not None:

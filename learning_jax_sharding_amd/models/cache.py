@@ -173,6 +173,33 @@ def _greedy_all(logits: ShardedArray, like: ShardedArray) -> ShardedArray:
                         loc)
 
 
+def _chunked_prefill(model, params, ids: ShardedArray, cache, pl: ShardedArray, chunk: int):
+    """The right-padded prompt ``ids`` (batch, T) fed from the empty cache in ``ceil(T / chunk)`` cached calls with
+    ``extend="chunk"`` (the last may be shorter): every position attends to the cache rows, its own included, so with an
+    MX-fp8 cache the whole prompt sees fp8 keys and values, as the decode steps will.  ``lens`` is advanced by each chunk and
+    set to ``pl`` (the prompt lengths, laid out like ``cache.lens``) at the end.  Returns ``(rows, cache)``: ``rows`` (batch, 1,
+    vocab) holds each sequence's logits at its last real position, taken on the devices from the chunk that holds it."""
+    T = ids.shape[1]
+    core.cache_set_lens(cache.lens, 0)
+    last = {d: t.long() - 1 for d, t in pl.local.items()}
+    loc, tile, logits = {}, None, None
+    for c0 in range(0, T, chunk):
+        n = min(chunk, T - c0)
+        logits, cache = model.apply({"params": params}, ids[:, c0:c0 + n], cache=cache, extend="chunk")
+        tile = logits.tile.unshard([1, 2])
+        if logits.tile != tile:
+            from ..spmd.reshard import reshard_tile
+            logits = reshard_tile(logits, tile, note="generate.logits")
+        for d, t in logits.local.items():
+            at = last[d] - c0
+            row = t[torch.arange(t.shape[0], device=t.device), at.clamp(0, n - 1)].unsqueeze(1)
+            loc[d] = row if c0 == 0 else torch.where(((at >= 0) & (at < n))[:, None, None], row, loc[d])
+    core.cache_set_lens(cache.lens, pl)
+    rows = ShardedArray((logits.shape[0], 1, logits.shape[2]), logits.dtype, sharding_from_tile(tile, like=[logits.sharding]),
+                        loc)
+    return rows, cache
+
+
 def _draft_request(model, draft, draft_tokens, key, eos_id):
     """The checks of ``generate``'s ``draft`` arguments, on the host before any launch: ``(draft_model, draft_params, k)``."""
     from ..ops.kernels import EXTEND_MAX_POSITIONS
@@ -299,7 +326,7 @@ def _sampling_request(V: int, key, temperature, top_k, top_p, eos_id, pad_id, st
 
 
 def _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p, eos,
-                      pad_id, stop_poll, weight_quant=None) -> torch.Tensor:
+                      pad_id, stop_poll, weight_quant=None, prefill_chunk=None) -> torch.Tensor:
     """``generate`` with a key and / or stop tokens: the prefill and the step end in ``sample_logits``.  ``done`` (int32
     (batch,), next to ``cache.lens``) is made before the capture and donated with the token."""
     from ..spmd.api import jit
@@ -311,6 +338,9 @@ def _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, ke
                         {d: torch.zeros_like(t) for d, t in lens.local.items()}) if eos else None
 
     def prefill(p, x, c, n):
+        if prefill_chunk is not None:
+            rows, c = _chunked_prefill(model, p, x, c, n, prefill_chunk)
+            return core.sample_logits(rows, None, key, pos=c.lens, done=done, dtype=x.dtype, **opts), c
         logits, c = model.apply({"params": p}, x, cache=c, prompt_lens=n)
         last = ShardedArray(n.shape, n.dtype, n.sharding, {d: t - 1 for d, t in n.local.items()})
         # pos = lens after the prefill set it: the position the new token will occupy
@@ -354,7 +384,8 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
              max_len: Optional[int] = None, cache_sharding: Optional[Sharding] = None, *, key=None,
              temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id=None,
              pad_id: Optional[int] = None, stop_poll: int = 16, return_lens: bool = False,
-             cache_quant: Optional[str] = None, draft=None, draft_tokens: int = 4, weight_quant: Optional[str] = None):
+             cache_quant: Optional[str] = None, draft=None, draft_tokens: int = 4, weight_quant: Optional[str] = None,
+             prefill_chunk: Optional[int] = None):
     """Decoding: ``max_new_tokens`` tokens after each prompt of ``ids`` (batch, T), as an int64 host tensor
     ``[batch, max_new_tokens]``; greedy without a ``key``.
 
@@ -378,7 +409,16 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
 
     ``cache_quant="mxfp8"``: the cache is MX-fp8 (:class:`KVCache`): about half the bytes per cached row, the launch
     count of a step unchanged.  The prefill attends to the prompt's unquantised K / V, so the first token is the
-    unquantised run's; the later ones attend to fp8 keys and values and may differ from it.
+    unquantised run's; the later ones attend to fp8 keys and values and may differ from it.  With ``prefill_chunk`` every
+    prompt position attends to the cache rows, its own included: the prefill then sees the fp8 keys and values the
+    decode steps will see, the first token with them.
+
+    ``prefill_chunk=N``: the right-padded prompt is fed from the empty cache in ``ceil(T / N)`` cached calls of at most ``N``
+    positions with ``extend="chunk"`` (one append and one MFMA ``attn_chunk`` launch per layer and call, activations bounded
+    by ``N``) instead of one prefill call; ``lens`` is advanced by each chunk and then set to ``prompt_lens``, and each
+    sequence's first token is taken from the chunk that holds its last real position (the host knows ``prompt_lens``: no
+    device read).  ``N < 1``, or ``prefill_chunk`` together with ``draft``, raises ``ValueError`` before any launch; None is
+    the single prefill call.
 
     ``weight_quant="mxfp8"``: every decode step, the LM head included, runs under ``ops.linear.weight_quant``: its dense
     layers read MX-fp8 weights (``skinny_mx<`` launches in place of ``skinny<``, the launch count of a step unchanged)
@@ -410,6 +450,12 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
     if weight_quant is not None and draft is not None:
         raise ValueError("generate: weight_quant does not go with draft= (the verification call has more than 16 rows and "
                          "would read bf16 weights where the single steps read fp8 ones)")
+    if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or int(prefill_chunk) != prefill_chunk
+                                      or prefill_chunk < 1):
+        raise ValueError(f"generate: prefill_chunk must be a positive int or None, got {prefill_chunk!r}")
+    if prefill_chunk is not None and draft is not None:
+        raise ValueError("generate: prefill_chunk does not go with draft= (the draft's prefill is a single call)")
+    prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
     B, T = ids.shape
     plens = _host_lens(prompt_lens, B, T)
     spec = _draft_request(model, draft, draft_tokens, key, eos_id) if draft is not None else None
@@ -435,10 +481,13 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
         return (out, torch.full((B,), max_new_tokens, dtype=torch.long), mean) if return_lens else out
     if key is not None or eos:
         out = _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p,
-                                eos, pad_id, stop_poll, weight_quant)
+                                eos, pad_id, stop_poll, weight_quant, prefill_chunk)
         return (out, _stop_lens(out, eos)) if return_lens else out
 
     def prefill(p, x, c, n):
+        if prefill_chunk is not None:
+            rows, c = _chunked_prefill(model, p, x, c, n, prefill_chunk)
+            return _greedy(rows, x), c
         logits, c = model.apply({"params": p}, x, cache=c, prompt_lens=n)
         last = ShardedArray(n.shape, n.dtype, n.sharding, {d: t - 1 for d, t in n.local.items()})
         return _greedy(logits, x, last), c

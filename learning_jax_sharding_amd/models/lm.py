@@ -111,7 +111,7 @@ class TransformerLM(Module):
                     K.rope_table(t.device, self.dim_head, float(self.rope_theta), max_len)
         return cache
 
-    def _cached(self, ids: ShardedArray, cache, prompt_lens, extend: bool = False):
+    def _cached(self, ids: ShardedArray, cache, prompt_lens, extend=False):
         """Prefill (more than one position: restarts the cache), one decode step, or with ``extend`` a step of
         several positions that continues the cache (module docstring)."""
         for name, bad in (("causal=False", not self.causal), ("fp8=True", self.fp8)):
@@ -126,7 +126,7 @@ class TransformerLM(Module):
             if prompt_lens is not None:
                 raise ValueError("TransformerLM: extend=True continues the cache at cache.lens; prompt_lens goes with a "
                                  "prefill")
-            if T > EXTEND_MAX_POSITIONS:
+            if extend is True and T > EXTEND_MAX_POSITIONS:
                 raise ValueError(f"TransformerLM: extend=True takes at most {EXTEND_MAX_POSITIONS} positions per call, "
                                  f"got {T}")
         if T > cache.max_len:
@@ -159,7 +159,7 @@ class TransformerLM(Module):
             x = self.final_norm(x)
             return with_logical_constraint(self.head(x), ("batch", "length", "vocab")), cache
 
-    def __call__(self, ids: ShardedArray, cache=None, prompt_lens=None, extend: bool = False):
+    def __call__(self, ids: ShardedArray, cache=None, prompt_lens=None, extend=False):
         """Token ids ``[batch, length]`` (int32 / int64) -> logits ``[batch, length, vocab_size]``.
 
         ``cache`` (a :class:`~.cache.KVCache` from :meth:`init_cache`): returns ``(logits, cache)``, the buffers
@@ -171,7 +171,11 @@ class TransformerLM(Module):
         ``extend=True`` (with a cache, without ``prompt_lens``, ``length <= 64``): the tokens of sequence b sit at positions
         ``cache.lens[b] .. cache.lens[b] + length - 1`` and continue the cache instead of restarting it; the logits are those
         of ``length`` decode steps, in one step's launches, and ``lens += length``.  A caller that keeps fewer of the
-        positions sets ``cache.lens`` back (``ops.core.cache_advance`` with a negative array): rows beyond ``lens`` are dead."""
+        positions sets ``cache.lens`` back (``ops.core.cache_advance`` with a negative array): rows beyond ``lens`` are dead.
+
+        ``extend="chunk"``: the same continuation for any ``length`` up to the cache's ``max_len``, the attention by the MFMA
+        chunked-prefill kernel (``ops.kernels.attn_chunk``): a long prompt fed in chunks, or a further turn appended to a
+        live cache.  The logits agree with ``extend=True``'s to rounding, not bit for bit."""
         if extend and cache is None:
             raise ValueError("TransformerLM: extend=True needs a cache (it continues a cached sequence)")
         if cache is not None:

@@ -69,7 +69,7 @@ class TransformerLayer(Module):
             self.norm1 = cls(dtype=self.dtype, name="norm1")
             self.norm2 = cls(dtype=self.dtype, name="norm2")
 
-    def __call__(self, x, cache=None, extend: bool = False):
+    def __call__(self, x, cache=None, extend=False):
         """``cache``: one layer ``(k, v, lens)`` of a :class:`~.cache.KVCache`: a cached decoder step or prefill
         (``MultiHeadAttention``), without gradient; returns ``(y, cache)``.  ``extend=True``: the call's positions
         continue the cached sequence (``MultiHeadAttention``)."""

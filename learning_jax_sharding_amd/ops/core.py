@@ -1109,7 +1109,7 @@ def _cache_layout(k: ShardedArray, v: ShardedArray, cache_layer, lens: Optional[
 
 def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_layer, lens: ShardedArray,
                      scale: Optional[float] = None, rope_theta: Optional[float] = None,
-                     extend: bool = False) -> ShardedArray:
+                     extend=False) -> ShardedArray:
     """One decode step of one layer: the single new position's ``k`` / ``v`` (batch, 1, kv_heads, head_dim)
     are appended to ``cache_layer = (kc, vc)`` at row ``lens[b]`` (k, and q with it, rotated at that
     position when ``rope_theta`` is given), and ``q`` (batch, 1, heads, head_dim) attends to rows ``[0,
@@ -1121,14 +1121,25 @@ def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_la
     ``extend=True``: ``T >= 1`` new positions per sequence (at most :data:`.kernels.EXTEND_MAX_POSITIONS`) are
     appended at rows ``lens[b] .. lens[b] + T - 1`` (q and k rotated at ``lens[b] + t``; rows at and beyond the capacity are
     not written) and position ``t`` attends to rows ``[0, lens[b] + t + 1)``: still one append and one attention launch
-    (:func:`.kernels.attn_extend`), and the result of ``T`` single steps."""
+    (:func:`.kernels.attn_extend`), and the result of ``T`` single steps.
+
+    ``extend="chunk"``: the same append and the same rows for any ``T >= 1`` (at most the capacity), the attention by one
+    MFMA launch over the cache (:func:`.kernels.attn_chunk`, csrc/kernels/prefill.hip): a chunk of a long prompt, or a
+    further turn appended to a live cache.  Its sums run in the flash forward's order, not the decode kernel's, so it
+    agrees with ``extend=True`` to rounding and not bit for bit."""
     T = q.shape[1]
     if k.shape[1] != T:
         raise ValueError(f"cached_attention: q has {T} new positions and k {k.shape[1]}")
+    chunk = isinstance(extend, str) and extend == "chunk"
+    if not chunk and not isinstance(extend, bool):
+        raise ValueError(f"cached_attention: extend is False, True or 'chunk', got {extend!r}")
+    if chunk and T > cache_layer[0].shape[1]:
+        raise ValueError(f"cached_attention: extend='chunk' takes at most the cache's capacity of "
+                         f"{cache_layer[0].shape[1]} positions per call, got {T}")
     if not extend and T != 1:
         raise ValueError(f"cached_attention: one new position per call, got {q.shape[1]} (a longer call is a "
                          "prefill: attention over the new tokens and cache_prefill; or extend=True)")
-    if extend and not 1 <= T <= K.EXTEND_MAX_POSITIONS:
+    if extend is True and not 1 <= T <= K.EXTEND_MAX_POSITIONS:
         raise ValueError(f"cached_attention: extend=True takes 1 to {K.EXTEND_MAX_POSITIONS} new positions per call, "
                          f"got {T}")
     if scale is None:
@@ -1144,13 +1155,15 @@ def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_la
             qr = K.kv_append_q8(k.local[d], v.local[d], *bufs, ln, q=qt if rope_theta is not None else None,
                                 theta=rope_theta)
             qn = qt if qr is None else qr
-            loc[d] = (K.attn_extend_q8(qn, *bufs, ln, float(scale)) if extend else
+            loc[d] = (K.attn_chunk_q8(qn, *bufs, ln, float(scale)) if chunk else
+                      K.attn_extend_q8(qn, *bufs, ln, float(scale)) if extend else
                       K.attn_decode_q8(qn, *bufs, ln, float(scale), extra=1))[0]
             continue
         qr = K.kv_append(k.local[d], v.local[d], kc.local[d], vc.local[d], ln,
                          q=qt if rope_theta is not None else None, theta=rope_theta)
         qn = qt if qr is None else qr
-        loc[d] = (K.attn_extend(qn, kc.local[d], vc.local[d], ln, float(scale)) if extend else
+        loc[d] = (K.attn_chunk(qn, kc.local[d], vc.local[d], ln, float(scale)) if chunk else
+                  K.attn_extend(qn, kc.local[d], vc.local[d], ln, float(scale)) if extend else
                   K.attn_decode(qn, kc.local[d], vc.local[d], ln, float(scale), extra=1))[0]
     return ShardedArray(q.shape, q.dtype if _quantised(cache_layer) else vc.dtype, q.sharding, loc)
 

@@ -20,7 +20,7 @@ import torch
 __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", "sum_all", "softmax_lastdim",
            "adam", "rng_fill", "colsum", "supports_cast", "norm", "xent", "xent_stats", "embed",
            "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "kv_append_q8", "attn_decode_q8", "plan_decode",
-           "lens_add", "attn_extend", "attn_extend_q8", "skinny",
+           "lens_add", "attn_extend", "attn_extend_q8", "attn_chunk", "attn_chunk_q8", "plan_chunk", "skinny",
            "skinny_plan", "skinny_supported", "set_skinny_waves", "skinny_mx", "skinny_mx_raw", "skinny_mx_plan",
            "skinny_mx_supported"]
 
@@ -93,6 +93,12 @@ _SIGS = {
     "ljs_attn_extend_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
                            c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_void_p],
     "ljs_extend_max_positions": [],
+    "ljs_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                       _LP, _LP, _LP, _LP, c_float, c_void_p],
+    "ljs_attn_chunk_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                          c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_void_p],
+    "ljs_chunk_plan": [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "ljs_chunk_set_rows": [c_int],
     "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_launch_plan": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_set_splits": [c_int, c_int],
@@ -2898,6 +2904,82 @@ def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     o, lse, ws = _extend_out(q, Hkv, kc.shape[1])
     _ck(attn_extend_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale), "ljs_attn_extend_q8")
     return o, lse.permute(0, 2, 1)
+
+
+# ---- chunked prefill: T >= 1 query positions per sequence over the cache by MFMA (csrc/kernels/prefill.hip)
+def set_chunk_rows(n: Optional[int]) -> None:
+    """Tests: force ``attn_chunk``'s row tile to 64 or 128 rows; None or 0 restores :func:`plan_chunk`."""
+    lib().ljs_chunk_set_rows(int(n or 0))
+
+
+def plan_chunk(B: int, T: int, H: int, Hkv: int, cus: Optional[int] = None):
+    """``(rows, grid)`` of ``attn_chunk`` for ``B`` sequences of ``T`` positions, ``H`` query and ``Hkv`` key/value heads on
+    a device of ``cus`` compute units (default: the current device's): 128 rows ``(t, g)`` per block, or 64 when the
+    ``T * H / Hkv`` rows of a group fit one such tile or 128-row tiles would leave compute units idle; the grid is ``(row
+    tiles, Hkv, B)``.  Pure: it depends on nothing else, the lengths least of all."""
+    out = (c_int * 4)()
+    rc = lib().ljs_chunk_plan(int(B), int(T), int(H), int(Hkv), int(cus if cus is not None else _cus()), out)
+    if rc != 0:
+        raise ValueError(f"plan_chunk: B={B}, T={T}, H={H}, Hkv={Hkv}, cus={cus} must be positive and H % Hkv == 0")
+    return int(out[0]), (int(out[1]), int(out[2]), int(out[3]))
+
+
+def chunk_supported(q, kc, vc, lens, kcs=None, vcs=None) -> bool:
+    """Whether prefill.hip takes these operands as they are: bf16 ``(B, T, H, 64)`` q, caches ``(B, cap, Hkv, 64)`` in bf16
+    (or uint8 with ``(B, cap, Hkv, 2)`` uint8 scales), 16-byte aligned bases and strides, an int32 ``[B]`` lens,
+    ``H % Hkv == 0`` and ``H / Hkv <= 16``."""
+    if not decode_supported(q) or kc.dim() != 4 or kc.shape[0] != q.shape[0] or lens is None or not _lens_ok(lens, q.shape[0]):
+        return False
+    cache_ok = _q8_cache_ok(kc, vc, kcs, vcs) if kcs is not None else (decode_supported(kc, vc) and kc.shape == vc.shape)
+    H, Hkv = q.shape[2], kc.shape[2]
+    return bool(cache_ok and H % Hkv == 0 and H // Hkv <= 16)
+
+
+def attn_chunk_raw(q, kc, vc, o, lse, lens, scale: float) -> int:
+    """One ``ljs_attn_chunk`` launch on the tensors as they are (``lse``: f32 ``(B, T, H)``); returns the launcher's code
+    (non-zero: rejected, nothing launched) instead of raising."""
+    B, T, H, _ = q.shape
+    return lib().ljs_attn_chunk(_p(q), _p(kc), _p(vc), _p(o), _p(lse), _p(lens), B, T, H, kc.shape[2], kc.shape[1],
+                                _longs(_strides3(q)), _longs(_strides3(kc)), _longs(_strides3(vc)), _longs(_strides3(o)),
+                                float(scale), _stream(q))
+
+
+def attn_chunk_q8_raw(q, kc, vc, kcs, vcs, o, lse, lens, scale: float) -> int:
+    """One ``ljs_attn_chunk_q8`` launch on the tensors as they are; returns the launcher's code instead of raising."""
+    B, T, H, _ = q.shape
+    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
+    return lib().ljs_attn_chunk_q8(_p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(o), _p(lse), _p(lens), B, T, H,
+                                   kc.shape[2], kc.shape[1], st(q), st(kc), st(vc), st(kcs), st(vcs), st(o), float(scale),
+                                   _stream(q))
+
+
+def _chunk_call(what, q, kc, vc, kcs, vcs, lens, scale):
+    if not (chunk_supported(q, kc, vc, lens, kcs, vcs) and scale > 0):
+        raise NotImplementedError(f"{what} kernel: bf16 q (B, T, H, 64), caches (B, cap, Hkv, 64) (bf16, or uint8 with uint8 "
+                                  f"scales (B, cap, Hkv, 2)) with 16-byte aligned bases and strides, H / Hkv <= 16, int32 [B] "
+                                  f"lens; got q {q.dtype} {tuple(q.shape)} strides {q.stride()}, cache {kc.dtype} "
+                                  f"{tuple(kc.shape)} strides {kc.stride()}")
+    B, T, H, _ = q.shape
+    o = torch.empty((B, T, H, 64), dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty((B, T, H), dtype=torch.float32, device=q.device)
+    if kcs is None:
+        _ck(attn_chunk_raw(q, kc, vc, o, lse, lens, scale), "ljs_attn_chunk")
+    else:
+        _ck(attn_chunk_q8_raw(q, kc, vc, kcs, vcs, o, lse, lens, scale), "ljs_attn_chunk_q8")
+    return o, lse.permute(0, 2, 1)
+
+
+def attn_chunk(q, kc, vc, lens, scale: float):
+    """Attention of ``q`` (B, T, H, 64), any ``T >= 1`` positions that a :func:`kv_append` has just written at rows ``lens[b]
+    .. lens[b] + T - 1``, over the caches: row ``(b, t, h)`` attends to rows ``[0, clamp(lens[b] + t + 1, 0, cap))``.  One MFMA
+    launch (``attn_chunk<R128>`` / ``<R64>``), no workspace.  ``(o`` bf16 (B, T, H, 64), ``lse2`` f32 (B, H, T)``)``."""
+    return _chunk_call("attn_chunk", q, kc, vc, None, None, lens, scale)
+
+
+def attn_chunk_q8(q, kc, vc, kcs, vcs, lens, scale: float):
+    """:func:`attn_chunk` over an MX-fp8 cache, dequantised on its way into LDS: the bits of :func:`attn_chunk` on the
+    dequantised cache."""
+    return _chunk_call("attn_chunk_q8", q, kc, vc, kcs, vcs, lens, scale)
 
 
 def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:

@@ -958,6 +958,85 @@ def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     return attn_extend_q8_reference(q, kc, vc, kcs, vcs, lens, scale)
 
 
+# ---- chunked prefill (csrc/kernels/prefill.hip, attn_chunk): attn_extend's definition for any T >= 1, stated as one
+# masked einsum, and served on a GPU by one MFMA launch over the cache buffers.
+def attn_chunk_reference(q, kc, vc, lens, scale: float):
+    """Plain torch attention of q (B, T, H, D) over a cache kc / vc (B, cap, Hkv, D) after an append of the T positions at
+    rows ``lens[b] .. lens[b] + T - 1`` that ``lens`` (int [B], never read on the host) does not count yet: row ``(b, t, h)``
+    attends to rows ``[0, n)``, ``n = clamp(lens[b] + t + 1, 0, cap)``, of key/value head ``h // G``.  Rows at and beyond the
+    sequence's largest ``n`` are selected away before any arithmetic and a row's own limit masks its scores, so
+    whatever dead rows hold (NaN, Inf) has no influence; ``n = 0`` gives ``o = 0``, ``lse2 = +inf``.  The forward's recipe:
+    f32 scores, probabilities rounded to v's dtype before P.V.  ``(o`` (B, T, H, D), ``lse2`` f32 (B, H, T)``)``."""
+    G = kv_groups(q, kc, vc)
+    T, cap = q.shape[1], kc.shape[1]
+    n = (lens.long()[:, None] + torch.arange(1, T + 1, device=q.device)[None, :]).clamp(0, cap)      # (B, T)
+    keys = torch.arange(cap, device=q.device)
+    sel = (keys[None, :] < n.amax(1)[:, None])[:, :, None, None]                                      # (B, cap, 1, 1)
+    k = expand_kv(torch.where(sel, kc, torch.zeros_like(kc)), G)
+    v = expand_kv(torch.where(sel, vc, torch.zeros_like(vc)), G)
+    live = (keys[None, None, :] < n[:, :, None])[:, None]                                             # (B, 1, T, cap)
+    s = torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) * scale
+    s = s.masked_fill(~live, float("-inf"))
+    m = s.amax(-1, keepdim=True)
+    empty = torch.isinf(m) & (m < 0)
+    m = torch.where(empty, torch.zeros_like(m), m)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    probs = (p / l.clamp(min=1e-30)).to(v.dtype).float()
+    o = torch.einsum("bhqk,bkhd->bqhd", probs, v.float()).to(v.dtype)
+    lse = (m + torch.log(l)) * _LOG2E
+    lse = torch.where(empty, torch.full_like(lse, float("inf")), lse)
+    return o, lse.squeeze(-1)
+
+
+def attn_chunk_q8_reference(q, kc, vc, kcs, vcs, lens, scale: float):
+    """:func:`attn_chunk_reference` over an MX-fp8 cache: the same function on the dequantised buffers in q's dtype, the
+    dead rows (at and beyond the sequence's largest limit) zeroed before the dequantisation, as
+    :func:`attn_decode_q8_reference` does."""
+    cap = kc.shape[1]
+    n = (lens.long() + q.shape[1]).clamp(0, cap)
+    sel = (torch.arange(cap, device=q.device)[None, :] < n[:, None])[:, :, None, None]
+    z = lambda t: torch.where(sel, t, torch.zeros_like(t))   # noqa: E731
+    return attn_chunk_reference(q, mx_cache_dequant(z(kc), z(kcs), q.dtype), mx_cache_dequant(z(vc), z(vcs), q.dtype),
+                                lens, scale)
+
+
+def _hip_chunk(what: str, q, cache, lens) -> bool:
+    """Whether prefill.hip takes these shards (``hip.chunk_supported``), in :func:`_hip_decode`'s style: host devices and
+    ``LJS_FUSED_DECODE=0`` run the torch formulation silently, anything else unsupported on a GPU runs it there with a
+    one-time warning per reason."""
+    if not use_hip(q) or not fused_decode_enabled():
+        return False
+    hip = _hip()
+    kc, vc = cache[0], cache[1]
+    ok = hip.chunk_supported(q, kc, vc, lens, *cache[2:])
+    if not ok:
+        key = (what, q.dtype, q.shape[-1], kc.dtype)
+        if key not in _WARNED_DECODE:
+            _WARNED_DECODE.add(key)
+            import warnings
+            warnings.warn(f"HIP {what} kernel takes bf16 (B, T, H, 64) q shards and (B, cap, Hkv, 64) caches (bf16, or uint8 "
+                          f"with uint8 (B, cap, Hkv, 2) scales) with 16-byte aligned bases and strides, an int32 lens and "
+                          f"heads / kv_heads <= 16; {q.dtype} {tuple(q.shape)} strides {q.stride()}, cache {kc.dtype} "
+                          f"{tuple(kc.shape)} strides {kc.stride()} runs the torch formulation on the GPU")
+    return ok
+
+
+def attn_chunk(q, kc, vc, lens, scale: float):
+    """Attention of one device's ``q`` (B, T, H, D), any ``T >= 1`` appended positions, over its caches: ``(o, lse2)``
+    (:func:`attn_chunk_reference`'s semantics).  One MFMA HIP launch on a GPU."""
+    if _hip_chunk("attn_chunk", q, (kc, vc), lens):
+        return _hip().attn_chunk(q, kc, vc, lens, scale)
+    return attn_chunk_reference(q, kc, vc, lens, scale)
+
+
+def attn_chunk_q8(q, kc, vc, kcs, vcs, lens, scale: float):
+    """:func:`attn_chunk` over one device's MX-fp8 caches (:func:`attn_chunk_q8_reference`'s semantics)."""
+    if _hip_chunk("attn_chunk_q8", q, (kc, vc, kcs, vcs), lens):
+        return _hip().attn_chunk_q8(q, kc, vc, kcs, vcs, lens, scale)
+    return attn_chunk_q8_reference(q, kc, vc, kcs, vcs, lens, scale)
+
+
 # ----------------------------------------------------------------------------- sampling
 # One token per row of logits: temperature, top-k, top-p, the Gumbel-max draw and the stop-token rule.
 # ``at``, ``pos`` and ``done`` are tensors ON THE DEVICE: nothing below reads them on the host, so a captured
