@@ -42,6 +42,17 @@ inline void ljs_launch_rec(const char* name, dim3 grid, unsigned block, int acc_
   r.acc_mode = acc_mode;
   ljs_launch_push(r);
 }
+// The casts and layout copies (cast, cast_transpose, swap01: elementwise.hip) record into a ring of
+// their own (ljs_launch_count_copy / ljs_launch_get_copy; ops/hip.py last_launch(copies=True)): a
+// decode step launches them between its compute kernels, and the main ring's 32 entries and its
+// count are what the tests of generate and of the decode steps pin launch for launch.
+inline LjsLaunchRec g_ljs_copy_ring[kLjsLaunchRing];
+inline long g_ljs_copy_count = 0;
+inline void ljs_launch_rec_copy(const char* name, dim3 grid, unsigned block) {
+  const LjsLaunchRec r = ljs_launch_make(name, grid, block);
+  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
+  g_ljs_copy_ring[g_ljs_copy_count++ % kLjsLaunchRing] = r;
+}
 
 // compute units of the current device, 256 if unknown (asked once per process: the launchers size
 // persistent grids by it)

@@ -117,29 +117,6 @@ __device__ __forceinline__ void add_chunk(float& s, const u32x4& v) {
   }
 }
 
-// 16-byte vectorised sum of a bf16 / f32 array
-template <typename T>
-__global__ void sum_all_vec_kernel(const T* __restrict__ in, long n, float* __restrict__ out) {
-  constexpr int V = 16 / sizeof(T);
-  float s = 0.f;
-  long nv = n / V;
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (; i < nv; i += stride) add_chunk<T>(s, *reinterpret_cast<const u32x4*>(in + i * V));
-  if (blockIdx.x == 0)
-    for (long j = nv * V + threadIdx.x; j < n; j += blockDim.x) s += load1(in + j);
-  s = warp_sum64(s);
-  __shared__ float part[16];
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) part[w] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += part[k];
-    atomicAdd(out, t);
-  }
-}
-
 // sum_all: the largest grid, and its persistent workspace in 4-byte words: one f32 partial per
 // block from 0, one per ticket group from kSumGroupPart, then the two-level ticket words
 constexpr int kMaxSumBlocks = 1024, kSumGroups = kMaxSumBlocks / (int)kTicketGroup;
@@ -206,7 +183,10 @@ __device__ __forceinline__ u32x4 relu_mask_bf16x8(const u32x4& v, const u32x4& m
   u32x4 o;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    // a bf16 is > 0 iff its sign bit is clear and it is not +0: keep each half where that holds
+    // a bf16 is > 0 iff its sign bit is clear and it is not +0: keep each half where that holds.
+    // Decided on bits, so the 127 positive-sign NaN masks (0x7f81 .. 0x7fff) are kept, where a float
+    // comparison would drop them; -0.0 and denormals agree with the comparison (pinned over all
+    // 65 536 patterns by tests/test_elementwise_oracle_gpu.py)
     const unsigned lo = (m[k] & 0x8000u) == 0 && (m[k] & 0x7fffu) != 0 ? 0x0000ffffu : 0u;
     const unsigned hi = (m[k] & 0x80000000u) == 0 && (m[k] & 0x7fff0000u) != 0 ? 0xffff0000u : 0u;
     o[k] = v[k] & (lo | hi);
@@ -1044,6 +1024,7 @@ __global__ void sum_n_kernel(SumPtrs sp, int n, long count, T* __restrict__ out)
 
 // ============================================================================ C ABI
 LJS_API int ljs_cast_f32_bf16(const void* in, void* out, long n, hipStream_t s) {
+  ljs_launch_rec_copy("cast<f32,bf16>", dim3(grid_for(n, 256 * 8)), 256);
   hipLaunchKernelGGL(cast_f32_bf16, dim3(grid_for(n, 256 * 8)), dim3(256), 0, s, (const float*)in, (bf16_t*)out, n);
   return (int)hipGetLastError();
 }
@@ -1053,6 +1034,7 @@ LJS_API int ljs_swap01_bf16(const void* in, int in_bf16, void* out, int B, int S
   const long nbk = (long)B * (K / 8);
   if (S > 65535 || nbk >= (1L << 31)) return (int)hipErrorInvalidValue;
   const dim3 g((unsigned)((nbk + 255) / 256 < 64 ? (nbk + 255) / 256 : 64), (unsigned)S);
+  ljs_launch_rec_copy(in_bf16 ? "swap01<bf16>" : "swap01<f32>", g, 256);
   if (in_bf16)
     hipLaunchKernelGGL(swap01_bf16_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, B, S,
                        K / 8);
@@ -1064,6 +1046,7 @@ LJS_API int ljs_swap01_bf16(const void* in, int in_bf16, void* out, int B, int S
 
 LJS_API int ljs_transpose_bf16(const void* in, void* out, int R, int C, long ldi, long ldo, hipStream_t s) {
   dim3 grid((C + 63) / 64, (R + 63) / 64);
+  ljs_launch_rec("transpose_bf16", grid, 256);
   hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, R, C, ldi, ldo);
   return (int)hipGetLastError();
 }
@@ -1077,6 +1060,7 @@ LJS_API int ljs_sum_n(const void* const* ins, int n, int is_bf16, long count, vo
     sp.p[j] = ins[j];
   }
   const int g = grid_for(count / (is_bf16 ? 8 : 4) + 1, 256);
+  ljs_launch_rec(is_bf16 ? "sum_n<bf16>" : "sum_n<f32>", dim3(g), 256);
   if (is_bf16)
     hipLaunchKernelGGL(sum_n_kernel<bf16_t>, dim3(g), dim3(256), 0, s, sp, n, count, (bf16_t*)out);
   else
@@ -1111,12 +1095,14 @@ __global__ __launch_bounds__(256) void rows_sum_f32_kernel(const float* __restri
 
 LJS_API int ljs_rows_sum_f32(const void* in, int R, int C, long ld, void* out, hipStream_t s) {
   if (R < 1 || C < 1 || ld < C) return (int)hipErrorInvalidValue;
+  ljs_launch_rec("rows_sum_f32", dim3((C + 63) / 64), 256);
   hipLaunchKernelGGL(rows_sum_f32_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const float*)in, R, C, ld,
                      (float*)out);
   return (int)hipGetLastError();
 }
 
 LJS_API int ljs_cast_bf16_f32(const void* in, void* out, long n, hipStream_t s) {
+  ljs_launch_rec_copy("cast<bf16,f32>", dim3(grid_for(n, 256 * 8)), 256);
   hipLaunchKernelGGL(cast_bf16_f32, dim3(grid_for(n, 256 * 8)), dim3(256), 0, s, (const bf16_t*)in, (float*)out, n);
   return (int)hipGetLastError();
 }
@@ -1126,6 +1112,8 @@ LJS_API int ljs_cast_transpose_f32_bf16(const void* in, void* out, int R, int C,
   dim3 grid((C + 31) / 32, (R + 31) / 32);
   const int vin = ldi % 4 == 0 && (((uintptr_t)in) & 15) == 0;
   const int vout = ldo % 4 == 0 && (((uintptr_t)out) & 7) == 0;
+  ljs_launch_rec_copy(vin ? (vout ? "cast_transpose<1,1>" : "cast_transpose<1,0>")
+                          : (vout ? "cast_transpose<0,1>" : "cast_transpose<0,0>"), grid, 256);
   hipLaunchKernelGGL(cast_transpose_f32_bf16, grid, dim3(256), 0, s, (const float*)in, (bf16_t*)out, R, C, ldi, ldo,
                      vin, vout);
   return (int)hipGetLastError();
@@ -1143,6 +1131,7 @@ LJS_API int ljs_sum_all(const void* in, int is_bf16, long n, void* out, int out_
     long per = 256L * (is_bf16 ? 8 : 4) * 16;
     int g = grid_for(n, (int)per);
     if (g > kMaxSumBlocks) g = kMaxSumBlocks;
+    ljs_launch_rec(is_bf16 ? "sum_all<bf16,ticket>" : "sum_all<f32,ticket>", dim3(g), 256);
     if (is_bf16)
       hipLaunchKernelGGL(sum_all_ticket_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)in, n, partials,
                          ticket, out, out_bf16);
@@ -1154,6 +1143,7 @@ LJS_API int ljs_sum_all(const void* in, int is_bf16, long n, void* out, int out_
   if (out_bf16) return (int)hipErrorInvalidValue;
   (void)hipMemsetAsync(out, 0, sizeof(float), s);
   int g = grid_for(n, 256 * 16);
+  ljs_launch_rec(is_bf16 ? "sum_all<bf16,atomic>" : "sum_all<f32,atomic>", dim3(g), 256);
   if (is_bf16)
     hipLaunchKernelGGL(sum_all_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)in, n, (float*)out);
   else
@@ -1169,6 +1159,7 @@ LJS_API long ljs_colsum_ws_floats() { return kColsumWsFloats; }
 LJS_API int ljs_colsum(const void* in, int is_bf16, int R, int C, long ld, void* out, int accumulate, void* ws,
                        hipStream_t s) {
   if (ld == 0) {  // one repeated row: out = R * row
+    ljs_launch_rec("colsum<bcast>", dim3((C + 255) / 256), 256);
     hipLaunchKernelGGL(colsum_bcast_kernel, dim3((C + 255) / 256), dim3(256), 0, s, in, is_bf16, R, C, (float*)out,
                        accumulate);
     return (int)hipGetLastError();
@@ -1182,12 +1173,14 @@ LJS_API int ljs_colsum(const void* in, int is_bf16, int R, int C, long ld, void*
     gy = (R + rpb - 1) / rpb;
     // workspace layout: [tickets: 4096 words][partials: gy * C floats]
     if (ws && cb <= 4096 && (long)gy * C + 4096 <= kColsumWsFloats) {
+      ljs_launch_rec("colsum<ticket>", dim3(cb, gy), 256);
       hipLaunchKernelGGL(colsum_ticket_kernel, dim3(cb, gy), dim3(256), 0, s, (const bf16_t*)in, R, C, ld, rpb,
                          (float*)ws + 4096, (unsigned*)ws, (float*)out, accumulate, (const bf16_t*)nullptr, 0L,
                          (bf16_t*)nullptr);
       return (int)hipGetLastError();
     }
     if (!accumulate) (void)hipMemsetAsync(out, 0, sizeof(float) * C, s);
+    ljs_launch_rec("colsum<vec>", dim3(cb, gy), 256);
     hipLaunchKernelGGL(colsum_vec_kernel, dim3(cb, gy), dim3(256), 0, s, (const bf16_t*)in, R, C, ld, rpb,
                        (float*)out);
     return (int)hipGetLastError();
@@ -1197,6 +1190,7 @@ LJS_API int ljs_colsum(const void* in, int is_bf16, int R, int C, long ld, void*
   if (gy < 1) gy = 1;
   if (gy > 64) gy = 64;
   dim3 grid((C + 255) / 256, gy);
+  ljs_launch_rec(is_bf16 ? "colsum<bf16>" : "colsum<f32>", grid, 256);
   if (is_bf16)
     hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)in, R, C, ld, (float*)out);
   else
@@ -1218,6 +1212,7 @@ LJS_API int ljs_slab_reduce(const void* slabs, int S, long slab_stride, int R, i
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
   if (out_bf16 && (((uintptr_t)out_bf16) & 7)) return (int)hipErrorInvalidValue;
+  ljs_launch_rec(slabs_bf16 ? "slab_reduce<bf16>" : "slab_reduce<f32>", dim3(grid), 256);
   if (slabs_bf16)
     hipLaunchKernelGGL(slab_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)slabs, S, slab_stride,
                        R, C, (float*)out, cb, out_bs, accumulate, (bf16_t*)out_bf16, (float*)tail,
@@ -1231,6 +1226,7 @@ LJS_API int ljs_slab_reduce(const void* slabs, int S, long slab_stride, int R, i
 
 LJS_API int ljs_bcast_scalar(const void* g, int g_bf16, int C, float R, void* row, void* db, void* db_bf16,
                              hipStream_t s) {
+  ljs_launch_rec("bcast_scalar", dim3((C + 255) / 256), 256);
   hipLaunchKernelGGL(bcast_scalar_kernel, dim3((C + 255) / 256), dim3(256), 0, s, g, g_bf16, C, R, (bf16_t*)row,
                      (float*)db, (bf16_t*)db_bf16);
   return (int)hipGetLastError();
@@ -1284,6 +1280,8 @@ LJS_API int ljs_pad_box(const void* src, void* out, int nd, const long* full, co
   if (total == 0) return 0;
   long grid = (total + 255) / 256;
   if (grid > 4096) grid = 4096;
+  if (esize == 2 || esize == 4 || esize == 8)
+    ljs_launch_rec(esize == 2 ? "pad_box<2>" : esize == 4 ? "pad_box<4>" : "pad_box<8>", dim3(grid), 256);
   if (esize == 2)
     hipLaunchKernelGGL(pad_box_kernel<unsigned short>, dim3(grid), dim3(256), 0, s, (const unsigned short*)src,
                        (unsigned short*)out, b, total);
@@ -1299,6 +1297,7 @@ LJS_API int ljs_pad_box(const void* src, void* out, int nd, const long* full, co
 }
 
 LJS_API int ljs_sum_partials(const void* p, int n, void* out, int out_bf16, hipStream_t s) {
+  ljs_launch_rec("sum_partials", dim3(1), 256);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const float*)p, n, out, out_bf16);
   return (int)hipGetLastError();
 }
@@ -1316,6 +1315,7 @@ LJS_API int ljs_relu_bwd_colsum(const void* in, const void* mask, int R, int C, 
   if (rpb < 32) rpb = 32;
   gy = (R + rpb - 1) / rpb;
   if (cb > 4096 || (long)gy * C + 4096 > kColsumWsFloats) return (int)hipErrorInvalidValue;
+  ljs_launch_rec("relu_bwd_colsum", dim3(cb, gy), 256);
   hipLaunchKernelGGL(colsum_ticket_kernel, dim3(cb, gy), dim3(256), 0, s, (const bf16_t*)in, R, C, ld, rpb,
                      (float*)ws + 4096, (unsigned*)ws, (float*)out, 0, (const bf16_t*)mask, mld,
                      (bf16_t*)masked_out);
@@ -1346,6 +1346,7 @@ LJS_API int ljs_relu_bwd(const void* in, const void* mask, int R, int C, long ld
   long grid = (n8 + 255) / 256;
   if (grid > 8192) grid = 8192;  // 32 workgroups per CU, then grid-stride
   if (grid < 1) grid = 1;
+  ljs_launch_rec("relu_bwd", dim3((unsigned)grid), 256);
   hipLaunchKernelGGL(relu_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)in, (const bf16_t*)mask,
                      C / 8, n8, ld, mld, (bf16_t*)masked_out);
   return (int)hipGetLastError();
@@ -1354,11 +1355,13 @@ LJS_API int ljs_relu_bwd(const void* in, const void* mask, int R, int C, long ld
 LJS_API int ljs_fill_row_bf16(const void* g, int g_bf16, void* out, long n, hipStream_t s) {
   int grid = grid_for(n, 256);
   if (grid > 1024) grid = 1024;
+  ljs_launch_rec("fill_row", dim3(grid), 256);
   hipLaunchKernelGGL(fill_row_kernel, dim3(grid), dim3(256), 0, s, g, g_bf16, (bf16_t*)out, n);
   return (int)hipGetLastError();
 }
 
 LJS_API int ljs_softmax_rows_f32(const void* in, void* out, long rows, int L, hipStream_t s) {
+  ljs_launch_rec("softmax_rows_f32", dim3((unsigned)((rows + 3) / 4)), 256);
   hipLaunchKernelGGL(softmax_rows_f32, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, (const float*)in,
                      (float*)out, rows, L);
   return (int)hipGetLastError();

@@ -1741,16 +1741,31 @@ LJS_API long ljs_launch_count() {
   return g_ljs_launch_count;
 }
 
-LJS_API int ljs_launch_get(long i, char* buf, int cap) {
-  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
-  if (i < 0 || i >= g_ljs_launch_count || i < g_ljs_launch_count - kLjsLaunchRing || !buf || cap <= 0) return -1;
-  const LjsLaunchRec r = g_ljs_launch_ring[i % kLjsLaunchRing];
+static int launch_get(const LjsLaunchRec* ring, long count, long i, char* buf, int cap) {
+  if (i < 0 || i >= count || i < count - kLjsLaunchRing || !buf || cap <= 0) return -1;
+  const LjsLaunchRec r = ring[i % kLjsLaunchRing];
   const int n = snprintf(buf, (size_t)cap,
                          "name=%s grid=%u,%u,%u block=%u requested_tile=%d resolved_tile=%d splitk=%d splitk1=%d "
                          "variant=%d acc_mode=%d",
                          r.name, r.gx, r.gy, r.gz, r.block, r.req_tile, r.res_tile, r.splitk, r.splitk1, r.variant,
                          r.acc_mode);
   return n < cap ? n : -1;
+}
+
+LJS_API int ljs_launch_get(long i, char* buf, int cap) {
+  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
+  return launch_get(g_ljs_launch_ring, g_ljs_launch_count, i, buf, cap);
+}
+
+// the same for the ring of the casts and layout copies (common.h, ljs_launch_rec_copy)
+LJS_API long ljs_launch_count_copy() {
+  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
+  return g_ljs_copy_count;
+}
+
+LJS_API int ljs_launch_get_copy(long i, char* buf, int cap) {
+  std::lock_guard<std::mutex> g(g_ljs_launch_mu);
+  return launch_get(g_ljs_copy_ring, g_ljs_copy_count, i, buf, cap);
 }
 
 // ============================================================================ f32 GEMM

@@ -206,6 +206,7 @@ LJS_API int ljs_mse_loss(const void* y, const void* tgt, int tgt_bf16, long n, f
   if (blocks < 1) blocks = 1;
   if (blocks > kMseMaxBlocks) blocks = kMseMaxBlocks;
   const dim3 g((unsigned)blocks), b(256);
+  ljs_launch_rec(tgt_bf16 ? (dy ? "mse<tbf16,dy>" : "mse<tbf16>") : (dy ? "mse<tf32,dy>" : "mse<tf32>"), g, 256);
 #define LJS_MSE(TB, WD)                                                                                        \
   hipLaunchKernelGGL((mse_kernel<TB, WD>), g, b, 0, s, (const bf16_t*)y, tgt, n, scale, (bf16_t*)dy, partials, \
                      ticket, (float*)out)
@@ -257,6 +258,7 @@ LJS_API int ljs_mse_colsum(const void* y, const void* tgt, int tgt_bf16, int R, 
   unsigned* tickets = (unsigned*)ws;
   float* col_part = (float*)ws + p.col_part;
   float* loss_part = (float*)ws + p.loss_part;
+  ljs_launch_rec(tgt_bf16 ? "mse_colsum<tbf16>" : "mse_colsum<tf32>", dim3(p.cb, p.gy), 256);
   if (tgt_bf16)
     hipLaunchKernelGGL(mse_colsum_kernel<true>, dim3(p.cb, p.gy), dim3(256), 0, s, (const bf16_t*)y, tgt, R, C, p.rpb,
                        scale, (bf16_t*)dy, col_part, loss_part, tickets, (float*)colsum, (float*)out);

@@ -182,6 +182,8 @@ _SIGS = {
     "ljs_swiglu_set_max_blocks": [c_int],
     "ljs_launch_count": [],
     "ljs_launch_get": [c_long, ctypes.c_char_p, c_int],
+    "ljs_launch_count_copy": [],
+    "ljs_launch_get_copy": [c_long, ctypes.c_char_p, c_int],
     "ljs_attn_set": [c_int, c_int],
     "ljs_attn_get": [c_int],
     "ljs_attn_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p), _LP, c_int, c_long,
@@ -206,15 +208,16 @@ def lib():
                 L.ljs_mse_colsum_ws_bytes.restype = c_long
                 L.ljs_norm_bwd_ws_bytes.restype = c_long
                 L.ljs_launch_count.restype = c_long
+                L.ljs_launch_count_copy.restype = c_long
                 for name in ("ljs_grad_sumsq_ws_words", "ljs_grad_sumsq_slot_word", "ljs_grad_sumsq_slots"):
                     getattr(L, name).restype = c_long
                 _LIB = L
     return _LIB
 
 
-def _launch_at(i: int) -> Optional[dict]:
+def _launch_at(i: int, copies: bool = False) -> Optional[dict]:
     buf = ctypes.create_string_buffer(256)
-    if lib().ljs_launch_get(i, buf, len(buf)) < 0:
+    if (lib().ljs_launch_get_copy if copies else lib().ljs_launch_get)(i, buf, len(buf)) < 0:
         return None
     rec = {}
     for item in buf.value.decode().split(" "):
@@ -229,7 +232,7 @@ def _launch_at(i: int) -> Optional[dict]:
     return rec
 
 
-def last_launch() -> dict:
+def last_launch(copies: bool = False) -> dict:
     """The host-side record of the last GEMM / attention / MX-fp8 kernel the library launched:
 
     ``name`` (the kernel instance, e.g. ``gemm_lean<256,192,4,2,2>``, ``gemm_dma<128,128,2,2,4,kc,kc,bf16>``,
@@ -239,6 +242,14 @@ def last_launch() -> dict:
     ``grad_sumsq``, ``step_hyper``, ``adam_f32``, ``adam_multi<32>`` / ``adam_multi_dyn<32>`` (the launch's tile height), ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
     ``attn_decode<G4>``, ``kv_append<rot,q,mx8>``, ``attn_decode<G4,mx8>`` (an MX-fp8 cache), ``attn_extend<G4,P2>`` / ``attn_extend<G4,P2,mx8>`` (heads per group, positions per block), ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
     the epilogue parts present; ``skinny_mx<...>`` likewise on MX-fp8 weights)),
+    the elementwise, reduction and loss kernels ``transpose_bf16``,
+    ``sum_n<f32>`` / ``sum_n<bf16>``, ``rows_sum_f32``, ``sum_all<bf16,ticket>`` / ``sum_all<f32,ticket>`` (16-byte
+    aligned input) and ``sum_all<bf16,atomic>`` / ``sum_all<f32,atomic>``, ``sum_partials``, ``colsum<bcast>`` /
+    ``colsum<ticket>`` / ``colsum<vec>`` / ``colsum<f32>`` / ``colsum<bf16>`` (the path ``ljs_colsum`` took),
+    ``relu_bwd_colsum``, ``relu_bwd``, ``slab_reduce<f32>`` / ``slab_reduce<bf16>``, ``bcast_scalar``, ``fill_row``,
+    ``pad_box<2>`` / ``pad_box<4>`` / ``pad_box<8>`` (element bytes), ``softmax_rows_f32``, ``mse<tbf16,dy>`` /
+    ``mse<tbf16>`` / ``mse<tf32,dy>`` / ``mse<tf32>`` (target type, gradient written or not) and ``mse_colsum<tf32>`` /
+    ``mse_colsum<tbf16>``,
     ``grid`` (x, y, z), ``blocks`` (their product), ``block`` (threads); for the bf16 and MX-fp8 GEMMs
     ``requested_tile`` / ``resolved_tile`` (the tile code passed in and the one the launcher turned
     it into), ``splitk`` (the launched split count; ``splitk1``: the second GEMM's in a grouped pair)
@@ -248,9 +259,15 @@ def last_launch() -> dict:
 
     The record is made where the launch is issued, so under graph capture it is made when the
     launch is *recorded* into the graph, not when the graph is replayed.  Launches of every host
-    thread (autograd's backward thread included) go into one ring of the last 32."""
-    n = lib().ljs_launch_count()
-    rec = _launch_at(n - 1) if n > 0 else None
+    thread (autograd's backward thread included) go into one ring of the last 32.
+
+    ``copies=True`` reads the ring of the casts and layout copies instead, which record apart from the
+    rest (a decode step launches them between its compute kernels, and the main ring and its count
+    are pinned launch for launch by the tests of ``generate``): ``cast<f32,bf16>`` / ``cast<bf16,f32>``,
+    ``cast_transpose<1,1>`` (the ``vin`` / ``vout`` 4-wide access flags the launcher chose, each 0 or 1)
+    and ``swap01<f32>`` / ``swap01<bf16>``."""
+    n = lib().ljs_launch_count_copy() if copies else lib().ljs_launch_count()
+    rec = _launch_at(n - 1, copies) if n > 0 else None
     if rec is None:
         raise RuntimeError("no kernel launch recorded yet")
     return rec
@@ -263,18 +280,20 @@ class LaunchLog(list):
 
 
 @contextlib.contextmanager
-def launch_log():
+def launch_log(copies: bool = False):
     """Context manager yielding a list that, on exit, holds the records (see :func:`last_launch`) of
     the launches made inside it, oldest first.  Like the record itself it sees launches as they are
-    issued: a graph replay adds nothing, the capture that recorded the graph does."""
+    issued: a graph replay adds nothing, the capture that recorded the graph does.  ``copies=True``:
+    the ring of the casts and layout copies (see :func:`last_launch`)."""
     log = LaunchLog()
-    start = lib().ljs_launch_count()
+    count = lib().ljs_launch_count_copy if copies else lib().ljs_launch_count
+    start = count()
     try:
         yield log
     finally:
-        end = lib().ljs_launch_count()
+        end = count()
         log.total = end - start
-        log.extend(r for r in (_launch_at(i) for i in range(max(start, end - 32), end)) if r is not None)
+        log.extend(r for r in (_launch_at(i, copies) for i in range(max(start, end - 32), end)) if r is not None)
 
 
 # the `which` of ljs_attn_set / ljs_attn_get: the rows of LJS_ATTN_SWITCHES (csrc/kernels/attention.hip)
@@ -1152,7 +1171,7 @@ class _MSELoss(torch.autograd.Function):
 
 def mse_loss(y: torch.Tensor, t: torch.Tensor, scale: float) -> torch.Tensor:
     ok = (y.dtype == torch.bfloat16 and t.dtype in (torch.float32, torch.bfloat16) and y.shape == t.shape
-          and y.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 0 and y.shape[-1] % 8 == 0)
+          and y.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 0 and y.numel() > 0)
     if not ok:
         return ((y.float() - t.float()) ** 2).sum() * scale
     return _MSELoss.apply(y, t, scale)

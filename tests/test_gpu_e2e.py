@@ -421,7 +421,10 @@ def test_mse_loss_kernel_matches_torch(gpu_devices):
         y = torch.randn(n, device="cuda").bfloat16().requires_grad_(True)
         t = torch.randn(n, device="cuda").to(tdt)
         scale = 1.0 / n
-        loss = hip.mse_loss(y, t, scale)
+        with hip.launch_log() as log:
+            loss = hip.mse_loss(y, t, scale)
+        want = "mse<tf32,dy>" if tdt == torch.float32 else "mse<tbf16,dy>"
+        assert [r["name"] for r in log if r["name"].startswith("mse")] == [want], list(log)   # the kernel, not the fallback
         (gy,) = torch.autograd.grad(loss, y, torch.tensor(1.0, device="cuda"))
         yf = y.detach().float()
         ref = ((yf - t.float()) ** 2).sum() * scale
