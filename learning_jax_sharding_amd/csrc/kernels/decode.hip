@@ -51,7 +51,7 @@
 // a serial merge tail in whichever block arrives last; with a kernel boundary in between, plain
 // stores are enough.)
 //
-// attn_extend (ljs_attn_extend, ljs_attn_extend_q8).  q is (B, T, H, 64), 1 <= T <= 64 positions per sequence that
+// attn_extend (ljs_attn_decode with T > 1 and extra = 1).  q is (B, T, H, 64), 1 <= T <= 64 positions per sequence that
 // a kv_append has just written at rows lens[b] .. lens[b] + T - 1 and lens does not count yet: row (b, t, h)
 // attends to the rows [0, clamp(lens[b] + t + 1, 0, cap)) and gets the bits attn_decode writes for (b, h) with
 // extra = t + 1 under the same plan (the same kernel, its EXT instances: a wave's heads become rows (t, g)
@@ -59,7 +59,7 @@
 // for G > 4), the row tiles sit beside the splits in grid.x, the partials and decode_merge are reused with
 // B T H outputs, and T == 1 launches attn_decode's own instances.
 //
-// MX-fp8 caches (the mx8 instances; ljs_kv_append_q8, ljs_attn_decode_q8).  kc / vc hold OCP e4m3 bytes (B,
+// MX-fp8 caches (the mx8 instances; a descriptor of kind kCacheMx8).  kc / vc hold OCP e4m3 bytes (B,
 // cap, Hkv, 64) and two more buffers one e8m0 byte per 32 elements (B, cap, Hkv, 2), in the encoding
 // ljs_quant_mx_rows writes (exponent + 127); strides of all four count bytes.  The append stores
 // quantize_mx_ref of the bf16 row the bf16 cache would hold (rope's bits first, then the quantiser;
@@ -68,6 +68,12 @@
 // two scaled conversions per 4 elements differ).  A zero scale byte is 2^-127, as for dequantize_mx_ref and the
 // block-scaled MFMA: a live row whose block exponent clamped carries it with non-zero bytes.  Rows beyond a
 // block's range read zero bytes (and a zero scale byte) through the descriptors: 0 x 2^-127 = 0.
+//
+// Entry points.  Two launchers, ljs_kv_append and ljs_attn_decode (T, extra), take the cache as ONE operand, an
+// LjsCache descriptor with an explicit kind (cache_common.h, which also states the alignment and reach checks
+// once; prefill.hip's ljs_attn_chunk takes the same descriptor).  The kind selects the kernel instances; the
+// kernels' argument structs are filled from the descriptor.
+#include "cache_common.h"
 #include "rowwise.h"
 
 namespace {
@@ -470,10 +476,6 @@ inline int decode_launch_plan(int B, int Hkv, int cap, int* splits, int* kps) {
   return 0;
 }
 
-inline bool dec_aligned(const void* p, const long* st) {
-  return p && st && (((uintptr_t)p) & 15u) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0;
-}
-
 // ---- kv_append
 struct AppTensor {
   const bf16_t* in;
@@ -492,63 +494,84 @@ struct AppendArgs {
   int nt, T, cap;
 };
 
+// One work item of either append kernel: chunks jj and jj + 4 of head row (b, tt, hd) of tensor `which`, bound
+// for row p of a cache (or row tt of q_out), as the bf16 cache holds them.
+struct AppRow {
+  int which, hd, tt, jj;
+  long b, p;
+  bf16_t* dst;                // where a bf16 output (q_out, a bf16 cache) takes chunk jj; formed before the loads
+  u32x4 lo, hi;
+};
+
+__device__ __forceinline__ void append_store_bf16(const AppRow& r) {
+  store16<kAligned16>(r.dst, r.lo);
+  store16<kAligned16>(r.dst + kDecD / 2, r.hi);
+}
+
+// What the two kernels share: the item's decode, the position rule, and the row's two chunks loaded as they are
+// or rotated (rope's bits, rounded to bf16).  False: the item is done -- a cache row outside [0, cap) stores
+// nothing, and q_out of such a position has just been zeroed.
+__device__ __forceinline__ bool append_row(const AppendArgs& a, long item, AppRow& r) {
+  constexpr int h = kDecD / 2;
+  r.which = 0;
+  if (item >= a.t[1].first) r.which = 1;              // k and v are always there
+  if (a.nt > 2 && item >= a.t[2].first) r.which = 2;
+  const AppTensor& x = a.t[r.which];
+  long i = item - x.first;
+  r.jj = (int)(i % 4);
+  i /= 4;
+  r.hd = (int)(i % x.H);
+  i /= x.H;
+  r.tt = (int)(i % a.T);
+  r.b = i / a.T;
+  r.p = (a.lens ? (long)a.lens[r.b] : 0L) + r.tt;
+  r.dst = x.out + r.b * x.ob + (x.cache ? r.p : (long)r.tt) * x.op + (long)r.hd * x.oh + r.jj * 8;
+  if (r.p < 0 || r.p >= a.cap) {
+    if (!x.cache) {                               // q_out of a sequence that is full: zeros
+      r.lo = r.hi = u32x4{0u, 0u, 0u, 0u};
+      append_store_bf16(r);
+    }
+    return false;                                 // no store outside the cache: neither rows nor scales
+  }
+  const bf16_t* src = x.in + r.b * x.ib + (long)r.tt * x.it + (long)r.hd * x.ih + r.jj * 8;
+  if (!x.rotate) {
+    r.lo = load16<u32x4, kAligned16>(src);
+    r.hi = load16<u32x4, kAligned16>(src + h);
+    return true;
+  }
+  const long trow = r.p * (long)h + r.jj * 8;
+  float x0[8], x1[8], c[8], sn[8], y0[8], y1[8];
+  load_chunk8(src, x0);
+  load_chunk8(src + h, x1);
+  load_chunk8(a.cos_t + trow, c);
+  load_chunk8(a.sin_t + trow, sn);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {                   // rope_kernel's expressions
+    const float sg = sn[e];
+    y0[e] = x0[e] * c[e] - x1[e] * sg;
+    y1[e] = x1[e] * c[e] + x0[e] * sg;
+  }
+  r.lo = pack_bf16x8(y0);
+  r.hi = pack_bf16x8(y1);
+  return true;
+}
+
 __global__ __launch_bounds__(kRowBlockThreads)
 void kv_append_kernel(const AppendArgs a) {
-  constexpr int h = kDecD / 2;
   const long step = (long)gridDim.x * kRowBlockThreads;
   for (long item = (long)blockIdx.x * kRowBlockThreads + threadIdx.x; item < a.total; item += step) {
-    int which = 0;
-    if (a.nt > 1 && item >= a.t[1].first) which = 1;
-    if (a.nt > 2 && item >= a.t[2].first) which = 2;
-    const AppTensor& x = a.t[which];
-    long r = item - x.first;
-    const int jj = (int)(r % 4);
-    r /= 4;
-    const int hd = (int)(r % x.H);
-    r /= x.H;
-    const int tt = (int)(r % a.T);
-    const long b = r / a.T;
-    const long p = (a.lens ? (long)a.lens[b] : 0L) + tt;
-    const bool inside = p >= 0 && p < a.cap;
-    if (x.cache && !inside) continue;             // no store outside the cache
-    bf16_t* dst = x.out + b * x.ob + (x.cache ? p : (long)tt) * x.op + (long)hd * x.oh + jj * 8;
-    if (!inside) {                                // q_out of a sequence that is full: zeros
-      const u32x4 z = {0u, 0u, 0u, 0u};
-      store16<kAligned16>(dst, z);
-      store16<kAligned16>(dst + h, z);
-      continue;
-    }
-    const bf16_t* src = x.in + b * x.ib + (long)tt * x.it + (long)hd * x.ih + jj * 8;
-    if (!x.rotate) {
-      const u32x4 lo = load16<u32x4, kAligned16>(src), hi = load16<u32x4, kAligned16>(src + h);
-      store16<kAligned16>(dst, lo);
-      store16<kAligned16>(dst + h, hi);
-      continue;
-    }
-    const long trow = p * (long)h + jj * 8;
-    float x0[8], x1[8], c[8], sn[8], y0[8], y1[8];
-    load_chunk8(src, x0);
-    load_chunk8(src + h, x1);
-    load_chunk8(a.cos_t + trow, c);
-    load_chunk8(a.sin_t + trow, sn);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {                 // rope_kernel's expressions
-      const float sg = sn[e];
-      y0[e] = x0[e] * c[e] - x1[e] * sg;
-      y1[e] = x1[e] * c[e] + x0[e] * sg;
-    }
-    store_chunk8(dst, y0);
-    store_chunk8(dst + h, y1);
+    AppRow r;
+    if (append_row(a, item, r)) append_store_bf16(r);
   }
 }
 
 // ---- kv_append into an MX-fp8 cache
 // The bf16 kernel's work items and position rule; a cached row is stored as quantize_mx_ref of the bf16
-// row the bf16 cache would hold: 64 e4m3 bytes and two e8m0 scale bytes (elements 0..31, 32..63).  The
-// four items of a row are the four lanes of a quad (item % 4 is the lane's, as the tensors' first
-// items, the total and the grid stride are all multiples of 4), and the quad takes every branch
-// together, so a block maximum is an integer max of bf16 magnitude bits over the lane's 8 elements and
-// then over the quad by two DPP quad_perm steps.  No LDS, no atomics, no workspace.
+// row the bf16 cache would hold (rope's bits first, then the quantiser): 64 e4m3 bytes and two e8m0 scale
+// bytes (elements 0..31, 32..63).  The four items of a row are the four lanes of a quad (item % 4 is the
+// lane's, as the tensors' first items, the total and the grid stride are all multiples of 4), and the quad
+// takes every branch together, so a block maximum is an integer max of bf16 magnitude bits over the lane's 8
+// elements and then over the quad by two DPP quad_perm steps.  No LDS, no atomics, no workspace.
 struct AppendQ8Args {
   AppendArgs a;               // t[0].out / t[1].out: the e4m3 bytes, their o* strides in bytes
   unsigned char* sc[2];       // the scales of k and v, (B, cap, Hkv, 2)
@@ -577,63 +600,22 @@ void kv_append_q8_kernel(const AppendQ8Args qa) {
   const AppendArgs& a = qa.a;
   const long step = (long)gridDim.x * kRowBlockThreads;
   for (long item = (long)blockIdx.x * kRowBlockThreads + threadIdx.x; item < a.total; item += step) {
-    int which = 0;
-    if (item >= a.t[1].first) which = 1;
-    if (a.nt > 2 && item >= a.t[2].first) which = 2;
-    const AppTensor& x = a.t[which];
-    long r = item - x.first;
-    const int jj = (int)(r % 4);
-    r /= 4;
-    const int hd = (int)(r % x.H);
-    r /= x.H;
-    const int tt = (int)(r % a.T);
-    const long b = r / a.T;
-    const long p = (a.lens ? (long)a.lens[b] : 0L) + tt;
-    const bool inside = p >= 0 && p < a.cap;
-    if (x.cache && !inside) continue;             // no store outside the cache: neither bytes nor scales
-    if (!x.cache && !inside) {                    // q_out of a sequence that is full: zeros
-      bf16_t* dst = x.out + b * x.ob + (long)tt * x.op + (long)hd * x.oh + jj * 8;
-      const u32x4 z = {0u, 0u, 0u, 0u};
-      store16<kAligned16>(dst, z);
-      store16<kAligned16>(dst + h, z);
+    AppRow r;
+    if (!append_row(a, item, r)) continue;
+    const AppTensor& x = a.t[r.which];
+    if (!x.cache) {                               // q_out stays bf16
+      append_store_bf16(r);
       continue;
     }
-    const bf16_t* src = x.in + b * x.ib + (long)tt * x.it + (long)hd * x.ih + jj * 8;
-    u32x4 lo, hi;                                 // the row's chunks jj and jj + 4 as the bf16 cache holds them
-    if (!x.rotate) {
-      lo = load16<u32x4, kAligned16>(src);
-      hi = load16<u32x4, kAligned16>(src + h);
-    } else {
-      const long trow = p * (long)h + jj * 8;
-      float x0[8], x1[8], c[8], sn[8], y0[8], y1[8];
-      load_chunk8(src, x0);
-      load_chunk8(src + h, x1);
-      load_chunk8(a.cos_t + trow, c);
-      load_chunk8(a.sin_t + trow, sn);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {               // rope_kernel's expressions
-        const float sg = sn[e];
-        y0[e] = x0[e] * c[e] - x1[e] * sg;
-        y1[e] = x1[e] * c[e] + x0[e] * sg;
-      }
-      lo = pack_bf16x8(y0);                       // rope's bits first, then the quantiser
-      hi = pack_bf16x8(y1);
-    }
-    if (!x.cache) {
-      bf16_t* dst = x.out + b * x.ob + (long)tt * x.op + (long)hd * x.oh + jj * 8;
-      store16<kAligned16>(dst, lo);
-      store16<kAligned16>(dst + h, hi);
-      continue;
-    }
-    const int e0 = mx_exponent(__uint_as_float(quad_max(amax_bits8(lo)) << 16));
-    const int e1 = mx_exponent(__uint_as_float(quad_max(amax_bits8(hi)) << 16));
+    const int e0 = mx_exponent(__uint_as_float(quad_max(amax_bits8(r.lo)) << 16));
+    const int e1 = mx_exponent(__uint_as_float(quad_max(amax_bits8(r.hi)) << 16));
     const float s0 = mx_scale_pow2(e0), s1 = mx_scale_pow2(e1);
-    unsigned char* dst = reinterpret_cast<unsigned char*>(x.out) + b * x.ob + p * x.op + (long)hd * x.oh + jj * 8;
-    *reinterpret_cast<u32x2*>(dst) = u32x2{cvt4_e4m3_bf16(lo[0], lo[1], s0), cvt4_e4m3_bf16(lo[2], lo[3], s0)};
-    *reinterpret_cast<u32x2*>(dst + h) = u32x2{cvt4_e4m3_bf16(hi[0], hi[1], s1), cvt4_e4m3_bf16(hi[2], hi[3], s1)};
-    if (jj == 0)
-      *reinterpret_cast<unsigned short*>(qa.sc[which] + b * qa.sb[which] + p * qa.sp[which] + (long)hd * qa.sh[which]) =
-          (unsigned short)((e0 + 127) | ((e1 + 127) << 8));
+    unsigned char* dst = reinterpret_cast<unsigned char*>(x.out) + r.b * x.ob + r.p * x.op + (long)r.hd * x.oh + r.jj * 8;
+    *reinterpret_cast<u32x2*>(dst) = u32x2{cvt4_e4m3_bf16(r.lo[0], r.lo[1], s0), cvt4_e4m3_bf16(r.lo[2], r.lo[3], s0)};
+    *reinterpret_cast<u32x2*>(dst + h) = u32x2{cvt4_e4m3_bf16(r.hi[0], r.hi[1], s1), cvt4_e4m3_bf16(r.hi[2], r.hi[3], s1)};
+    if (r.jj == 0)
+      *reinterpret_cast<unsigned short*>(qa.sc[r.which] + r.b * qa.sb[r.which] + r.p * qa.sp[r.which] +
+                                         (long)r.hd * qa.sh[r.which]) = (unsigned short)((e0 + 127) | ((e1 + 127) << 8));
   }
 }
 
@@ -669,36 +651,30 @@ LJS_API int ljs_decode_launch_plan(int B, int Hkv, int cap, int* out) {
   return decode_launch_plan(B, Hkv, cap, out, out + 1);
 }
 
+LJS_API int ljs_cache_desc_size() { return (int)sizeof(LjsCache); }
+
 namespace {
 
-// an MX-fp8 cache operand: e4m3 bytes (B, cap, Hkv, 64), 16-byte aligned base and byte strides; its e8m0
-// scales (B, cap, Hkv, 2): a 2-byte aligned base and even byte strides (one lane stores both bytes)
-inline bool q8_aligned(const void* p, const long* st) {
-  return p && st && (((uintptr_t)p) & 15u) == 0 && st[0] % 16 == 0 && st[1] % 16 == 0 && st[2] % 16 == 0;
-}
-inline bool q8_scale_aligned(const void* p, const long* st) {
-  return p && st && (((uintptr_t)p) & 1u) == 0 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0;
-}
-
-// the checks and the work items the two append launchers share (the cache operands' own alignment is
-// the caller's): 0 and *a filled, or hipErrorInvalidValue
-inline int append_plan(const void* k, const void* v, const void* q, void* kc, void* vc, void* q_out, int B, int T,
-                       int H, int Hkv, int cap, const long* sk, const long* sv, const long* sq, const long* skc,
-                       const long* svc, const long* sqo, const void* lens, const void* cos_t, const void* sin_t,
-                       long table_rows, AppendArgs* out) {
+// the checks and the work items of an append into cache c (either kind): 0 and *out filled, or
+// hipErrorInvalidValue
+inline int append_plan(const void* k, const void* v, const void* q, const LjsCache* c, void* q_out, int B, int T, int H,
+                       const long* sk, const long* sv, const long* sq, const long* sqo, const void* lens,
+                       const void* cos_t, const void* sin_t, long table_rows, AppendArgs* out) {
   const bool rot = cos_t != nullptr;
-  if (B < 1 || T < 1 || Hkv < 1 || cap < 1 || (cos_t == nullptr) != (sin_t == nullptr) ||
+  if (!c || !cache_aligned(*c)) return (int)hipErrorInvalidValue;
+  if (B < 1 || T < 1 || c->Hkv < 1 || c->cap < 1 || (cos_t == nullptr) != (sin_t == nullptr) ||
       (q == nullptr) != (q_out == nullptr) || (q && (!rot || H < 1)))
     return (int)hipErrorInvalidValue;
-  if (rot && (table_rows < cap || (((uintptr_t)cos_t) & 15u) || (((uintptr_t)sin_t) & 15u)))
+  if (rot && (table_rows < c->cap || (((uintptr_t)cos_t) & 15u) || (((uintptr_t)sin_t) & 15u)))
     return (int)hipErrorInvalidValue;
   if (lens && (((uintptr_t)lens) & 3u)) return (int)hipErrorInvalidValue;
-  if (!dec_aligned(k, sk) || !dec_aligned(v, sv) || (q && (!dec_aligned(q, sq) || !dec_aligned(q_out, sqo))))
+  if (!bf16_aligned(k, sk) || !bf16_aligned(v, sv) || (q && (!bf16_aligned(q, sq) || !bf16_aligned(q_out, sqo))))
     return (int)hipErrorInvalidValue;
   AppendArgs a{};
+  const int Hkv = c->Hkv;
   const long per_kv = (long)B * T * Hkv * 4;
-  a.t[0] = AppTensor{(const bf16_t*)k, (bf16_t*)kc, sk[0], sk[1], sk[2], skc[0], skc[1], skc[2], 0, Hkv, rot, 1};
-  a.t[1] = AppTensor{(const bf16_t*)v, (bf16_t*)vc, sv[0], sv[1], sv[2], svc[0], svc[1], svc[2], per_kv, Hkv, 0, 1};
+  a.t[0] = AppTensor{(const bf16_t*)k, (bf16_t*)c->k, sk[0], sk[1], sk[2], c->sk[0], c->sk[1], c->sk[2], 0, Hkv, rot, 1};
+  a.t[1] = AppTensor{(const bf16_t*)v, (bf16_t*)c->v, sv[0], sv[1], sv[2], c->sv[0], c->sv[1], c->sv[2], per_kv, Hkv, 0, 1};
   a.nt = 2;
   a.total = 2 * per_kv;
   if (q) {
@@ -710,64 +686,42 @@ inline int append_plan(const void* k, const void* v, const void* q, void* kc, vo
   a.sin_t = (const float*)sin_t;
   a.lens = (const int*)lens;
   a.T = T;
-  a.cap = cap;
+  a.cap = c->cap;
   *out = a;
   return 0;
 }
 
-inline dim3 append_grid(const AppendArgs& a) {
-  const long need = (a.total + kRowBlockThreads - 1) / kRowBlockThreads;
-  const long most = (long)ljs_device_cus() * kAppBlocksPerCu;
-  return dim3((unsigned)(need < most ? need : most));
-}
-
 }  // namespace
 
-// k, v (B, T, Hkv, 64) -> kc, vc (B, cap, Hkv, 64) at rows base[b] + t, base = lens (int32 [B], device)
-// or 0 when lens is null; q (B, T, H, 64) -> q_out (B, T, H, 64) when both are given.  cos_t / sin_t (f32
+// k, v (B, T, Hkv, 64) -> the cache c (cache_common.h; either kind) at rows base[b] + t, base = lens (int32 [B],
+// device) or 0 when lens is null; q (B, T, H, 64) -> q_out (B, T, H, 64) when both are given.  cos_t / sin_t (f32
 // [table_rows][32], table_rows >= cap) rotate k and q; both null: k is copied as it is.  s*: the
-// (batch, position, head) strides in elements.  Returns hipErrorInvalidValue, and launches and records
-// nothing, for an empty shape, a misaligned base or stride, one of q / q_out alone, q without a
-// table, or a table shorter than the cache.
-LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, void* kc, void* vc, void* q_out, int B, int T,
-                          int H, int Hkv, int cap, const long* sk, const long* sv, const long* sq, const long* skc,
-                          const long* svc, const long* sqo, const void* lens, const void* cos_t, const void* sin_t,
-                          long table_rows, hipStream_t st) {
-  if (!dec_aligned(kc, skc) || !dec_aligned(vc, svc)) return (int)hipErrorInvalidValue;
-  AppendArgs a{};
-  if (append_plan(k, v, q, kc, vc, q_out, B, T, H, Hkv, cap, sk, sv, sq, skc, svc, sqo, lens, cos_t, sin_t, table_rows,
-                  &a) != 0)
-    return (int)hipErrorInvalidValue;
-  const dim3 grid = append_grid(a);
-  hipLaunchKernelGGL(kv_append_kernel, grid, dim3(kRowBlockThreads), 0, st, a);
-  ljs_launch_rec(q ? "kv_append<rot,q>" : (cos_t ? "kv_append<rot>" : "kv_append<copy>"), grid, kRowBlockThreads);
-  return (int)hipGetLastError();
-}
-
-// ljs_kv_append into an MX-fp8 cache: kc / vc are e4m3 bytes (B, cap, Hkv, 64) and kcs / vcs their e8m0
-// scales (B, cap, Hkv, 2) -- of every row written, quantize_mx_ref of the bf16 row ljs_kv_append would
-// have stored; q_out stays bf16.  skc / svc / skcs / svcs: (batch, position, head) strides in bytes.
-// Refuses what ljs_kv_append refuses, and a null or odd scale base, an odd scale stride, or a cache
-// base or stride that is not a multiple of 16 bytes.
-LJS_API int ljs_kv_append_q8(const void* k, const void* v, const void* q, void* kc, void* vc, void* kcs, void* vcs,
-                             void* q_out, int B, int T, int H, int Hkv, int cap, const long* sk, const long* sv,
-                             const long* sq, const long* skc, const long* svc, const long* skcs, const long* svcs,
-                             const long* sqo, const void* lens, const void* cos_t, const void* sin_t, long table_rows,
-                             hipStream_t st) {
-  if (!q8_aligned(kc, skc) || !q8_aligned(vc, svc) || !q8_scale_aligned(kcs, skcs) || !q8_scale_aligned(vcs, svcs))
-    return (int)hipErrorInvalidValue;
+// (batch, position, head) strides in elements.  An MX-fp8 cache gets, of every row written, quantize_mx_ref
+// of the bf16 row a bf16 cache would have got; q_out stays bf16.  Returns hipErrorInvalidValue, and launches
+// and records nothing, for an empty shape, a misaligned base or stride, a cache cache_aligned refuses (a kind
+// that does not match its scale bases among them), one of q / q_out alone, q without a table, or a table
+// shorter than the cache.
+LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, const LjsCache* c, void* q_out, int B, int T,
+                          int H, const long* sk, const long* sv, const long* sq, const long* sqo, const void* lens,
+                          const void* cos_t, const void* sin_t, long table_rows, hipStream_t st) {
   AppendQ8Args qa{};
-  if (append_plan(k, v, q, kc, vc, q_out, B, T, H, Hkv, cap, sk, sv, sq, skc, svc, sqo, lens, cos_t, sin_t, table_rows,
-                  &qa.a) != 0)
+  if (append_plan(k, v, q, c, q_out, B, T, H, sk, sv, sq, sqo, lens, cos_t, sin_t, table_rows, &qa.a) != 0)
     return (int)hipErrorInvalidValue;
-  qa.sc[0] = (unsigned char*)kcs;
-  qa.sc[1] = (unsigned char*)vcs;
-  qa.sb[0] = skcs[0]; qa.sp[0] = skcs[1]; qa.sh[0] = skcs[2];
-  qa.sb[1] = svcs[0]; qa.sp[1] = svcs[1]; qa.sh[1] = svcs[2];
-  const dim3 grid = append_grid(qa.a);
-  hipLaunchKernelGGL(kv_append_q8_kernel, grid, dim3(kRowBlockThreads), 0, st, qa);
-  ljs_launch_rec(q ? "kv_append<rot,q,mx8>" : (cos_t ? "kv_append<rot,mx8>" : "kv_append<copy,mx8>"), grid,
-                 kRowBlockThreads);
+  const long need = (qa.a.total + kRowBlockThreads - 1) / kRowBlockThreads;
+  const long most = (long)ljs_device_cus() * kAppBlocksPerCu;
+  const dim3 grid((unsigned)(need < most ? need : most));
+  if (c->kind == kCacheMx8) {
+    qa.sc[0] = (unsigned char*)c->ks;
+    qa.sc[1] = (unsigned char*)c->vs;
+    qa.sb[0] = c->sks[0]; qa.sp[0] = c->sks[1]; qa.sh[0] = c->sks[2];
+    qa.sb[1] = c->svs[0]; qa.sp[1] = c->svs[1]; qa.sh[1] = c->svs[2];
+    hipLaunchKernelGGL(kv_append_q8_kernel, grid, dim3(kRowBlockThreads), 0, st, qa);
+    ljs_launch_rec(q ? "kv_append<rot,q,mx8>" : (cos_t ? "kv_append<rot,mx8>" : "kv_append<copy,mx8>"), grid,
+                   kRowBlockThreads);
+  } else {
+    hipLaunchKernelGGL(kv_append_kernel, grid, dim3(kRowBlockThreads), 0, st, qa.a);
+    ljs_launch_rec(q ? "kv_append<rot,q>" : (cos_t ? "kv_append<rot>" : "kv_append<copy>"), grid, kRowBlockThreads);
+  }
   return (int)hipGetLastError();
 }
 
@@ -793,51 +747,42 @@ inline ExtInstance extend_instance(int G, int T, bool mx8) {
   return {1, 8, names[mx8][G <= 8 ? 6 : 7]};
 }
 
-// the launch the decode and extend entries share: T = 1 is attn_decode, T > 1 attn_extend over the keys
-// [0, lens[b] + extra + t); ES: bytes per cache element; kcs / vcs: the scales (MX8 only)
+// the launch of ljs_attn_decode over a cache of the template's kind (c.kind has chosen it): T = 1 is attn_decode,
+// T > 1 attn_extend over the keys [0, lens[b] + extra + t)
 template <bool MX8>
-int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o, void* lse,
-                  void* ws, long ws_floats, const void* lens, int B, int T, int H, int Hkv, int cap, const long* sq,
-                  const long* skc, const long* svc, const long* skcs, const long* svcs, const long* so, float scale,
-                  int extra, hipStream_t st) {
-  constexpr long ES = MX8 ? 1 : 2;
+int decode_launch(const void* q, const LjsCache& c, void* o, void* lse, void* ws, long ws_floats, const void* lens,
+                  int B, int T, int H, const long* sq, const long* so, float scale, int extra, hipStream_t st) {
+  const int Hkv = c.Hkv, cap = c.cap;
   if (T < 1 || T > kExtMaxT) return (int)hipErrorInvalidValue;
   if (B < 1 || H < 1 || Hkv < 1 || cap < 1 || H % Hkv != 0 || H / Hkv > kDecMaxG || !(scale > 0.f) || extra < 0 ||
       B > 65535 || Hkv > 65535 || (long)B * T * H > 0x7fffffffL || !lens || !lse || (((uintptr_t)lens) & 3u) || (((uintptr_t)lse) & 3u))
     return (int)hipErrorInvalidValue;
-  if (!dec_aligned(q, sq) || !dec_aligned(o, so)) return (int)hipErrorInvalidValue;
-  if (MX8 ? (!q8_aligned(kc, skc) || !q8_aligned(vc, svc) || !q8_scale_aligned(kcs, skcs) || !q8_scale_aligned(vcs, svcs))
-          : (!dec_aligned(kc, skc) || !dec_aligned(vc, svc)))
-    return (int)hipErrorInvalidValue;
-  // a load's byte offset (of up to one unrolled block step past the cache) stays a positive int
-  const long reach = (long)cap + kDecKeyTile * kDecUnroll;
-  if (skc[1] < kDecD || svc[1] < kDecD || reach * skc[1] * ES >= 0x7fffffffL || reach * svc[1] * ES >= 0x7fffffffL)
-    return (int)hipErrorInvalidValue;
-  if (MX8 && (skcs[1] < 2 || svcs[1] < 2 || reach * skcs[1] >= 0x7fffffffL || reach * svcs[1] >= 0x7fffffffL))
-    return (int)hipErrorInvalidValue;
+  if (!bf16_aligned(q, sq) || !bf16_aligned(o, so) || !cache_aligned(c)) return (int)hipErrorInvalidValue;
+  // a load reaches up to one unrolled block step past the cache
+  if (!cache_reach_ok(c, (long)cap + kDecKeyTile * kDecUnroll)) return (int)hipErrorInvalidValue;
   DecodeArgs a{};
   if (decode_launch_plan(B, Hkv, cap, &a.splits, &a.kps) != 0) return (int)hipErrorInvalidValue;
   if (a.splits > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < (long)B * T * H * a.splits * kDecPart))
     return (int)hipErrorInvalidValue;
   a.q = (const bf16_t*)q;
-  a.kc = (const bf16_t*)kc;
-  a.vc = (const bf16_t*)vc;
+  a.kc = (const bf16_t*)c.k;
+  a.vc = (const bf16_t*)c.v;
   a.o = (bf16_t*)o;
   a.lse = (float*)lse;
   a.ws = (float*)ws;
   a.lens = (const int*)lens;
   a.qb = sq[0]; a.qt = sq[1]; a.qh = sq[2];
-  a.kb = skc[0]; a.ks = skc[1]; a.kh = skc[2];
-  a.vb = svc[0]; a.vs = svc[1]; a.vh = svc[2];
+  a.kb = c.sk[0]; a.ks = c.sk[1]; a.kh = c.sk[2];
+  a.vb = c.sv[0]; a.vs = c.sv[1]; a.vh = c.sv[2];
   a.ob = so[0]; a.ot = so[1]; a.oh = so[2];
   a.T = T; a.P = 1;
   a.B = B; a.H = H; a.Hkv = Hkv; a.G = H / Hkv; a.cap = cap; a.extra = extra;
   a.scale_log2 = scale * 1.4426950408889634f;
   if (MX8) {
-    a.ksc = (const unsigned char*)kcs;
-    a.vsc = (const unsigned char*)vcs;
-    a.ksb = skcs[0]; a.kss = skcs[1]; a.ksh = skcs[2];
-    a.vsb = svcs[0]; a.vss = svcs[1]; a.vsh = svcs[2];
+    a.ksc = (const unsigned char*)c.ks;
+    a.vsc = (const unsigned char*)c.vs;
+    a.ksb = c.sks[0]; a.kss = c.sks[1]; a.ksh = c.sks[2];
+    a.vsb = c.svs[0]; a.vss = c.svs[1]; a.vsh = c.svs[2];
   }
   dim3 grid((unsigned)a.splits, (unsigned)Hkv, (unsigned)B);
   const char* name;
@@ -879,53 +824,23 @@ int decode_launch(const void* q, const void* kc, const void* vc, const void* kcs
 
 }  // namespace
 
-// q (B, 1, H, 64), kc / vc (B, cap, Hkv, 64) -> o (B, 1, H, 64) bf16, lse (B, H) f32 over the keys [0,
-// min(lens[b] + extra, cap)) (the head of the file).  ws: f32 workspace of ws_floats floats, at least B H
-// splits kDecPart of them when the plan has more than one split.  s*: (batch, position, head) strides in
-// elements.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty shape, H %
-// Hkv != 0, H / Hkv > 16, scale <= 0, extra < 0, a misaligned base or stride, a key stride below 64, a
-// cache whose byte offsets do not fit 31 bits, an invalid forced plan or a workspace that is too small.
-LJS_API int ljs_attn_decode(const void* q, const void* kc, const void* vc, void* o, void* lse, void* ws, long ws_floats,
-                            const void* lens, int B, int H, int Hkv, int cap, const long* sq, const long* skc,
-                            const long* svc, const long* so, float scale, int extra, hipStream_t st) {
-  return decode_launch<false>(q, kc, vc, nullptr, nullptr, o, lse, ws, ws_floats, lens, B, 1, H, Hkv, cap, sq, skc, svc,
-                              nullptr, nullptr, so, scale, extra, st);
-}
-
-// ljs_attn_decode over an MX-fp8 cache: kc / vc e4m3 bytes (B, cap, Hkv, 64), kcs / vcs their e8m0 scales
-// (B, cap, Hkv, 2), all four with (batch, position, head) strides in bytes; q, o, lse, ws, the plan and
-// the merge launch as there.  The same refusals, with the 31-bit offset check on 1-byte elements and
-// on the scales, plus: a null or odd scale base, an odd scale stride, a scale row stride below 2, a
-// cache base or stride that is not a multiple of 16 bytes.
-LJS_API int ljs_attn_decode_q8(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o,
-                               void* lse, void* ws, long ws_floats, const void* lens, int B, int H, int Hkv, int cap,
-                               const long* sq, const long* skc, const long* svc, const long* skcs, const long* svcs,
-                               const long* so, float scale, int extra, hipStream_t st) {
-  return decode_launch<true>(q, kc, vc, kcs, vcs, o, lse, ws, ws_floats, lens, B, 1, H, Hkv, cap, sq, skc, svc, skcs,
-                             svcs, so, scale, extra, st);
-}
-
 LJS_API int ljs_extend_max_positions() { return kExtMaxT; }
 
-// q (B, T, H, 64) -> o (B, T, H, 64) bf16, lse (B, T, H) f32: row (b, t, h) over the keys [0, clamp(lens[b] + t + 1,
-// 0, cap)), after an append of the T positions that lens does not count yet -- the bits ljs_attn_decode
-// writes for (b, h) with extra = t + 1 under the same plan.  T == 1 IS that call (its launches, its
-// records).  ws: at least B T H splits kDecPart floats when the plan has more than one split.  Refuses
-// what ljs_attn_decode refuses, and T outside [1, 64].
-LJS_API int ljs_attn_extend(const void* q, const void* kc, const void* vc, void* o, void* lse, void* ws, long ws_floats,
-                            const void* lens, int B, int T, int H, int Hkv, int cap, const long* sq, const long* skc,
-                            const long* svc, const long* so, float scale, hipStream_t st) {
-  return decode_launch<false>(q, kc, vc, nullptr, nullptr, o, lse, ws, ws_floats, lens, B, T, H, Hkv, cap, sq, skc, svc,
-                              nullptr, nullptr, so, scale, 1, st);
-}
-
-// ljs_attn_extend over an MX-fp8 cache (ljs_attn_decode_q8's operands and refusals)
-LJS_API int ljs_attn_extend_q8(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o,
-                               void* lse, void* ws, long ws_floats, const void* lens, int B, int T, int H, int Hkv,
-                               int cap, const long* sq, const long* skc, const long* svc, const long* skcs,
-                               const long* svcs, const long* so, float scale, hipStream_t st) {
-  return decode_launch<true>(q, kc, vc, kcs, vcs, o, lse, ws, ws_floats, lens, B, T, H, Hkv, cap, sq, skc, svc, skcs,
-                             svcs, so, scale, 1, st);
+// q (B, T, H, 64) over the cache c (cache_common.h; either kind) -> o (B, T, H, 64) bf16, lse (B, T, H) f32: row (b, t, h)
+// over the keys [0, clamp(lens[b] + extra + t, 0, cap)) (the head of the file).  T = 1 is attn_decode (extra = 1 after
+// an append that lens does not count yet); 1 < T <= 64 with extra = 1 is attn_extend, whose row t has the bits
+// of the T = 1 call with extra = t + 1 under the same plan.  ws: f32 workspace of ws_floats floats, at least
+// B T H splits kDecPart of them when the plan has more than one split.  sq / so: (batch, position, head) strides in
+// elements.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty shape, T outside
+// [1, 64], H % Hkv != 0, H / Hkv > 16, scale <= 0, extra < 0, a misaligned base or stride, a cache cache_aligned or
+// cache_reach_ok refuses (a kind that does not match its scale bases, a key stride below 64 or a scale row
+// stride below 2, byte offsets that do not fit 31 bits), an invalid forced plan or a workspace that is too small.
+LJS_API int ljs_attn_decode(const void* q, const LjsCache* c, void* o, void* lse, void* ws, long ws_floats,
+                            const void* lens, int B, int T, int H, const long* sq, const long* so, float scale,
+                            int extra, hipStream_t st) {
+  if (!c) return (int)hipErrorInvalidValue;
+  return c->kind == kCacheMx8 ? decode_launch<true>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st)
+                              : decode_launch<false>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st);
 }
 
 // lens[0 .. B) += n: one small launch after the last layer of a decode step

@@ -45,6 +45,10 @@
 //
 // Output.  The ring is idle after the sweep: a wave stages its rows in 2 or 4 KiB of it and they leave
 // as whole 128-byte rows.  No atomics, no memset, no workspace, no tickets; the same bits on every run.
+//
+// Entry point.  ljs_attn_chunk takes the cache as one LjsCache descriptor with an explicit kind
+// (cache_common.h: the struct, the alignment rules and the reach check decode.hip's launchers use too).
+#include "cache_common.h"
 #include "common.h"
 
 namespace {
@@ -379,51 +383,35 @@ inline void plan_chunk(int B, int T, int H, int Hkv, int cus, int* rows, unsigne
   grid[2] = (unsigned)B;
 }
 
-inline bool bf16_aligned(const void* p, const long* st) {
-  return p && st && (((uintptr_t)p) & 15u) == 0 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0;
-}
-inline bool q8_aligned(const void* p, const long* st) {
-  return p && st && (((uintptr_t)p) & 15u) == 0 && st[0] % 16 == 0 && st[1] % 16 == 0 && st[2] % 16 == 0;
-}
-inline bool scale_aligned(const void* p, const long* st) {
-  return p && st && (((uintptr_t)p) & 1u) == 0 && st[0] % 2 == 0 && st[1] % 2 == 0 && st[2] % 2 == 0;
-}
-
+// the launch of ljs_attn_chunk over a cache of the template's kind (c.kind has chosen it)
 template <bool MX8>
-int chunk_launch(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o, void* lse,
-                 const void* lens, int B, int T, int H, int Hkv, int cap, const long* sq, const long* skc,
-                 const long* svc, const long* skcs, const long* svcs, const long* so, float scale, hipStream_t st) {
+int chunk_launch(const void* q, const LjsCache& c, void* o, void* lse, const void* lens, int B, int T, int H,
+                 const long* sq, const long* so, float scale, hipStream_t st) {
   constexpr long ES = MX8 ? 1 : 2;       // bytes per cache element
+  const int Hkv = c.Hkv, cap = c.cap;
   if (B < 1 || T < 1 || H < 1 || Hkv < 1 || cap < 1 || H % Hkv != 0 || H / Hkv > kMaxG || !(scale > 0.f) ||
       B > 65535 || Hkv > 65535 || (long)T * H > 0x3fffffffL || (long)B * T * H > 0x7fffffffL || !lens || !lse ||
       (((uintptr_t)lens) & 3u) || (((uintptr_t)lse) & 3u))
     return (int)hipErrorInvalidValue;
-  if (!bf16_aligned(q, sq) || !bf16_aligned(o, so)) return (int)hipErrorInvalidValue;
-  if (MX8 ? (!q8_aligned(kc, skc) || !q8_aligned(vc, svc) || !scale_aligned(kcs, skcs) || !scale_aligned(vcs, svcs))
-          : (!bf16_aligned(kc, skc) || !bf16_aligned(vc, svc)))
-    return (int)hipErrorInvalidValue;
-  // a load's byte offset (of up to one tile past the cache) stays a positive int
-  const long reach = (long)cap + kKeys;
-  if (skc[1] < kD || svc[1] < kD || reach * skc[1] * ES >= 0x7fffffffL || reach * svc[1] * ES >= 0x7fffffffL)
-    return (int)hipErrorInvalidValue;
-  if (MX8 && (skcs[1] < 2 || svcs[1] < 2 || reach * skcs[1] >= 0x7fffffffL || reach * svcs[1] >= 0x7fffffffL))
-    return (int)hipErrorInvalidValue;
+  if (!bf16_aligned(q, sq) || !bf16_aligned(o, so) || !cache_aligned(c)) return (int)hipErrorInvalidValue;
+  // a load reaches up to one tile past the cache
+  if (!cache_reach_ok(c, (long)cap + kKeys)) return (int)hipErrorInvalidValue;
   ChunkArgs a{};
   a.q = (const bf16_t*)q;
-  a.kc = (const unsigned char*)kc;
-  a.vc = (const unsigned char*)vc;
+  a.kc = (const unsigned char*)c.k;
+  a.vc = (const unsigned char*)c.v;
   a.o = (bf16_t*)o;
   a.lse = (float*)lse;
   a.lens = (const int*)lens;
   a.qb = sq[0]; a.qt = sq[1]; a.qh = sq[2];
   a.ob = so[0]; a.ot = so[1]; a.oh = so[2];
-  a.kb = skc[0] * ES; a.ks = skc[1] * ES; a.kh = skc[2] * ES;
-  a.vb = svc[0] * ES; a.vs = svc[1] * ES; a.vh = svc[2] * ES;
+  a.kb = c.sk[0] * ES; a.ks = c.sk[1] * ES; a.kh = c.sk[2] * ES;
+  a.vb = c.sv[0] * ES; a.vs = c.sv[1] * ES; a.vh = c.sv[2] * ES;
   if (MX8) {
-    a.ksc = (const unsigned char*)kcs;
-    a.vsc = (const unsigned char*)vcs;
-    a.ksb = skcs[0]; a.kss = skcs[1]; a.ksh = skcs[2];
-    a.vsb = svcs[0]; a.vss = svcs[1]; a.vsh = svcs[2];
+    a.ksc = (const unsigned char*)c.ks;
+    a.vsc = (const unsigned char*)c.vs;
+    a.ksb = c.sks[0]; a.kss = c.sks[1]; a.ksh = c.sks[2];
+    a.vsb = c.svs[0]; a.vss = c.svs[1]; a.vsh = c.svs[2];
   }
   a.T = T; a.H = H; a.G = H / Hkv; a.cap = cap;
   a.scale_log2 = scale * kLog2e;
@@ -459,25 +447,16 @@ LJS_API int ljs_chunk_plan(int B, int T, int H, int Hkv, int cus, int* out) {
   return 0;
 }
 
-// q (B, T, H, 64), kc / vc (B, cap, Hkv, 64) bf16 -> o (B, T, H, 64) bf16, lse (B, T, H) f32: row (b, t, h) over the
-// cache rows [0, clamp(lens[b] + t + 1, 0, cap)) (the head of the file).  s*: (batch, position, head) strides in
-// elements.  One launch.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty
-// shape, H % Hkv != 0, H / Hkv > 16, scale <= 0, a null or misaligned lens or lse, a base or stride that
-// is not 16-byte aligned, a key stride below 64, or a cache whose byte offsets do not fit 31 bits.
-LJS_API int ljs_attn_chunk(const void* q, const void* kc, const void* vc, void* o, void* lse, const void* lens, int B,
-                           int T, int H, int Hkv, int cap, const long* sq, const long* skc, const long* svc,
-                           const long* so, float scale, hipStream_t st) {
-  return chunk_launch<false>(q, kc, vc, nullptr, nullptr, o, lse, lens, B, T, H, Hkv, cap, sq, skc, svc, nullptr,
-                             nullptr, so, scale, st);
-}
-
-// ljs_attn_chunk over an MX-fp8 cache: kc / vc e4m3 bytes (B, cap, Hkv, 64), kcs / vcs their e8m0 scales (B, cap,
-// Hkv, 2), all four with strides in bytes.  The same refusals, plus: a null or odd scale base, an odd
-// scale stride, a scale row stride below 2, a cache base or stride that is not a multiple of 16 bytes.
-LJS_API int ljs_attn_chunk_q8(const void* q, const void* kc, const void* vc, const void* kcs, const void* vcs, void* o,
-                              void* lse, const void* lens, int B, int T, int H, int Hkv, int cap, const long* sq,
-                              const long* skc, const long* svc, const long* skcs, const long* svcs, const long* so,
-                              float scale, hipStream_t st) {
-  return chunk_launch<true>(q, kc, vc, kcs, vcs, o, lse, lens, B, T, H, Hkv, cap, sq, skc, svc, skcs, svcs, so, scale,
-                            st);
+// q (B, T, H, 64) over the cache c (cache_common.h; either kind) -> o (B, T, H, 64) bf16, lse (B, T, H) f32: row (b, t, h)
+// over the cache rows [0, clamp(lens[b] + t + 1, 0, cap)) (the head of the file).  sq / so: (batch, position, head) strides
+// in elements.  One launch.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty
+// shape, H % Hkv != 0, H / Hkv > 16, scale <= 0, a null or misaligned lens or lse, a base or stride of q or o
+// that is not 16-byte aligned, or a cache cache_aligned or cache_reach_ok refuses (a kind that does not match
+// its scale bases, a misaligned buffer, a key stride below 64 or a scale row stride below 2, byte offsets that
+// do not fit 31 bits).
+LJS_API int ljs_attn_chunk(const void* q, const LjsCache* c, void* o, void* lse, const void* lens, int B, int T, int H,
+                           const long* sq, const long* so, float scale, hipStream_t st) {
+  if (!c) return (int)hipErrorInvalidValue;
+  return c->kind == kCacheMx8 ? chunk_launch<true>(q, *c, o, lse, lens, B, T, H, sq, so, scale, st)
+                              : chunk_launch<false>(q, *c, o, lse, lens, B, T, H, sq, so, scale, st);
 }

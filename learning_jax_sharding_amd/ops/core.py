@@ -1147,24 +1147,12 @@ def cached_attention(q: ShardedArray, k: ShardedArray, v: ShardedArray, cache_la
     q, k, v = _cache_layout(k, v, cache_layer, lens, q)
     kc, vc = cache_layer[:2]
     _plan.record("cached_attention", tiles=kc.tile.tile_shape, kv_heads=k.shape[2])
+    mode = "chunk" if chunk else ("extend" if extend else "decode")
     loc = {}
     for d, qt in q.local.items():
-        ln = lens.local[d]
-        if _quantised(cache_layer):
-            bufs = [c.local[d] for c in cache_layer]
-            qr = K.kv_append_q8(k.local[d], v.local[d], *bufs, ln, q=qt if rope_theta is not None else None,
-                                theta=rope_theta)
-            qn = qt if qr is None else qr
-            loc[d] = (K.attn_chunk_q8(qn, *bufs, ln, float(scale)) if chunk else
-                      K.attn_extend_q8(qn, *bufs, ln, float(scale)) if extend else
-                      K.attn_decode_q8(qn, *bufs, ln, float(scale), extra=1))[0]
-            continue
-        qr = K.kv_append(k.local[d], v.local[d], kc.local[d], vc.local[d], ln,
-                         q=qt if rope_theta is not None else None, theta=rope_theta)
-        qn = qt if qr is None else qr
-        loc[d] = (K.attn_chunk(qn, kc.local[d], vc.local[d], ln, float(scale)) if chunk else
-                  K.attn_extend(qn, kc.local[d], vc.local[d], ln, float(scale)) if extend else
-                  K.attn_decode(qn, kc.local[d], vc.local[d], ln, float(scale), extra=1))[0]
+        ln, bufs = lens.local[d], [c.local[d] for c in cache_layer]
+        qr = K.cache_append(k.local[d], v.local[d], bufs, ln, qt if rope_theta is not None else None, rope_theta)
+        loc[d] = K.cache_attend(qt if qr is None else qr, bufs, ln, float(scale), mode)[0]
     return ShardedArray(q.shape, q.dtype if _quantised(cache_layer) else vc.dtype, q.sharding, loc)
 
 
@@ -1178,9 +1166,8 @@ def cache_prefill(k: ShardedArray, v: ShardedArray, cache_layer) -> None:
         raise ValueError(f"KV cache: a prompt of {k.shape[1]} positions does not fit max_len {kc.shape[1]}")
     _, k, v = _cache_layout(k, v, cache_layer, None)
     _plan.record("cache_prefill", tiles=kc.tile.tile_shape)
-    append = K.kv_append_q8 if _quantised(cache_layer) else K.kv_append
     for d, kt in k.local.items():
-        append(kt, v.local[d], *[c.local[d] for c in cache_layer])
+        K.cache_append(kt, v.local[d], [c.local[d] for c in cache_layer])
 
 
 def cache_set_lens(lens: ShardedArray, value) -> None:

@@ -34,6 +34,18 @@ c_void_p, c_int, c_long, c_float, c_uint = ctypes.c_void_p, ctypes.c_int, ctypes
 c_double = ctypes.c_double
 _LP = ctypes.POINTER(ctypes.c_long)
 
+
+class _CacheDesc(ctypes.Structure):
+    """``LjsCache`` of csrc/kernels/cache_common.h: a KV cache as one operand, of an explicit ``kind``.  Strides are
+    the (batch, position, head) ones, in elements for bf16 buffers and in bytes for e4m3 and scale buffers."""
+    _fields_ = [("kind", c_int), ("cap", c_int), ("Hkv", c_int), ("k", c_void_p), ("v", c_void_p),
+                ("sk", c_long * 3), ("sv", c_long * 3), ("ks", c_void_p), ("vs", c_void_p),
+                ("sks", c_long * 3), ("svs", c_long * 3)]
+
+
+_CP, _L3 = ctypes.POINTER(_CacheDesc), c_long * 3
+CACHE_BF16, CACHE_MX8 = 0, 1        # _CacheDesc.kind
+
 _SIGS = {
     "ljs_pack_rows": [c_void_p, c_int, c_void_p, c_long, c_long, c_long, c_int, c_void_p, c_void_p],
     "ljs_gemm_group_end": [c_void_p],
@@ -79,24 +91,14 @@ _SIGS = {
     "ljs_gqa_reduce": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP,
                        c_void_p],
     "ljs_gqa_set_max_blocks": [c_int],
-    "ljs_kv_append": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                      _LP, _LP, _LP, _LP, _LP, _LP, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
-    "ljs_attn_decode": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int,
-                        c_int, c_int, _LP, _LP, _LP, _LP, c_float, c_int, c_void_p],
-    "ljs_kv_append_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                         c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, _LP, _LP, c_void_p, c_void_p, c_void_p, c_long,
-                         c_void_p],
-    "ljs_attn_decode_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
-                           c_void_p, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_int, c_void_p],
-    "ljs_attn_extend": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int,
-                        c_int, c_int, c_int, _LP, _LP, _LP, _LP, c_float, c_void_p],
-    "ljs_attn_extend_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
-                           c_void_p, c_int, c_int, c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_void_p],
+    # the cached-decoding entries take the cache as one descriptor (_CacheDesc below)
+    "ljs_cache_desc_size": [],
+    "ljs_kv_append": [c_void_p, c_void_p, c_void_p, _CP, c_void_p, c_int, c_int, c_int, _LP, _LP, _LP, _LP, c_void_p,
+                      c_void_p, c_void_p, c_long, c_void_p],
+    "ljs_attn_decode": [c_void_p, _CP, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, _LP, _LP,
+                        c_float, c_int, c_void_p],
     "ljs_extend_max_positions": [],
-    "ljs_attn_chunk": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                       _LP, _LP, _LP, _LP, c_float, c_void_p],
-    "ljs_attn_chunk_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                          c_int, c_int, c_int, _LP, _LP, _LP, _LP, _LP, _LP, c_float, c_void_p],
+    "ljs_attn_chunk": [c_void_p, _CP, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _LP, _LP, c_float, c_void_p],
     "ljs_chunk_plan": [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_chunk_set_rows": [c_int],
     "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
@@ -211,6 +213,9 @@ def lib():
                 L.ljs_launch_count_copy.restype = c_long
                 for name in ("ljs_grad_sumsq_ws_words", "ljs_grad_sumsq_slot_word", "ljs_grad_sumsq_slots"):
                     getattr(L, name).restype = c_long
+                if L.ljs_cache_desc_size() != ctypes.sizeof(_CacheDesc):
+                    raise RuntimeError(f"{_LIBPATH}: LjsCache has {L.ljs_cache_desc_size()} bytes and its ctypes mirror "
+                                       f"{ctypes.sizeof(_CacheDesc)}: rebuild the library")
                 _LIB = L
     return _LIB
 
@@ -2670,48 +2675,115 @@ def _decode_launch_plan(B: int, Hkv: int, cap: int):
     return int(out[0]), int(out[1])
 
 
+def _rows_supported(ts, dtype, width: int, base: int, unit: int) -> bool:
+    """The operand rule of decode.hip and prefill.hip: ``dtype`` ``(B, S, H, width)`` GPU tensors, the last dim contiguous,
+    the base a multiple of ``base`` bytes and the three outer strides multiples of ``unit``."""
+    return all(t.is_cuda and t.dim() == 4 and t.dtype == dtype and t.shape[-1] == width and t.numel()
+               and t.stride(-1) == 1 and t.data_ptr() % base == 0 and all(t.stride(i) % unit == 0 for i in range(3))
+               for t in ts)
+
+
 def decode_supported(*ts: torch.Tensor) -> bool:
     """Whether decode.hip takes these operands as they are: bf16 ``(B, S, H, 64)`` GPU tensors, the head
     dim contiguous, the base and the three outer strides 16-byte aligned."""
-    return all(t.is_cuda and t.dim() == 4 and t.dtype == torch.bfloat16 and t.shape[-1] == 64 and t.numel()
-               and t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(t.stride(i) % 8 == 0 for i in range(3))
-               for t in ts)
+    return _rows_supported(ts, torch.bfloat16, 64, 16, 8)
+
+
+def decode_q8_supported(*ts: torch.Tensor) -> bool:
+    """Whether decode.hip takes these MX-fp8 cache buffers as they are: uint8 ``(B, S, H, 64)`` GPU tensors (e4m3
+    bytes), the head dim contiguous, the base and the three outer strides multiples of 16 bytes."""
+    return _rows_supported(ts, torch.uint8, 64, 16, 16)
+
+
+def decode_scale_supported(*ts: torch.Tensor) -> bool:
+    """Whether decode.hip takes these e8m0 scale buffers as they are: uint8 ``(B, S, H, 2)`` GPU tensors, the
+    last dim contiguous, the base and the three outer strides even (one 2-byte store writes a row's two)."""
+    return _rows_supported(ts, torch.uint8, 2, 2, 2)
 
 
 def _lens_ok(lens: Optional[torch.Tensor], B: int) -> bool:
     return lens is None or (lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous())
 
 
-def kv_append_raw(k, v, kc, vc, lens=None, q=None, q_out=None, cos=None, sin=None) -> int:
-    """One ``ljs_kv_append`` launch on the tensors as they are; returns the launcher's code (non-zero:
-    rejected, nothing launched) instead of raising."""
-    B, T, Hkv, _ = k.shape
-    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
-    return lib().ljs_kv_append(_p(k), _p(v), _p(q), _p(kc), _p(vc), _p(q_out), B, T, q.shape[2] if q is not None else 0,
-                               Hkv, kc.shape[1], st(k), st(v), st(q), st(kc), st(vc), st(q_out), _p(lens), _p(cos),
-                               _p(sin), cos.shape[0] if cos is not None else 0, _stream(k))
+# ---- the cache as one operand.  A cache is ``(kc, vc)``, bf16 ``(B, cap, Hkv, 64)``, or the MX-fp8 ``(kc, vc, kcs, vcs)``:
+# e4m3 bytes ``(B, cap, Hkv, 64)`` and e8m0 scale bytes ``(B, cap, Hkv, 2)``, all uint8.  The C entries take it as a
+# _CacheDesc whose kind is stated by the caller, never inferred from which buffers are there.
+def _cache_desc(kind: int, kc, vc, kcs=None, vcs=None) -> _CacheDesc:
+    """The descriptor of these buffers as they are (None: a null base), of the stated ``kind``."""
+    d = _CacheDesc(kind, kc.shape[1], kc.shape[2], kc.data_ptr(), vc.data_ptr(), _L3(*kc.stride()[:3]), _L3(*vc.stride()[:3]))
+    if kcs is not None:
+        d.ks, d.sks = kcs.data_ptr(), _L3(*kcs.stride()[:3])
+    if vcs is not None:
+        d.vs, d.svs = vcs.data_ptr(), _L3(*vcs.stride()[:3])
+    return d
 
 
-def kv_append(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
-    """``vc[b, p] = v[b, t]`` and ``kc[b, p] = k[b, t]`` for ``p = base[b] + t``, ``base = lens`` (int32 ``[B]`` on
-    the device) or 0 without it; with ``theta`` k is rotated by the rotary embedding at position ``p`` on
-    its way (rope.hip's bits), and a ``q`` is rotated the same way into the returned tensor.  Rows with
-    ``p >= cap`` are not written.  One launch."""
+def _cache_kind(cache) -> int:
+    return CACHE_MX8 if len(cache) == 4 else CACHE_BF16
+
+
+def _cache_supported(cache) -> bool:
+    """Whether the kernels take this cache as it is: the buffers' dtype, shape and alignment, k and v alike, and
+    scales of shape ``kc.shape[:3] + (2,)``."""
+    kc, vc = cache[:2]
+    if len(cache) == 2:
+        return decode_supported(kc, vc) and kc.shape == vc.shape
+    return decode_q8_supported(kc, vc) and decode_scale_supported(*cache[2:]) and kc.shape == vc.shape \
+        and cache[2].shape == cache[3].shape == kc.shape[:3] + (2,)
+
+
+def _refusal(what: str, x, cache, positions: str = "T") -> NotImplementedError:
+    kc = cache[0]
+    got = f"got {x.dtype} {tuple(x.shape)} strides {x.stride()}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}"
+    if len(cache) == 4:
+        got += f", scales {cache[2].dtype} {tuple(cache[2].shape)} strides {cache[2].stride()}"
+    return NotImplementedError(f"{what} kernel: bf16 (B, {positions}, H, 64) q / k / v and caches (B, cap, Hkv, 64), bf16 or uint8 "
+                               f"with uint8 scales (B, cap, Hkv, 2) of even strides, all with 16-byte aligned bases and "
+                               f"strides, H / Hkv <= {decode_max_group()}, an int32 [B] lens; {got}")
+
+
+def _kv_append_desc(desc: _CacheDesc, k, v, lens=None, q=None, q_out=None, cos=None, sin=None) -> int:
+    """One ``ljs_kv_append`` launch on the tensors as they are into the cache ``desc`` describes; returns the launcher's
+    code (non-zero: rejected, nothing launched) instead of raising."""
+    B, T = k.shape[:2]
+    st = lambda t: _L3(*t.stride()[:3]) if t is not None else None   # noqa: E731
+    return lib().ljs_kv_append(_p(k), _p(v), _p(q), ctypes.byref(desc), _p(q_out), B, T, q.shape[2] if q is not None else 0,
+                               st(k), st(v), st(q), st(q_out), _p(lens), _p(cos), _p(sin),
+                               cos.shape[0] if cos is not None else 0, _stream(k))
+
+
+def _attn_decode_desc(desc: _CacheDesc, q, o, lse, ws, lens, scale: float, extra: int) -> int:
+    """One ``ljs_attn_decode`` call (the launch over ``q``'s ``T`` positions, and the merge launch when the plan has more
+    than one split) on the tensors as they are (``lse``: f32 ``B T H`` values); returns the launcher's code."""
+    B, T, H, _ = q.shape
+    return lib().ljs_attn_decode(_p(q), ctypes.byref(desc), _p(o), _p(lse), _p(ws), ws.numel() if ws is not None else 0,
+                                 _p(lens), B, T, H, _L3(*q.stride()[:3]), _L3(*o.stride()[:3]), float(scale), int(extra),
+                                 _stream(q))
+
+
+def _attn_chunk_desc(desc: _CacheDesc, q, o, lse, lens, scale: float) -> int:
+    """One ``ljs_attn_chunk`` launch on the tensors as they are (``lse``: f32 ``(B, T, H)``); returns the launcher's code."""
+    B, T, H, _ = q.shape
+    return lib().ljs_attn_chunk(_p(q), ctypes.byref(desc), _p(o), _p(lse), _p(lens), B, T, H, _L3(*q.stride()[:3]),
+                                _L3(*o.stride()[:3]), float(scale), _stream(q))
+
+
+def cache_append(what: str, k, v, cache, lens, q, theta):
+    """The checked append behind :func:`kv_append` / :func:`kv_append_q8` (``what``: the name refusals carry)."""
+    kc = cache[0]
     B = k.shape[0]
-    ok = decode_supported(k, v, kc, vc) and (q is None or decode_supported(q)) and _lens_ok(lens, B) \
-        and k.shape == v.shape and kc.shape == vc.shape and kc.shape[0] == B and kc.shape[2] == k.shape[2] \
+    ok = decode_supported(k, v) and (q is None or decode_supported(q)) and _lens_ok(lens, B) and _cache_supported(cache) \
+        and k.shape == v.shape and kc.shape[0] == B and kc.shape[2] == k.shape[2] \
         and (q is None or (theta is not None and q.shape[:2] == k.shape[:2]))
     if not ok:
-        raise NotImplementedError(f"kv_append kernel: bf16 (B, T, H, 64) operands with 16-byte aligned bases and "
-                                  f"strides and an int32 [B] lens; got k {k.dtype} {tuple(k.shape)} strides "
-                                  f"{k.stride()}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}")
+        raise _refusal(what, k, cache)
     cos = sin = q_out = None
     if theta is not None:
         from .kernels import rope_table
         cos, sin = rope_table(k.device, 64, theta, kc.shape[1])
     if q is not None:
         q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-    _ck(kv_append_raw(k, v, kc, vc, lens, q, q_out, cos, sin), "ljs_kv_append")
+    _ck(_kv_append_desc(_cache_desc(_cache_kind(cache), *cache), k, v, lens, q, q_out, cos, sin), "ljs_kv_append")
     return q_out
 
 
@@ -2732,67 +2804,46 @@ def _decode_ws(dev: torch.device, floats: int) -> torch.Tensor:
     return t
 
 
-def attn_decode_raw(q, kc, vc, o, lse, ws, lens, scale: float, extra: int = 1) -> int:
-    """One ``ljs_attn_decode`` call (the decode launch, and the merge launch when the plan has more than
-    one split) on the tensors as they are; returns the launcher's code instead of raising."""
-    B, _, H, _ = q.shape
-    return lib().ljs_attn_decode(_p(q), _p(kc), _p(vc), _p(o), _p(lse), _p(ws), ws.numel() if ws is not None else 0,
-                                 _p(lens), B, H, kc.shape[2], kc.shape[1], _longs(_strides3(q)),
-                                 _longs(_strides3(kc)), _longs(_strides3(vc)), _longs(_strides3(o)), float(scale),
-                                 int(extra), _stream(q))
-
-
-def attn_decode(q, kc, vc, lens, scale: float, extra: int = 1):
-    """Single-query attention of ``q`` (B, 1, H, 64) over rows ``[0, min(lens[b] + extra, cap))`` of the caches
-    ``kc`` / ``vc`` (B, cap, Hkv, 64): ``(o`` bf16 (B, 1, H, 64), ``lse2`` f32 (B, H, 1)``)``; a sequence without
-    keys gets ``o = 0``, ``lse2 = +inf``."""
+def cache_attend(what: str, q, cache, lens, scale: float, max_t: Optional[int], extra: int = 1):
+    """The checked call behind the ``attn_*`` functions below (``what``: the name refusals carry).  Attention of ``q`` over ``cache``: by ``ljs_attn_decode`` for up to ``max_t`` positions (with its workspace), by
+    ``ljs_attn_chunk`` when ``max_t`` is None.  ``(o`` (B, T, H, 64), ``lse2`` (B, H, T)``)``."""
     B, T, H, _ = q.shape
-    Hkv = kc.shape[2]
-    ok = decode_supported(q, kc, vc) and T == 1 and kc.shape == vc.shape and kc.shape[0] == B and lens is not None \
-        and _lens_ok(lens, B) and H % Hkv == 0 and H // Hkv <= decode_max_group() and scale > 0
+    kc = cache[0]
+    ok = decode_supported(q) and kc.dim() == 4 and kc.shape[0] == B and lens is not None and _lens_ok(lens, B) \
+        and _cache_supported(cache) and H % kc.shape[2] == 0 and H // kc.shape[2] <= decode_max_group() and scale > 0 \
+        and (max_t is None or 1 <= T <= max_t)
     if not ok:
-        raise NotImplementedError(f"attn_decode kernel: bf16 q (B, 1, H, 64) and caches (B, cap, Hkv, 64) with 16-byte "
-                                  f"aligned bases and strides, H / Hkv <= {decode_max_group()}, int32 [B] lens; got q "
-                                  f"{q.dtype} {tuple(q.shape)}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}")
-    splits, _ = _decode_launch_plan(B, Hkv, kc.shape[1])
-    ws = _decode_ws(q.device, B * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
-    o = torch.empty((B, 1, H, 64), dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device)
-    _ck(attn_decode_raw(q, kc, vc, o, lse, ws, lens, scale, extra), "ljs_attn_decode")
-    return o, lse
+        raise _refusal(what, q, cache, "T" if max_t is None else ("1" if max_t == 1 else f"T <= {max_t}"))
+    desc = _cache_desc(_cache_kind(cache), *cache)
+    o = torch.empty((B, T, H, 64), dtype=torch.bfloat16, device=q.device)
+    if max_t is None:
+        lse = torch.empty((B, T, H), dtype=torch.float32, device=q.device)
+        _ck(_attn_chunk_desc(desc, q, o, lse, lens, scale), "ljs_attn_chunk")
+        return o, lse.permute(0, 2, 1)
+    splits, _ = _decode_launch_plan(B, kc.shape[2], kc.shape[1])
+    ws = _decode_ws(q.device, B * T * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
+    lse = torch.empty((B, H, 1) if max_t == 1 else (B, T, H), dtype=torch.float32, device=q.device)
+    _ck(_attn_decode_desc(desc, q, o, lse, ws, lens, scale, extra), "ljs_attn_decode")
+    return o, (lse if max_t == 1 else lse.permute(0, 2, 1))
 
 
-# ---- the MX-fp8 cache: e4m3 bytes (B, cap, Hkv, 64) and e8m0 scale bytes (B, cap, Hkv, 2), both uint8
-def decode_q8_supported(*ts: torch.Tensor) -> bool:
-    """Whether decode.hip takes these MX-fp8 cache buffers as they are: uint8 ``(B, S, H, 64)`` GPU tensors (e4m3
-    bytes), the head dim contiguous, the base and the three outer strides multiples of 16 bytes."""
-    return all(t.is_cuda and t.dim() == 4 and t.dtype == torch.uint8 and t.shape[-1] == 64 and t.numel()
-               and t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(t.stride(i) % 16 == 0 for i in range(3))
-               for t in ts)
-
-
-def decode_scale_supported(*ts: torch.Tensor) -> bool:
-    """Whether decode.hip takes these e8m0 scale buffers as they are: uint8 ``(B, S, H, 2)`` GPU tensors, the
-    last dim contiguous, the base and the three outer strides even (one 2-byte store writes a row's two)."""
-    return all(t.is_cuda and t.dim() == 4 and t.dtype == torch.uint8 and t.shape[-1] == 2 and t.numel()
-               and t.stride(-1) == 1 and t.data_ptr() % 2 == 0 and all(t.stride(i) % 2 == 0 for i in range(3))
-               for t in ts)
-
-
-def _q8_cache_ok(kc, vc, kcs, vcs) -> bool:
-    return decode_q8_supported(kc, vc) and decode_scale_supported(kcs, vcs) and kc.shape == vc.shape \
-        and kcs.shape == vcs.shape == kc.shape[:3] + (2,)
+# ---- the public names: one forward each, the cache kind stated by the name
+def kv_append_raw(k, v, kc, vc, lens=None, q=None, q_out=None, cos=None, sin=None) -> int:
+    """:func:`_kv_append_desc` into a bf16 cache."""
+    return _kv_append_desc(_cache_desc(CACHE_BF16, kc, vc), k, v, lens, q, q_out, cos, sin)
 
 
 def kv_append_q8_raw(k, v, kc, vc, kcs, vcs, lens=None, q=None, q_out=None, cos=None, sin=None) -> int:
-    """One ``ljs_kv_append_q8`` launch on the tensors as they are; returns the launcher's code (non-zero:
-    rejected, nothing launched) instead of raising."""
-    B, T, Hkv, _ = k.shape
-    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
-    return lib().ljs_kv_append_q8(_p(k), _p(v), _p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(q_out), B, T,
-                                  q.shape[2] if q is not None else 0, Hkv, kc.shape[1], st(k), st(v), st(q), st(kc),
-                                  st(vc), st(kcs), st(vcs), st(q_out), _p(lens), _p(cos), _p(sin),
-                                  cos.shape[0] if cos is not None else 0, _stream(k))
+    """:func:`_kv_append_desc` into an MX-fp8 cache (a None scale is refused: the kind stays MX-fp8)."""
+    return _kv_append_desc(_cache_desc(CACHE_MX8, kc, vc, kcs, vcs), k, v, lens, q, q_out, cos, sin)
+
+
+def kv_append(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
+    """``vc[b, p] = v[b, t]`` and ``kc[b, p] = k[b, t]`` for ``p = base[b] + t``, ``base = lens`` (int32 ``[B]`` on
+    the device) or 0 without it; with ``theta`` k is rotated by the rotary embedding at position ``p`` on
+    its way (rope.hip's bits), and a ``q`` is rotated the same way into the returned tensor.  Rows with
+    ``p >= cap`` are not written.  One launch."""
+    return cache_append("kv_append", k, v, (kc, vc), lens, q, theta)
 
 
 def kv_append_q8(k, v, kc, vc, kcs, vcs, lens=None, q=None, theta: Optional[float] = None):
@@ -2800,91 +2851,47 @@ def kv_append_q8(k, v, kc, vc, kcs, vcs, lens=None, q=None, theta: Optional[floa
     ``theta``: rope.hip's bits; v as it is) goes through ``fp8.quantize_mx_ref``'s rule into 64 e4m3 bytes of ``kc``
     / ``vc`` and two e8m0 bytes of ``kcs`` / ``vcs`` (uint8 ``(B, cap, Hkv, 64)`` and ``(B, cap, Hkv, 2)``); rows with
     ``p >= cap`` write neither.  Returns the rotated ``q`` in bf16, as :func:`kv_append` does.  One launch."""
-    B = k.shape[0]
-    ok = decode_supported(k, v) and (q is None or decode_supported(q)) and _lens_ok(lens, B) \
-        and _q8_cache_ok(kc, vc, kcs, vcs) and k.shape == v.shape and kc.shape[0] == B \
-        and kc.shape[2] == k.shape[2] and (q is None or (theta is not None and q.shape[:2] == k.shape[:2]))
-    if not ok:
-        raise NotImplementedError(f"kv_append_q8 kernel: bf16 (B, T, H, 64) k / v / q, uint8 (B, cap, Hkv, 64) caches "
-                                  f"with 16-byte aligned bases and strides, uint8 (B, cap, Hkv, 2) scales with even "
-                                  f"strides and an int32 [B] lens; got k {k.dtype} {tuple(k.shape)} strides {k.stride()}, "
-                                  f"cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}, scales {kcs.dtype} "
-                                  f"{tuple(kcs.shape)} strides {kcs.stride()}")
-    cos = sin = q_out = None
-    if theta is not None:
-        from .kernels import rope_table
-        cos, sin = rope_table(k.device, 64, theta, kc.shape[1])
-    if q is not None:
-        q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-    _ck(kv_append_q8_raw(k, v, kc, vc, kcs, vcs, lens, q, q_out, cos, sin), "ljs_kv_append_q8")
-    return q_out
+    return cache_append("kv_append_q8", k, v, (kc, vc, kcs, vcs), lens, q, theta)
+
+
+def attn_decode_raw(q, kc, vc, o, lse, ws, lens, scale: float, extra: int = 1) -> int:
+    """:func:`_attn_decode_desc` over a bf16 cache (``q``: one position)."""
+    return _attn_decode_desc(_cache_desc(CACHE_BF16, kc, vc), q[:, :1], o, lse, ws, lens, scale, extra)
 
 
 def attn_decode_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale: float, extra: int = 1) -> int:
-    """One ``ljs_attn_decode_q8`` call (the decode launch, and the merge launch when the plan has more than
-    one split) on the tensors as they are; returns the launcher's code instead of raising."""
-    B, _, H, _ = q.shape
-    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
-    return lib().ljs_attn_decode_q8(_p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(o), _p(lse), _p(ws),
-                                    ws.numel() if ws is not None else 0, _p(lens), B, H, kc.shape[2], kc.shape[1],
-                                    st(q), st(kc), st(vc), st(kcs), st(vcs), st(o), float(scale), int(extra), _stream(q))
+    """:func:`_attn_decode_desc` over an MX-fp8 cache (``q``: one position; a None scale is refused)."""
+    return _attn_decode_desc(_cache_desc(CACHE_MX8, kc, vc, kcs, vcs), q[:, :1], o, lse, ws, lens, scale, extra)
+
+
+def attn_decode(q, kc, vc, lens, scale: float, extra: int = 1):
+    """Single-query attention of ``q`` (B, 1, H, 64) over rows ``[0, min(lens[b] + extra, cap))`` of the caches
+    ``kc`` / ``vc`` (B, cap, Hkv, 64): ``(o`` bf16 (B, 1, H, 64), ``lse2`` f32 (B, H, 1)``)``; a sequence without
+    keys gets ``o = 0``, ``lse2 = +inf``."""
+    return cache_attend("attn_decode", q, (kc, vc), lens, scale, 1, extra)
 
 
 def attn_decode_q8(q, kc, vc, kcs, vcs, lens, scale: float, extra: int = 1):
     """:func:`attn_decode` over an MX-fp8 cache (e4m3 bytes ``kc`` / ``vc``, e8m0 scale bytes ``kcs`` / ``vcs``): the
     attention of bf16 ``q`` over the dequantised rows ``[0, min(lens[b] + extra, cap))``, which are exact bf16
     values; the same plan, workspace and merge launch.  ``(o`` bf16, ``lse2`` f32``)``."""
-    B, T, H, _ = q.shape
-    Hkv = kc.shape[2]
-    ok = decode_supported(q) and _q8_cache_ok(kc, vc, kcs, vcs) and T == 1 and kc.shape[0] == B and lens is not None \
-        and _lens_ok(lens, B) and H % Hkv == 0 and H // Hkv <= decode_max_group() and scale > 0
-    if not ok:
-        raise NotImplementedError(f"attn_decode_q8 kernel: bf16 q (B, 1, H, 64), uint8 caches (B, cap, Hkv, 64) with "
-                                  f"16-byte aligned bases and strides and uint8 scales (B, cap, Hkv, 2) with even strides, "
-                                  f"H / Hkv <= {decode_max_group()}, int32 [B] lens; got q {q.dtype} {tuple(q.shape)}, "
-                                  f"cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}, scales {kcs.dtype} "
-                                  f"{tuple(kcs.shape)} strides {kcs.stride()}")
-    splits, _ = _decode_launch_plan(B, Hkv, kc.shape[1])
-    ws = _decode_ws(q.device, B * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
-    o = torch.empty((B, 1, H, 64), dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty((B, H, 1), dtype=torch.float32, device=q.device)
-    _ck(attn_decode_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale, extra), "ljs_attn_decode_q8")
-    return o, lse
+    return cache_attend("attn_decode_q8", q, (kc, vc, kcs, vcs), lens, scale, 1, extra)
 
 
-# ---- several query positions per sequence over the cache (attn_extend: decode.hip's EXT instances)
+# ---- several query positions per sequence over the cache (attn_extend: decode.hip's EXT instances, extra = 1)
 def extend_max_positions() -> int:
     """The most query positions per sequence one ``attn_extend`` call takes."""
     return lib().ljs_extend_max_positions()
 
 
 def attn_extend_raw(q, kc, vc, o, lse, ws, lens, scale: float) -> int:
-    """One ``ljs_attn_extend`` call (the launch, and the merge launch when the plan has more than one split) on
-    the tensors as they are (``lse``: f32 ``(B, T, H)``); returns the launcher's code instead of raising."""
-    B, T, H, _ = q.shape
-    return lib().ljs_attn_extend(_p(q), _p(kc), _p(vc), _p(o), _p(lse), _p(ws), ws.numel() if ws is not None else 0,
-                                 _p(lens), B, T, H, kc.shape[2], kc.shape[1], _longs(_strides3(q)),
-                                 _longs(_strides3(kc)), _longs(_strides3(vc)), _longs(_strides3(o)), float(scale),
-                                 _stream(q))
+    """:func:`_attn_decode_desc` of ``q``'s ``T`` positions over a bf16 cache, ``extra = 1`` (``lse``: f32 ``(B, T, H)``)."""
+    return _attn_decode_desc(_cache_desc(CACHE_BF16, kc, vc), q, o, lse, ws, lens, scale, 1)
 
 
 def attn_extend_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale: float) -> int:
-    """One ``ljs_attn_extend_q8`` call on the tensors as they are; returns the launcher's code instead of raising."""
-    B, T, H, _ = q.shape
-    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
-    return lib().ljs_attn_extend_q8(_p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(o), _p(lse), _p(ws),
-                                    ws.numel() if ws is not None else 0, _p(lens), B, T, H, kc.shape[2], kc.shape[1],
-                                    st(q), st(kc), st(vc), st(kcs), st(vcs), st(o), float(scale), _stream(q))
-
-
-def _extend_out(q, Hkv: int, cap: int):
-    """(o, lse (B, T, H), ws) of an extend call on ``q``: the workspace holds ``B T H`` partials per split."""
-    B, T, H, _ = q.shape
-    splits, _ = _decode_launch_plan(B, Hkv, cap)
-    ws = _decode_ws(q.device, B * T * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
-    o = torch.empty((B, T, H, 64), dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty((B, T, H), dtype=torch.float32, device=q.device)
-    return o, lse, ws
+    """:func:`attn_extend_raw` over an MX-fp8 cache."""
+    return _attn_decode_desc(_cache_desc(CACHE_MX8, kc, vc, kcs, vcs), q, o, lse, ws, lens, scale, 1)
 
 
 def attn_extend(q, kc, vc, lens, scale: float):
@@ -2892,37 +2899,12 @@ def attn_extend(q, kc, vc, lens, scale: float):
     ``lens[b] .. lens[b] + T - 1``, over the caches: row ``(b, t, h)`` attends to rows ``[0, min(lens[b] + t + 1, cap))``
     and has the bits :func:`attn_decode` gives ``(b, h)`` with ``extra = t + 1``.  ``(o`` bf16 (B, T, H, 64), ``lse2`` f32
     (B, H, T)``)``; ``T == 1`` is :func:`attn_decode`'s launches."""
-    B, T, H, _ = q.shape
-    Hkv = kc.shape[2]
-    ok = decode_supported(q, kc, vc) and 1 <= T <= extend_max_positions() and kc.shape == vc.shape \
-        and kc.shape[0] == B and lens is not None and _lens_ok(lens, B) and H % Hkv == 0 \
-        and H // Hkv <= decode_max_group() and scale > 0
-    if not ok:
-        raise NotImplementedError(f"attn_extend kernel: bf16 q (B, T <= {extend_max_positions()}, H, 64) and caches (B, cap, "
-                                  f"Hkv, 64) with 16-byte aligned bases and strides, H / Hkv <= {decode_max_group()}, int32 "
-                                  f"[B] lens; got q {q.dtype} {tuple(q.shape)}, cache {kc.dtype} {tuple(kc.shape)} strides "
-                                  f"{kc.stride()}")
-    o, lse, ws = _extend_out(q, Hkv, kc.shape[1])
-    _ck(attn_extend_raw(q, kc, vc, o, lse, ws, lens, scale), "ljs_attn_extend")
-    return o, lse.permute(0, 2, 1)
+    return cache_attend("attn_extend", q, (kc, vc), lens, scale, extend_max_positions())
 
 
 def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     """:func:`attn_extend` over an MX-fp8 cache: the bits of :func:`attn_decode_q8` with ``extra = t + 1``."""
-    B, T, H, _ = q.shape
-    Hkv = kc.shape[2]
-    ok = decode_supported(q) and _q8_cache_ok(kc, vc, kcs, vcs) and 1 <= T <= extend_max_positions() \
-        and kc.shape[0] == B and lens is not None and _lens_ok(lens, B) and H % Hkv == 0 \
-        and H // Hkv <= decode_max_group() and scale > 0
-    if not ok:
-        raise NotImplementedError(f"attn_extend_q8 kernel: bf16 q (B, T <= {extend_max_positions()}, H, 64), uint8 caches (B, "
-                                  f"cap, Hkv, 64) with 16-byte aligned bases and strides and uint8 scales (B, cap, Hkv, 2) "
-                                  f"with even strides, H / Hkv <= {decode_max_group()}, int32 [B] lens; got q {q.dtype} "
-                                  f"{tuple(q.shape)}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}, scales "
-                                  f"{kcs.dtype} {tuple(kcs.shape)} strides {kcs.stride()}")
-    o, lse, ws = _extend_out(q, Hkv, kc.shape[1])
-    _ck(attn_extend_q8_raw(q, kc, vc, kcs, vcs, o, lse, ws, lens, scale), "ljs_attn_extend_q8")
-    return o, lse.permute(0, 2, 1)
+    return cache_attend("attn_extend_q8", q, (kc, vc, kcs, vcs), lens, scale, extend_max_positions())
 
 
 # ---- chunked prefill: T >= 1 query positions per sequence over the cache by MFMA (csrc/kernels/prefill.hip)
@@ -2949,56 +2931,31 @@ def chunk_supported(q, kc, vc, lens, kcs=None, vcs=None) -> bool:
     ``H % Hkv == 0`` and ``H / Hkv <= 16``."""
     if not decode_supported(q) or kc.dim() != 4 or kc.shape[0] != q.shape[0] or lens is None or not _lens_ok(lens, q.shape[0]):
         return False
-    cache_ok = _q8_cache_ok(kc, vc, kcs, vcs) if kcs is not None else (decode_supported(kc, vc) and kc.shape == vc.shape)
     H, Hkv = q.shape[2], kc.shape[2]
-    return bool(cache_ok and H % Hkv == 0 and H // Hkv <= 16)
+    return bool(_cache_supported((kc, vc) if kcs is None else (kc, vc, kcs, vcs)) and H % Hkv == 0 and H // Hkv <= 16)
 
 
 def attn_chunk_raw(q, kc, vc, o, lse, lens, scale: float) -> int:
-    """One ``ljs_attn_chunk`` launch on the tensors as they are (``lse``: f32 ``(B, T, H)``); returns the launcher's code
-    (non-zero: rejected, nothing launched) instead of raising."""
-    B, T, H, _ = q.shape
-    return lib().ljs_attn_chunk(_p(q), _p(kc), _p(vc), _p(o), _p(lse), _p(lens), B, T, H, kc.shape[2], kc.shape[1],
-                                _longs(_strides3(q)), _longs(_strides3(kc)), _longs(_strides3(vc)), _longs(_strides3(o)),
-                                float(scale), _stream(q))
+    """:func:`_attn_chunk_desc` over a bf16 cache."""
+    return _attn_chunk_desc(_cache_desc(CACHE_BF16, kc, vc), q, o, lse, lens, scale)
 
 
 def attn_chunk_q8_raw(q, kc, vc, kcs, vcs, o, lse, lens, scale: float) -> int:
-    """One ``ljs_attn_chunk_q8`` launch on the tensors as they are; returns the launcher's code instead of raising."""
-    B, T, H, _ = q.shape
-    st = lambda t: _longs(_strides3(t)) if t is not None else None   # noqa: E731
-    return lib().ljs_attn_chunk_q8(_p(q), _p(kc), _p(vc), _p(kcs), _p(vcs), _p(o), _p(lse), _p(lens), B, T, H,
-                                   kc.shape[2], kc.shape[1], st(q), st(kc), st(vc), st(kcs), st(vcs), st(o), float(scale),
-                                   _stream(q))
-
-
-def _chunk_call(what, q, kc, vc, kcs, vcs, lens, scale):
-    if not (chunk_supported(q, kc, vc, lens, kcs, vcs) and scale > 0):
-        raise NotImplementedError(f"{what} kernel: bf16 q (B, T, H, 64), caches (B, cap, Hkv, 64) (bf16, or uint8 with uint8 "
-                                  f"scales (B, cap, Hkv, 2)) with 16-byte aligned bases and strides, H / Hkv <= 16, int32 [B] "
-                                  f"lens; got q {q.dtype} {tuple(q.shape)} strides {q.stride()}, cache {kc.dtype} "
-                                  f"{tuple(kc.shape)} strides {kc.stride()}")
-    B, T, H, _ = q.shape
-    o = torch.empty((B, T, H, 64), dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty((B, T, H), dtype=torch.float32, device=q.device)
-    if kcs is None:
-        _ck(attn_chunk_raw(q, kc, vc, o, lse, lens, scale), "ljs_attn_chunk")
-    else:
-        _ck(attn_chunk_q8_raw(q, kc, vc, kcs, vcs, o, lse, lens, scale), "ljs_attn_chunk_q8")
-    return o, lse.permute(0, 2, 1)
+    """:func:`_attn_chunk_desc` over an MX-fp8 cache (a None scale is refused)."""
+    return _attn_chunk_desc(_cache_desc(CACHE_MX8, kc, vc, kcs, vcs), q, o, lse, lens, scale)
 
 
 def attn_chunk(q, kc, vc, lens, scale: float):
     """Attention of ``q`` (B, T, H, 64), any ``T >= 1`` positions that a :func:`kv_append` has just written at rows ``lens[b]
     .. lens[b] + T - 1``, over the caches: row ``(b, t, h)`` attends to rows ``[0, clamp(lens[b] + t + 1, 0, cap))``.  One MFMA
     launch (``attn_chunk<R128>`` / ``<R64>``), no workspace.  ``(o`` bf16 (B, T, H, 64), ``lse2`` f32 (B, H, T)``)``."""
-    return _chunk_call("attn_chunk", q, kc, vc, None, None, lens, scale)
+    return cache_attend("attn_chunk", q, (kc, vc), lens, scale, None)
 
 
 def attn_chunk_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     """:func:`attn_chunk` over an MX-fp8 cache, dequantised on its way into LDS: the bits of :func:`attn_chunk` on the
     dequantised cache."""
-    return _chunk_call("attn_chunk_q8", q, kc, vc, kcs, vcs, lens, scale)
+    return cache_attend("attn_chunk_q8", q, (kc, vc, kcs, vcs), lens, scale, None)
 
 
 def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:

@@ -756,15 +756,22 @@ def attn_decode_reference(q, kc, vc, lens, scale: float, extra: int = 1):
     partition function of the scaled scores); ``n_b = 0`` gives ``o = 0``, ``lse2 = +inf``.  Rows at and beyond
     ``n_b`` are selected away before any arithmetic, so whatever they hold (NaN, Inf) has no influence.
     The recipe of :func:`attention_fwd_lse`: f32 scores, probabilities rounded to v's dtype before P.V."""
-    G = kv_groups(q, kc, vc)
     cap = kc.shape[1]
     n = (lens.long() + int(extra)).clamp(0, cap)              # (B,)
     live = torch.arange(cap, device=q.device)[None, :] < n[:, None]      # (B, cap)
-    sel = live[:, :, None, None]
+    return _masked_attention(q, kc, vc, live[:, :, None, None], live[:, None, None, :], scale)
+
+
+def _masked_attention(q, kc, vc, sel, live, scale: float):
+    """The body the cache references share: attention of q (B, T, H, D) over the cache rows ``sel`` (B, cap, 1, 1) keeps
+    (the others are replaced by zeros before any arithmetic), a score counting where ``live`` (broadcastable to (B, H,
+    T, cap)) says so.  f32 scores, probabilities rounded to v's dtype before P.V; a row without a live key gets ``o =
+    0``, ``lse2 = +inf``.  ``(o`` (B, T, H, D), ``lse2`` f32 (B, H, T)``)``."""
+    G = kv_groups(q, kc, vc)
     k = expand_kv(torch.where(sel, kc, torch.zeros_like(kc)), G)
     v = expand_kv(torch.where(sel, vc, torch.zeros_like(vc)), G)
     s = torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) * scale
-    s = s.masked_fill(~live[:, None, None, :], float("-inf"))
+    s = s.masked_fill(~live, float("-inf"))
     m = s.amax(-1, keepdim=True)
     empty = torch.isinf(m) & (m < 0)
     m = torch.where(empty, torch.zeros_like(m), m)
@@ -777,47 +784,72 @@ def attn_decode_reference(q, kc, vc, lens, scale: float, extra: int = 1):
     return o, lse.squeeze(-1)
 
 
+# ---- the dispatch, stated once for both cache kinds.  A cache is ``(kc, vc)`` (B, cap, Hkv, D) or the MX-fp8 ``(kc, vc,
+# kcs, vcs)`` (below); the operation's name gets ``_q8`` for the latter.
 _WARNED_DECODE = set()
 
 
-def _hip_decode(what: str, ts, lens, G: int = 1) -> bool:
-    """Whether decode.hip takes these shards: bf16 ``(B, S, H, 64)`` GPU tensors with 16-byte aligned bases
-    and strides, an int32 lens and at most 16 query heads per key/value head.  Anything else on a GPU
-    runs the torch formulation there, with a one-time warning per reason; host devices and
-    ``LJS_FUSED_DECODE=0`` run it silently."""
+def _hip_cache(what: str, ts, cache, lens, G: int = 1) -> bool:
+    """Whether decode.hip / prefill.hip take these shards: bf16 ``(B, S, H, 64)`` GPU tensors ``ts`` and a cache
+    ``hip._cache_supported`` accepts, with 16-byte aligned bases and strides (even ones for the scales), an int32 lens
+    and at most 16 query heads per key/value head.  Anything else on a GPU runs the torch formulation there, with a
+    one-time warning per reason; host devices and ``LJS_FUSED_DECODE=0`` run it silently."""
     if not use_hip(ts[0]) or not fused_decode_enabled():
         return False
     hip = _hip()
-    ok = hip.decode_supported(*ts) and (lens is None or lens.dtype == torch.int32) and G <= hip.decode_max_group()
+    kc = cache[0]
+    ok = hip.decode_supported(*ts) and hip._cache_supported(cache) and hip._lens_ok(lens, ts[0].shape[0]) \
+        and kc.shape[0] == ts[0].shape[0] and G <= hip.decode_max_group()
     if not ok:
-        key = (what, ts[0].dtype, ts[0].shape[-1], G > hip.decode_max_group())
+        key = (what, ts[0].dtype, ts[0].shape[-1], kc.dtype, G > hip.decode_max_group())
         if key not in _WARNED_DECODE:
             _WARNED_DECODE.add(key)
             import warnings
-            warnings.warn(f"HIP {what} kernel takes bf16 (B, S, H, 64) shards with 16-byte aligned bases and strides, "
-                          f"an int32 lens and heads / kv_heads <= {hip.decode_max_group()}; {ts[0].dtype} "
-                          f"{tuple(ts[0].shape)} strides {ts[0].stride()} with heads / kv_heads = {G} runs the torch "
-                          "formulation on the GPU")
+            warnings.warn(f"HIP {what} kernel takes bf16 (B, S, H, 64) shards and (B, cap, Hkv, 64) caches (bf16, or uint8 "
+                          f"with uint8 (B, cap, Hkv, 2) scales of even strides) with 16-byte aligned bases and strides, an "
+                          f"int32 lens and heads / kv_heads <= {hip.decode_max_group()}; {ts[0].dtype} {tuple(ts[0].shape)} "
+                          f"strides {ts[0].stride()}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()} with heads / "
+                          f"kv_heads = {G} runs the torch formulation on the GPU")
     return ok
 
 
+def _q8(name: str, cache) -> str:
+    return name + "_q8" if len(cache) == 4 else name
+
+
+def cache_append(k, v, cache, lens=None, q=None, theta: Optional[float] = None):
+    """Append one device's new ``k`` / ``v`` (B, T, Hkv, D) to its ``cache`` in place (:func:`kv_append_reference`'s
+    semantics, :func:`kv_append_q8_reference`'s for an MX-fp8 cache); returns the rotated ``q`` (or None).  One HIP
+    launch on a GPU."""
+    what = _q8("kv_append", cache)
+    if _hip_cache(what, [k, v] + ([q] if q is not None else []), cache, lens):
+        return _hip().cache_append(what, k, v, tuple(cache), lens, q, theta)
+    return globals()[what + "_reference"](k, v, *cache, lens, q, theta)
+
+
+def cache_attend(q, cache, lens, scale: float, mode: str, extra: int = 1):
+    """Attention of one device's ``q`` over its ``cache``: ``(o, lse2)``.  ``mode`` ``"decode"``: one position over rows
+    ``[0, lens[b] + extra)`` (:func:`attn_decode_reference`); ``"extend"``: up to :data:`EXTEND_MAX_POSITIONS` appended
+    positions, a key limit each (:func:`attn_extend_reference`; ``extra`` is 1); ``"chunk"``: the same for any ``T >= 1``
+    by one MFMA launch (:func:`attn_chunk_reference`).  An MX-fp8 cache: their ``_q8`` forms."""
+    what = _q8("attn_" + mode, cache)
+    if _hip_cache(what, [q], cache, lens, kv_groups(q, cache[0], cache[1])):
+        max_t = {"decode": 1, "extend": EXTEND_MAX_POSITIONS, "chunk": None}[mode]
+        return _hip().cache_attend(what, q, tuple(cache), lens, scale, max_t, extra)
+    ref = globals()[what + "_reference"]
+    return ref(q, *cache, lens, scale, extra) if mode == "decode" else ref(q, *cache, lens, scale)
+
+
 def kv_append(k, v, kc, vc, lens=None, q=None, theta: Optional[float] = None):
-    """Append one device's new ``k`` / ``v`` (B, T, Hkv, D) to its caches ``kc`` / ``vc`` (B, cap, Hkv, D) in place
-    (:func:`kv_append_reference`'s semantics); returns the rotated ``q`` (or None).  One HIP launch on a GPU."""
-    ts = [k, v, kc, vc] + ([q] if q is not None else [])
-    if _hip_decode("kv_append", ts, lens):
-        return _hip().kv_append(k, v, kc, vc, lens, q, theta)
-    return kv_append_reference(k, v, kc, vc, lens, q, theta)
+    """:func:`cache_append` to the bf16 caches ``kc`` / ``vc`` (B, cap, Hkv, D)."""
+    return cache_append(k, v, (kc, vc), lens, q, theta)
 
 
 def attn_decode(q, kc, vc, lens, scale: float, extra: int = 1):
     """Single-query attention of one device's ``q`` (B, 1, H, D) over its caches: ``(o, lse2)``
     (:func:`attn_decode_reference`'s semantics).  One HIP launch, and a small merge launch when the
     key axis is split, on a GPU."""
-    G = kv_groups(q, kc, vc)
-    if _hip_decode("attn_decode", [q, kc, vc], lens, G):
-        return _hip().attn_decode(q, kc, vc, lens, scale, extra)
-    return attn_decode_reference(q, kc, vc, lens, scale, extra)
+    return cache_attend(q, (kc, vc), lens, scale, "decode", extra)
 
 
 # ---- the MX-fp8 cache.  A quantised layer holds e4m3 bytes ``kc`` / ``vc`` (uint8 (B, cap, Hkv, D)) and e8m0
@@ -853,53 +885,27 @@ def attn_decode_q8_reference(q, kc, vc, kcs, vcs, lens, scale: float, extra: int
     """Plain torch single-query attention over an MX-fp8 cache: :func:`attn_decode_reference` on the dequantised
     cache in q's dtype.  Dead rows (at and beyond ``n_b``) are selected away BEFORE the dequantisation, so
     whatever their bytes and scale bytes hold (0x7F / 0xFF: the e4m3 and e8m0 NaNs) has no influence."""
-    cap = kc.shape[1]
-    n = (lens.long() + int(extra)).clamp(0, cap)
-    sel = (torch.arange(cap, device=q.device)[None, :] < n[:, None])[:, :, None, None]
+    n = (lens.long() + int(extra)).clamp(0, kc.shape[1])
+    return attn_decode_reference(q, *_dequant_live(q, kc, vc, kcs, vcs, n), lens, scale, extra)
+
+
+def _dequant_live(q, kc, vc, kcs, vcs, n):
+    """What the MX-fp8 attention references share: the rows at and beyond ``n[b]`` zeroed, bytes and scale bytes, and
+    then the buffers dequantised in q's dtype: ``(k, v)``."""
+    sel = (torch.arange(kc.shape[1], device=q.device)[None, :] < n[:, None])[:, :, None, None]
     z = lambda t: torch.where(sel, t, torch.zeros_like(t))   # noqa: E731
-    return attn_decode_reference(q, mx_cache_dequant(z(kc), z(kcs), q.dtype), mx_cache_dequant(z(vc), z(vcs), q.dtype),
-                                 lens, scale, extra)
-
-
-def _hip_decode_q8(what: str, ts, cache, lens, G: int = 1) -> bool:
-    """:func:`_hip_decode` for an MX-fp8 cache ``(kc, vc, kcs, vcs)``: bf16 ``(B, S, H, 64)`` ``ts`` next to uint8
-    buffers decode.hip takes.  The same rule: anything else on a GPU runs the torch formulation there with a
-    one-time warning per reason; host devices and ``LJS_FUSED_DECODE=0`` run it silently."""
-    if not use_hip(ts[0]) or not fused_decode_enabled():
-        return False
-    hip = _hip()
-    kc, vc, kcs, vcs = cache
-    ok = hip.decode_supported(*ts) and hip.decode_q8_supported(kc, vc) and hip.decode_scale_supported(kcs, vcs) \
-        and (lens is None or lens.dtype == torch.int32) and G <= hip.decode_max_group()
-    if not ok:
-        key = (what, ts[0].dtype, ts[0].shape[-1], G > hip.decode_max_group())
-        if key not in _WARNED_DECODE:
-            _WARNED_DECODE.add(key)
-            import warnings
-            warnings.warn(f"HIP {what} kernel takes bf16 (B, S, H, 64) shards and uint8 (B, cap, Hkv, 64) / (B, cap, Hkv, 2) "
-                          f"cache buffers with 16-byte aligned bases and strides (even ones for the scales), an int32 lens "
-                          f"and heads / kv_heads <= {hip.decode_max_group()}; {ts[0].dtype} {tuple(ts[0].shape)} strides "
-                          f"{ts[0].stride()}, cache strides {kc.stride()} / {kcs.stride()} with heads / kv_heads = {G} "
-                          "runs the torch formulation on the GPU")
-    return ok
+    return mx_cache_dequant(z(kc), z(kcs), q.dtype), mx_cache_dequant(z(vc), z(vcs), q.dtype)
 
 
 def kv_append_q8(k, v, kc, vc, kcs, vcs, lens=None, q=None, theta: Optional[float] = None):
-    """Append one device's new ``k`` / ``v`` to its MX-fp8 caches in place (:func:`kv_append_q8_reference`'s
-    semantics); returns the rotated ``q`` (or None).  One HIP launch on a GPU."""
-    ts = [k, v] + ([q] if q is not None else [])
-    if _hip_decode_q8("kv_append_q8", ts, (kc, vc, kcs, vcs), lens):
-        return _hip().kv_append_q8(k, v, kc, vc, kcs, vcs, lens, q, theta)
-    return kv_append_q8_reference(k, v, kc, vc, kcs, vcs, lens, q, theta)
+    """:func:`cache_append` to MX-fp8 caches (:func:`kv_append_q8_reference`'s semantics)."""
+    return cache_append(k, v, (kc, vc, kcs, vcs), lens, q, theta)
 
 
 def attn_decode_q8(q, kc, vc, kcs, vcs, lens, scale: float, extra: int = 1):
     """Single-query attention of one device's ``q`` over its MX-fp8 caches: ``(o, lse2)``
     (:func:`attn_decode_q8_reference`'s semantics).  The launches of :func:`attn_decode`, in their ``mx8`` instances."""
-    G = kv_groups(q, kc, vc)
-    if _hip_decode_q8("attn_decode_q8", [q], (kc, vc, kcs, vcs), lens, G):
-        return _hip().attn_decode_q8(q, kc, vc, kcs, vcs, lens, scale, extra)
-    return attn_decode_q8_reference(q, kc, vc, kcs, vcs, lens, scale, extra)
+    return cache_attend(q, (kc, vc, kcs, vcs), lens, scale, "decode", extra)
 
 
 def lens_add(lens: torch.Tensor, n: int = 1) -> torch.Tensor:
@@ -944,18 +950,12 @@ def attn_extend(q, kc, vc, lens, scale: float):
     """Attention of one device's ``q`` (B, T, H, D) over its caches, a key limit per position: ``(o, lse2)``
     (:func:`attn_extend_reference`'s semantics).  One HIP launch (and the merge launch of a split key axis) on a
     GPU; ``T == 1`` is :func:`attn_decode`'s."""
-    G = kv_groups(q, kc, vc)
-    if _hip_decode("attn_extend", [q, kc, vc], lens, G):
-        return _hip().attn_extend(q, kc, vc, lens, scale)
-    return attn_extend_reference(q, kc, vc, lens, scale)
+    return cache_attend(q, (kc, vc), lens, scale, "extend")
 
 
 def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     """:func:`attn_extend` over one device's MX-fp8 caches (:func:`attn_extend_q8_reference`'s semantics)."""
-    G = kv_groups(q, kc, vc)
-    if _hip_decode_q8("attn_extend_q8", [q], (kc, vc, kcs, vcs), lens, G):
-        return _hip().attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale)
-    return attn_extend_q8_reference(q, kc, vc, kcs, vcs, lens, scale)
+    return cache_attend(q, (kc, vc, kcs, vcs), lens, scale, "extend")
 
 
 # ---- chunked prefill (csrc/kernels/prefill.hip, attn_chunk): attn_extend's definition for any T >= 1, stated as one
@@ -967,74 +967,31 @@ def attn_chunk_reference(q, kc, vc, lens, scale: float):
     sequence's largest ``n`` are selected away before any arithmetic and a row's own limit masks its scores, so
     whatever dead rows hold (NaN, Inf) has no influence; ``n = 0`` gives ``o = 0``, ``lse2 = +inf``.  The forward's recipe:
     f32 scores, probabilities rounded to v's dtype before P.V.  ``(o`` (B, T, H, D), ``lse2`` f32 (B, H, T)``)``."""
-    G = kv_groups(q, kc, vc)
     T, cap = q.shape[1], kc.shape[1]
     n = (lens.long()[:, None] + torch.arange(1, T + 1, device=q.device)[None, :]).clamp(0, cap)      # (B, T)
     keys = torch.arange(cap, device=q.device)
     sel = (keys[None, :] < n.amax(1)[:, None])[:, :, None, None]                                      # (B, cap, 1, 1)
-    k = expand_kv(torch.where(sel, kc, torch.zeros_like(kc)), G)
-    v = expand_kv(torch.where(sel, vc, torch.zeros_like(vc)), G)
     live = (keys[None, None, :] < n[:, :, None])[:, None]                                             # (B, 1, T, cap)
-    s = torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) * scale
-    s = s.masked_fill(~live, float("-inf"))
-    m = s.amax(-1, keepdim=True)
-    empty = torch.isinf(m) & (m < 0)
-    m = torch.where(empty, torch.zeros_like(m), m)
-    p = torch.exp(s - m)
-    l = p.sum(-1, keepdim=True)
-    probs = (p / l.clamp(min=1e-30)).to(v.dtype).float()
-    o = torch.einsum("bhqk,bkhd->bqhd", probs, v.float()).to(v.dtype)
-    lse = (m + torch.log(l)) * _LOG2E
-    lse = torch.where(empty, torch.full_like(lse, float("inf")), lse)
-    return o, lse.squeeze(-1)
+    return _masked_attention(q, kc, vc, sel, live, scale)
 
 
 def attn_chunk_q8_reference(q, kc, vc, kcs, vcs, lens, scale: float):
     """:func:`attn_chunk_reference` over an MX-fp8 cache: the same function on the dequantised buffers in q's dtype, the
     dead rows (at and beyond the sequence's largest limit) zeroed before the dequantisation, as
     :func:`attn_decode_q8_reference` does."""
-    cap = kc.shape[1]
-    n = (lens.long() + q.shape[1]).clamp(0, cap)
-    sel = (torch.arange(cap, device=q.device)[None, :] < n[:, None])[:, :, None, None]
-    z = lambda t: torch.where(sel, t, torch.zeros_like(t))   # noqa: E731
-    return attn_chunk_reference(q, mx_cache_dequant(z(kc), z(kcs), q.dtype), mx_cache_dequant(z(vc), z(vcs), q.dtype),
-                                lens, scale)
-
-
-def _hip_chunk(what: str, q, cache, lens) -> bool:
-    """Whether prefill.hip takes these shards (``hip.chunk_supported``), in :func:`_hip_decode`'s style: host devices and
-    ``LJS_FUSED_DECODE=0`` run the torch formulation silently, anything else unsupported on a GPU runs it there with a
-    one-time warning per reason."""
-    if not use_hip(q) or not fused_decode_enabled():
-        return False
-    hip = _hip()
-    kc, vc = cache[0], cache[1]
-    ok = hip.chunk_supported(q, kc, vc, lens, *cache[2:])
-    if not ok:
-        key = (what, q.dtype, q.shape[-1], kc.dtype)
-        if key not in _WARNED_DECODE:
-            _WARNED_DECODE.add(key)
-            import warnings
-            warnings.warn(f"HIP {what} kernel takes bf16 (B, T, H, 64) q shards and (B, cap, Hkv, 64) caches (bf16, or uint8 "
-                          f"with uint8 (B, cap, Hkv, 2) scales) with 16-byte aligned bases and strides, an int32 lens and "
-                          f"heads / kv_heads <= 16; {q.dtype} {tuple(q.shape)} strides {q.stride()}, cache {kc.dtype} "
-                          f"{tuple(kc.shape)} strides {kc.stride()} runs the torch formulation on the GPU")
-    return ok
+    n = (lens.long() + q.shape[1]).clamp(0, kc.shape[1])
+    return attn_chunk_reference(q, *_dequant_live(q, kc, vc, kcs, vcs, n), lens, scale)
 
 
 def attn_chunk(q, kc, vc, lens, scale: float):
     """Attention of one device's ``q`` (B, T, H, D), any ``T >= 1`` appended positions, over its caches: ``(o, lse2)``
     (:func:`attn_chunk_reference`'s semantics).  One MFMA HIP launch on a GPU."""
-    if _hip_chunk("attn_chunk", q, (kc, vc), lens):
-        return _hip().attn_chunk(q, kc, vc, lens, scale)
-    return attn_chunk_reference(q, kc, vc, lens, scale)
+    return cache_attend(q, (kc, vc), lens, scale, "chunk")
 
 
 def attn_chunk_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     """:func:`attn_chunk` over one device's MX-fp8 caches (:func:`attn_chunk_q8_reference`'s semantics)."""
-    if _hip_chunk("attn_chunk_q8", q, (kc, vc, kcs, vcs), lens):
-        return _hip().attn_chunk_q8(q, kc, vc, kcs, vcs, lens, scale)
-    return attn_chunk_q8_reference(q, kc, vc, kcs, vcs, lens, scale)
+    return cache_attend(q, (kc, vc, kcs, vcs), lens, scale, "chunk")
 
 
 # ----------------------------------------------------------------------------- sampling

@@ -2,7 +2,9 @@
 GEMMs compute on a fixed list of small seeded cases, one ``case-name sha256`` line per output tensor:
 two builds of the library compute the same bits exactly when their lines are equal.  The ``gemm``
 group also prints each case's launch record, so equal lines mean the same kernels on the same grids
-too; the ``mx`` group prints hashes only, so it also runs on a library that records no fp8 launch.
+too; the ``mx`` group prints hashes only, so it also runs on a library that records no fp8 launch.  The
+``cache`` group (the KV-cache append, decode, extend and chunk kernels through the public ``hip.*`` names)
+prints every launch record of a case with its hashes.
 
     python scripts/kernel_digest.py [--json out.json] [--grep norm]
     LJS_KERNELS_LIB=path/to/libljs_kernels.so python scripts/kernel_digest.py    # another build
@@ -337,7 +339,112 @@ def mx_cases(out):
         run(f"mx/fix{fix}/160x160x{K}", c, 160, 160, K, None, 1282, relu=fix == 1, copies=True)
 
 
-GROUPS = {"gemm": gemm_cases, "mx": mx_cases, "norm": norm_cases, "xent": xent_cases, "sum": sum_cases, "colsum": colsum_cases, "mse": mse_cases,
+def cache_cases(out):
+    """decode.hip and prefill.hip through the public ``hip.*`` names, bf16 and MX-fp8 caches alike: every output tensor
+    (the cache buffers whole, untouched rows included) and every launch record of a case.  The shapes are the
+    smallest of tests/test_decode_gpu.py, test_kvq_gpu.py, test_extend_gpu.py and test_chunk_gpu.py: the appends'
+    three instances at device positions, in host-base mode and past the capacity; every decode instance under a
+    forced plan of 1 and of 2 splits, and ``extra = 0`` on an empty sequence; one (G, T) per extend instance; the
+    chunk kernel's forced 64- and 128-row tiles at T = 1 and at a T that is no multiple of the tile, and a strided
+    cache view."""
+    THETA, SCALE = 10000.0, 0.125
+    tile = hip.decode_key_tile()
+
+    def fresh(kind, B, cap, Hkv, strided=False):
+        """A cache of sentinels: (kc, vc) or (kc, vc, kcs, vcs); strided: column blocks of buffers twice as wide."""
+        w = 2 if strided else 1
+        if kind == "bf16":
+            bufs = [torch.full((B, cap, Hkv, 64 * w), -7.0, dtype=BF16, device=DEV) for _ in range(2)]
+        else:
+            bufs = [torch.full((B, cap, Hkv, n * w), 0xAB, dtype=torch.uint8, device=DEV) for n in (64, 64, 2, 2)]
+        return [b[..., :b.shape[-1] // w] for b in bufs]
+
+    def append(kind, *a, **kw):
+        return (hip.kv_append if kind == "bf16" else hip.kv_append_q8)(*a, **kw)
+
+    def filled(name, kind, B, cap, Hkv, strided=False):
+        """A cache whose rows are all written (host-base append of seeded rows, k rotated)."""
+        g = _gen(name + "/fill")
+        cache = fresh(kind, B, cap, Hkv, strided)
+        append(kind, _randn(g, (B, cap, Hkv, 64), BF16), _randn(g, (B, cap, Hkv, 64), BF16), *cache, None, theta=THETA)
+        return cache
+
+    def logged(name, log, tensors):
+        for i, r in enumerate(log):
+            out.lines.append((f"{name}/record{i}", ",".join(f"{k}={r[k]}" for k in sorted(r)).replace(" ", "")))
+            print(*out.lines[-1], flush=True)
+        for k, t in tensors:
+            if t is not None:
+                out.add(f"{name}/{k}", t)
+
+    for kind in ("bf16", "mx8"):
+        names = ("kc", "vc") if kind == "bf16" else ("kc", "vc", "kcs", "vcs")
+        # ---- append: B = 3, H = 8, Hkv = 2, cap = 32
+        B, H, Hkv, cap = 3, 8, 2, 32
+        cases = [(f"{inst}/lens", 1, [0, 17, cap - 1], inst) for inst in ("copy", "rot", "rot,q")]
+        cases += [(f"{inst}/host-base", 5, None, inst) for inst in ("copy", "rot")]
+        cases += [("rot,q/past-cap-T3", 3, [cap - 1, cap - 2, 10], "rot,q")]
+        for cname, T, lens, inst in cases:
+            name = f"cache/{kind}/append/{cname}"
+            g = _gen(name)
+            q, k, v = _randn(g, (B, T, H, 64), BF16), _randn(g, (B, T, Hkv, 64), BF16), _randn(g, (B, T, Hkv, 64), BF16)
+            cache = fresh(kind, B, cap, Hkv)
+            lt = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=DEV)
+            with hip.launch_log() as log:
+                q_out = append(kind, k, v, *cache, lt, q=q if inst == "rot,q" else None,
+                               theta=None if inst == "copy" else THETA)
+            logged(name, log, [("q_out", q_out)] + list(zip(names, cache)))
+        # ---- decode and extend: cap = 2 key tiles, forced plans of 1 and 2 splits
+        B, cap = 2, 2 * tile
+        decode = hip.attn_decode if kind == "bf16" else hip.attn_decode_q8
+        extend = hip.attn_extend if kind == "bf16" else hip.attn_extend_q8
+        try:
+            for splits in (1, 2):
+                hip.set_decode_splits(splits, cap // splits)
+                for G in (1, 2, 4, 8, 16):
+                    Hkv = 1 if G == 16 else 2
+                    name = f"cache/{kind}/decode/G{G}/s{splits}"
+                    cache = filled(name, kind, B, cap, Hkv)
+                    q = _randn(_gen(name), (B, 1, G * Hkv, 64), BF16)
+                    lt = torch.tensor([cap - 25, cap - 1], dtype=torch.int32, device=DEV)
+                    with hip.launch_log() as log:
+                        o, lse = decode(q, *cache, lt, SCALE, 1)
+                    logged(name, log, [("o", o), ("lse", lse)])
+                name = f"cache/{kind}/decode/empty-extra0/s{splits}"
+                cache = filled(name, kind, B, cap, 2)
+                lt = torch.tensor([0, 5], dtype=torch.int32, device=DEV)
+                with hip.launch_log() as log:
+                    o, lse = decode(_randn(_gen(name), (B, 1, 8, 64), BF16), *cache, lt, SCALE, 0)
+                logged(name, log, [("o", o), ("lse", lse)])
+                for G, T in ((1, 2), (1, 3), (1, 5), (2, 2), (2, 3), (4, 2), (8, 2), (16, 2)):
+                    Hkv = 1 if G == 16 else 2
+                    name = f"cache/{kind}/extend/G{G}T{T}/s{splits}"
+                    cache = filled(name, kind, B, cap, Hkv)
+                    q = _randn(_gen(name), (B, T, G * Hkv, 64), BF16)
+                    lt = torch.tensor([0, cap - 27], dtype=torch.int32, device=DEV)
+                    with hip.launch_log() as log:
+                        o, lse = extend(q, *cache, lt, SCALE)
+                    logged(name, log, [("o", o), ("lse", lse)])
+        finally:
+            hip.set_decode_splits(None)
+        # ---- chunk: H = 8, Hkv = 2, cap = 128, a non-empty cache
+        chunk = hip.attn_chunk if kind == "bf16" else hip.attn_chunk_q8
+        B, H, Hkv, cap = 2, 8, 2, 128
+        try:
+            for rows in (64, 128):
+                hip.set_chunk_rows(rows)
+                for T, strided in ((1, False), (37, False), (37, True)):
+                    name = f"cache/{kind}/chunk/R{rows}/T{T}{'/strided' if strided else ''}"
+                    cache = filled(name, kind, B, cap, Hkv, strided)
+                    lt = torch.tensor([5, 20], dtype=torch.int32, device=DEV)
+                    with hip.launch_log() as log:
+                        o, lse = chunk(_randn(_gen(name), (B, T, H, 64), BF16), *cache, lt, SCALE)
+                    logged(name, log, [("o", o), ("lse", lse)])
+        finally:
+            hip.set_chunk_rows(None)
+
+
+GROUPS = {"cache": cache_cases, "gemm": gemm_cases, "mx": mx_cases, "norm": norm_cases, "xent": xent_cases, "sum": sum_cases, "colsum": colsum_cases, "mse": mse_cases,
           "misc": misc_cases}
 
 

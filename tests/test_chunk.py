@@ -62,6 +62,24 @@ def test_chunk_reference_is_extend_reference_to_one_ulp(T):
         assert torch.equal(got[0], deq[0]) and torch.equal(got[1], deq[1])
 
 
+def test_chunk_reference_of_one_position_is_the_decode_reference():
+    """``T = 1``: the chunk references are the decode references with ``extra = 1``, bit for bit and for both cache kinds;
+    a sequence without a key (``lens = -1``) and one at capacity included."""
+    from learning_jax_sharding_amd.ops import kernels as K
+    B, H, Hkv, cap = 4, 8, 2, 48
+    q = _inputs("plain", B, H, Hkv, 1, cap)[0]
+    kf, vf = (torch.randn(B, cap, Hkv, 64, generator=torch.Generator().manual_seed(s)).to(BF16) for s in (1, 2))
+    lt = torch.tensor([-1, 0, 17, cap], dtype=torch.int32)
+    got, want = K.attn_chunk_reference(q, kf, vf, lt, SCALE), K.attn_decode_reference(q, kf, vf, lt, SCALE, extra=1)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert (got[0][0] == 0).all() and torch.isinf(got[1][0]).all() and torch.isfinite(got[1][1:]).all()
+    cache = (*K._mx_bytes(kf), *K._mx_bytes(vf))
+    cache = (cache[0], cache[2], cache[1], cache[3])      # (kc, vc, kcs, vcs)
+    got, want = K.attn_chunk_q8_reference(q, *cache, lt, SCALE), K.attn_decode_q8_reference(q, *cache, lt, SCALE, extra=1)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert (got[0][0] == 0).all() and torch.isinf(got[1][0]).all() and torch.isfinite(got[1][1:]).all()
+
+
 @pytest.mark.parametrize("shape,cus,want", [
     ((1, 1, 8, 8), 256, (64, (1, 8, 1))),           # a lone row
     ((4, 33, 8, 2), 256, (64, (3, 2, 4))),          # 132 rows: 16 blocks of 128 rows would leave CUs idle

@@ -37,6 +37,13 @@ def test_kernel_library_abi(built):
     assert "__device_stub__" not in und
 
 
+def test_cache_descriptor_mirror_has_the_library_size(built):
+    """ops/hip.py's ctypes mirror of ``LjsCache`` (csrc/kernels/cache_common.h) is as large as the struct the
+    library was compiled with."""
+    from learning_jax_sharding_amd.ops.hip import _CacheDesc
+    assert ctypes.CDLL(built[0]).ljs_cache_desc_size() == ctypes.sizeof(_CacheDesc) == 144
+
+
 def test_runtime_library_abi(built):
     ex = _exports(built[1])
     for n in ("ljs_comm_init", "ljs_comm_split", "ljs_comm_async_error", "ljs_comm_abort", "ljs_comm_all_reduce",
