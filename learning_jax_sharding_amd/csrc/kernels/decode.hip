@@ -1,7 +1,8 @@
 // Decoding with a key/value cache: the cache append (with the rotary embedding of the new q and k at
 // a position read on the device) and single-query split-K attention over the cache.
 //
-// Layout.  q is (B, T, H, 64), new k / v are (B, T, Hkv, 64), the caches kc / vc are (B, cap, Hkv, 64),
+// Layout.  q is (B, T, H, D), new k / v are (B, T, Hkv, D), the caches kc / vc are (B, cap, Hkv, D), D = 64
+// or 128 (every kernel below is a template on D; the text describes 64 and "Head dim 128" what changes),
 // all bf16 with the head dim contiguous and their own (batch, position, head) strides in elements
 // (column blocks of a fused projection buffer are read in place); every base and stride is 16-byte
 // aligned and offsets are 64-bit.  lens is int32 [B] ON THE DEVICE: no kernel argument depends on the
@@ -69,27 +70,49 @@
 // block-scaled MFMA: a live row whose block exponent clamped carries it with non-zero bytes.  Rows beyond a
 // block's range read zero bytes (and a zero scale byte) through the descriptors: 0 x 2^-127 = 0.
 //
+// Head dim 128 (the instances logged as kv_append128<..>, attn_decode128<G..>, attn_extend128<G..,P..>,
+// decode_merge128).  A key row is 16 chunks: 16 lanes (one DPP row) hold a key, a wave 4 keys per step and a
+// block 16 (the key tile; the plan's units of 32 keys are multiples of it, so plan_decode is the same function).
+// A lane's state per head is unchanged (4 dwords of q, 8 accumulators), so 8 heads per wave, the wave pairs for G
+// > 8 and attn_extend's row tiling stand.  The score's DPP sum takes a fourth step (row_mirror), the wave's 4
+// slots merge in two shuffle steps, a partial is acc[128], m, l in 136 floats (17 KiB of LDS at 8 heads per
+// wave) and decode_merge's wave is 4 slots of 16 chunks.  MX-fp8: four scale bytes per row, the lane's chunk in
+// block c / 4 of four.  kv_append's work item is the chunks j and j + 8 of a head row, j in 0..7; its MX-fp8
+// form is described at the kernel.  The 64 instances compile to the code they had before the template.
+//
 // Entry points.  Two launchers, ljs_kv_append and ljs_attn_decode (T, extra), take the cache as ONE operand, an
-// LjsCache descriptor with an explicit kind (cache_common.h, which also states the alignment and reach checks
-// once; prefill.hip's ljs_attn_chunk takes the same descriptor).  The kind selects the kernel instances; the
+// LjsCache descriptor with an explicit kind and head dim (cache_common.h, which also states the alignment and reach checks
+// once; prefill.hip's ljs_attn_chunk takes the same descriptor, at 64 only).  The kind and the dim select the kernel instances; the
 // kernels' argument structs are filled from the descriptor.
 #include "cache_common.h"
 #include "rowwise.h"
 
+#ifndef LJS_DEC128_UNROLL
+#define LJS_DEC128_UNROLL 4   // (a build variant for the A/B timing next to Dec<128>::kUnroll)
+#endif
+
 namespace {
 
-constexpr int kDecD = 64;                 // head dim
-constexpr int kDecChunks = kDecD / 8;     // 16-byte chunks per head row = lanes per key
 constexpr int kDecThreads = 256;
 constexpr int kDecWaves = kDecThreads / 64;
-constexpr int kDecSlots = 64 / kDecChunks;             // keys a wave holds per step
-constexpr int kDecKeyTile = kDecWaves * kDecSlots;     // keys a block holds per step: 32
-constexpr int kDecUnroll = 4;             // steps whose loads are in flight together (8 measured slower at
-                                          // one head per wave: 119.7 against 112.6 us at B = 64, 4096 keys)
+// How the head dim D (64 or 128) cuts the wave: everything below that depends on the row width
+template <int D>
+struct Dec {
+  static_assert(D == 64 || D == 128, "head dim");
+  static constexpr int kChunks = D / 8;               // 16-byte chunks per head row = lanes per key: 8 / 16
+  static constexpr int kLog = D == 64 ? 3 : 4;        // log2 of it
+  static constexpr int kSlots = 64 / kChunks;         // keys a wave holds per step: 8 / 4
+  static constexpr int kKeyTile = kDecWaves * kSlots; // keys a block holds per step: 32 / 16
+  static constexpr int kPart = D + 8;                 // floats of one partial: acc[D], m, l, padded to 16 bytes
+  // steps whose loads are in flight together.  64: 8 measured slower at one head per wave, 119.7 against 112.6
+  // us at B = 64, 4096 keys.  128 (4 keys a wave step, so 8 steps hold the bytes 4 hold at 64): 8 measured slower
+  // too, 232.8 against 207.8 us at B = 64, 4096 keys, 8/8 heads (61.3 against 62.1 us at 8/2: no gain either)
+  static constexpr int kUnroll = D == 64 ? 4 : LJS_DEC128_UNROLL;
+};
+constexpr int kDecKeyTile = Dec<64>::kKeyTile;         // the plan's unit of keys, at either width (32 = 2 x 16)
 constexpr int kDecWaveHeads = 8;          // query heads one wave carries
 constexpr int kDecMaxG = 2 * kDecWaveHeads;
 constexpr int kExtMaxT = 64;              // query positions per sequence one attn_extend call takes
-constexpr int kDecPart = 72;              // floats of one partial: acc[64], m, l, padded to 16 bytes
 constexpr int kDecBlocksPerCu = 4;        // the plan's target: blocks per compute unit
 constexpr int kDecMinTiles = 8;           // a split sweeps at least 8 key tiles (256 keys), 4 on an unfilled chip
 constexpr int kDecOneSplitTiles = 16;     // up to 512 rows of capacity: one split (no merge launch)
@@ -103,12 +126,14 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
   return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xf, 0xf, false));
 }
-// sum over the 8 lanes of a key; every one of them ends up with the same bits (each step adds the
-// same two numbers in both partners)
-__device__ __forceinline__ float sum8(float v) {
+// sum over the 8 (D = 64) or 16 (D = 128) lanes of a key; every one of them ends up with the same bits
+// (each step adds the same two numbers in both partners)
+template <int D>
+__device__ __forceinline__ float sum_key(float v) {
   v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
   v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
   v += dpp_mov<0x141>(v);   // row_half_mirror: lane i <-> 7 - i, the other quad
+  if constexpr (D == 128) v += dpp_mov<0x140>(v);   // row_mirror: lane i <-> 15 - i, the other half row
   return v;
 }
 
@@ -136,7 +161,7 @@ struct DecodeArgs {
   const bf16_t *q, *kc, *vc;
   bf16_t* o;
   float* lse;                 // [B][H]
-  float* ws;                  // [B][H][splits][kDecPart]
+  float* ws;                  // [B][H][splits][Dec<D>::kPart]
   const int* lens;
   long qb, qh;                // strides (elements): batch, head (one position)
   long kb, ks, kh, vb, vs, vh, ob, oh;
@@ -147,7 +172,7 @@ struct DecodeArgs {
   long qt, ot;
   int T, P;
   // MX-fp8 caches only (kc / vc are then e4m3 bytes and their strides count bytes): the e8m0 scales
-  // (B, cap, Hkv, 2) and their (batch, position, head) strides in bytes
+  // (B, cap, Hkv, D / 32) and their (batch, position, head) strides in bytes
   const unsigned char *ksc, *vsc;
   long ksb, kss, ksh, vsb, vss, vsh;
 };
@@ -166,8 +191,8 @@ __device__ __forceinline__ void dec_store_out(bf16_t* o, float* lse, int cc, flo
 // zero byte is 2^-127: tests/test_mx_quant_oracle_gpu.py reads clamped blocks back through attn_decode)
 __device__ __forceinline__ float e8m0_f32(unsigned e) { return __uint_as_float(e << 23); }
 
-// MX8: kc / vc hold e4m3 bytes with one e8m0 scale per 32 elements.  A key row is 64 bytes, the lane's
-// chunk 8 of them (inside one scale block: block c / 4); the gfx950 scaled conversions turn them into
+// MX8: kc / vc hold e4m3 bytes with one e8m0 scale per 32 elements.  A key row is D bytes, the lane's
+// chunk 8 of them (inside one scale block: block c / 4 of D / 32); the gfx950 scaled conversions turn them into
 // the packed bf16 of K (exact: 4 significant bits times a power of two) and the f32 of V, after which
 // the sweep is the bf16 one.
 //
@@ -178,14 +203,21 @@ __device__ __forceinline__ float e8m0_f32(unsigned e) { return __uint_as_float(e
 // beyond its own limit are -inf: p = 0 there, so m, l and acc keep their bits (alpha = exp2(0) = 1, +0
 // products of the finite rows the step itself appended), and row (t, g) ends with attn_decode's bits
 // for extra + t.
-template <int HW, bool MX8 = false, bool EXT = false>
+//
+// D = 128: a key row is 16 chunks, so 16 lanes (one DPP row) hold a key, a wave 4 keys and a block 16 per step;
+// a lane's state per head (4 dwords of q, 8 accumulators) is what it is at 64, and so are the heads per wave,
+// the wave pairs and the EXT row tiling.  The score's sum takes one more DPP step, the wave's 4 slots two shuffle
+// steps, and a partial is 136 floats (17 KiB of LDS at HW = 8).
+template <int D, int HW, bool MX8 = false, bool EXT = false>
 __global__ __launch_bounds__(kDecThreads)
 void attn_decode_kernel(const DecodeArgs a) {
+  constexpr int kDecD = D, kDecChunks = Dec<D>::kChunks, kDecSlots = Dec<D>::kSlots, kDecPart = Dec<D>::kPart,
+                kDecUnroll = Dec<D>::kUnroll;
   __shared__ alignas(16) float sh[kDecWaves][HW][kDecPart];
   const int split = EXT ? blockIdx.x % a.splits : blockIdx.x, j = blockIdx.y, b = blockIdx.z;
   const int t0 = EXT ? (blockIdx.x / a.splits) * a.P : 0;       // the block's first query position
   const int rows = EXT ? a.P * a.G : a.G;                       // rows (t, g) of the block
-  const int lane = threadIdx.x & 63, slot = lane >> 3, c = lane & 7;
+  const int lane = threadIdx.x & 63, slot = lane >> Dec<D>::kLog, c = lane & (kDecChunks - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int parts = (rows + HW - 1) / HW;      // 1, or 2 for G > 8
   const int wpp = kDecWaves / parts;           // waves sweeping the range for one part's heads
@@ -233,8 +265,8 @@ void attn_decode_kernel(const DecodeArgs a) {
   __amdgpu_buffer_rsrc_t rks = rk, rvs = rv;
   int ksstep = 0, vsstep = 0;
   if constexpr (MX8) {
-    rks = make_rsrc(a.ksc + (long)b * a.ksb + (long)j * a.ksh, any_key ? (long)(k1 - 1) * a.kss + 2 : 0);
-    rvs = make_rsrc(a.vsc + (long)b * a.vsb + (long)j * a.vsh, any_key ? (long)(k1 - 1) * a.vss + 2 : 0);
+    rks = make_rsrc(a.ksc + (long)b * a.ksb + (long)j * a.ksh, any_key ? (long)(k1 - 1) * a.kss + kDecD / 32 : 0);
+    rvs = make_rsrc(a.vsc + (long)b * a.vsb + (long)j * a.vsh, any_key ? (long)(k1 - 1) * a.vss + kDecD / 32 : 0);
     ksstep = (int)a.kss;
     vsstep = (int)a.vss;
   }
@@ -302,7 +334,7 @@ void attn_decode_kernel(const DecodeArgs a) {
         float d = 0.f;
 #pragma unroll
         for (int w = 0; w < 4; ++w) d = dot2_bf16(kr[u][w], qw[i][w], d);
-        d = sum8(d);
+        d = sum_key<D>(d);
         s[u] = key[u] < (EXT ? k1r[i] : k1) ? d : -INFINITY;
       }
       float tmax = s[0];
@@ -336,7 +368,7 @@ void attn_decode_kernel(const DecodeArgs a) {
     }
   }
 
-  // the 8 slots of the wave, merged into slot 0 (lanes 0..7) in a fixed order
+  // the slots of the wave, merged into slot 0 (the first key's lanes) in a fixed order
 #pragma unroll
   for (int i = 0; i < HW; ++i) {
     float av[8];
@@ -367,7 +399,7 @@ void attn_decode_kernel(const DecodeArgs a) {
   // the waves of a head's part, in ascending order: thread (g, chunk)
   const int t = threadIdx.x;
   if (t < rows * kDecChunks) {
-    const int r = t >> 3, cc = t & 7, pg = r / HW, gi = r % HW;
+    const int r = t >> Dec<D>::kLog, cc = t & (kDecChunks - 1), pg = r / HW, gi = r % HW;
     float mm = -INFINITY, ll = 0.f, av[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int w = pg * wpp; w < (pg + 1) * wpp; ++w) {
       float a2[8];
@@ -396,11 +428,14 @@ void attn_decode_kernel(const DecodeArgs a) {
 // The partials of one (b, t, h) per wave (T = 1 for attn_decode): lane = (slot, chunk).  Pass 1 finds the largest m of all splits
 // (exact, whatever the order).  Pass 2: slot j adds the splits j, j + 8, .. in ascending order, each
 // weighted by exp2(m_s - M), with the loads of 4 splits in flight; the 8 slots are then added by a
-// fixed tree of plain adds.  Every order is fixed, so the bits are the same on every run.
+// fixed tree of plain adds.  Every order is fixed, so the bits are the same on every run.  (D = 128: 4 slots of
+// 16 chunks, so slot j adds the splits j, j + 4, ..)
 constexpr int kMergeUnroll = 4;
+template <int D>
 __global__ __launch_bounds__(64)
 void decode_merge_kernel(const DecodeArgs a) {
-  const int lane = threadIdx.x, slot = lane >> 3, cc = lane & 7;
+  constexpr int kDecD = D, kDecChunks = Dec<D>::kChunks, kDecSlots = Dec<D>::kSlots, kDecPart = Dec<D>::kPart;
+  const int lane = threadIdx.x, slot = lane >> Dec<D>::kLog, cc = lane & (kDecChunks - 1);
   const long bh = blockIdx.x;
   const float* base = a.ws + bh * a.splits * kDecPart;
   float mx = -INFINITY;
@@ -465,9 +500,10 @@ inline void plan_decode(int B, int Hkv, int cap, int cus, int* splits, int* kps)
   *splits = (int)((tiles + per - 1) / per);
 }
 
-inline int decode_launch_plan(int B, int Hkv, int cap, int* splits, int* kps) {
+// (`tile`: the key tile of the launch's head dim, which a forced plan's keys are a multiple of)
+inline int decode_launch_plan(int B, int Hkv, int cap, int tile, int* splits, int* kps) {
   if (g_dec_splits > 0) {
-    if (g_dec_keys % kDecKeyTile != 0 || (long)g_dec_splits * g_dec_keys < cap) return (int)hipErrorInvalidValue;
+    if (g_dec_keys % tile != 0 || (long)g_dec_splits * g_dec_keys < cap) return (int)hipErrorInvalidValue;
     *splits = g_dec_splits;
     *kps = g_dec_keys;
     return 0;
@@ -494,7 +530,7 @@ struct AppendArgs {
   int nt, T, cap;
 };
 
-// One work item of either append kernel: chunks jj and jj + 4 of head row (b, tt, hd) of tensor `which`, bound
+// One work item of either append kernel: chunks jj and jj + D / 16 of head row (b, tt, hd) of tensor `which`, bound
 // for row p of a cache (or row tt of q_out), as the bf16 cache holds them.
 struct AppRow {
   int which, hd, tt, jj;
@@ -503,23 +539,25 @@ struct AppRow {
   u32x4 lo, hi;
 };
 
+template <int D>
 __device__ __forceinline__ void append_store_bf16(const AppRow& r) {
   store16<kAligned16>(r.dst, r.lo);
-  store16<kAligned16>(r.dst + kDecD / 2, r.hi);
+  store16<kAligned16>(r.dst + D / 2, r.hi);
 }
 
 // What the two kernels share: the item's decode, the position rule, and the row's two chunks loaded as they are
 // or rotated (rope's bits, rounded to bf16).  False: the item is done -- a cache row outside [0, cap) stores
 // nothing, and q_out of such a position has just been zeroed.
+template <int D>
 __device__ __forceinline__ bool append_row(const AppendArgs& a, long item, AppRow& r) {
-  constexpr int h = kDecD / 2;
+  constexpr int h = D / 2, kItems = D / 16;       // a row's work items: 4 / 8
   r.which = 0;
   if (item >= a.t[1].first) r.which = 1;              // k and v are always there
   if (a.nt > 2 && item >= a.t[2].first) r.which = 2;
   const AppTensor& x = a.t[r.which];
   long i = item - x.first;
-  r.jj = (int)(i % 4);
-  i /= 4;
+  r.jj = (int)(i % kItems);
+  i /= kItems;
   r.hd = (int)(i % x.H);
   i /= x.H;
   r.tt = (int)(i % a.T);
@@ -529,7 +567,7 @@ __device__ __forceinline__ bool append_row(const AppendArgs& a, long item, AppRo
   if (r.p < 0 || r.p >= a.cap) {
     if (!x.cache) {                               // q_out of a sequence that is full: zeros
       r.lo = r.hi = u32x4{0u, 0u, 0u, 0u};
-      append_store_bf16(r);
+      append_store_bf16<D>(r);
     }
     return false;                                 // no store outside the cache: neither rows nor scales
   }
@@ -556,12 +594,13 @@ __device__ __forceinline__ bool append_row(const AppendArgs& a, long item, AppRo
   return true;
 }
 
+template <int D>
 __global__ __launch_bounds__(kRowBlockThreads)
 void kv_append_kernel(const AppendArgs a) {
   const long step = (long)gridDim.x * kRowBlockThreads;
   for (long item = (long)blockIdx.x * kRowBlockThreads + threadIdx.x; item < a.total; item += step) {
     AppRow r;
-    if (append_row(a, item, r)) append_store_bf16(r);
+    if (append_row<D>(a, item, r)) append_store_bf16<D>(r);
   }
 }
 
@@ -572,9 +611,14 @@ void kv_append_kernel(const AppendArgs a) {
 // lane's, as the tensors' first items, the total and the grid stride are all multiples of 4), and the quad
 // takes every branch together, so a block maximum is an integer max of bf16 magnitude bits over the lane's 8
 // elements and then over the quad by two DPP quad_perm steps.  No LDS, no atomics, no workspace.
+//
+// D = 128: 128 e4m3 bytes and four scale bytes.  A row's 8 items are 8 aligned lanes (the same argument with 8 for
+// 4): item jj holds chunk jj of block jj / 4 and chunk jj + 8 of block 2 + jj / 4, so each quad still holds two
+// whole blocks and the maxima stay the two quad_perm steps; the two quads then swap their exponent pairs by one
+// row_half_mirror (lane i <-> 7 - i) and lane 0 stores the row's four scale bytes with one 4-byte store.
 struct AppendQ8Args {
   AppendArgs a;               // t[0].out / t[1].out: the e4m3 bytes, their o* strides in bytes
-  unsigned char* sc[2];       // the scales of k and v, (B, cap, Hkv, 2)
+  unsigned char* sc[2];       // the scales of k and v, (B, cap, Hkv, D / 32)
   long sb[2], sp[2], sh[2];   // their (batch, position, head) strides in bytes
 };
 
@@ -594,17 +638,18 @@ __device__ __forceinline__ unsigned amax_bits8(const u32x4& w) {
   return mx;
 }
 
+template <int D>
 __global__ __launch_bounds__(kRowBlockThreads)
 void kv_append_q8_kernel(const AppendQ8Args qa) {
-  constexpr int h = kDecD / 2;
+  constexpr int h = D / 2;
   const AppendArgs& a = qa.a;
   const long step = (long)gridDim.x * kRowBlockThreads;
   for (long item = (long)blockIdx.x * kRowBlockThreads + threadIdx.x; item < a.total; item += step) {
     AppRow r;
-    if (!append_row(a, item, r)) continue;
+    if (!append_row<D>(a, item, r)) continue;
     const AppTensor& x = a.t[r.which];
     if (!x.cache) {                               // q_out stays bf16
-      append_store_bf16(r);
+      append_store_bf16<D>(r);
       continue;
     }
     const int e0 = mx_exponent(__uint_as_float(quad_max(amax_bits8(r.lo)) << 16));
@@ -613,9 +658,18 @@ void kv_append_q8_kernel(const AppendQ8Args qa) {
     unsigned char* dst = reinterpret_cast<unsigned char*>(x.out) + r.b * x.ob + r.p * x.op + (long)r.hd * x.oh + r.jj * 8;
     *reinterpret_cast<u32x2*>(dst) = u32x2{cvt4_e4m3_bf16(r.lo[0], r.lo[1], s0), cvt4_e4m3_bf16(r.lo[2], r.lo[3], s0)};
     *reinterpret_cast<u32x2*>(dst + h) = u32x2{cvt4_e4m3_bf16(r.hi[0], r.hi[1], s1), cvt4_e4m3_bf16(r.hi[2], r.hi[3], s1)};
-    if (r.jj == 0)
-      *reinterpret_cast<unsigned short*>(qa.sc[r.which] + r.b * qa.sb[r.which] + r.p * qa.sp[r.which] +
-                                         (long)r.hd * qa.sh[r.which]) = (unsigned short)((e0 + 127) | ((e1 + 127) << 8));
+    if constexpr (D == 64) {
+      if (r.jj == 0)
+        *reinterpret_cast<unsigned short*>(qa.sc[r.which] + r.b * qa.sb[r.which] + r.p * qa.sp[r.which] +
+                                           (long)r.hd * qa.sh[r.which]) = (unsigned short)((e0 + 127) | ((e1 + 127) << 8));
+    } else {
+      // own: blocks jj / 4 and 2 + jj / 4; the other quad's pair comes from lane 7 - jj
+      const unsigned own = (unsigned)(e0 + 127) | ((unsigned)(e1 + 127) << 16);
+      const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(0, (int)own, 0x141, 0xf, 0xf, false);
+      if (r.jj == 0)
+        *reinterpret_cast<unsigned*>(qa.sc[r.which] + r.b * qa.sb[r.which] + r.p * qa.sp[r.which] +
+                                     (long)r.hd * qa.sh[r.which]) = (own & 0x00ff00ffu) | ((other & 0x00ff00ffu) << 8);
+    }
   }
 }
 
@@ -633,8 +687,9 @@ LJS_API int ljs_decode_set_splits(int n, int keys) {
   return 0;
 }
 
-LJS_API int ljs_decode_key_tile() { return kDecKeyTile; }
-LJS_API int ljs_decode_part_floats() { return kDecPart; }
+// of head dim 64 or 128 (0 for any other): the keys one block holds per step, the floats of one partial
+LJS_API int ljs_decode_key_tile(int dim) { return dim == 64 ? Dec<64>::kKeyTile : (dim == 128 ? Dec<128>::kKeyTile : 0); }
+LJS_API int ljs_decode_part_floats(int dim) { return dim == 64 ? Dec<64>::kPart : (dim == 128 ? Dec<128>::kPart : 0); }
 LJS_API int ljs_decode_max_group() { return kDecMaxG; }
 
 // out[0] = splits, out[1] = keys_per_split of (B, Hkv, cap) on a device of `cus` compute units: pure
@@ -644,11 +699,11 @@ LJS_API int ljs_decode_plan(int B, int Hkv, int cap, int cus, int* out) {
   return 0;
 }
 
-// the plan the next ljs_attn_decode of this shape launches (the forced one, or the pure plan for this
-// device): what the workspace is sized from
-LJS_API int ljs_decode_launch_plan(int B, int Hkv, int cap, int* out) {
-  if (B < 1 || Hkv < 1 || cap < 1 || !out) return (int)hipErrorInvalidValue;
-  return decode_launch_plan(B, Hkv, cap, out, out + 1);
+// the plan the next ljs_attn_decode of this shape and head dim launches (the forced one, or the pure plan for
+// this device): what the workspace is sized from
+LJS_API int ljs_decode_launch_plan(int B, int Hkv, int cap, int dim, int* out) {
+  if (B < 1 || Hkv < 1 || cap < 1 || !out || ljs_decode_key_tile(dim) == 0) return (int)hipErrorInvalidValue;
+  return decode_launch_plan(B, Hkv, cap, ljs_decode_key_tile(dim), out, out + 1);
 }
 
 LJS_API int ljs_cache_desc_size() { return (int)sizeof(LjsCache); }
@@ -672,7 +727,8 @@ inline int append_plan(const void* k, const void* v, const void* q, const LjsCac
     return (int)hipErrorInvalidValue;
   AppendArgs a{};
   const int Hkv = c->Hkv;
-  const long per_kv = (long)B * T * Hkv * 4;
+  const int items = c->dim / 16;                  // work items of a head row
+  const long per_kv = (long)B * T * Hkv * items;
   a.t[0] = AppTensor{(const bf16_t*)k, (bf16_t*)c->k, sk[0], sk[1], sk[2], c->sk[0], c->sk[1], c->sk[2], 0, Hkv, rot, 1};
   a.t[1] = AppTensor{(const bf16_t*)v, (bf16_t*)c->v, sv[0], sv[1], sv[2], c->sv[0], c->sv[1], c->sv[2], per_kv, Hkv, 0, 1};
   a.nt = 2;
@@ -680,7 +736,7 @@ inline int append_plan(const void* k, const void* v, const void* q, const LjsCac
   if (q) {
     a.t[2] = AppTensor{(const bf16_t*)q, (bf16_t*)q_out, sq[0], sq[1], sq[2], sqo[0], sqo[1], sqo[2], a.total, H, 1, 0};
     a.nt = 3;
-    a.total += (long)B * T * H * 4;
+    a.total += (long)B * T * H * items;
   }
   a.cos_t = (const float*)cos_t;
   a.sin_t = (const float*)sin_t;
@@ -691,11 +747,29 @@ inline int append_plan(const void* k, const void* v, const void* q, const LjsCac
   return 0;
 }
 
+// the launch of ljs_kv_append at head dim D (c.dim has chosen it)
+#define LJS_DEC_NAME(op, inst) (D == 64 ? op inst : op "128" inst)
+template <int D>
+int append_launch(const AppendQ8Args& qa, const LjsCache& c, bool has_q, bool rot, dim3 grid, hipStream_t st) {
+  if (c.kind == kCacheMx8) {
+    hipLaunchKernelGGL(kv_append_q8_kernel<D>, grid, dim3(kRowBlockThreads), 0, st, qa);
+    ljs_launch_rec(has_q ? LJS_DEC_NAME("kv_append", "<rot,q,mx8>")
+                         : (rot ? LJS_DEC_NAME("kv_append", "<rot,mx8>") : LJS_DEC_NAME("kv_append", "<copy,mx8>")),
+                   grid, kRowBlockThreads);
+  } else {
+    hipLaunchKernelGGL(kv_append_kernel<D>, grid, dim3(kRowBlockThreads), 0, st, qa.a);
+    ljs_launch_rec(has_q ? LJS_DEC_NAME("kv_append", "<rot,q>")
+                         : (rot ? LJS_DEC_NAME("kv_append", "<rot>") : LJS_DEC_NAME("kv_append", "<copy>")),
+                   grid, kRowBlockThreads);
+  }
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
-// k, v (B, T, Hkv, 64) -> the cache c (cache_common.h; either kind) at rows base[b] + t, base = lens (int32 [B],
-// device) or 0 when lens is null; q (B, T, H, 64) -> q_out (B, T, H, 64) when both are given.  cos_t / sin_t (f32
-// [table_rows][32], table_rows >= cap) rotate k and q; both null: k is copied as it is.  s*: the
+// k, v (B, T, Hkv, D) -> the cache c (cache_common.h; either kind; D = c.dim, 64 or 128) at rows base[b] + t, base =
+// lens (int32 [B], device) or 0 when lens is null; q (B, T, H, D) -> q_out (B, T, H, D) when both are given.  cos_t /
+// sin_t (f32 [table_rows][D / 2], table_rows >= cap) rotate k and q; both null: k is copied as it is.  s*: the
 // (batch, position, head) strides in elements.  An MX-fp8 cache gets, of every row written, quantize_mx_ref
 // of the bf16 row a bf16 cache would have got; q_out stays bf16.  Returns hipErrorInvalidValue, and launches
 // and records nothing, for an empty shape, a misaligned base or stride, a cache cache_aligned refuses (a kind
@@ -715,14 +789,9 @@ LJS_API int ljs_kv_append(const void* k, const void* v, const void* q, const Ljs
     qa.sc[1] = (unsigned char*)c->vs;
     qa.sb[0] = c->sks[0]; qa.sp[0] = c->sks[1]; qa.sh[0] = c->sks[2];
     qa.sb[1] = c->svs[0]; qa.sp[1] = c->svs[1]; qa.sh[1] = c->svs[2];
-    hipLaunchKernelGGL(kv_append_q8_kernel, grid, dim3(kRowBlockThreads), 0, st, qa);
-    ljs_launch_rec(q ? "kv_append<rot,q,mx8>" : (cos_t ? "kv_append<rot,mx8>" : "kv_append<copy,mx8>"), grid,
-                   kRowBlockThreads);
-  } else {
-    hipLaunchKernelGGL(kv_append_kernel, grid, dim3(kRowBlockThreads), 0, st, qa.a);
-    ljs_launch_rec(q ? "kv_append<rot,q>" : (cos_t ? "kv_append<rot>" : "kv_append<copy>"), grid, kRowBlockThreads);
   }
-  return (int)hipGetLastError();
+  return c->dim == 128 ? append_launch<128>(qa, *c, q != nullptr, cos_t != nullptr, grid, st)
+                       : append_launch<64>(qa, *c, q != nullptr, cos_t != nullptr, grid, st);
 }
 
 namespace {
@@ -734,12 +803,15 @@ struct ExtInstance {
   int P, HW;
   const char* name;
 };
+#define LJS_EXT_NAMES(W, M)                                                                                          \
+  {"attn_extend" W "<G1,P2" M ">", "attn_extend" W "<G1,P4" M ">", "attn_extend" W "<G1,P8" M ">",                       \
+   "attn_extend" W "<G2,P2" M ">", "attn_extend" W "<G2,P4" M ">", "attn_extend" W "<G4,P2" M ">",                       \
+   "attn_extend" W "<G8,P1" M ">", "attn_extend" W "<G16,P1" M ">"}
+template <int D>
 inline ExtInstance extend_instance(int G, int T, bool mx8) {
-  static const char* const names[2][8] = {
-      {"attn_extend<G1,P2>", "attn_extend<G1,P4>", "attn_extend<G1,P8>", "attn_extend<G2,P2>", "attn_extend<G2,P4>",
-       "attn_extend<G4,P2>", "attn_extend<G8,P1>", "attn_extend<G16,P1>"},
-      {"attn_extend<G1,P2,mx8>", "attn_extend<G1,P4,mx8>", "attn_extend<G1,P8,mx8>", "attn_extend<G2,P2,mx8>",
-       "attn_extend<G2,P4,mx8>", "attn_extend<G4,P2,mx8>", "attn_extend<G8,P1,mx8>", "attn_extend<G16,P1,mx8>"}};
+  static const char* const names64[2][8] = {LJS_EXT_NAMES("", ""), LJS_EXT_NAMES("", ",mx8")};
+  static const char* const names128[2][8] = {LJS_EXT_NAMES("128", ""), LJS_EXT_NAMES("128", ",mx8")};
+  const char* const(&names)[2][8] = D == 64 ? names64 : names128;
   const int t2 = T <= 2 ? 2 : (T <= 4 ? 4 : 8);
   if (G == 1) return {t2, t2, names[mx8][t2 == 2 ? 0 : (t2 == 4 ? 1 : 2)]};
   if (G == 2) return t2 == 2 ? ExtInstance{2, 4, names[mx8][3]} : ExtInstance{4, 8, names[mx8][4]};
@@ -749,7 +821,7 @@ inline ExtInstance extend_instance(int G, int T, bool mx8) {
 
 // the launch of ljs_attn_decode over a cache of the template's kind (c.kind has chosen it): T = 1 is attn_decode,
 // T > 1 attn_extend over the keys [0, lens[b] + extra + t)
-template <bool MX8>
+template <int D, bool MX8>
 int decode_launch(const void* q, const LjsCache& c, void* o, void* lse, void* ws, long ws_floats, const void* lens,
                   int B, int T, int H, const long* sq, const long* so, float scale, int extra, hipStream_t st) {
   const int Hkv = c.Hkv, cap = c.cap;
@@ -759,10 +831,10 @@ int decode_launch(const void* q, const LjsCache& c, void* o, void* lse, void* ws
     return (int)hipErrorInvalidValue;
   if (!bf16_aligned(q, sq) || !bf16_aligned(o, so) || !cache_aligned(c)) return (int)hipErrorInvalidValue;
   // a load reaches up to one unrolled block step past the cache
-  if (!cache_reach_ok(c, (long)cap + kDecKeyTile * kDecUnroll)) return (int)hipErrorInvalidValue;
+  if (!cache_reach_ok(c, (long)cap + Dec<D>::kKeyTile * Dec<D>::kUnroll)) return (int)hipErrorInvalidValue;
   DecodeArgs a{};
-  if (decode_launch_plan(B, Hkv, cap, &a.splits, &a.kps) != 0) return (int)hipErrorInvalidValue;
-  if (a.splits > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < (long)B * T * H * a.splits * kDecPart))
+  if (decode_launch_plan(B, Hkv, cap, Dec<D>::kKeyTile, &a.splits, &a.kps) != 0) return (int)hipErrorInvalidValue;
+  if (a.splits > 1 && (!ws || (((uintptr_t)ws) & 15u) || ws_floats < (long)B * T * H * a.splits * Dec<D>::kPart))
     return (int)hipErrorInvalidValue;
   a.q = (const bf16_t*)q;
   a.kc = (const bf16_t*)c.k;
@@ -787,38 +859,38 @@ int decode_launch(const void* q, const LjsCache& c, void* o, void* lse, void* ws
   dim3 grid((unsigned)a.splits, (unsigned)Hkv, (unsigned)B);
   const char* name;
   if (T > 1) {
-    const ExtInstance x = extend_instance(a.G, T, MX8);
+    const ExtInstance x = extend_instance<D>(a.G, T, MX8);
     a.P = x.P;
     grid.x = (unsigned)(a.splits * ((T + x.P - 1) / x.P));      // (row tile, split)
     name = x.name;
     if (x.HW == 2)
-      hipLaunchKernelGGL((attn_decode_kernel<2, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
+      hipLaunchKernelGGL((attn_decode_kernel<D, 2, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
     else if (x.HW == 4)
-      hipLaunchKernelGGL((attn_decode_kernel<4, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
+      hipLaunchKernelGGL((attn_decode_kernel<D, 4, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
     else
-      hipLaunchKernelGGL((attn_decode_kernel<8, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
+      hipLaunchKernelGGL((attn_decode_kernel<D, 8, MX8, true>), grid, dim3(kDecThreads), 0, st, a);
   } else if (a.G == 1) {
-    hipLaunchKernelGGL((attn_decode_kernel<1, MX8>), grid, dim3(kDecThreads), 0, st, a);
-    name = MX8 ? "attn_decode<G1,mx8>" : "attn_decode<G1>";
+    hipLaunchKernelGGL((attn_decode_kernel<D, 1, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? LJS_DEC_NAME("attn_decode", "<G1,mx8>") : LJS_DEC_NAME("attn_decode", "<G1>");
   } else if (a.G == 2) {
-    hipLaunchKernelGGL((attn_decode_kernel<2, MX8>), grid, dim3(kDecThreads), 0, st, a);
-    name = MX8 ? "attn_decode<G2,mx8>" : "attn_decode<G2>";
+    hipLaunchKernelGGL((attn_decode_kernel<D, 2, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? LJS_DEC_NAME("attn_decode", "<G2,mx8>") : LJS_DEC_NAME("attn_decode", "<G2>");
   } else if (a.G <= 4) {
-    hipLaunchKernelGGL((attn_decode_kernel<4, MX8>), grid, dim3(kDecThreads), 0, st, a);
-    name = MX8 ? "attn_decode<G4,mx8>" : "attn_decode<G4>";
+    hipLaunchKernelGGL((attn_decode_kernel<D, 4, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? LJS_DEC_NAME("attn_decode", "<G4,mx8>") : LJS_DEC_NAME("attn_decode", "<G4>");
   } else if (a.G <= 8) {
-    hipLaunchKernelGGL((attn_decode_kernel<8, MX8>), grid, dim3(kDecThreads), 0, st, a);
-    name = MX8 ? "attn_decode<G8,mx8>" : "attn_decode<G8>";
+    hipLaunchKernelGGL((attn_decode_kernel<D, 8, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? LJS_DEC_NAME("attn_decode", "<G8,mx8>") : LJS_DEC_NAME("attn_decode", "<G8>");
   } else {
-    hipLaunchKernelGGL((attn_decode_kernel<8, MX8>), grid, dim3(kDecThreads), 0, st, a);
-    name = MX8 ? "attn_decode<G16,mx8>" : "attn_decode<G16>";
+    hipLaunchKernelGGL((attn_decode_kernel<D, 8, MX8>), grid, dim3(kDecThreads), 0, st, a);
+    name = MX8 ? LJS_DEC_NAME("attn_decode", "<G16,mx8>") : LJS_DEC_NAME("attn_decode", "<G16>");
   }
   ljs_launch_rec(name, grid, kDecThreads);
   int rc = (int)hipGetLastError();
   if (rc != 0 || a.splits == 1) return rc;
   const dim3 mgrid((unsigned)(B * T * H));
-  hipLaunchKernelGGL(decode_merge_kernel, mgrid, dim3(64), 0, st, a);
-  ljs_launch_rec("decode_merge", mgrid, 64);
+  hipLaunchKernelGGL(decode_merge_kernel<D>, mgrid, dim3(64), 0, st, a);
+  ljs_launch_rec(LJS_DEC_NAME("decode_merge", ""), mgrid, 64);
   return (int)hipGetLastError();
 }
 
@@ -826,21 +898,25 @@ int decode_launch(const void* q, const LjsCache& c, void* o, void* lse, void* ws
 
 LJS_API int ljs_extend_max_positions() { return kExtMaxT; }
 
-// q (B, T, H, 64) over the cache c (cache_common.h; either kind) -> o (B, T, H, 64) bf16, lse (B, T, H) f32: row (b, t, h)
+// q (B, T, H, D) over the cache c (cache_common.h; either kind; D = c.dim, 64 or 128) -> o (B, T, H, D) bf16, lse (B, T, H) f32: row (b, t, h)
 // over the keys [0, clamp(lens[b] + extra + t, 0, cap)) (the head of the file).  T = 1 is attn_decode (extra = 1 after
 // an append that lens does not count yet); 1 < T <= 64 with extra = 1 is attn_extend, whose row t has the bits
 // of the T = 1 call with extra = t + 1 under the same plan.  ws: f32 workspace of ws_floats floats, at least
-// B T H splits kDecPart of them when the plan has more than one split.  sq / so: (batch, position, head) strides in
+// B T H splits (D + 8) of them when the plan has more than one split.  sq / so: (batch, position, head) strides in
 // elements.  Returns hipErrorInvalidValue, and launches and records nothing, for an empty shape, T outside
 // [1, 64], H % Hkv != 0, H / Hkv > 16, scale <= 0, extra < 0, a misaligned base or stride, a cache cache_aligned or
-// cache_reach_ok refuses (a kind that does not match its scale bases, a key stride below 64 or a scale row
-// stride below 2, byte offsets that do not fit 31 bits), an invalid forced plan or a workspace that is too small.
+// cache_reach_ok refuses (a head dim that is neither 64 nor 128, a kind that does not match its scale bases, a key
+// stride below D or a scale row stride below D / 32, byte offsets that do not fit 31 bits), an invalid forced plan or a workspace that is too small.
 LJS_API int ljs_attn_decode(const void* q, const LjsCache* c, void* o, void* lse, void* ws, long ws_floats,
                             const void* lens, int B, int T, int H, const long* sq, const long* so, float scale,
                             int extra, hipStream_t st) {
-  if (!c) return (int)hipErrorInvalidValue;
-  return c->kind == kCacheMx8 ? decode_launch<true>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st)
-                              : decode_launch<false>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st);
+  if (!c || !cache_dim_ok(*c)) return (int)hipErrorInvalidValue;
+  if (c->dim == 128)
+    return c->kind == kCacheMx8
+               ? decode_launch<128, true>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st)
+               : decode_launch<128, false>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st);
+  return c->kind == kCacheMx8 ? decode_launch<64, true>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st)
+                              : decode_launch<64, false>(q, *c, o, lse, ws, ws_floats, lens, B, T, H, sq, so, scale, extra, st);
 }
 
 // lens[0 .. B) += n: one small launch after the last layer of a decode step

@@ -453,10 +453,10 @@ LJS_API int ljs_chunk_plan(int B, int T, int H, int Hkv, int cus, int* out) {
 // shape, H % Hkv != 0, H / Hkv > 16, scale <= 0, a null or misaligned lens or lse, a base or stride of q or o
 // that is not 16-byte aligned, or a cache cache_aligned or cache_reach_ok refuses (a kind that does not match
 // its scale bases, a misaligned buffer, a key stride below 64 or a scale row stride below 2, byte offsets that
-// do not fit 31 bits).
+// do not fit 31 bits), or a cache whose head dim is not 64 (the kernel exists at 64 only).
 LJS_API int ljs_attn_chunk(const void* q, const LjsCache* c, void* o, void* lse, const void* lens, int B, int T, int H,
                            const long* sq, const long* so, float scale, hipStream_t st) {
-  if (!c) return (int)hipErrorInvalidValue;
+  if (!c || c->dim != 64) return (int)hipErrorInvalidValue;
   return c->kind == kCacheMx8 ? chunk_launch<true>(q, *c, o, lse, lens, B, T, H, sq, so, scale, st)
                               : chunk_launch<false>(q, *c, o, lse, lens, B, T, H, sq, so, scale, st);
 }

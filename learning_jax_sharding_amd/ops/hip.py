@@ -37,8 +37,9 @@ _LP = ctypes.POINTER(ctypes.c_long)
 
 class _CacheDesc(ctypes.Structure):
     """``LjsCache`` of csrc/kernels/cache_common.h: a KV cache as one operand, of an explicit ``kind``.  Strides are
-    the (batch, position, head) ones, in elements for bf16 buffers and in bytes for e4m3 and scale buffers."""
-    _fields_ = [("kind", c_int), ("cap", c_int), ("Hkv", c_int), ("k", c_void_p), ("v", c_void_p),
+    the (batch, position, head) ones, in elements for bf16 buffers and in bytes for e4m3 and scale buffers; ``dim``
+    is the head dim, 64 or 128 (it sits where the ABI pads the three ints, so the size and the other offsets stand)."""
+    _fields_ = [("kind", c_int), ("cap", c_int), ("Hkv", c_int), ("dim", c_int), ("k", c_void_p), ("v", c_void_p),
                 ("sk", c_long * 3), ("sv", c_long * 3), ("ks", c_void_p), ("vs", c_void_p),
                 ("sks", c_long * 3), ("svs", c_long * 3)]
 
@@ -102,7 +103,7 @@ _SIGS = {
     "ljs_chunk_plan": [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_chunk_set_rows": [c_int],
     "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
-    "ljs_decode_launch_plan": [c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "ljs_decode_launch_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_decode_set_splits": [c_int, c_int],
     "ljs_skinny_set_waves": [c_int],
     "ljs_skinny_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
@@ -111,8 +112,8 @@ _SIGS = {
     "ljs_skinny_mx_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_skinny_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long,
                       c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_void_p],
-    "ljs_decode_key_tile": [],
-    "ljs_decode_part_floats": [],
+    "ljs_decode_key_tile": [c_int],
+    "ljs_decode_part_floats": [c_int],
     "ljs_decode_max_group": [],
     "ljs_lens_add": [c_void_p, c_int, c_int, c_void_p],
     "ljs_attn_bwd_proj_enabled": [c_int, c_int],
@@ -2648,9 +2649,25 @@ def set_decode_splits(n: Optional[int], keys: int = 0) -> None:
     lib().ljs_decode_set_splits(int(n or 0), int(keys))
 
 
-def decode_key_tile() -> int:
-    """Keys one block of the decode kernel holds per step: ``keys_per_split`` is a multiple of it."""
-    return lib().ljs_decode_key_tile()
+def decode_key_tile(dim: int = 64) -> int:
+    """Keys one block of the decode kernel holds per step at head dim ``dim`` (32 at 64, 16 at 128):
+    ``keys_per_split`` is a multiple of it."""
+    return lib().ljs_decode_key_tile(int(dim))
+
+
+def decode_part_floats(dim: int = 64) -> int:
+    """The f32 values of one split partial at head dim ``dim``: what the workspace is sized by."""
+    return lib().ljs_decode_part_floats(int(dim))
+
+
+# Which cached operation has a kernel at which head dim: the one statement of it (ops.kernels' dispatch reads it)
+CACHE_OP_DIMS = {"append": (64, 128), "decode": (64, 128), "extend": (64, 128), "chunk": (64,)}
+
+
+def cache_op_supported(op: str, dim: int) -> bool:
+    """Whether the cached operation ``op`` (``"append"``, ``"decode"``, ``"extend"``, ``"chunk"``, or a public name of
+    one: ``"kv_append_q8"``, ``"attn_chunk"``) exists at head dim ``dim``."""
+    return dim in CACHE_OP_DIMS[op.replace("_q8", "").split("_")[-1]]
 
 
 def decode_max_group() -> int:
@@ -2669,48 +2686,51 @@ def plan_decode(B: int, Hkv: int, cap: int, cus: Optional[int] = None):
     return int(out[0]), int(out[1])
 
 
-def _decode_launch_plan(B: int, Hkv: int, cap: int):
+def _decode_launch_plan(B: int, Hkv: int, cap: int, dim: int = 64):
     out = (c_int * 2)()
-    _ck(lib().ljs_decode_launch_plan(int(B), int(Hkv), int(cap), out), "ljs_decode_launch_plan")
+    _ck(lib().ljs_decode_launch_plan(int(B), int(Hkv), int(cap), int(dim), out), "ljs_decode_launch_plan")
     return int(out[0]), int(out[1])
 
 
-def _rows_supported(ts, dtype, width: int, base: int, unit: int) -> bool:
-    """The operand rule of decode.hip and prefill.hip: ``dtype`` ``(B, S, H, width)`` GPU tensors, the last dim contiguous,
-    the base a multiple of ``base`` bytes and the three outer strides multiples of ``unit``."""
-    return all(t.is_cuda and t.dim() == 4 and t.dtype == dtype and t.shape[-1] == width and t.numel()
-               and t.stride(-1) == 1 and t.data_ptr() % base == 0 and all(t.stride(i) % unit == 0 for i in range(3))
-               for t in ts)
+def _rows_supported(ts, dtype, widths, base: int, unit: int) -> bool:
+    """The operand rule of decode.hip and prefill.hip: ``dtype`` ``(B, S, H, width)`` GPU tensors of one ``width`` among
+    ``widths``, the last dim contiguous, the base a multiple of ``base`` bytes and the three outer strides multiples
+    of ``unit``."""
+    return all(t.is_cuda and t.dim() == 4 and t.dtype == dtype and t.shape[-1] in widths and t.shape[-1] == ts[0].shape[-1]
+               and t.numel() and t.stride(-1) == 1 and t.data_ptr() % base == 0
+               and all(t.stride(i) % unit == 0 for i in range(3)) for t in ts)
 
 
 def decode_supported(*ts: torch.Tensor) -> bool:
-    """Whether decode.hip takes these operands as they are: bf16 ``(B, S, H, 64)`` GPU tensors, the head
-    dim contiguous, the base and the three outer strides 16-byte aligned."""
-    return _rows_supported(ts, torch.bfloat16, 64, 16, 8)
+    """Whether decode.hip takes these operands as they are: bf16 ``(B, S, H, D)`` GPU tensors of one head dim ``D``, 64
+    or 128, contiguous, the base and the three outer strides 16-byte aligned."""
+    return _rows_supported(ts, torch.bfloat16, (64, 128), 16, 8)
 
 
 def decode_q8_supported(*ts: torch.Tensor) -> bool:
-    """Whether decode.hip takes these MX-fp8 cache buffers as they are: uint8 ``(B, S, H, 64)`` GPU tensors (e4m3
-    bytes), the head dim contiguous, the base and the three outer strides multiples of 16 bytes."""
-    return _rows_supported(ts, torch.uint8, 64, 16, 16)
+    """Whether decode.hip takes these MX-fp8 cache buffers as they are: uint8 ``(B, S, H, D)`` GPU tensors (e4m3
+    bytes) of one head dim, 64 or 128, contiguous, the base and the three outer strides multiples of 16 bytes."""
+    return _rows_supported(ts, torch.uint8, (64, 128), 16, 16)
 
 
 def decode_scale_supported(*ts: torch.Tensor) -> bool:
-    """Whether decode.hip takes these e8m0 scale buffers as they are: uint8 ``(B, S, H, 2)`` GPU tensors, the
-    last dim contiguous, the base and the three outer strides even (one 2-byte store writes a row's two)."""
-    return _rows_supported(ts, torch.uint8, 2, 2, 2)
+    """Whether decode.hip takes these e8m0 scale buffers as they are: uint8 ``(B, S, H, n)`` GPU tensors, ``n = D / 32``
+    (2 or 4), the last dim contiguous, the base and the three outer strides multiples of ``n`` (one ``n``-byte access
+    moves a row's scales)."""
+    n = ts[0].shape[-1] if ts and ts[0].dim() == 4 else 0
+    return _rows_supported(ts, torch.uint8, (2, 4), n, n)
 
 
 def _lens_ok(lens: Optional[torch.Tensor], B: int) -> bool:
     return lens is None or (lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous())
 
 
-# ---- the cache as one operand.  A cache is ``(kc, vc)``, bf16 ``(B, cap, Hkv, 64)``, or the MX-fp8 ``(kc, vc, kcs, vcs)``:
-# e4m3 bytes ``(B, cap, Hkv, 64)`` and e8m0 scale bytes ``(B, cap, Hkv, 2)``, all uint8.  The C entries take it as a
+# ---- the cache as one operand.  A cache is ``(kc, vc)``, bf16 ``(B, cap, Hkv, D)``, or the MX-fp8 ``(kc, vc, kcs, vcs)``:
+# e4m3 bytes ``(B, cap, Hkv, D)`` and e8m0 scale bytes ``(B, cap, Hkv, D / 32)``, all uint8; D is 64 or 128.  The C entries take it as a
 # _CacheDesc whose kind is stated by the caller, never inferred from which buffers are there.
 def _cache_desc(kind: int, kc, vc, kcs=None, vcs=None) -> _CacheDesc:
-    """The descriptor of these buffers as they are (None: a null base), of the stated ``kind``."""
-    d = _CacheDesc(kind, kc.shape[1], kc.shape[2], kc.data_ptr(), vc.data_ptr(), _L3(*kc.stride()[:3]), _L3(*vc.stride()[:3]))
+    """The descriptor of these buffers as they are (None: a null base), of the stated ``kind``; the head dim is ``kc``'s."""
+    d = _CacheDesc(kind, kc.shape[1], kc.shape[2], kc.shape[-1], kc.data_ptr(), vc.data_ptr(), _L3(*kc.stride()[:3]), _L3(*vc.stride()[:3]))
     if kcs is not None:
         d.ks, d.sks = kcs.data_ptr(), _L3(*kcs.stride()[:3])
     if vcs is not None:
@@ -2724,12 +2744,12 @@ def _cache_kind(cache) -> int:
 
 def _cache_supported(cache) -> bool:
     """Whether the kernels take this cache as it is: the buffers' dtype, shape and alignment, k and v alike, and
-    scales of shape ``kc.shape[:3] + (2,)``."""
+    scales of shape ``kc.shape[:3] + (D / 32,)``."""
     kc, vc = cache[:2]
     if len(cache) == 2:
         return decode_supported(kc, vc) and kc.shape == vc.shape
     return decode_q8_supported(kc, vc) and decode_scale_supported(*cache[2:]) and kc.shape == vc.shape \
-        and cache[2].shape == cache[3].shape == kc.shape[:3] + (2,)
+        and cache[2].shape == cache[3].shape == kc.shape[:3] + (kc.shape[3] // 32,)
 
 
 def _refusal(what: str, x, cache, positions: str = "T") -> NotImplementedError:
@@ -2737,8 +2757,10 @@ def _refusal(what: str, x, cache, positions: str = "T") -> NotImplementedError:
     got = f"got {x.dtype} {tuple(x.shape)} strides {x.stride()}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()}"
     if len(cache) == 4:
         got += f", scales {cache[2].dtype} {tuple(cache[2].shape)} strides {cache[2].stride()}"
-    return NotImplementedError(f"{what} kernel: bf16 (B, {positions}, H, 64) q / k / v and caches (B, cap, Hkv, 64), bf16 or uint8 "
-                               f"with uint8 scales (B, cap, Hkv, 2) of even strides, all with 16-byte aligned bases and "
+    dims = " or ".join(str(d) for d in (64, 128) if cache_op_supported(what, d))
+    return NotImplementedError(f"{what} kernel: bf16 (B, {positions}, H, D) q / k / v and caches (B, cap, Hkv, D) of one head dim "
+                               f"D = {dims}, bf16 or uint8 with uint8 scales (B, cap, Hkv, D / 32) whose bases and strides "
+                               f"are multiples of D / 32, all with 16-byte aligned bases and "
                                f"strides, H / Hkv <= {decode_max_group()}, an int32 [B] lens; {got}")
 
 
@@ -2773,14 +2795,15 @@ def cache_append(what: str, k, v, cache, lens, q, theta):
     kc = cache[0]
     B = k.shape[0]
     ok = decode_supported(k, v) and (q is None or decode_supported(q)) and _lens_ok(lens, B) and _cache_supported(cache) \
-        and k.shape == v.shape and kc.shape[0] == B and kc.shape[2] == k.shape[2] \
+        and k.shape == v.shape and kc.shape[0] == B and kc.shape[2:] == k.shape[2:] \
+        and (q is None or q.shape[-1] == k.shape[-1]) and cache_op_supported(what, k.shape[-1]) \
         and (q is None or (theta is not None and q.shape[:2] == k.shape[:2]))
     if not ok:
         raise _refusal(what, k, cache)
     cos = sin = q_out = None
     if theta is not None:
         from .kernels import rope_table
-        cos, sin = rope_table(k.device, 64, theta, kc.shape[1])
+        cos, sin = rope_table(k.device, k.shape[-1], theta, kc.shape[1])
     if q is not None:
         q_out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     _ck(_kv_append_desc(_cache_desc(_cache_kind(cache), *cache), k, v, lens, q, q_out, cos, sin), "ljs_kv_append")
@@ -2798,7 +2821,8 @@ def _decode_ws(dev: torch.device, floats: int) -> torch.Tensor:
                                f"and {floats} are needed, and it cannot be created during a graph capture: run the "
                                "function once outside the capture first")
         if t is not None:
-            _WS[(dev.index, "decode", t.data_ptr())] = t     # a captured graph may still write into it
+            # a captured graph may still write into it (a (device, name) key like every entry of _WS)
+            _WS[(dev.index, f"decode/retired/{t.data_ptr()}")] = t
         t = torch.empty(max(floats, 1 << 16), dtype=torch.float32, device=dev)
         _WS[key] = t
     return t
@@ -2806,22 +2830,23 @@ def _decode_ws(dev: torch.device, floats: int) -> torch.Tensor:
 
 def cache_attend(what: str, q, cache, lens, scale: float, max_t: Optional[int], extra: int = 1):
     """The checked call behind the ``attn_*`` functions below (``what``: the name refusals carry).  Attention of ``q`` over ``cache``: by ``ljs_attn_decode`` for up to ``max_t`` positions (with its workspace), by
-    ``ljs_attn_chunk`` when ``max_t`` is None.  ``(o`` (B, T, H, 64), ``lse2`` (B, H, T)``)``."""
-    B, T, H, _ = q.shape
+    ``ljs_attn_chunk`` when ``max_t`` is None.  ``(o`` (B, T, H, D), ``lse2`` (B, H, T)``)``."""
+    B, T, H, D = q.shape
     kc = cache[0]
     ok = decode_supported(q) and kc.dim() == 4 and kc.shape[0] == B and lens is not None and _lens_ok(lens, B) \
         and _cache_supported(cache) and H % kc.shape[2] == 0 and H // kc.shape[2] <= decode_max_group() and scale > 0 \
-        and (max_t is None or 1 <= T <= max_t)
+        and (max_t is None or 1 <= T <= max_t) and kc.shape[3] == D \
+        and cache_op_supported(what, D)
     if not ok:
         raise _refusal(what, q, cache, "T" if max_t is None else ("1" if max_t == 1 else f"T <= {max_t}"))
     desc = _cache_desc(_cache_kind(cache), *cache)
-    o = torch.empty((B, T, H, 64), dtype=torch.bfloat16, device=q.device)
+    o = torch.empty((B, T, H, D), dtype=torch.bfloat16, device=q.device)
     if max_t is None:
         lse = torch.empty((B, T, H), dtype=torch.float32, device=q.device)
         _ck(_attn_chunk_desc(desc, q, o, lse, lens, scale), "ljs_attn_chunk")
         return o, lse.permute(0, 2, 1)
-    splits, _ = _decode_launch_plan(B, kc.shape[2], kc.shape[1])
-    ws = _decode_ws(q.device, B * T * H * splits * lib().ljs_decode_part_floats()) if splits > 1 else None
+    splits, _ = _decode_launch_plan(B, kc.shape[2], kc.shape[1], D)
+    ws = _decode_ws(q.device, B * T * H * splits * decode_part_floats(D)) if splits > 1 else None
     lse = torch.empty((B, H, 1) if max_t == 1 else (B, T, H), dtype=torch.float32, device=q.device)
     _ck(_attn_decode_desc(desc, q, o, lse, ws, lens, scale, extra), "ljs_attn_decode")
     return o, (lse if max_t == 1 else lse.permute(0, 2, 1))
@@ -2929,7 +2954,8 @@ def chunk_supported(q, kc, vc, lens, kcs=None, vcs=None) -> bool:
     """Whether prefill.hip takes these operands as they are: bf16 ``(B, T, H, 64)`` q, caches ``(B, cap, Hkv, 64)`` in bf16
     (or uint8 with ``(B, cap, Hkv, 2)`` uint8 scales), 16-byte aligned bases and strides, an int32 ``[B]`` lens,
     ``H % Hkv == 0`` and ``H / Hkv <= 16``."""
-    if not decode_supported(q) or kc.dim() != 4 or kc.shape[0] != q.shape[0] or lens is None or not _lens_ok(lens, q.shape[0]):
+    if not decode_supported(q) or kc.dim() != 4 or kc.shape[0] != q.shape[0] or lens is None or not _lens_ok(lens, q.shape[0]) \
+            or kc.shape[3] != q.shape[3] or not cache_op_supported("chunk", q.shape[3]):
         return False
     H, Hkv = q.shape[2], kc.shape[2]
     return bool(_cache_supported((kc, vc) if kcs is None else (kc, vc, kcs, vcs)) and H % Hkv == 0 and H // Hkv <= 16)

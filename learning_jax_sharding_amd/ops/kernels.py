@@ -790,23 +790,28 @@ _WARNED_DECODE = set()
 
 
 def _hip_cache(what: str, ts, cache, lens, G: int = 1) -> bool:
-    """Whether decode.hip / prefill.hip take these shards: bf16 ``(B, S, H, 64)`` GPU tensors ``ts`` and a cache
-    ``hip._cache_supported`` accepts, with 16-byte aligned bases and strides (even ones for the scales), an int32 lens
-    and at most 16 query heads per key/value head.  Anything else on a GPU runs the torch formulation there, with a
-    one-time warning per reason; host devices and ``LJS_FUSED_DECODE=0`` run it silently."""
+    """Whether decode.hip / prefill.hip take these shards: bf16 ``(B, S, H, D)`` GPU tensors ``ts`` and a cache
+    ``hip._cache_supported`` accepts, all of one head dim ``D`` at which ``hip.cache_op_supported`` has the operation
+    (append, decode and extend at 64 and 128, chunk at 64), with 16-byte aligned bases and strides (multiples of D / 32
+    for the scales), an int32 lens and at most 16 query heads per key/value head.  Anything else on a GPU runs the
+    torch formulation there, with a one-time warning per reason; host devices and ``LJS_FUSED_DECODE=0`` run it
+    silently."""
     if not use_hip(ts[0]) or not fused_decode_enabled():
         return False
     hip = _hip()
     kc = cache[0]
     ok = hip.decode_supported(*ts) and hip._cache_supported(cache) and hip._lens_ok(lens, ts[0].shape[0]) \
-        and kc.shape[0] == ts[0].shape[0] and G <= hip.decode_max_group()
+        and kc.shape[0] == ts[0].shape[0] and G <= hip.decode_max_group() and kc.shape[-1] == ts[0].shape[-1] \
+        and hip.cache_op_supported(what, ts[0].shape[-1])
     if not ok:
         key = (what, ts[0].dtype, ts[0].shape[-1], kc.dtype, G > hip.decode_max_group())
         if key not in _WARNED_DECODE:
             _WARNED_DECODE.add(key)
             import warnings
-            warnings.warn(f"HIP {what} kernel takes bf16 (B, S, H, 64) shards and (B, cap, Hkv, 64) caches (bf16, or uint8 "
-                          f"with uint8 (B, cap, Hkv, 2) scales of even strides) with 16-byte aligned bases and strides, an "
+            dims = " or ".join(str(d) for d in (64, 128) if hip.cache_op_supported(what, d))
+            warnings.warn(f"HIP {what} kernel takes bf16 (B, S, H, D) shards and (B, cap, Hkv, D) caches of one head dim D = "
+                          f"{dims} (bf16, or uint8 with uint8 (B, cap, Hkv, D / 32) scales whose bases and strides are "
+                          f"multiples of D / 32) with 16-byte aligned bases and strides, an "
                           f"int32 lens and heads / kv_heads <= {hip.decode_max_group()}; {ts[0].dtype} {tuple(ts[0].shape)} "
                           f"strides {ts[0].stride()}, cache {kc.dtype} {tuple(kc.shape)} strides {kc.stride()} with heads / "
                           f"kv_heads = {G} runs the torch formulation on the GPU")
