@@ -432,11 +432,12 @@ int chunk_launch(const void* q, const LjsCache& c, void* o, void* lse, const voi
 
 }  // namespace
 
-// tests: force 64- or 128-row tiles; anything else restores the plan
+// tests: force 64- or 128-row tiles, here and in prefill128.hip (which reads it back); anything else restores the plan
 LJS_API int ljs_chunk_set_rows(int n) {
   g_chunk_rows = (n == 64 || n == 128) ? n : 0;
   return 0;
 }
+LJS_API int ljs_chunk_get_rows() { return g_chunk_rows; }
 
 // out = {rows, grid x, y, z} of (B, T, H, Hkv) on a device of `cus` compute units: pure
 LJS_API int ljs_chunk_plan(int B, int T, int H, int Hkv, int cus, int* out) {

@@ -100,6 +100,7 @@ _SIGS = {
                         c_float, c_int, c_void_p],
     "ljs_extend_max_positions": [],
     "ljs_attn_chunk": [c_void_p, _CP, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _LP, _LP, c_float, c_void_p],
+    "ljs_attn_chunk128": [c_void_p, _CP, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, _LP, _LP, c_float, c_void_p],
     "ljs_chunk_plan": [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_chunk_set_rows": [c_int],
     "ljs_decode_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
@@ -2666,8 +2667,14 @@ CACHE_OP_DIMS = {"append": (64, 128), "decode": (64, 128), "extend": (64, 128), 
 
 def cache_op_supported(op: str, dim: int) -> bool:
     """Whether the cached operation ``op`` (``"append"``, ``"decode"``, ``"extend"``, ``"chunk"``, or a public name of
-    one: ``"kv_append_q8"``, ``"attn_chunk"``) exists at head dim ``dim``."""
-    return dim in CACHE_OP_DIMS[op.replace("_q8", "").split("_")[-1]]
+    one: ``"kv_append_q8"``, ``"attn_chunk"``) is served at head dim ``dim``: :data:`CACHE_OP_DIMS`, and chunk at 128
+    (csrc/kernels/prefill128.hip) under ``LJS_ATTN_D128=1``, the switch of the MFMA attention kernels at 128, read at
+    every call."""
+    op = op.replace("_q8", "").split("_")[-1]
+    if op == "chunk" and dim == 128:
+        from .kernels import attn_d128_enabled
+        return attn_d128_enabled()
+    return dim in CACHE_OP_DIMS[op]
 
 
 def decode_max_group() -> int:
@@ -2790,6 +2797,18 @@ def _attn_chunk_desc(desc: _CacheDesc, q, o, lse, lens, scale: float) -> int:
                                 _L3(*o.stride()[:3]), float(scale), _stream(q))
 
 
+def _attn_chunk128_desc(desc: _CacheDesc, q, o, lse, lens, scale: float) -> int:
+    """:func:`_attn_chunk_desc` at head dim 128: one ``ljs_attn_chunk128`` launch."""
+    B, T, H, _ = q.shape
+    return lib().ljs_attn_chunk128(_p(q), ctypes.byref(desc), _p(o), _p(lse), _p(lens), B, T, H, _L3(*q.stride()[:3]),
+                                   _L3(*o.stride()[:3]), float(scale), _stream(q))
+
+
+def _chunk_entry(q):
+    """The chunk entry of q's width: ``(launch, C name)``."""
+    return (_attn_chunk128_desc, "ljs_attn_chunk128") if q.shape[-1] == 128 else (_attn_chunk_desc, "ljs_attn_chunk")
+
+
 def cache_append(what: str, k, v, cache, lens, q, theta):
     """The checked append behind :func:`kv_append` / :func:`kv_append_q8` (``what``: the name refusals carry)."""
     kc = cache[0]
@@ -2830,7 +2849,7 @@ def _decode_ws(dev: torch.device, floats: int) -> torch.Tensor:
 
 def cache_attend(what: str, q, cache, lens, scale: float, max_t: Optional[int], extra: int = 1):
     """The checked call behind the ``attn_*`` functions below (``what``: the name refusals carry).  Attention of ``q`` over ``cache``: by ``ljs_attn_decode`` for up to ``max_t`` positions (with its workspace), by
-    ``ljs_attn_chunk`` when ``max_t`` is None.  ``(o`` (B, T, H, D), ``lse2`` (B, H, T)``)``."""
+    ``ljs_attn_chunk`` (``ljs_attn_chunk128`` at head dim 128) when ``max_t`` is None.  ``(o`` (B, T, H, D), ``lse2`` (B, H, T)``)``."""
     B, T, H, D = q.shape
     kc = cache[0]
     ok = decode_supported(q) and kc.dim() == 4 and kc.shape[0] == B and lens is not None and _lens_ok(lens, B) \
@@ -2843,7 +2862,8 @@ def cache_attend(what: str, q, cache, lens, scale: float, max_t: Optional[int], 
     o = torch.empty((B, T, H, D), dtype=torch.bfloat16, device=q.device)
     if max_t is None:
         lse = torch.empty((B, T, H), dtype=torch.float32, device=q.device)
-        _ck(_attn_chunk_desc(desc, q, o, lse, lens, scale), "ljs_attn_chunk")
+        launch, name = _chunk_entry(q)
+        _ck(launch(desc, q, o, lse, lens, scale), name)
         return o, lse.permute(0, 2, 1)
     splits, _ = _decode_launch_plan(B, kc.shape[2], kc.shape[1], D)
     ws = _decode_ws(q.device, B * T * H * splits * decode_part_floats(D)) if splits > 1 else None
@@ -2932,9 +2952,10 @@ def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     return cache_attend("attn_extend_q8", q, (kc, vc, kcs, vcs), lens, scale, extend_max_positions())
 
 
-# ---- chunked prefill: T >= 1 query positions per sequence over the cache by MFMA (csrc/kernels/prefill.hip)
+# ---- chunked prefill: T >= 1 query positions per sequence over the cache by MFMA (csrc/kernels/prefill.hip at head
+# dim 64, prefill128.hip at 128 under LJS_ATTN_D128=1)
 def set_chunk_rows(n: Optional[int]) -> None:
-    """Tests: force ``attn_chunk``'s row tile to 64 or 128 rows; None or 0 restores :func:`plan_chunk`."""
+    """Tests: force ``attn_chunk``'s row tile to 64 or 128 rows, at both head dims; None or 0 restores :func:`plan_chunk`."""
     lib().ljs_chunk_set_rows(int(n or 0))
 
 
@@ -2942,7 +2963,7 @@ def plan_chunk(B: int, T: int, H: int, Hkv: int, cus: Optional[int] = None):
     """``(rows, grid)`` of ``attn_chunk`` for ``B`` sequences of ``T`` positions, ``H`` query and ``Hkv`` key/value heads on
     a device of ``cus`` compute units (default: the current device's): 128 rows ``(t, g)`` per block, or 64 when the
     ``T * H / Hkv`` rows of a group fit one such tile or 128-row tiles would leave compute units idle; the grid is ``(row
-    tiles, Hkv, B)``.  Pure: it depends on nothing else, the lengths least of all."""
+    tiles, Hkv, B)``.  Pure: it depends on nothing else, the lengths least of all, nor on the head dim."""
     out = (c_int * 4)()
     rc = lib().ljs_chunk_plan(int(B), int(T), int(H), int(Hkv), int(cus if cus is not None else _cus()), out)
     if rc != 0:
@@ -2951,9 +2972,9 @@ def plan_chunk(B: int, T: int, H: int, Hkv: int, cus: Optional[int] = None):
 
 
 def chunk_supported(q, kc, vc, lens, kcs=None, vcs=None) -> bool:
-    """Whether prefill.hip takes these operands as they are: bf16 ``(B, T, H, 64)`` q, caches ``(B, cap, Hkv, 64)`` in bf16
-    (or uint8 with ``(B, cap, Hkv, 2)`` uint8 scales), 16-byte aligned bases and strides, an int32 ``[B]`` lens,
-    ``H % Hkv == 0`` and ``H / Hkv <= 16``."""
+    """Whether prefill.hip / prefill128.hip take these operands as they are: bf16 ``(B, T, H, D)`` q, caches ``(B, cap, Hkv,
+    D)`` in bf16 (or uint8 with ``(B, cap, Hkv, D / 32)`` uint8 scales), ``D`` 64 (or 128 under ``LJS_ATTN_D128=1``), 16-byte
+    aligned bases and strides, an int32 ``[B]`` lens, ``H % Hkv == 0`` and ``H / Hkv <= 16``."""
     if not decode_supported(q) or kc.dim() != 4 or kc.shape[0] != q.shape[0] or lens is None or not _lens_ok(lens, q.shape[0]) \
             or kc.shape[3] != q.shape[3] or not cache_op_supported("chunk", q.shape[3]):
         return False
@@ -2962,19 +2983,20 @@ def chunk_supported(q, kc, vc, lens, kcs=None, vcs=None) -> bool:
 
 
 def attn_chunk_raw(q, kc, vc, o, lse, lens, scale: float) -> int:
-    """:func:`_attn_chunk_desc` over a bf16 cache."""
-    return _attn_chunk_desc(_cache_desc(CACHE_BF16, kc, vc), q, o, lse, lens, scale)
+    """:func:`_attn_chunk_desc` (q of width 128: :func:`_attn_chunk128_desc`) over a bf16 cache."""
+    return _chunk_entry(q)[0](_cache_desc(CACHE_BF16, kc, vc), q, o, lse, lens, scale)
 
 
 def attn_chunk_q8_raw(q, kc, vc, kcs, vcs, o, lse, lens, scale: float) -> int:
-    """:func:`_attn_chunk_desc` over an MX-fp8 cache (a None scale is refused)."""
-    return _attn_chunk_desc(_cache_desc(CACHE_MX8, kc, vc, kcs, vcs), q, o, lse, lens, scale)
+    """:func:`attn_chunk_raw` over an MX-fp8 cache (a None scale is refused)."""
+    return _chunk_entry(q)[0](_cache_desc(CACHE_MX8, kc, vc, kcs, vcs), q, o, lse, lens, scale)
 
 
 def attn_chunk(q, kc, vc, lens, scale: float):
-    """Attention of ``q`` (B, T, H, 64), any ``T >= 1`` positions that a :func:`kv_append` has just written at rows ``lens[b]
+    """Attention of ``q`` (B, T, H, D), any ``T >= 1`` positions that a :func:`kv_append` has just written at rows ``lens[b]
     .. lens[b] + T - 1``, over the caches: row ``(b, t, h)`` attends to rows ``[0, clamp(lens[b] + t + 1, 0, cap))``.  One MFMA
-    launch (``attn_chunk<R128>`` / ``<R64>``), no workspace.  ``(o`` bf16 (B, T, H, 64), ``lse2`` f32 (B, H, T)``)``."""
+    launch (``attn_chunk<R128>`` / ``<R64>`` at ``D`` = 64; ``attn_chunk128<..>`` at 128, under ``LJS_ATTN_D128=1`` only), no
+    workspace.  ``(o`` bf16 (B, T, H, D), ``lse2`` f32 (B, H, T)``)``."""
     return cache_attend("attn_chunk", q, (kc, vc), lens, scale, None)
 
 

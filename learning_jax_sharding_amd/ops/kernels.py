@@ -556,9 +556,9 @@ _WARNED_DH = set()
 
 
 def attn_d128_enabled() -> bool:
-    # LJS_ATTN_D128=1: head_dim 128 attention runs the HIP kernels of csrc/kernels/attention128.hip
-    # (read at every call); default: the torch formulation with its one-time warning, as for every
-    # head_dim other than 64
+    # LJS_ATTN_D128=1: the MFMA attention kernels at head_dim 128 -- training (csrc/kernels/attention128.hip) and
+    # chunked prefill over the cache (prefill128.hip) -- read at every call; default: the torch formulation with
+    # its one-time warning, as for every head_dim other than 64
     return os.environ.get("LJS_ATTN_D128", "0") == "1"
 
 
@@ -792,7 +792,7 @@ _WARNED_DECODE = set()
 def _hip_cache(what: str, ts, cache, lens, G: int = 1) -> bool:
     """Whether decode.hip / prefill.hip take these shards: bf16 ``(B, S, H, D)`` GPU tensors ``ts`` and a cache
     ``hip._cache_supported`` accepts, all of one head dim ``D`` at which ``hip.cache_op_supported`` has the operation
-    (append, decode and extend at 64 and 128, chunk at 64), with 16-byte aligned bases and strides (multiples of D / 32
+    (append, decode and extend at 64 and 128, chunk at 64 and, under ``LJS_ATTN_D128=1``, at 128), with 16-byte aligned bases and strides (multiples of D / 32
     for the scales), an int32 lens and at most 16 query heads per key/value head.  Anything else on a GPU runs the
     torch formulation there, with a one-time warning per reason; host devices and ``LJS_FUSED_DECODE=0`` run it
     silently."""
@@ -963,7 +963,7 @@ def attn_extend_q8(q, kc, vc, kcs, vcs, lens, scale: float):
     return cache_attend(q, (kc, vc, kcs, vcs), lens, scale, "extend")
 
 
-# ---- chunked prefill (csrc/kernels/prefill.hip, attn_chunk): attn_extend's definition for any T >= 1, stated as one
+# ---- chunked prefill (csrc/kernels/prefill.hip and prefill128.hip, attn_chunk): attn_extend's definition for any T >= 1, stated as one
 # masked einsum, and served on a GPU by one MFMA launch over the cache buffers.
 def attn_chunk_reference(q, kc, vc, lens, scale: float):
     """Plain torch attention of q (B, T, H, D) over a cache kc / vc (B, cap, Hkv, D) after an append of the T positions at
