@@ -218,7 +218,7 @@ def _draft_request(model, draft, draft_tokens, key, eos_id):
 
 
 def _generate_speculative(model, params, draft, dparams, k: int, ids, plens, max_new_tokens: int, cache, dcache, pl,
-                          capture, stop_poll: int):
+                          capture, stop_poll: int, weight_quant=None):
     """Greedy speculative decoding (``generate``'s ``draft=``): ``(tokens [batch, max_new_tokens], mean tokens per round)``.
 
     One round, captured once, no host read inside.  State per sequence: ``pair``, the last two tokens of the sequence
@@ -270,7 +270,8 @@ def _generate_speculative(model, params, draft, dparams, k: int, ids, plens, max
 
     rnd_j = jit(rnd, donate_argnums=(2, 3, 4), capture=capture)
     with torch.no_grad():
-        tok, cache, dcache = prefill(params, dparams, ids, cache, dcache, pl)
+        with _lin.weight_quant(weight_quant):
+            tok, cache, dcache = prefill(params, dparams, ids, cache, dcache, pl)
         first = tok.to_torch().reshape(B, 1).long()
         if max_new_tokens == 1:
             return first, 0.0
@@ -288,7 +289,8 @@ def _generate_speculative(model, params, draft, dparams, k: int, ids, plens, max
         st = (pair, toks, cnt, n_out)
         kept = []
         for r in range(1, max_new_tokens):             # a round gives every unfinished sequence at least one token
-            st, cache, dcache = rnd_j(params, dparams, st, cache, dcache)
+            with _lin.weight_quant(weight_quant):
+                st, cache, dcache = rnd_j(params, dparams, st, cache, dcache)
             kept.append(({d: t.clone() for d, t in st[1].local.items()}, {d: t.clone() for d, t in st[2].local.items()}))
             # outside the graph: one host read of the counts every stop_poll rounds
             if stop_poll and r % int(stop_poll) == 0 and all(
@@ -353,7 +355,8 @@ def _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, ke
 
     step_j = jit(step, donate_argnums=(1, 2), capture=capture)
     with torch.no_grad():
-        tok, cache = prefill(params, ids, cache, pl)
+        with _lin.weight_quant(_lin.prefill_weight_quant(weight_quant)):
+            tok, cache = prefill(params, ids, cache, pl)
         st = (tok, done) if eos else (tok,)
         kept = [{d: t.clone() for d, t in tok.local.items()}]
         for s in range(1, max_new_tokens):
@@ -424,9 +427,15 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
     layers read MX-fp8 weights (``skinny_mx<`` launches in place of ``skinny<``, the launch count of a step unchanged)
     wherever ``K % 128 == 0`` and the weight is ``shadow.mx_eligible``.  The prefill has more than 16 rows, runs on the tile
     GEMMs and reads bf16 weights, so the first token has seen bf16 weights and the later ones fp8 weights.  It composes
-    with ``cache_quant``, ``key``, the filters and stop tokens; any other value, and ``weight_quant`` together with ``draft``
+    with ``cache_quant``, ``key``, the filters and stop tokens; any other value, and ``"mxfp8"`` together with ``draft``
     (the verification call has more than 16 rows and would read other weights than the single steps), raise
     ``ValueError`` before any launch.
+
+    ``weight_quant="mxfp8-all"``: the prefill -- the single call or every ``prefill_chunk`` call -- runs under the mode as well as
+    every step, and calls of more than 16 rows read the same MX-fp8 shadows on the W8A16 tile GEMM (one ``gemm_w8<``
+    launch where the default run has a bf16 tile GEMM): every generated token, the first included, has seen the same fp8
+    weights.  It goes with ``draft=``: the draft's calls and the target's verification call run under it, so the tokens are
+    plain greedy ``generate``'s under the same mode.
 
     ``draft=(draft_model, draft_params)``: greedy speculative decoding.  Per round the draft (a cheaper model of the same
     vocabulary, with a cache and a prefill of its own) proposes ``draft_tokens`` tokens and the target checks them in ONE
@@ -445,11 +454,13 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
         raise ValueError(f"generate: max_new_tokens must be positive, got {max_new_tokens}")
     if cache_quant not in (None, QUANT_MXFP8):
         raise ValueError(f"generate: cache_quant must be None or {QUANT_MXFP8!r}, got {cache_quant!r}")
-    if weight_quant not in (None, _lin.WEIGHT_QUANT_MXFP8):
-        raise ValueError(f"generate: weight_quant must be None or {_lin.WEIGHT_QUANT_MXFP8!r}, got {weight_quant!r}")
-    if weight_quant is not None and draft is not None:
-        raise ValueError("generate: weight_quant does not go with draft= (the verification call has more than 16 rows and "
-                         "would read bf16 weights where the single steps read fp8 ones)")
+    if weight_quant not in (None,) + _lin.WEIGHT_QUANT_MODES:
+        raise ValueError(f"generate: weight_quant must be None, {_lin.WEIGHT_QUANT_MXFP8!r} or "
+                         f"{_lin.WEIGHT_QUANT_MXFP8_ALL!r}, got {weight_quant!r}")
+    if weight_quant == _lin.WEIGHT_QUANT_MXFP8 and draft is not None:
+        raise ValueError(f"generate: weight_quant={_lin.WEIGHT_QUANT_MXFP8!r} does not go with draft= (the verification call "
+                         "has more than 16 rows and would read bf16 weights where the single steps read fp8 ones); "
+                         f"{_lin.WEIGHT_QUANT_MXFP8_ALL!r} does")
     if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or int(prefill_chunk) != prefill_chunk
                                       or prefill_chunk < 1):
         raise ValueError(f"generate: prefill_chunk must be a positive int or None, got {prefill_chunk!r}")
@@ -477,7 +488,7 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
     if spec:
         dcache = spec[0].init_cache(B, cap, sharding=cache_sharding, **({"quant": cache_quant} if cache_quant else {}))
         out, mean = _generate_speculative(model, params, spec[0], spec[1], spec[2], ids, plens, max_new_tokens, cache,
-                                          dcache, pl, capture, stop_poll)
+                                          dcache, pl, capture, stop_poll, weight_quant)
         return (out, torch.full((B,), max_new_tokens, dtype=torch.long), mean) if return_lens else out
     if key is not None or eos:
         out = _generate_sampled(model, params, ids, max_new_tokens, cache, pl, capture, key, temperature, top_k, top_p,
@@ -501,7 +512,8 @@ def generate(model, params, ids: ShardedArray, max_new_tokens: int, prompt_lens=
 
     step_j = jit(step, donate_argnums=(1, 2), capture=capture)
     with torch.no_grad():
-        tok, cache = prefill(params, ids, cache, pl)
+        with _lin.weight_quant(_lin.prefill_weight_quant(weight_quant)):
+            tok, cache = prefill(params, ids, cache, pl)
         out = [tok.to_torch().clone()] if max_new_tokens == 1 else []
         if max_new_tokens > 1:
             # the step's token buffers are rewritten at every step: keep a copy of each, on the devices

@@ -22,7 +22,7 @@ __all__ = ["lib", "available", "gemm", "bmm_nt", "linear", "attention", "cast", 
            "embed_grad", "rope", "swiglu", "kv_append", "attn_decode", "kv_append_q8", "attn_decode_q8", "plan_decode",
            "lens_add", "attn_extend", "attn_extend_q8", "attn_chunk", "attn_chunk_q8", "plan_chunk", "skinny",
            "skinny_plan", "skinny_supported", "set_skinny_waves", "skinny_mx", "skinny_mx_raw", "skinny_mx_plan",
-           "skinny_mx_supported"]
+           "skinny_mx_supported", "gemm_w8", "gemm_w8_raw", "gemm_w8_plan", "gemm_w8_supported", "set_gemm_w8_rows"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LJS_KERNELS_LIB: an alternative build of the library (A/B timing of kernel variants)
@@ -113,6 +113,10 @@ _SIGS = {
     "ljs_skinny_mx_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
     "ljs_skinny_mx": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long,
                       c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_void_p],
+    "ljs_gemm_w8_set_rows": [c_int],
+    "ljs_gemm_w8_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)],
+    "ljs_gemm_w8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long,
+                    c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_void_p],
     "ljs_decode_key_tile": [c_int],
     "ljs_decode_part_floats": [c_int],
     "ljs_decode_max_group": [],
@@ -248,7 +252,8 @@ def last_launch(copies: bool = False) -> dict:
     ``quant_mx_cols<generic>``, ``quant_mx_both<bf16>`` / ``quant_mx_both<f32>``, ``bcast_scalar_mx`` / ``bcast_scalar_mx2``,
     ``grad_sumsq``, ``step_hyper``, ``adam_f32``, ``adam_multi<32>`` / ``adam_multi_dyn<32>`` (the launch's tile height), ``kv_append<rot,q>`` / ``kv_append<rot>`` / ``kv_append<copy>``,
     ``attn_decode<G4>``, ``kv_append<rot,q,mx8>``, ``attn_decode<G4,mx8>`` (an MX-fp8 cache), ``attn_extend<G4,P2>`` / ``attn_extend<G4,P2,mx8>`` (heads per group, positions per block), ``decode_merge``, ``lens_add``, ``skinny<8,bf16,bias,relu,res>`` (waves per block, output type and
-    the epilogue parts present; ``skinny_mx<...>`` likewise on MX-fp8 weights)),
+    the epilogue parts present; ``skinny_mx<...>`` likewise on MX-fp8 weights), ``gemm_w8<R128,bf16,bias,relu,res>`` (the
+    W8A16 tile GEMM: rows of the block tile, output type, epilogue parts),
     the elementwise, reduction and loss kernels ``transpose_bf16``,
     ``sum_n<f32>`` / ``sum_n<bf16>``, ``rows_sum_f32``, ``sum_all<bf16,ticket>`` / ``sum_all<f32,ticket>`` (16-byte
     aligned input) and ``sum_all<bf16,atomic>`` / ``sum_all<f32,atomic>``, ``sum_partials``, ``colsum<bcast>`` /
@@ -1831,7 +1836,9 @@ def linear(x: torch.Tensor, ws: List[torch.Tensor], b: Optional[torch.Tensor], c
     # (at most 16 rows without a backward: the skinny GEMM takes any row count, so M = 1 .. 7 and other
     # non-multiples of 8 do not leave through the padded path)
     if compute_dtype == torch.bfloat16:
-        sk = _lin.skinny_route(x, ws, b)       # (False at once with grad enabled; evaluated once per call)
+        # (False at once with grad enabled; evaluated once per call.  gemm_w8_route: more than 16 rows under
+        # weight_quant("mxfp8-all"), any row count, so those do not leave through the padded path either)
+        sk = _lin.skinny_route(x, ws, b) or _lin.gemm_w8_route(x, ws, b)
         if sk or _lin.supported(x, ws, b):
             return _lin.linear(x, list(ws), b, relu, out_dtype, residual=residual, skinny=sk)
     from . import shadow
@@ -3153,6 +3160,77 @@ def skinny_mx(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, out: torch.Tens
                                   f"f32 output; got M={M} N={N} K={K} lda={lda} ldq={ldq} lds={lds} ldc={ldc} x {x.dtype} "
                                   f"q {q.dtype} s {s.dtype} out {out.dtype}")
     _ck(skinny_mx_raw(x, q, s, out, M, N, K, lda, ldc, bias, relu, res, res_ld, ldq, lds), "ljs_skinny_mx")
+
+
+# ---- the same product for any M >= 1 (csrc/kernels/gemm_w8.hip): a tile GEMM whose B operand is dequantised on its
+# way into LDS; skinny_mx's operands, argument order and epilogue
+GEMM_W8_ROWS = (64, 128)            # the block tiles' rows
+
+
+def set_gemm_w8_rows(n: Optional[int]) -> None:
+    """Tests: force ``gemm_w8``'s block tile to ``n`` rows (one of :data:`GEMM_W8_ROWS`); None or 0 restores
+    :func:`gemm_w8_plan`."""
+    if lib().ljs_gemm_w8_set_rows(int(n or 0)) != 0:
+        raise ValueError(f"set_gemm_w8_rows: {n} is not one of {GEMM_W8_ROWS}")
+
+
+def gemm_w8_plan(M: int, N: int, K: int, cus: int = 256):
+    """``(rows, blocks)`` of :func:`gemm_w8` on a device of ``cus`` compute units (``ljs_gemm_w8_plan``: needs the library,
+    not a GPU): 64-row tiles when ``M <= 64`` or when 128-row tiles would leave compute units without a block, else
+    128; one block per ``rows x 128`` output tile.  Pure.  ValueError outside ``M >= 1, K % 128 == 0, N % 8 == 0``."""
+    out = (c_int * 2)()
+    if lib().ljs_gemm_w8_plan(int(M), int(N), int(K), int(cus), out) != 0:
+        raise ValueError(f"gemm_w8_plan: M={M}, N={N}, K={K}, cus={cus}: M >= 1, K % 128 == 0, N % 8 == 0 and cus >= 1 are "
+                         "required")
+    return int(out[0]), int(out[1])
+
+
+def gemm_w8_supported(M: int, N: int, K: int, lda: int, ldq: int, lds: int, ldc: int, out_dtype: torch.dtype,
+                      x_addr: int = 0, q_addr: int = 0, s_addr: int = 0, out_addr: int = 0,
+                      bias_dtype: Optional[torch.dtype] = None, bias_addr: int = 0,
+                      res_dtype: Optional[torch.dtype] = None, res_ld: int = 0, res_addr: int = 0,
+                      x_dtype: torch.dtype = torch.bfloat16, q_dtype: torch.dtype = torch.uint8,
+                      s_dtype: torch.dtype = torch.uint8) -> bool:
+    """``ljs_gemm_w8``'s gate as a pure predicate: :func:`skinny_mx_supported`'s rules for any ``M >= 1``, and every byte
+    offset of an operand within 31 bits (x counted up to the last row of its last 128-row tile)."""
+    if M < 1:
+        return False
+    esz = lambda d: 4 if d == torch.float32 else 2      # noqa: E731
+    if (((M + 127) // 128 * 128 * lda + K) * 2 >= 2 ** 31 or N * ldq + K >= 2 ** 31 or (M * ldc + N) * esz(out_dtype) >= 2 ** 31
+            or (res_dtype is not None and (M * res_ld + N) * esz(res_dtype) >= 2 ** 31)):
+        return False
+    return skinny_mx_supported(1, N, K, lda, ldq, lds, ldc, out_dtype, x_addr, q_addr, s_addr, out_addr, bias_dtype,
+                               bias_addr, res_dtype, res_ld, res_addr, x_dtype, q_dtype, s_dtype)
+
+
+def gemm_w8_raw(x, q, s, out, M: int, N: int, K: int, lda: int, ldc: int, bias=None, relu: bool = False, res=None,
+                res_ld: int = 0, ldq: Optional[int] = None, lds: Optional[int] = None) -> int:
+    """One ``ljs_gemm_w8`` call on the operands as they are (any of them may be None: a null operand); returns the
+    launcher's code (non-zero: rejected, nothing launched or recorded) instead of raising."""
+    f32 = torch.float32
+    return lib().ljs_gemm_w8(_p(x), _p(q), _p(s), _p(out), _p(bias), _p(res), int(M), int(N), int(K), int(lda),
+                             int(K if ldq is None else ldq), int(K // 32 if lds is None else lds), int(ldc),
+                             int(res_ld), int(out.dtype == f32), int(bias is not None and bias.dtype == f32),
+                             int(res is not None and res.dtype == f32), int(bool(relu)), _stream(out))
+
+
+def gemm_w8(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, out: torch.Tensor, M: int, N: int, K: int, lda: int,
+            ldc: int, bias: Optional[torch.Tensor] = None, relu: bool = False, res: Optional[torch.Tensor] = None,
+            res_ld: int = 0, ldq: Optional[int] = None, lds: Optional[int] = None) -> None:
+    """:func:`skinny_mx`'s product for any ``M >= 1`` on the W8A16 tile GEMM (:func:`~.kernels.skinny_mx_reference` states it
+    in torch): one ``gemm_w8<`` launch, deterministic, no workspace; the bits of :func:`gemm` at ``tile=1282`` on the
+    dequantised weight.  Raises for anything :func:`gemm_w8_supported` refuses."""
+    ldq, lds = K if ldq is None else ldq, K // 32 if lds is None else lds
+    ok = all(t is None or t.is_cuda for t in (x, q, s, out, bias, res)) and gemm_w8_supported(
+        M, N, K, lda, ldq, lds, ldc, out.dtype, x.data_ptr(), q.data_ptr(), s.data_ptr(), out.data_ptr(),
+        None if bias is None else bias.dtype, 0 if bias is None else bias.data_ptr(),
+        None if res is None else res.dtype, res_ld, 0 if res is None else res.data_ptr(), x.dtype, q.dtype, s.dtype)
+    if not ok:
+        raise NotImplementedError(f"gemm_w8 kernel: bf16 GPU x [M >= 1][K % 128 == 0], uint8 codes [N % 8 == 0][K] with "
+                                  f"16-byte aligned rows and uint8 scales [N][K / 32] with 4-byte aligned rows, a bf16 / "
+                                  f"f32 output; got M={M} N={N} K={K} lda={lda} ldq={ldq} lds={lds} ldc={ldc} x {x.dtype} "
+                                  f"q {q.dtype} s {s.dtype} out {out.dtype}")
+    _ck(gemm_w8_raw(x, q, s, out, M, N, K, lda, ldc, bias, relu, res, res_ld, ldq, lds), "ljs_gemm_w8")
 
 
 # ============================================================================ optimizer

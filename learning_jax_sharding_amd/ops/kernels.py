@@ -436,7 +436,9 @@ def dot_general(a: torch.Tensor, b: torch.Tensor, lc, rc, lb, rb, out_dtype: tor
 def skinny_mx_reference(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, bias: Optional[torch.Tensor] = None,
                         relu: bool = False, res: Optional[torch.Tensor] = None,
                         out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
-    """Plain torch statement of ``hip.skinny_mx`` (weight-only MX-fp8, W8A16): ``y = epi(bf16(x) @ W_hat^T)`` with f32
+    """Plain torch statement of ``hip.skinny_mx`` (``M <= 16``) and of ``hip.gemm_w8`` (the W8A16 tile GEMM: the same product
+    for any ``M``, what a prefill or a verification call runs under ``weight_quant("mxfp8-all")``); nothing here depends on
+    ``M``.  Weight-only MX-fp8, W8A16: ``y = epi(bf16(x) @ W_hat^T)`` with f32
     accumulation, ``W_hat[n][k] = e4m3(q[n][k]) * 2^(s[n][k // 32] - 127)`` from the uint8 codes ``q [N][K]`` and scale bytes
     ``s [N][K / 32]`` (an exact bf16 value for every scale the quantiser produces from finite weights); x ``[M][K]`` is
     rounded to bf16 and never quantised.  ``epi``, in this order: ``+ bias`` in f32, ReLU, one rounding to ``out_dtype``,

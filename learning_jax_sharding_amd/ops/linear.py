@@ -1055,6 +1055,13 @@ def skinny_route(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
 
 
 WEIGHT_QUANT_MXFP8 = "mxfp8"
+WEIGHT_QUANT_MXFP8_ALL = "mxfp8-all"
+WEIGHT_QUANT_MODES = (WEIGHT_QUANT_MXFP8, WEIGHT_QUANT_MXFP8_ALL)
+
+
+def prefill_weight_quant(mode: Optional[str]) -> Optional[str]:
+    """The mode a prefill runs under when the steps run under ``mode``: only "mxfp8-all" reaches calls of more than 16 rows."""
+    return mode if mode == WEIGHT_QUANT_MXFP8_ALL else None
 
 
 @contextlib.contextmanager
@@ -1065,9 +1072,16 @@ def weight_quant(mode: Optional[str]):
     of the ``skinny<`` one, x still bf16 (W8A16, ``kernels.skinny_mx_reference``).  Everything else is unchanged,
     launch for launch: more than 16 rows, grad enabled, other K, ineligible weights.  Host devices run the
     reference on ``fp8.quantize_mx_ref`` of the bf16 transposed weight for the same calls, and so does a GPU under
-    ``LJS_SKINNY_MX=0``, on the shadows.  ``jit`` keys its traced and captured steps by the mode.  ``None``: off."""
-    if mode not in (None, WEIGHT_QUANT_MXFP8):
-        raise ValueError(f"weight_quant: the mode must be None or {WEIGHT_QUANT_MXFP8!r}, got {mode!r}")
+    ``LJS_SKINNY_MX=0``, on the shadows.  ``jit`` keys its traced and captured steps by the mode.  ``None``: off.
+
+    ``"mxfp8-all"``: the same, and a call of MORE than 16 rows (:func:`gemm_w8_route`: no grad, a GPU activation in f32 or
+    bf16, weights the fused path takes, ``K % 128 == 0``, MX-eligible weights) runs one ``gemm_w8<`` launch
+    (``hip.gemm_w8``, the W8A16 tile GEMM) on the same "QT" shadows, so a prefill and a verification call read the
+    weights the single steps read.  Calls of at most 16 rows go where ``"mxfp8"`` sends them; everything else keeps its
+    launches.  Host devices run the reference for the same calls; a GPU under ``LJS_GEMM_W8=0`` runs it on the shadows."""
+    if mode not in (None,) + WEIGHT_QUANT_MODES:
+        raise ValueError(f"weight_quant: the mode must be None, {WEIGHT_QUANT_MXFP8!r} or {WEIGHT_QUANT_MXFP8_ALL!r}, "
+                         f"got {mode!r}")
     with _state.weight_quant_mode(mode):
         yield
 
@@ -1085,14 +1099,33 @@ def _mx_weight_ok(w: torch.Tensor) -> bool:
 def skinny_mx_weights(x: torch.Tensor, ws: Sequence[torch.Tensor]) -> bool:
     """Whether a call :func:`skinny_route` accepts reads MX-fp8 weights: the :func:`weight_quant` mode is on, ``K % 128
     == 0`` and every weight has "QT" shadows (MX proxies: one weight per call, they hold buffers of their own)."""
-    return (_state.weight_quant() == WEIGHT_QUANT_MXFP8 and x.shape[-1] % 128 == 0 and all(_mx_weight_ok(w) for w in ws)
+    return (_state.weight_quant() in WEIGHT_QUANT_MODES and x.shape[-1] % 128 == 0 and all(_mx_weight_ok(w) for w in ws)
             and (len(ws) == 1 or not any(shadow.is_proxy(w) for w in ws)))
 
 
+def _many_rows_mx(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
+    # what "mxfp8-all" adds, on any device: more than 16 rows, no grad, MX-eligible weights the fused path takes
+    if _state.weight_quant() != WEIGHT_QUANT_MXFP8_ALL or torch.is_grad_enabled():
+        return False
+    K = x.shape[-1]
+    return (x.numel() // max(1, K) > hip.SKINNY_MAX_M and x.dtype in (torch.float32, torch.bfloat16)
+            and weights_supported(x, ws, b) and skinny_mx_weights(x, ws))
+
+
+def gemm_w8_route(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
+    """Whether :func:`linear` runs this call on the W8A16 tile GEMM (hip.gemm_w8): the mode is "mxfp8-all", no gradient is
+    being recorded, more than 16 rows of a GPU activation in f32 or bf16 (read through ``reshape(-1, K)``: any row order),
+    weights the fused path takes, ``K % 128 == 0`` and MX-eligible weights (:func:`skinny_mx_weights`)."""
+    return x.is_cuda and _many_rows_mx(x, ws, b)
+
+
 def skinny_mx_host_route(x: torch.Tensor, ws: Sequence[torch.Tensor], b) -> bool:
-    """:func:`skinny_route` and :func:`skinny_mx_weights` for a host activation: what a GPU would run on ``skinny_mx<``."""
+    """:func:`skinny_route` and :func:`skinny_mx_weights` for a host activation: what a GPU would run on ``skinny_mx<``, and
+    under "mxfp8-all" what it would run on ``gemm_w8<`` (:func:`gemm_w8_route`)."""
     K = x.shape[-1]
     M = x.numel() // max(1, K)
+    if not x.is_cuda and _many_rows_mx(x, ws, b):
+        return True
     return (not torch.is_grad_enabled() and 1 <= M <= hip.SKINNY_MAX_M and not x.is_cuda
             and x.dtype in (torch.float32, torch.bfloat16) and weights_supported(x, ws, b) and skinny_enabled()
             and x.is_contiguous() and skinny_mx_weights(x, ws))
@@ -1104,14 +1137,23 @@ def skinny_mx_kernel_enabled() -> bool:
     return os.environ.get("LJS_SKINNY_MX", "1") != "0"
 
 
+def gemm_w8_kernel_enabled() -> bool:
+    # LJS_GEMM_W8=0: under weight_quant("mxfp8-all") a GPU runs kernels.skinny_mx_reference on the same shadows
+    # instead of the gemm_w8 kernel for the calls of more than 16 rows (an A/B baseline and an escape hatch)
+    return os.environ.get("LJS_GEMM_W8", "1") != "0"
+
+
 def _skinny_mx_launch(xb, ws, out, M, N, K, bias, relu, r2, r_ld) -> None:
-    """``out = epi(xb @ W_hat^T)`` on the MX-fp8 weights of ``ws``: the kernel, or its reference."""
+    """``out = epi(xb @ W_hat^T)`` on the MX-fp8 weights of ``ws``: the kernel M chooses (``skinny_mx<`` up to 16 rows,
+    ``gemm_w8<`` above), or their reference."""
     from . import fp8, kernels
     nw = len(ws)
     if xb.is_cuda:
         q, s = shadow.get_mx(ws[0], "QT") if nw == 1 else shadow.get_mx_stacked(ws)
-        if skinny_mx_kernel_enabled():
-            hip.skinny_mx(xb, q, s, out, M, nw * N, K, K, nw * N, bias=bias, relu=relu, res=r2, res_ld=r_ld)
+        many = M > hip.SKINNY_MAX_M
+        if gemm_w8_kernel_enabled() if many else skinny_mx_kernel_enabled():
+            (hip.gemm_w8 if many else hip.skinny_mx)(xb, q, s, out, M, nw * N, K, K, nw * N, bias=bias, relu=relu,
+                                                     res=r2, res_ld=r_ld)
             return
     else:
         wt = torch.cat([w.to(torch.bfloat16).t() for w in ws]).contiguous()       # the "T" shadows' values
@@ -1167,8 +1209,8 @@ def _linear_skinny(x, ws, b, relu, out_dtype, res) -> List[torch.Tensor]:
 def linear(x: torch.Tensor, ws: List[torch.Tensor], b: Optional[torch.Tensor], relu: bool,
            out_dtype: torch.dtype, residual: Optional[torch.Tensor] = None,
            skinny: Optional[bool] = None) -> List[torch.Tensor]:
-    """``skinny``: :func:`skinny_route` of this call when the caller has evaluated it already."""
-    if skinny_route(x, ws, b) if skinny is None else skinny:
+    """``skinny``: :func:`skinny_route` (or :func:`gemm_w8_route`) of this call when the caller has evaluated it already."""
+    if (skinny_route(x, ws, b) or gemm_w8_route(x, ws, b)) if skinny is None else skinny:
         if residual is not None and (relu or len(ws) != 1):
             ys = _linear_skinny(x, ws, b, relu, out_dtype, None)
             return [ys[0] + residual.to(ys[0].dtype)] + ys[1:]

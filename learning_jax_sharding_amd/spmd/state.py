@@ -62,7 +62,7 @@ def is_donated(t) -> bool:
 
 
 def weight_quant():
-    """The weight-quantisation mode of the dense layers run now (``ops.linear.weight_quant``): None or "mxfp8".  It
+    """The weight-quantisation mode of the dense layers run now (``ops.linear.weight_quant``): None, "mxfp8" or "mxfp8-all".  It
     changes which kernels a function launches, so ``jit`` keys its traced and captured steps by it."""
     return getattr(_TLS, "weight_quant", None)
 
