@@ -2053,10 +2053,10 @@ __global__ __launch_bounds__(FT) void attn_bwd_fused_kernel(AttnArgs a) {
 //   * BCAST instance (dy_ld == 0: one cotangent row for every token, y.sum()'s; the launcher picks it on
 //     the stride, under the same launch record): the 256 rows of dO_h are one 64-vector, so the dY
 //     stream is one copy of the row in LDS (fetched once, behind the images), only the 4 KiB weight
-//     tiles stream -- sixteen [64][32] stages over the same region, three groups of four in flight --
+//     tiles stream -- sixteen [64][32] stages over the same region, all issued before the pieces --
 //     and tile wave j runs ONE MFMA per K-tile, on the 16 weight rows it loads itself (no barrier in
-//     the loop), then stores its 16 columns to all 256 rows; the piece waves issue every piece before it.
-//     GEMM phase 19.6k -> 15.3k cycles at B = 64 (profiles/PERF_NOTES.md).  Same instruction, A rows,
+//     the loop), then stores its 16 columns to all 256 rows; the piece waves issue every piece beside it.
+//     GEMM phase 19.6k -> 15.3k -> 12.5k cycles at B = 64 (profiles/PERF_NOTES.md).  Same instruction, A rows,
 //     B column values and k order per element: the same bits as the general phase
 //     (tests/test_attn_bwd_proj_bcast_gpu.py).
 //   * dO_h stays in LDS for the whole sweep ([256][64], img16 per 64-row block); block it's image is
@@ -2079,10 +2079,10 @@ constexpr int PJ_Q = PJ_DO + FK * D, PJ_OS = PJ_Q + 2 * BLK * D, PJ_ROWC = PJ_OS
 constexpr int PJ_LDS = PJ_ROWC + 2 * 2 * BLK * 2;   // 153 KiB
 static_assert(3 * PJ_STAGE <= PJ_Q - PJ_DST, "the ring fits the dS^T and dO images");
 static_assert(PJ_LDS * 2 <= 160 * 1024, "LDS");
-// BCAST (dy_ld == 0, M <= PJB_ROW): weight-only stages over the same region, PJB_G tiles per counted
-// wait with PJB_AHEAD groups in flight, and one copy of the row behind the images
+// BCAST (dy_ld == 0, M <= PJB_ROW): weight-only stages over the same region, all PJB_NST issued before
+// the loop, PJB_G tiles per counted wait, and one copy of the row behind the images
 constexpr int PJB_STAGE = D * PJ_BK;   // elements (4 KiB)
-constexpr int PJB_G = 4, PJB_AHEAD = 3, PJB_NST = (PJB_AHEAD + 1) * PJB_G;
+constexpr int PJB_G = 4, PJB_NST = 16;
 constexpr int PJB_ROW = 2048;          // elements of the row copy: one 1 KiB piece per tile wave
 static_assert((PJB_NST & (PJB_NST - 1)) == 0 && PJB_NST * PJB_STAGE <= PJ_Q - PJ_DST, "the stages fit the two images");
 static_assert((PJ_LDS + PJB_ROW) * 2 <= 160 * 1024, "LDS");
@@ -2208,9 +2208,12 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
       // kt + 8 g .. + 7, the same for every lane & 15) is read from one copy of the row behind the
       // kernel's images; the weight tiles stream through PJB_NST stages of [64][32] (the general ring's
       // weight image and swizzle).  Per element: the general loop's instruction, A row, B column and k
-      // order -- the same bits.  The piece waves are not in the loop: they issue every piece and wait for
-      // the phase's end (the first weight tiles then arrive behind that burst, 8.8k cycles into the block:
-      // the open variant in the notes).
+      // order -- the same bits.  The piece waves are not in the loop: they issue every piece once the row
+      // copy landed and wait for the phase's end.  (Issued before that barrier, the pieces filled the
+      // memory queue, the piece waves stalled in their issue and reached the barrier 8.7k cycles into the
+      // block, so no tile wave started before then; now the first group is usable after 3.2k cycles and the
+      // phase ends with the burst: 15.0k -> 12.5k cycles, profiles/PERF_NOTES.md, "Weight tiles ahead of
+      // the burst".)
       const bf16_t* const rowi = smem + PJ_LDS;
       // weight K-tile kt (this tile wave's 16 rows) into stage kt % PJB_NST; past the last tile the piece
       // reads nothing, so every group counts PJB_G loads
@@ -2221,37 +2224,44 @@ __global__ __launch_bounds__(FT) void attn_bwd_proj_kernel(AttnArgs a, BwdProjAr
       if (tw) {
         dma_lds_x4_at(ra, va[0], sb + 2 * (PJ_LDS + pw * 512));   // (past M: zeros, never read as a fragment)
 #pragma unroll
-        for (int kt = 0; kt < PJB_AHEAD * PJB_G; ++kt) issue_w(kt);
-        // the row piece is the oldest of these 1 + PJB_AHEAD PJB_G loads
-        static_assert(PJB_AHEAD * PJB_G == 12, "the counted wait below");
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      } else {
-        for (; pi < PJ_NPW; ++pi) issue_piece(pi);
+        for (int kt = 0; kt < PJB_NST; ++kt) issue_w(kt);
+        // the row piece is the oldest of these 1 + PJB_NST loads
+        static_assert(PJB_NST == 16, "the counted wait below");
+        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
       }
       __builtin_amdgcn_s_barrier();   // every tile wave's piece of the row copy landed
-      if (tw) {
-        for (int k0 = 0, gi = 0; k0 < nk; k0 += PJB_G, ++gi) {
-          // This wave has issued, in order, its row piece, then PJB_G loads per group: 1 + (PJB_AHEAD + gi)
-          // PJB_G so far.  Group gi is usable once the first 1 + (gi + 1) PJB_G of them retired:
-          // (PJB_AHEAD - 1) PJB_G = 8 may stay in flight (groups gi + 1 and gi + 2).  Only this wave reads
-          // the 16 rows it loads; its reads of group gi - 1 are done (lgkmcnt) before group gi +
-          // PJB_AHEAD goes into those stages (PJB_NST = (PJB_AHEAD + 1) PJB_G).
-          static_assert((PJB_AHEAD - 1) * PJB_G == 8, "the counted wait below");
-          asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!tw) {
+        for (; pi < PJ_NPW; ++pi) issue_piece(pi);
+      } else {
+        // One group of PJB_G K-tiles from k0 (FULL: all of them below nk).  This wave has issued, in order,
+        // its row piece, then PJB_G loads per group: 1 + PJB_NST + gi PJB_G so far.  Group gi is usable once
+        // the first 1 + (gi + 1) PJB_G of them retired: PJB_NST - PJB_G = 12 may stay in flight.  Only this
+        // wave reads the 16 rows it loads.  The group's fragment reads go ahead of its MFMAs, and once they
+        // returned, the group PJB_NST tiles on goes into the stages they read.
+        auto group = [&](int k0, int gi, auto full) {
+          constexpr bool FULL = decltype(full)::value;
+          static_assert(PJB_NST - PJB_G == 12, "the counted wait below");
+          asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
           sstamp(gi);
-#pragma unroll
-          for (int i = 0; i < PJB_G; ++i) issue_w(k0 + PJB_AHEAD * PJB_G + i);
+          bf16x8 wf[PJB_G], rf[PJB_G];
 #pragma unroll
           for (int i = 0; i < PJB_G; ++i) {
             const int kt = k0 + i;
-            if (kt < nk) {
-              const bf16x8 wf = frag(dSt + (kt & (PJB_NST - 1)) * PJB_STAGE, 16 * pw);
-              const bf16x8 rf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rowi + kt * PJ_BK + 8 * g));
-              acc[0][0] = mfma16x16x32(wf, rf, acc[0][0]);   // C^T block
+            if (FULL || kt < nk) {
+              wf[i] = frag(dSt + (kt & (PJB_NST - 1)) * PJB_STAGE, 16 * pw);
+              rf[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(rowi + kt * PJ_BK + 8 * g));
             }
           }
-        }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+          for (int i = 0; i < PJB_G; ++i) issue_w(k0 + PJB_NST + i);
+#pragma unroll
+          for (int i = 0; i < PJB_G; ++i)
+            if (FULL || k0 + i < nk) acc[0][0] = mfma16x16x32(wf[i], rf[i], acc[0][0]);   // C^T block
+        };
+        int k0 = 0, gi = 0;
+        for (; k0 + PJB_G <= nk; k0 += PJB_G, ++gi) group(k0, gi, std::true_type{});
+        if (k0 < nk) group(k0, gi, std::false_type{});
       }
       // everything landed (the past-the-end tiles too: they cover the image below), every wave is done
       // with the ring
